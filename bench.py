@@ -10,7 +10,7 @@ Device memory: batch x 160 MiB of pixel buffers (in, out, index) + 10 MiB of qua
 Multi-GPU (driver: torch.distributed.run, one rank per GPU): every rank converts its own batches (independent units,
 no data-path collective; RCCL only for the barrier / max-over-ranks of the time) -> "scaling": "weak".
 
-Prints ONE JSON line on rank 0 (contract in the round prompt) with extra objects:
+Prints ONE JSON line on rank 0 with extra objects:
   roofline       -- dominant per-pixel kernel (gilbert_fast_kernel = nearest-colour + dither pass), algorithmic bytes
                     8 B/pixel (4 B ARGB read + 4 B ARGB write) / its average duration measured with HIP
                     events on the launch stream inside the timed region, against the 8 TB/s HBM peak;
@@ -25,8 +25,14 @@ Prints ONE JSON line on rank 0 (contract in the round prompt) with extra objects
                     histogram: 2970 bins, sorted-by-yDiff queue, generic dither kernel); the PCIe-inclusive rate of
                     nq_convert_batch over page-locked host buffers (never the headline `value`);
   amortised_ms_per_image -- the three phases of a batch call (HIP events on the launch stream) divided by the batch size;
+  single_convert_latency_ms, single_convert_stages_ms, merge_stats -- one image alone (before the warm-up; merge_stats from an extra
+                    convert through the stamped merge kernel);
+  output check   -- every output pixel of three images of the last step is its palette entry, palettes are full and differ;
   cpu_baseline   -- the CPU oracle (C restatement of the reference's sequential Java path, 1 core) on the SAME 4096x4096 image
                     and seed as slot 0 of the batch (--cpu-sample shrinks it; the size is in its "sample" field), rank 0, N=1 only.
+A plain run sets up, warms up, times --steps steps, writes what the last step computed (--dump-outputs DIR) and prints the line with
+the objects derived from the timed steps themselves: config, amortised_ms_per_image, roofline, roofline_whole.  Everything else above
+(measured or checked after the timed region, or before the warm-up) needs --full.
 
 --config cfg3 (default) is the headline above.  The other two BASELINE configurations exercise the multi-GPU shapes:
   --config cfg4  batch of 64 x 1920x1080 frames, frame f on rank f mod N (independent units, no data-path collective; strong scaling);
@@ -46,8 +52,10 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 # One hardware queue per in-flight convert: ROCm multiplexes HIP streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues, and
-# a short kernel queued behind another stream's long merge kernel in the same hardware queue would wait for it.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "64")
+# a short kernel queued behind another stream's long merge kernel in the same hardware queue would wait for it.  32 leaves a queue for
+# every stream a step opens at the default --concurrency (its launch stream and up to 8 prepare lanes).  Set, not defaulted: under an
+# inherited 4 the prepare phase of the headline takes 0.44 instead of 0.37 ms per image (3 % of a step).
+os.environ["GPU_MAX_HW_QUEUES"] = "32"
 
 import numpy as np
 import torch
@@ -192,6 +200,34 @@ def measured_traffic(w, h, path=None):
     return None
 
 
+DUMP_IMAGES, DUMP_PIXELS, DUMP_PALETTES = 8, 1 << 21, 8192       # at most 8 images, 2 Mi sampled pixels over them, 8192 palettes
+
+
+def dump_outputs(path, pals, outs, idxs):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files under `path` (< 64 MB in all, the same files
+    for the same arguments).  palette[i] = the palette of image palette_images[i] (ARGB as unsigned 32-bit numbers, -1 past
+    palette_size[i]); argb[j] / index[j] = the output pixels / palette indices of image sample_images[j] at the positions sample_pixels
+    (a fixed seeded sample, the same in every image, or every pixel of a small image)."""
+    n, npx = len(pals), outs[0].numel()
+    rng = np.random.default_rng(20261016)
+    imgs = np.sort(rng.choice(n, min(n, DUMP_IMAGES), replace=False))
+    k = min(npx, DUMP_PIXELS // len(imgs))
+    pos = np.arange(npx) if k == npx else np.sort(rng.choice(npx, k, replace=False))
+    pal_imgs = np.arange(n) if n <= DUMP_PALETTES else np.sort(rng.choice(n, DUMP_PALETTES, replace=False))
+    kmax = max(len(pals[i]) for i in pal_imgs)
+    pal = np.full((len(pal_imgs), kmax), -1.0)
+    for r, i in enumerate(pal_imgs):
+        pal[r, :len(pals[i])] = pals[i].astype(np.int64) & 0xFFFFFFFF
+    pos_t = torch.from_numpy(pos).to(outs[0].device)
+    arrays = {"palette": pal, "palette_images": pal_imgs, "palette_size": np.array([len(pals[i]) for i in pal_imgs]),
+              "sample_images": imgs, "sample_pixels": pos,
+              "argb": np.stack([(outs[i][pos_t].to(torch.int64) & 0xFFFFFFFF).cpu().numpy() for i in imgs]),
+              "index": np.stack([(idxs[i][pos_t].to(torch.int64) & 0xFFFF).cpu().numpy() for i in imgs])}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
 def _claim_stdout():
     """The contract is ONE JSON line on stdout.  Libraries loaded later write there too (RCCL prints a version banner to stdout when its
     communicator starts), so file descriptor 1 is pointed at stderr for the whole run and the line goes to the saved descriptor."""
@@ -224,7 +260,7 @@ def main():
                     help="gradient_noise = BASELINE cfg 3 type (b), the headline; uniform = type (a), 65 536 bins; photo = the reference's sample.jpg tiled to --size")
     ap.add_argument("--tile", type=int, default=0, help="tile side of the PARALLEL_TILED decomposition (0 = automatic)")
     ap.add_argument("--cpu-sample", type=int, default=4096,
-                    help="side of the CPU-baseline image (default: the headline's own 4096, ~80 s on one core; 0 = skip)")
+                    help="--full: side of the CPU-baseline image (default: the headline's own 4096, ~30 s on one core; 0 = skip)")
     ap.add_argument("--no-dither", action="store_true", help="cfg5 only: convert(256, dither=false) -- the BlueNoise leg with the image-wide "
                                                              "distinct-colour count (presence-table all-reduce)")
     ap.add_argument("--batch", type=int, default=1536,
@@ -233,10 +269,15 @@ def main():
     ap.add_argument("--concurrency", type=int, default=1,
                     help="host threads / HIP streams a step's batch is split over (measured: one call for the whole batch is best -- the "
                          "library then runs 128-thread merge workgroups, four per CU, and the per-pixel stages have the chip to themselves)")
-    ap.add_argument("--no-extras", action="store_true", help="skip batch_sweep / cfg3a_uniform / photo / host_batch (N = 1 only, after the timed region)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip batch_sweep / cfg3a_uniform / photo / host_batch (N = 1 only, after the timed region)")
     ap.add_argument("--stagger", type=float, default=0.0,
                     help="with --concurrency T > 1: host thread t starts its first batch t * stagger seconds late, so that the merge loops of "
                          "one sub-batch (which leave most issue slots idle) run while another sub-batch is in its per-pixel stages")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (single-convert latency, merge_stats, the output "
+                         "check, roofline_lookup, the extras, the CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy (float64, < 64 MB)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -346,23 +387,24 @@ def main():
             if gr["err"] is not None:
                 raise gr["err"]
 
-    # single-convert latency (one image, one stream, nothing else in flight), untimed
     q0 = slots[0]["q"]
-    q0.convert_device(slots[0]["in"].data_ptr(), 256, True, slots[0]["out"].data_ptr(), slots[0]["idx"].data_ptr())
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    q0.convert_device(slots[0]["in"].data_ptr(), 256, True, slots[0]["out"].data_ptr(), slots[0]["idx"].data_ptr())
-    torch.cuda.synchronize()
-    latency_ms = (time.perf_counter() - t0) * 1e3
-    single_stages = q0.stage_ms()
-    # the same convert once more with the STAMPED build of the merge kernel (NQ_MERGE_STATS=1: phase ticks for "merge_stats"; ~4 % slower, untimed)
-    os.environ["NQ_MERGE_STATS"] = "1"
-    try:
+    if args.full:
+        # single-convert latency (one image, one stream, nothing else in flight), untimed
         q0.convert_device(slots[0]["in"].data_ptr(), 256, True, slots[0]["out"].data_ptr(), slots[0]["idx"].data_ptr())
         torch.cuda.synchronize()
-    finally:
-        del os.environ["NQ_MERGE_STATS"]
-    single_merge_stats = q0.merge_stats()
+        t0 = time.perf_counter()
+        q0.convert_device(slots[0]["in"].data_ptr(), 256, True, slots[0]["out"].data_ptr(), slots[0]["idx"].data_ptr())
+        torch.cuda.synchronize()
+        latency_ms = (time.perf_counter() - t0) * 1e3
+        single_stages = q0.stage_ms()
+        # the same convert once more with the STAMPED build of the merge kernel (NQ_MERGE_STATS=1: phase ticks for "merge_stats"; ~4 % slower, untimed)
+        os.environ["NQ_MERGE_STATS"] = "1"
+        try:
+            q0.convert_device(slots[0]["in"].data_ptr(), 256, True, slots[0]["out"].data_ptr(), slots[0]["idx"].data_ptr())
+            torch.cuda.synchronize()
+        finally:
+            del os.environ["NQ_MERGE_STATS"]
+        single_merge_stats = q0.merge_stats()
     run_all(args.warmup, False)
 
     def barrier():
@@ -392,19 +434,22 @@ def main():
             phases[k] = phases.get(k, 0.0) + v
     phases = {k: v / max(nrec, 1) for k, v in phases.items()}        # per image: a group's phase span / its images, averaged over the steps
     pals = groups[0]["pals"]
-    # sanity of the timed work itself: every output pixel is its palette entry, palettes are full and differ between images
-    g0 = groups[0]
-    for k in sorted({0, len(g0["slots"]) // 2, len(g0["slots"]) - 1}):
-        sk = g0["slots"][k]
-        palt = torch.from_numpy(pals[k]).cuda()
-        if len(pals[k]) != 256 or not bool((palt[(sk["idx"].to(torch.int64) & 0xFFFF)] == sk["out"]).all()):
-            raise SystemExit("bench: output pixels of image %d do not match palette[index]" % k)
-    if len(g0["slots"]) > 1 and args.workload == "gradient_noise" and bool((pals[0] == pals[-1]).all()):
-        raise SystemExit("bench: distinct images produced identical palettes")
+    if args.dump_outputs and rank == 0:        # before anything below overwrites an output buffer
+        dump_outputs(args.dump_outputs, [p for gr in groups for p in gr["pals"]], [s["out"] for s in slots], [s["idx"] for s in slots])
+    if args.full:
+        # sanity of the timed work itself: every output pixel is its palette entry, palettes are full and differ between images
+        g0 = groups[0]
+        for k in sorted({0, len(g0["slots"]) // 2, len(g0["slots"]) - 1}):
+            sk = g0["slots"][k]
+            palt = torch.from_numpy(pals[k]).cuda()
+            if len(pals[k]) != 256 or not bool((palt[(sk["idx"].to(torch.int64) & 0xFFFF)] == sk["out"]).all()):
+                raise SystemExit("bench: output pixels of image %d do not match palette[index]" % k)
+        if len(g0["slots"]) > 1 and args.workload == "gradient_noise" and bool((pals[0] == pals[-1]).all()):
+            raise SystemExit("bench: distinct images produced identical palettes")
 
     # LOOKUP_ONLY (nearestColorIndex per pixel, no diffusion) on slot 0 with its palette: the HBM-streaming kernel of the path
     lookup_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         reps = 20
         acc = 0.0
         for r in range(reps + 2):
@@ -434,15 +479,12 @@ def main():
                        "parallelism": "independent images per GPU, no collective",
                        "collective_backend": (backend if world > 1 else None),
                        "batch": Bn, "concurrency": T, "images_per_s": round(world * images / dt, 2),
-                       "ms_per_image": round(dt / images * 1e3, 3),
-                       "single_convert_latency_ms": round(latency_ms, 2)},
+                       "ms_per_image": round(dt / images * 1e3, 3)},
             "amortised_ms_per_image": {"prepare (pre-scan + histogram + initial find_nn pass)": round(phases.get("prepare", 0.0), 4),
                                        "merge (all merge loops of the batch in one launch + palette fill)": round(phases.get("merge", 0.0), 4),
                                        "finish (palette read-back + candidate lists + saliency + dither pass)": round(phases.get("finish", 0.0), 4),
                                        "of which the dither kernel": round(kernel_ms, 4),
                                        "sum": round(phases.get("total", 0.0), 4)},
-            "single_convert_stages_ms": {k: round(v, 3) for k, v in single_stages.items()},
-            "merge_stats": single_merge_stats,
             "pass_mpixels_s": round(npx / (kernel_ms * 1e-3) / 1e6, 1) if kernel_ms > 0 else None,
             "roofline": {"bound": "hbm", "kernel": "gilbert_fast_kernel (per-pixel nearest/closest colour + error diffusion, csrc/nq_dither_fast.hip)",
                          "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -463,9 +505,13 @@ def main():
         line["roofline_whole"] = {"bound": "hbm", "what": "8 B/pixel over the whole convert() of one image (all stages, batch amortised)",
                                   "achieved": round(BYTES_PER_PIXEL * npx / (whole_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                                   "frac": round(BYTES_PER_PIXEL * npx / (whole_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5), "ms_per_image": round(whole_ms, 3)}
-        if world == 1 and not args.no_extras and T == 1:
+        if args.full:
+            line["config"]["single_convert_latency_ms"] = round(latency_ms, 2)
+            line["single_convert_stages_ms"] = {k: round(v, 3) for k, v in single_stages.items()}
+            line["merge_stats"] = single_merge_stats
+        if args.full and world == 1 and not args.no_extras and T == 1:
             line.update(run_extras(nq, synth, slots, W, H, latency_ms, tile))
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             line["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_sample)
         else:
             line["cpu_baseline"] = None
@@ -518,9 +564,12 @@ def bench_cfg4(args, nq, synth, dist, rank, local_rank, world):
         dither_ms += sum(s["q"].stage_ms()["dither"] for s in slots)
     _barrier(dist)
     dt = _max_over_ranks(time.perf_counter() - t0, dist)
-    palt = torch.from_numpy(pals[0]).cuda()
-    if not bool((palt[(slots[0]["idx"].to(torch.int64) & 0xFFFF)] == slots[0]["out"]).all()):
-        raise SystemExit("bench cfg4: output pixels do not match palette[index]")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pals, [s["out"] for s in slots], [s["idx"] for s in slots])
+    if args.full:
+        palt = torch.from_numpy(pals[0]).cuda()
+        if not bool((palt[(slots[0]["idx"].to(torch.int64) & 0xFFFF)] == slots[0]["out"]).all()):
+            raise SystemExit("bench cfg4: output pixels do not match palette[index]")
     if rank == 0:
         kernel_ms = dither_ms / (args.steps * len(slots))
         achieved = BYTES_PER_PIXEL * npx / (kernel_ms * 1e-3) / 1e9
@@ -574,9 +623,12 @@ def bench_cfg5(args, nq, synth, dist, rank, local_rank, world):
         dither_ms += q.stage_ms()["dither"]
     _barrier(dist)
     dt = _max_over_ranks(time.perf_counter() - t0, dist)
-    palt = torch.from_numpy(pal).cuda()
-    if rows and not bool((palt[(d_idx.to(torch.int64) & 0xFFFF)] == d_out).all()):
-        raise SystemExit("bench cfg5: output pixels do not match palette[index]")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [pal], [d_out[:rows * W]], [d_idx[:rows * W]])
+    if args.full and rows:
+        palt = torch.from_numpy(pal).cuda()
+        if not bool((palt[(d_idx.to(torch.int64) & 0xFFFF)] == d_out).all()):
+            raise SystemExit("bench cfg5: output pixels do not match palette[index]")
     if rank == 0:
         kernel_ms = dither_ms / args.steps
         band_px = rows * W

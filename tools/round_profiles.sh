@@ -9,8 +9,8 @@ mkdir -p $O/pmc
 cd $GRAFT_REPO_ROOT
 want() { [ "$PART" = all ] || [ "$PART" = "$1" ]; }
 if want bench; then
-  # 1. the default bench command (with the CPU baseline on the headline image)
-  python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+  # 1. the full bench command (the extras and the CPU baseline on the headline image)
+  python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
   cut -c1-400 $O/bench_default.json
 fi
 if want prof; then
