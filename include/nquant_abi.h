@@ -173,6 +173,39 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
                      uint32_t* const* out_argb, uint16_t* const* out_index,
                      uint32_t* out_palettes, int32_t palette_stride, int32_t* out_K);
 
+/* ---- one palette for a sequence of frames: an animated GIF's global colour table, a video shot, a set of images shown side by side.
+ *      Frames 0..n-1 are ARGB_8888, row-major, each with its own width and height; pointer arrays are host arrays of n pointers.
+ *  * Palette and params are what convert() computes for ONE image whose int[] is all the frames' pixels one after another (frame 0
+ *    first): the alpha pre-scan (transparentPixelIndex is an index into that sequence, transparentColor the colour there), the
+ *    histogram (LAB: the float32 per-bin sums run in sequence order), the few-colours early return of the LAB class
+ *    (NQ/PnnLABQuantizer.java:193-206: the HashMap keySet of the sequence's distinct colours, first-occurrence order), quanFn / ratio /
+ *    weight and the merge loop.  nq_params.distinctColors counts over the whole sequence.  The palette equals nq_pnnquan_device run on a
+ *    concatenated copy of the frames, bit for bit -- but the frames are read in place, no copy is made.
+ *  * Frame i's pixels are what nq_set_params(h, <those params>) followed by nq_dither_device(h, frame i, palette, K, dither,
+ *    rng_seeds[i], mode, ...) returns: each frame is dithered as an image of its own (its own tiles and automatic tile size, saliency
+ *    map and random streams); it shares the palette, the params and the BlueNoise weight.  All three modes are allowed.
+ *  * The sequence may hold at most 2^31 - 1 pixels (one Java int[]); for the convert forms every frame has the per-image dither limits
+ *    (side <= 65535, nMaxColors <= 8192).  Anything else returns NQ_ERR_INVALID before any device work is done.
+ *  * n = 1 gives nq_convert_device's results in every output (palette, K, params, ARGB, index), the nMaxColors <= 2 rewrite included.
+ *  RGB sums are integers, so for the RGB kind the order of the frames does not change the palette; for the LAB kind it does, and the
+ *  sequence order above is the definition (not the band-order partial sums of nq_palette_from_histograms_device).
+ *  nq_pnnquan_frames_device leaves the params in h, like nq_pnnquan: followed by nq_dither_device per frame it is the "palettegen /
+ *  paletteuse" split -- a palette from some frames, applied to others.  nq_convert_frames_device: d_out_index and its entries may be
+ *  NULL; all work runs on the handle's stream; if frame i fails its status is returned and nq_last_error names the frame.
+ *  nq_get_stage_ms covers the whole call: prescan and histogram span all frames, `dither` runs from the first frame's dither pass to the
+ *  last frame's end (the BlueNoise post-passes included; `bluenoise` is 0 for n > 1).  nq_convert_frames: the same with HOST buffers
+ *  (all frames are uploaded, the device form runs, the results are copied back; out_index and its entries may be NULL). ---- */
+int nq_pnnquan_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             int nMaxColors, uint32_t* out_palette, int32_t* out_K);
+int nq_convert_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
+                             uint32_t* const* d_out_argb, uint16_t* const* d_out_index,
+                             uint32_t* out_palette, int32_t* out_K);
+int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                      int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
+                      uint32_t* const* out_argb, uint16_t* const* out_index,
+                      uint32_t* out_palette, int32_t* out_K);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

@@ -202,6 +202,18 @@ struct nq_handle {
     std::vector<int32_t> ext_distinct;
     DevBuf<int> d_ints;               // [0] maxbins, [1] status, [8..71] occupied slots per 1024-slot slice
     DevBuf<int> heap;
+    // nq_pnnquan_frames_device / nq_convert_frames_device: the frame table and the (frame, chunk) work list of the current call (host copies
+    // stay alive for the asynchronous uploads), and while such a call runs: frames_active (the pixel source of distinct_colors /
+    // palette_prepare is the frame table), reuse_lists (dither_device builds the candidate lists once and keeps them for the next
+    // frames), rec_skip (stage boundaries a frame's dither pass does not record)
+    std::vector<nq::FrameDesc> h_frames;
+    std::vector<nq::FrameChunk> h_items;
+    DevBuf<nq::FrameDesc> d_frames;
+    DevBuf<nq::FrameChunk> d_items;
+    int64_t frames_total = 0;
+    bool frames_active = false, reuse_lists = false, lists_built = false;
+    nq::ListsView saved_lv;
+    unsigned rec_skip = 0;
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
@@ -327,6 +339,19 @@ int prepare_lists(nq_handle* h, const DevParams& P, nq::ListsView* out, const in
     return NQ_OK;
 }
 
+// prepare_lists of one dither pass; in a frames call (reuse_lists) the lists of the first frame serve every later frame -- same palette,
+// same params, so the same lists -- and a saliency map wanted there is left to the caller (launch_saliency)
+int lists_for_call(nq_handle* h, const DevParams& P, nq::ListsView* out, const int* sal_pixels = nullptr, int64_t sal_n = 0, int sal_subst = 0,
+                   bool* sal_done = nullptr) {
+    if (h->reuse_lists && h->lists_built) {
+        if (sal_done) *sal_done = false;
+        *out = h->saved_lv;
+        return NQ_OK;
+    }
+    const int rc = prepare_lists(h, P, out, sal_pixels, sal_n, sal_subst, sal_done);
+    if (!rc && h->reuse_lists) { h->saved_lv = *out; h->lists_built = true; }
+    return rc;
+}
 
 int get_path(nq_handle* h, int w, int hgt, const uint32_t** out) {
     auto key = std::make_pair(w, hgt);
@@ -368,14 +393,19 @@ int reserve_palette_ws(nq_handle* h, int64_t n) {
 }
 
 // number of distinct colours of the image as the histogram sees it (= pixelMap.size() after the histogram); when it is
-// <= cap the colours are returned in first-occurrence order (the insertion order of the reference's HashMap)
+// <= cap the colours are returned in first-occurrence order (the insertion order of the reference's HashMap).
+// d_argb == nullptr: the pixels are the frame sequence of the running frames call (global first-occurrence indices)
 int distinct_colors(nq_handle* h, const uint32_t* d_argb, int64_t n, int64_t cap, int64_t* out_count, std::vector<int32_t>* out_colors) {
+    if (!d_argb && !h->frames_active) NQ_FAIL(h, NQ_ERR_INVALID, "distinct colours without pixels (internal error)");
     const bool want = out_colors != nullptr && cap > 0;
     NQ_HIP(h, h->sc->dk_a.reserve((size_t) n)); NQ_HIP(h, h->sc->dk_b.reserve((size_t) n));
     if (want) { NQ_HIP(h, h->sc->di_a.reserve((size_t) n)); NQ_HIP(h, h->sc->di_b.reserve((size_t) n)); NQ_HIP(h, h->sc->dheads.reserve((size_t) cap + 1)); }
     const size_t tb = sort32_temp_bytes(n, want) + 256;
     NQ_HIP(h, h->sc->dtmp.reserve(tb));
     unsigned long long* d_out = reinterpret_cast<unsigned long long*>(h->d_scalars.p + 20);
+    if (!d_argb)
+        launch_frames_pass(FRAMES_SUBST, h->d_frames.p, (int) h->h_frames.size(), h->d_items.p, (int) h->h_items.size(), nullptr, h->sc->dk_a.p,
+                           want ? h->sc->di_a.p : nullptr, h->params.transparentColor, 0, h->stream);
     launch_distinct((const int*) d_argb, n, h->params.transparentColor, h->sc->dk_a.p, h->sc->dk_b.p, want ? h->sc->di_a.p : nullptr,
                     want ? h->sc->di_b.p : nullptr, h->sc->dtmp.p, tb, d_out, want ? (void*) h->sc->dheads.p : nullptr, (unsigned) cap, h->stream);
     unsigned long long res[2] = {0, 0};
@@ -427,6 +457,7 @@ void apply_scan(nq_handle* h, int nMaxColors, int64_t transparent_index, uint32_
 // the per-pixel pass (what bench.py's roofline needs)
 void rec(nq_handle* h, int i) {
     if (h->light_events && ((i >= 1 && i <= 4) || i == 7)) return;
+    if ((h->rec_skip >> i) & 1u) return;
     (void) hipEventRecord(h->ev[i], h->stream);
 }
 
@@ -484,7 +515,7 @@ int palette_prepare(nq_handle* h, const double* d_hists, int n_bands, int nMaxCo
             // pixelMap.size() <= nMaxColors is only possible here (every occupied bin holds >= 1 distinct colour)
             int64_t cnt = 0;
             std::vector<int32_t> inserted;
-            if (d_argb) {
+            if (d_argb || h->frames_active) {               // (a frames call: the sequence's colours, d_argb == nullptr)
                 int rcd = distinct_colors(h, d_argb, n_pixels, nMaxColors, &cnt, &inserted);
                 if (rcd) return rcd;
             } else if (h->ext_distinct_valid) {                 // split pipeline: the caller merged the bands' lists
@@ -494,7 +525,7 @@ int palette_prepare(nq_handle* h, const double* d_hists, int n_bands, int nMaxCo
                 NQ_FAIL(h, NQ_ERR_UNSUPPORTED, "<= nMaxColors occupied bins in the multi-band path: exchange the bands' distinct colours "
                         "(nq_band_distinct_device / nq_set_distinct) before nq_palette_from_histograms_device "
                         "(NQ/PnnLABQuantizer.java:193-206)");
-            p.distinctColors = (!d_argb && h->ext_distinct_many) ? 0 : cnt;     // (0 = not known: "more than nMaxColors")
+            p.distinctColors = (!d_argb && !h->frames_active && h->ext_distinct_many) ? 0 : cnt;     // (0 = not known: "more than nMaxColors")
             if (cnt <= nMaxColors) {
                 // NQ/PnnLABQuantizer.java:193-206: palette = pixelMap.keySet() in HashMap order, a transparent colour swapped to slot 0
                 std::vector<int32_t> keys = java_hashmap_keyset(inserted);
@@ -702,6 +733,111 @@ int pnnquan_device(nq_handle* h, const uint32_t* d_argb, int width, int height, 
     return palette_finish(h, job, out_palette, out_K);
 }
 
+// ---- one palette for a sequence of frames (nq_pnnquan_frames_device / nq_convert_frames_device) ----
+// Arguments of a frames call, checked from the host arrays alone (no device memory is touched): *out_total = pixels of the sequence
+int frames_check(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights, int nMaxColors,
+                 bool for_dither, int64_t* out_total) {
+    if (n <= 0 || !d_argb || !widths || !heights) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument (n = %d)", n);
+    if (nMaxColors < 1 || nMaxColors > (for_dither ? 8192 : 32767)) NQ_FAIL(h, NQ_ERR_INVALID, "nMaxColors out of range");
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!d_argb[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: null pixel pointer", i);
+        if (widths[i] <= 0 || heights[i] <= 0) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: bad size %d x %d", i, widths[i], heights[i]);
+        if (for_dither && (widths[i] > 65535 || heights[i] > 65535)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: side > 65535", i);
+        total += (int64_t) widths[i] * heights[i];
+        if (total > 2147483647LL) NQ_FAIL(h, NQ_ERR_INVALID, "the sequence holds more pixels than a Java int[] (frame %d)", i);
+    }
+    *out_total = total;
+    return NQ_OK;
+}
+
+// the frame table and the (frame, chunk) work list of this call, uploaded on the handle's stream
+int frames_upload(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights) {
+    h->h_frames.clear(); h->h_items.clear();
+    int64_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t px = (int64_t) widths[i] * heights[i];
+        h->h_frames.push_back({(const int*) d_argb[i], (long long) px, (long long) off});
+        for (int64_t b = 0; b < px; b += NQ_FRAME_CHUNK)
+            h->h_items.push_back({i, (int) std::min<int64_t>(NQ_FRAME_CHUNK, px - b), (long long) b});
+        off += px;
+    }
+    h->frames_total = off;
+    NQ_HIP(h, h->d_frames.reserve(h->h_frames.size()));
+    NQ_HIP(h, h->d_items.reserve(h->h_items.size()));
+    NQ_HIP(h, hipMemcpyAsync(h->d_frames.p, h->h_frames.data(), h->h_frames.size() * sizeof(nq::FrameDesc), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemcpyAsync(h->d_items.p, h->h_items.data(), h->h_items.size() * sizeof(nq::FrameChunk), hipMemcpyHostToDevice, h->stream));
+    return NQ_OK;
+}
+
+// the per-call state of a frames call, cleared on every way out
+struct FramesScope {
+    nq_handle* h;
+    explicit FramesScope(nq_handle* hh) : h(hh) { h->frames_active = true; h->reuse_lists = false; h->lists_built = false; h->rec_skip = 0; }
+    ~FramesScope() { h->frames_active = false; h->reuse_lists = false; h->lists_built = false; h->rec_skip = 0; }
+};
+
+// pnnquan_prepare over the frame table (frames_upload first): the pre-scan with global indices, the histogram words of all frames in one
+// buffer at their global offsets -- then the histogram, compaction and the initial find_nn pass exactly as for one image of N pixels
+int pnnquan_frames_prepare(nq_handle* h, int nMaxColors, uint32_t* out_palette, int32_t* out_K, PaletteJob* job) {
+    job->merge = false;
+    const int64_t n = h->frames_total;
+    const int nf = (int) h->h_frames.size(), ni = (int) h->h_items.size();
+    long long* d_scan3 = h->d_scalars.p + 1;
+    rec(h, 0);
+    // the common case (nMaxColors >= 64) gets the speculative 5-6-5 sort words with the scan's read, as front_kernel does for one image
+    const bool words = nMaxColors >= 64;
+    if (words) {
+        int rcw = reserve_palette_ws(h, n);
+        if (rcw) return rcw;
+    }
+    launch_frames_pass(words ? FRAMES_FRONT : FRAMES_SCAN, h->d_frames.p, nf, h->d_items.p, ni, d_scan3,
+                       words ? reinterpret_cast<unsigned*>(h->sc->vals_a.p) : nullptr, nullptr, (int) 0x00FFFFFFu, 0, h->stream);
+    long long scan3[3];
+    NQ_HIP(h, hipMemcpyAsync(scan3, d_scan3, sizeof scan3, hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    NQ_HIP(h, launch_status());
+    apply_scan(h, nMaxColors, scan3[0], (uint32_t) scan3[1], scan3[2]);
+    rec(h, 1);
+    nq_params& p = h->params;
+    if (nMaxColors <= 2) {
+        // NQ/PnnQuantizer.java:441-452
+        p.weight = 1;
+        if (p.transparentPixelIndex >= 0) { out_palette[0] = (uint32_t) p.transparentColor; out_palette[1] = 0xFF000000u; }
+        else { out_palette[0] = 0xFF000000u; out_palette[1] = 0xFFFFFFFFu; }
+        p.paletteLength = nMaxColors; *out_K = nMaxColors;
+        rec(h, 2); rec(h, 3); rec(h, 4); rec(h, 5);
+        return NQ_OK;
+    }
+    int rc = reserve_palette_ws(h, n);
+    if (rc) return rc;
+    nq::HistParams hp;
+    hp.hasSemi = p.hasSemiTransparency; hp.hasTransp = nMaxColors < 64 || p.transparentPixelIndex >= 0;
+    hp.transparentColor = p.transparentColor; hp.rewriteTransparent = 0;
+    nq::SortWorkspace ws;
+    ws.keys_a = h->sc->keys_a.p; ws.keys_b = h->sc->keys_b.p; ws.vals_a = h->sc->vals_a.p; ws.vals_b = h->sc->vals_b.p;
+    ws.tmp = h->sc->sort_tmp.p; ws.tmp_bytes = h->sc->sort_tmp.n; ws.seg_start = h->sc->seg.p; ws.seg_end = h->sc->seg.p + 65536;
+    if (!(words && !hp.hasSemi && !hp.hasTransp))
+        launch_frames_pass(FRAMES_KEYS, h->d_frames.p, nf, h->d_items.p, ni, nullptr, reinterpret_cast<unsigned*>(h->sc->vals_a.p), nullptr,
+                           hp.transparentColor, hp.hasSemi ? 2 : hp.hasTransp ? 1 : 0, h->stream);
+    launch_histogram(h->kind, nullptr, n, hp, ws, h->sc->hist.p, h->stream, true);
+    return palette_prepare(h, h->sc->hist.p, 1, nMaxColors, out_palette, out_K, nullptr, n, job);
+}
+
+int pnnquan_frames(nq_handle* h, int nMaxColors, uint32_t* out_palette, int32_t* out_K) {
+    PaletteJob job;
+    int rc = pnnquan_frames_prepare(h, nMaxColors, out_palette, out_K, &job);
+    if (rc || !job.merge) return rc;
+    const PaletteJob* jp = &job;
+    rc = merge_launch(h, &jp, 1);
+    if (rc) return rc;
+    rec(h, 4);
+    return palette_finish(h, job, out_palette, out_K);
+}
+
+int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, const uint32_t* palette, int K, int dither,
+                  int64_t seed, int mode, uint32_t* d_out_argb, uint16_t* d_out_index);
+
 int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, const uint32_t* palette, int K, int dither,
                   int64_t seed, int mode, uint32_t* d_out_argb, uint16_t* d_out_index) {
     if (!d_argb || width <= 0 || height <= 0 || !palette || K < 1 || !d_out_argb) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
@@ -718,7 +854,7 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
     if (mode == NQ_MODE_LOOKUP_ONLY) {
         DevParams P = dev_params(h, K);
         nq::ListsView lv;
-        int rcl = prepare_lists(h, P, &lv);
+        int rcl = lists_for_call(h, P, &lv);
         if (rcl) return rcl;
         const bool fast_lookup = h->use_fast_dither && fast_lookup_eligible(P, lv);
         if (fast_lookup) NQ_HIP(h, h->sc->lookup_todo.reserve((size_t) n + 1));
@@ -808,7 +944,7 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
     nq::ListsView lv;
     bool sal_done = false;
     const bool want_sal = !staged && hasSal;            // (the map of THIS call's pixels; the builders and the map share one launch where they can)
-    { int rcl = prepare_lists(h, P, &lv, want_sal ? (const int*) d_argb : nullptr, n, salSubst ? 1 : 0, &sal_done); if (rcl) return rcl; }
+    { int rcl = lists_for_call(h, P, &lv, want_sal ? (const int*) d_argb : nullptr, n, salSubst ? 1 : 0, &sal_done); if (rcl) return rcl; }
     const float* d_sal = nullptr;
     if (staged) d_sal = hasSal ? ov.d_sal : nullptr;
     else if (hasSal) {
@@ -1156,6 +1292,102 @@ int nq_convert_device(nq_handle* h, const uint32_t* d_argb, int width, int heigh
     if (rc) return rc;
     NQ_HIP(h, hipStreamSynchronize(h->stream));
     finish_timing(h);
+    return NQ_OK;
+}
+
+// ---- one palette for a sequence of frames ----
+int nq_pnnquan_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             int nMaxColors, uint32_t* out_palette, int32_t* out_K) {
+    if (!h) return NQ_ERR_INVALID;
+    int64_t total = 0;
+    int rc = frames_check(h, n, d_argb, widths, heights, nMaxColors, false, &total);
+    if (rc) return rc;
+    if (!out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
+    rc = use_device(h);
+    if (rc) return rc;
+    FramesScope scope(h);
+    rc = frames_upload(h, n, d_argb, widths, heights);
+    if (rc) return rc;
+    return pnnquan_frames(h, nMaxColors, out_palette, out_K);
+}
+
+int nq_convert_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
+                             uint32_t* const* d_out_argb, uint16_t* const* d_out_index, uint32_t* out_palette, int32_t* out_K) {
+    if (!h) return NQ_ERR_INVALID;
+    int64_t total = 0;
+    int rc = frames_check(h, n, d_argb, widths, heights, nMaxColors, true, &total);
+    if (rc) return rc;
+    if (!rng_seeds || !d_out_argb || !out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n; ++i) if (!d_out_argb[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: null output pointer", i);
+    if (mode != NQ_MODE_REFERENCE_SEQUENTIAL && mode != NQ_MODE_PARALLEL_TILED && mode != NQ_MODE_LOOKUP_ONLY) NQ_FAIL(h, NQ_ERR_INVALID, "unknown mode %d", mode);
+    rc = use_device(h);
+    if (rc) return rc;
+    FramesScope scope(h);
+    rc = frames_upload(h, n, d_argb, widths, heights);
+    if (rc) return rc;
+    rc = pnnquan_frames(h, nMaxColors, out_palette, out_K);
+    if (rc) return rc;
+    const int K = *out_K;
+    nq_params& p = h->params;
+    // the BlueNoise weight of convert(n, false) counts the SEQUENCE's distinct colours (what dither_device would count for one image)
+    if (h->kind == NQ_KIND_LAB && !dither && K > 32 && mode == NQ_MODE_PARALLEL_TILED && p.distinctColors <= 0) {
+        int64_t cnt = 0;
+        rc = distinct_colors(h, nullptr, total, 0, &cnt, nullptr);
+        if (rc) return rc;
+        p.distinctColors = cnt;
+    }
+    // frame after frame on the stream, no host wait in between; the candidate lists are built for the first frame only.  Stage events:
+    // `dither` runs from the first frame's dither pass to the last frame's end (BlueNoise post-passes included, `bluenoise` = 0)
+    h->frames_active = false;
+    h->reuse_lists = true;
+    for (int i = 0; i < n; ++i) {
+        if (n > 1) h->rec_skip = i == 0 ? (1u << 6 | 1u << 7) : (1u << 5 | 1u << 6 | 1u << 7);
+        rc = dither_device(h, d_argb[i], widths[i], heights[i], out_palette, K, dither, rng_seeds[i], mode, d_out_argb[i],
+                           d_out_index ? d_out_index[i] : nullptr);
+        if (rc) { h->err = "frame " + std::to_string(i) + ": " + h->err; return rc; }
+    }
+    h->rec_skip = 0;
+    if (n > 1) { rec(h, 6); rec(h, 7); }
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    finish_timing(h);
+    return NQ_OK;
+}
+
+int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                      int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
+                      uint32_t* const* out_argb, uint16_t* const* out_index, uint32_t* out_palette, int32_t* out_K) {
+    if (!h) return NQ_ERR_INVALID;
+    int64_t total = 0;
+    int rc = frames_check(h, n, argb, widths, heights, nMaxColors, true, &total);
+    if (rc) return rc;
+    if (!out_argb || !rng_seeds || !out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n; ++i) if (!out_argb[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: null output pointer", i);
+    if (mode != NQ_MODE_REFERENCE_SEQUENTIAL && mode != NQ_MODE_PARALLEL_TILED && mode != NQ_MODE_LOOKUP_ONLY) NQ_FAIL(h, NQ_ERR_INVALID, "unknown mode %d", mode);
+    rc = use_device(h);
+    if (rc) return rc;
+    NQ_HIP(h, h->d_in.reserve((size_t) total)); NQ_HIP(h, h->d_out_argb.reserve((size_t) total)); NQ_HIP(h, h->d_out_index.reserve((size_t) total));
+    std::vector<const uint32_t*> src(n);
+    std::vector<uint32_t*> dst(n);
+    std::vector<uint16_t*> idx(n);
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t px = (size_t) widths[i] * heights[i];
+        NQ_HIP(h, hipMemcpyAsync(h->d_in.p + off, argb[i], px * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        src[i] = (const uint32_t*) (h->d_in.p + off); dst[i] = (uint32_t*) (h->d_out_argb.p + off); idx[i] = h->d_out_index.p + off;
+        off += px;
+    }
+    rc = nq_convert_frames_device(h, n, src.data(), widths, heights, nMaxColors, dither, rng_seeds, mode, dst.data(), idx.data(), out_palette, out_K);
+    if (rc) return rc;
+    off = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t px = (size_t) widths[i] * heights[i];
+        NQ_HIP(h, hipMemcpyAsync(out_argb[i], h->d_out_argb.p + off, px * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (out_index && out_index[i])
+            NQ_HIP(h, hipMemcpyAsync(out_index[i], h->d_out_index.p + off, px * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+        off += px;
+    }
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
     return NQ_OK;
 }
 

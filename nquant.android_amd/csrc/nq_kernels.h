@@ -132,6 +132,7 @@ struct SortWorkspace {
 };
 size_t sort_temp_bytes(int64_t n);
 size_t sort32_temp_bytes(int64_t n, bool pairs);
+// (d_pixels == nullptr: keys_a / idx_a already hold the substituted colours and indices, launch_frames_pass FRAMES_SUBST)
 void launch_distinct(const int* d_pixels, int64_t n, int transparentColor, unsigned* keys_a, unsigned* keys_b, unsigned* idx_a,
                      unsigned* idx_b, void* tmp, size_t tmp_bytes, unsigned long long* d_out, void* d_heads, unsigned cap, hipStream_t s);
 // colours present in a band: opaque ones mark d_bytes[rgb] (2^24 bytes, NOT cleared here: bands accumulate), the others enter the set
@@ -144,6 +145,17 @@ void launch_prescan(const int* d_pixels, int64_t n, int64_t index_offset, long l
 // reports no alpha == 0 pixel and no semi-transparency and nMaxColors >= 64 (launch_histogram(..., words_ready = true)).
 bool launch_front(const int* d_pixels, int64_t n, long long* d_scan3, int* d_words /* SortWorkspace::vals_a */, int defaultTransparent,
                   hipStream_t s);
+// ---- the same passes over a sequence of frames read in place (nq_palette.inc frames_kernel): frame f's pixel i has the global index
+// offset + i; the work list holds (frame, chunk) items of at most NQ_FRAME_CHUNK pixels, none crossing a frame boundary ----
+struct FrameDesc { const int* pixels; long long n; long long offset; };
+struct FrameChunk { int frame; int count; long long begin; };     // pixels [begin, begin + count) of frame `frame`
+#define NQ_FRAME_CHUNK 16384
+enum { FRAMES_SCAN = 0, FRAMES_FRONT = 1, FRAMES_KEYS = 2, FRAMES_SUBST = 3 };
+// FRAMES_SCAN: launch_prescan's result in d_scan3 (global indices); FRAMES_FRONT: the same + launch_front's speculative words in d_words
+// (color = the default transparent colour); FRAMES_KEYS: bin_keys_kernel's words (color = m_transparentColor, keyfmt as launch_histogram's);
+// FRAMES_SUBST: subst_colors_kernel's keys in d_words and global indices in d_idx (nullable)
+void launch_frames_pass(int op, const FrameDesc* d_frames, int n_frames, const FrameChunk* d_items, int n_items, long long* d_scan3,
+                        unsigned* d_words, unsigned* d_idx, int color, int keyfmt, hipStream_t s);
 void launch_histogram(int kind, const int* d_pixels, int64_t n, const HistParams& hp, const SortWorkspace& ws,
                       double* d_hist, hipStream_t s, bool words_ready = false);
 // d_blockcnt: int[64] scratch (occupied bins per 1024-bin slice)

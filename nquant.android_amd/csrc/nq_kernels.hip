@@ -192,8 +192,9 @@ size_t sort32_temp_bytes(int64_t n, bool pairs) {
 void launch_distinct(const int* d_pixels, int64_t n, int transparentColor, unsigned* keys_a, unsigned* keys_b, unsigned* idx_a,
                      unsigned* idx_b, void* tmp, size_t tmp_bytes, unsigned long long* d_out, void* d_heads, unsigned cap, hipStream_t s) {
     (void) hipMemsetAsync(d_out, 0, 2 * sizeof(unsigned long long), s);
-    hipLaunchKernelGGL(subst_colors_kernel, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, d_pixels, (long long) n, transparentColor,
-                       keys_a, idx_a);
+    if (d_pixels)
+        hipLaunchKernelGGL(subst_colors_kernel, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, d_pixels, (long long) n, transparentColor,
+                           keys_a, idx_a);
     size_t tb = tmp_bytes;
     if (idx_a)
         (void) rocprim::radix_sort_pairs(tmp, tb, (const unsigned*) keys_a, keys_b, (const unsigned*) idx_a, idx_b, (size_t) n, 0, 32, s);
@@ -226,6 +227,19 @@ bool launch_front(const int* d_pixels, int64_t n, long long* d_scan3, int* d_wor
                        d_scan3, (uint4*) d_words, defaultTransparent);
     hipLaunchKernelGGL(prescan_color_kernel, dim3(1), dim3(1), 0, s, d_pixels, (long long) n, 0LL, d_scan3);
     return true;
+}
+void launch_frames_pass(int op, const FrameDesc* d_frames, int n_frames, const FrameChunk* d_items, int n_items, long long* d_scan3,
+                        unsigned* d_words, unsigned* d_idx, int color, int keyfmt, hipStream_t s) {
+    const dim3 grid(std::max(1, std::min(n_items, 256 * 8))), block(256);
+    const bool scan = op == FRAMES_SCAN || op == FRAMES_FRONT;
+    if (scan) (void) hipMemsetAsync(d_scan3, 0xFF, 3 * sizeof(long long), s);      // {-1, -1, -1}: frames_prescan_color_kernel adds the 1
+    switch (op) {
+    case FRAMES_SCAN:  hipLaunchKernelGGL(frames_kernel<FRAMES_SCAN>, grid, block, 0, s, d_frames, d_items, n_items, d_scan3, d_words, d_idx, color, keyfmt); break;
+    case FRAMES_FRONT: hipLaunchKernelGGL(frames_kernel<FRAMES_FRONT>, grid, block, 0, s, d_frames, d_items, n_items, d_scan3, d_words, d_idx, color, keyfmt); break;
+    case FRAMES_KEYS:  hipLaunchKernelGGL(frames_kernel<FRAMES_KEYS>, grid, block, 0, s, d_frames, d_items, n_items, d_scan3, d_words, d_idx, color, keyfmt); break;
+    default:           hipLaunchKernelGGL(frames_kernel<FRAMES_SUBST>, grid, block, 0, s, d_frames, d_items, n_items, d_scan3, d_words, d_idx, color, keyfmt); break;
+    }
+    if (scan) hipLaunchKernelGGL(frames_prescan_color_kernel, dim3(1), dim3(1), 0, s, d_frames, n_frames, d_scan3);
 }
 void launch_histogram(int kind, const int* d_pixels, int64_t n, const HistParams& hp, const SortWorkspace& ws,
                       double* d_hist, hipStream_t s, bool words_ready) {

@@ -128,6 +128,89 @@ __global__ void __launch_bounds__(256) subst_colors_kernel(const int* __restrict
         if (idx) idx[i] = (unsigned) i;
     }
 }
+// ---- the same per-pixel passes over a SEQUENCE of frames read in place (nq_pnnquan_frames_device): pixel i of frame f has the global
+// index frames[f].offset + i, the index of that pixel in the concatenation of the frames, and every output word sits at that global
+// index -- what the single-image kernels above compute for a concatenated copy, without the copy.  The work list holds (frame, chunk)
+// items of at most NQ_FRAME_CHUNK pixels that never cross a frame boundary; one workgroup takes an item at a time.  Frames may have odd
+// pixel counts and 4-byte-aligned pointers: an item reads its pixels as 16-byte loads from the first 16-byte boundary of the SOURCE on
+// (head and tail pixels one by one), and stores a group of four words as one 16-byte store only where the destination is aligned too.
+// OP: FRAMES_SCAN = pre-scan (prescan_kernel), FRAMES_FRONT = pre-scan + speculative 5-6-5 words (front_kernel), FRAMES_KEYS = sort
+// words with the histogram's keys (bin_keys_kernel), FRAMES_SUBST = substituted colours + global index (subst_colors_kernel).
+template <int OP>
+__global__ void __launch_bounds__(256) frames_kernel(const FrameDesc* __restrict__ frames, const FrameChunk* __restrict__ items, int n_items,
+                                                     long long* __restrict__ scan3, unsigned* __restrict__ words, unsigned* __restrict__ idx,
+                                                     int color, int keyfmt) {
+    constexpr bool SCAN = OP == FRAMES_SCAN || OP == FRAMES_FRONT, STORE = OP != FRAMES_SCAN;
+    long long maxIdx = -1, semi = 0;
+    // one pixel at global index g: the scan's counters, the word written at g
+    auto word_of = [&](int px, long long g) -> unsigned {
+        const int alfa = c_alpha(px);
+        if (SCAN && alfa < 0xE0) {
+            if (alfa == 0) maxIdx = max(maxIdx, g);
+            else if (alfa > 0xF) ++semi;
+        }
+        if (OP == FRAMES_SCAN) return 0u;
+        if (OP == FRAMES_SUBST) return (unsigned) (alfa <= 0xF ? color : px);
+        return pack_bin_pixel(alfa <= 0xF ? color : px, OP == FRAMES_FRONT ? 0 : keyfmt);
+    };
+    auto put = [&](long long g, unsigned w) {
+        if (!STORE) return;
+        words[g] = w;
+        if (OP == FRAMES_SUBST && idx) idx[g] = (unsigned) g;
+    };
+    for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
+        const FrameChunk c = items[it];
+        const int* __restrict__ p = frames[c.frame].pixels + c.begin;
+        const long long g0 = frames[c.frame].offset + c.begin;
+        const int count = c.count;
+        int head = count;                              // (a pointer that is not 4-byte aligned: every pixel one by one)
+        if (!((uintptr_t) p & 3)) head = min(count, (int) (((16u - ((unsigned) (uintptr_t) p & 15u)) & 15u) >> 2));
+        const int body4 = (count - head) >> 2, tail0 = head + 4 * body4;
+        const bool vstore = STORE && !(((uintptr_t) (words + g0 + head)) & 15) && (OP != FRAMES_SUBST || !idx || !(((uintptr_t) (idx + g0 + head)) & 15));
+        for (int t = threadIdx.x; t < head; t += blockDim.x) put(g0 + t, word_of(p[t], g0 + t));
+        const int4* __restrict__ p4 = reinterpret_cast<const int4*>(p + head);
+        for (int j = threadIdx.x; j < body4; j += blockDim.x) {
+            const int4 v = p4[j];
+            const long long g = g0 + head + 4LL * j;
+            const unsigned w0 = word_of(v.x, g), w1 = word_of(v.y, g + 1), w2 = word_of(v.z, g + 2), w3 = word_of(v.w, g + 3);
+            if (!STORE) continue;
+            if (vstore) {
+                reinterpret_cast<uint4*>(words + g)[0] = make_uint4(w0, w1, w2, w3);
+                if (OP == FRAMES_SUBST && idx)
+                    reinterpret_cast<uint4*>(idx + g)[0] = make_uint4((unsigned) g, (unsigned) g + 1u, (unsigned) g + 2u, (unsigned) g + 3u);
+            } else {
+                put(g, w0); put(g + 1, w1); put(g + 2, w2); put(g + 3, w3);
+            }
+        }
+        for (int t = tail0 + threadIdx.x; t < count; t += blockDim.x) put(g0 + t, word_of(p[t], g0 + t));
+    }
+    if (!SCAN) return;
+    for (int off = 32; off > 0; off >>= 1) {
+        long long o = __shfl_down(maxIdx, off, 64); if (o > maxIdx) maxIdx = o;
+        semi += __shfl_down(semi, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (maxIdx >= 0) atomicMax((long long*) &scan3[0], maxIdx);
+        if (semi) atomicAdd((unsigned long long*) &scan3[2], (unsigned long long) semi);
+    }
+}
+// prescan_color_kernel of a frame sequence: the colour at the winning GLOBAL index, read from the frame that holds it
+__global__ void frames_prescan_color_kernel(const FrameDesc* __restrict__ frames, int n_frames, long long* scan3) {
+    const long long idx = scan3[0];
+    long long c = -1;
+    if (idx >= 0) {
+        int lo = 0, hi = n_frames - 1;                 // last frame whose offset <= idx
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (frames[mid].offset <= idx) lo = mid; else hi = mid - 1;
+        }
+        const long long i = idx - frames[lo].offset;
+        if (i >= 0 && i < frames[lo].n) c = (long long) (unsigned) frames[lo].pixels[i];
+    }
+    scan3[1] = c;
+    scan3[2] += 1;
+}
+
 // Which colours does a band hold (after the histogram's alpha substitution)?  Opaque colours set their byte of a 2^24-byte table
 // (bands of one image combine by byte-wise MAX, SURVEY 8e item 3), the others go into an open-addressing set of `slots` words
 // (0xFFFFFFFF = empty: no non-opaque colour has that value); counters[0] = set entries, counters[1] = 1 when the set overflowed.

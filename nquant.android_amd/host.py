@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "nq_dither_device", "nq_nearest_index", "nq_closest_tuple", "nq_band_scan_device", "nq_set_scan",
     "nq_band_histogram_device", "nq_palette_from_histograms_device", "nq_band_distinct_device", "nq_set_distinct", "nq_get_stage_ms", "nq_get_merge_stats",
     "nq_get_dither_path", "nq_get_batch_phase_ms", "nq_get_team_stats", "nq_set_band", "nq_band_color_presence_device", "nq_gilbert_dither", "nq_bluenoise_dither", "nq_selftest_ciede",
+    "nq_pnnquan_frames_device", "nq_convert_frames_device", "nq_convert_frames",
 ]
 OPT_CELL_LISTS, OPT_FAST_DITHER, OPT_MERGE_WALL_SECONDS = 1, 2, 3
 
@@ -126,6 +127,9 @@ def load_library():
     L.nq_gilbert_dither.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.c_double, i32, i64, i32, vp, vp]
     L.nq_bluenoise_dither.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.c_float, i64, i32, vp]
     L.nq_band_color_presence_device.argtypes = [vp, vp, i64, vp, i32, C.POINTER(C.c_int64), vp]
+    L.nq_pnnquan_frames_device.argtypes = [vp, i32, vp, vp, vp, i32, vp, C.POINTER(C.c_int32)]
+    L.nq_convert_frames_device.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_int32)]
+    L.nq_convert_frames.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_int32)]
     _LIB = L
     return L
 
@@ -382,6 +386,79 @@ def convert_batch_device(quantizers, d_pixels, nMaxColors, dither, d_out_argb, d
                                             sd.ctypes.data, int(q0.mode if mode is None else mode), dst, idx, pal.ctypes.data,
                                             stride, K.ctypes.data))
     return [pal[i, :K[i]].copy() for i in range(n)]
+
+
+def _frame_sizes(widths, heights, n):
+    w = np.ascontiguousarray(widths, np.int32).reshape(-1)
+    h = np.ascontiguousarray(heights, np.int32).reshape(-1)
+    if w.size != n or h.size != n:
+        raise ValueError("one width and one height per frame")
+    return w, h
+
+
+def pnnquan_frames_device(q, d_pixels, widths, heights, nMaxColors):
+    """nq_pnnquan_frames_device: ONE palette for a sequence of frames (HIP device addresses d_pixels[i], frame i of widths[i] x
+    heights[i]) on the handle and kind of quantizer `q`; equals pnnquan on the concatenated frames.  The params stay in `q`, so
+    q.dither_device(...) per frame applies the palette ("palettegen / paletteuse")."""
+    n = len(d_pixels)
+    w, h = _frame_sizes(widths, heights, n)
+    src = (C.c_void_p * n)(*[int(a) for a in d_pixels])
+    pal = np.zeros(max(int(nMaxColors), 2), np.int32)
+    K = C.c_int32(0)
+    q._check(q._L.nq_pnnquan_frames_device(q._h, n, src, w.ctypes.data, h.ctypes.data, int(nMaxColors), pal.ctypes.data, C.byref(K)))
+    return pal[:K.value].copy()
+
+
+def convert_frames_device(q, d_pixels, widths, heights, nMaxColors, dither, d_out_argb, d_out_index=None, mode=None, seeds=None):
+    """nq_convert_frames_device: one shared palette for the frames, then every frame dithered with it (device addresses).  seeds[i]
+    (default: q.seed for every frame) is frame i's random seed.  Returns the palette."""
+    n = len(d_pixels)
+    w, h = _frame_sizes(widths, heights, n)
+    src = (C.c_void_p * n)(*[int(a) for a in d_pixels])
+    dst = (C.c_void_p * n)(*[int(a) for a in d_out_argb])
+    idx = (C.c_void_p * n)(*[int(a) or None for a in d_out_index]) if d_out_index is not None else None
+    sd = np.array([q.seed] * n if seeds is None else list(seeds), np.int64)
+    if sd.size != n:
+        raise ValueError("one seed per frame")
+    pal = np.zeros(max(int(nMaxColors), 2), np.int32)
+    K = C.c_int32(0)
+    q._check(q._L.nq_convert_frames_device(q._h, n, src, w.ctypes.data, h.ctypes.data, int(nMaxColors), int(bool(dither)), sd.ctypes.data,
+                                           int(q.mode if mode is None else mode), dst, idx, pal.ctypes.data, C.byref(K)))
+    return pal[:K.value].copy()
+
+
+def convert_frames(kind, frames, nMaxColors, dither, device=0, mode=MODE_PARALLEL_TILED, seeds=None, tile=None):
+    """nq_convert_frames on host arrays: `frames` is a sequence of 2-D int32/uint32 ARGB_8888 arrays (sizes may differ).  Returns
+    (palette, [QuantizedImage per frame]) -- one palette shared by all frames (include/nquant_abi.h, "one palette for a sequence of
+    frames").  seeds[i] defaults to 0 for every frame; tile as for the quantizer objects (None = automatic)."""
+    frames = [_as_i32(f) for f in frames]
+    n = len(frames)
+    if n == 0:
+        raise ValueError("no frames")
+    for f in frames:
+        if f.ndim != 2:
+            raise ValueError("every frame must be a 2-D (height, width) array")
+    cls = PnnLABQuantizer if int(kind) == NQ_KIND_LAB else PnnQuantizer
+    q = cls(frames[0], device=device, mode=mode, tile=tile)
+    hs = np.array([f.shape[0] for f in frames], np.int32)
+    ws = np.array([f.shape[1] for f in frames], np.int32)
+    sd = np.array([0] * n if seeds is None else list(seeds), np.int64)
+    if sd.size != n:
+        raise ValueError("one seed per frame")
+    outs = [np.empty(f.shape, np.int32) for f in frames]
+    idxs = [np.empty(f.shape, np.uint16) for f in frames]
+    src = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
+    dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    idx = (C.c_void_p * n)(*[o.ctypes.data for o in idxs])
+    pal = np.zeros(max(int(nMaxColors), 2), np.int32)
+    K = C.c_int32(0)
+    try:
+        q._check(q._L.nq_convert_frames(q._h, n, src, ws.ctypes.data, hs.ctypes.data, int(nMaxColors), int(bool(dither)), sd.ctypes.data,
+                                        int(mode), dst, idx, pal.ctypes.data, C.byref(K)))
+        palette = pal[:K.value].copy()
+        return palette, [QuantizedImage(o, i, palette) for o, i in zip(outs, idxs)]
+    finally:
+        q.close()
 
 
 class PnnLABQuantizer(PnnQuantizer):

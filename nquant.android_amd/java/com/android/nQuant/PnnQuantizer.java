@@ -72,6 +72,22 @@ public class PnnQuantizer {
 	private static native int[][] nqConvertBatch(long[] handles, java.nio.IntBuffer[] in, int[] widths, int[] heights,
 			int nMaxColors, boolean dither, long[] seeds, int mode, java.nio.IntBuffer[] out);
 
+	/** One palette for a sequence of frames (nq_convert_frames): an animated GIF's global colour table, a video shot.  The palette
+	 *  is what convert() computes for one image holding all frames' pixels one after another; every frame is then dithered as an
+	 *  image of its own with that palette and seeds[i].  in[i] / out[i] are DIRECT buffers of widths[i]*heights[i] ints; kind: 0 =
+	 *  PnnQuantizer, 1 = PnnLABQuantizer.  Returns the palette. */
+	public static int[] convertFrames(int kind, java.nio.IntBuffer[] in, int[] widths, int[] heights, int nMaxColors, boolean dither,
+			long[] seeds, java.nio.IntBuffer[] out) {
+		long h = nqCreate(kind, 0);
+		try {
+			return nqConvertFrames(h, in, widths, heights, nMaxColors, dither, seeds, MODE_PARALLEL_TILED, out);
+		} finally {
+			nqDestroy(h);
+		}
+	}
+	private static native int[] nqConvertFrames(long h, java.nio.IntBuffer[] in, int[] widths, int[] heights, int nMaxColors,
+			boolean dither, long[] seeds, int mode, java.nio.IntBuffer[] out);
+
 	@Override
 	protected void finalize() throws Throwable {
 		if (handle != 0) { nqDestroy(handle); handle = 0; }

@@ -101,3 +101,35 @@ JNIEXPORT jobjectArray JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertBat
     free(K); free(palettes); free(dst); free(src); free(hs);
     return result;
 }
+
+/* convertFrames(): one palette for a sequence of frames -> nq_convert_frames.  Direct IntBuffers in and out; returns the palette. */
+JNIEXPORT jintArray JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertFrames(JNIEnv* env, jclass c, jlong hh, jobjectArray in,
+        jintArray widths, jintArray heights, jint nMaxColors, jboolean dither, jlongArray seeds, jint mode, jobjectArray out) {
+    nq_handle* h = (nq_handle*) (intptr_t) hh;
+    const jsize n = (*env)->GetArrayLength(env, in);
+    const int cap = nMaxColors > 2 ? nMaxColors : 2;
+    const uint32_t** src = malloc(sizeof(*src) * (n > 0 ? n : 1));
+    uint32_t** dst = malloc(sizeof(*dst) * (n > 0 ? n : 1));
+    uint32_t* palette = malloc(sizeof(uint32_t) * (size_t) cap);
+    if (!src || !dst || !palette) { free(palette); free(dst); free(src); throw_rt(env, "out of memory"); return NULL; }
+    int32_t K = 0;
+    jlong* sd = (*env)->GetLongArrayElements(env, seeds, NULL);
+    jint* w = (*env)->GetIntArrayElements(env, widths, NULL);
+    jint* hg = (*env)->GetIntArrayElements(env, heights, NULL);
+    for (jsize i = 0; i < n; ++i) {
+        src[i] = (const uint32_t*) (*env)->GetDirectBufferAddress(env, (*env)->GetObjectArrayElement(env, in, i));
+        dst[i] = (uint32_t*) (*env)->GetDirectBufferAddress(env, (*env)->GetObjectArrayElement(env, out, i));
+    }
+    const int rc = nq_convert_frames(h, n, src, (const int32_t*) w, (const int32_t*) hg, nMaxColors, dither ? 1 : 0,
+                                     (const int64_t*) sd, mode, dst, NULL, palette, &K);
+    jintArray pal = NULL;
+    if (rc != NQ_OK) throw_rt(env, nq_last_error(h));
+    else {
+        pal = (*env)->NewIntArray(env, K);
+        if (pal) (*env)->SetIntArrayRegion(env, pal, 0, K, (const jint*) palette);
+    }
+    (*env)->ReleaseIntArrayElements(env, heights, hg, JNI_ABORT); (*env)->ReleaseIntArrayElements(env, widths, w, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, seeds, sd, JNI_ABORT);
+    free(palette); free(dst); free(src);
+    return pal;
+}
