@@ -206,6 +206,36 @@ int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const in
                       uint32_t* const* out_argb, uint16_t* const* out_index,
                       uint32_t* out_palette, int32_t* out_K);
 
+/* ---- GIF encoding: palette index maps (what the convert calls write to out_index) to a GIF89a file, on the GPU.  Frames 0..n-1 are
+ *      uint16 index maps, row-major, each with its own width and height; they share one global colour table, the K ARGB entries of
+ *      `palette` (host memory).  The file is standard: every GIF decoder reads it.
+ *  * Colour table: N = the smallest value in 0..7 with 2^(N+1) >= max(K, 2); 2^(N+1) RGB entries, zeros after entry K-1.  GIF has
+ *    1-bit transparency: t = the first palette entry whose alpha is 0 (none: -1) is the transparent index; every other alpha
+ *    value is dropped.  Screen: the largest width and height of the frames, background index t (t < 0: 0).
+ *  * n > 1: a NETSCAPE2.0 loop block with loop_count (0 = for ever; -1 = no block, play once) and per frame a graphic control
+ *    extension with delays_cs[i] (hundredths of a second; delays_cs NULL: 0) and disposal 2 (restore to background).  n = 1: an
+ *    extension only when t >= 0.  Every frame sits at (0, 0).
+ *  * LZW: the minimum code size is m = max(2, N + 1).  Each frame's indices are cut into segments of segment_pixels pixels (0: the
+ *    default 16384; the last segment may be shorter) and every segment is one LZW chain with a fresh dictionary: the frame's first
+ *    segment starts with a Clear code, every segment but the last ends with a Clear code, the last one with End-of-Information.  The
+ *    chains run in parallel on the GPU.  A longer segment compresses a little better (1.02x the bytes of one chain over the whole
+ *    frame at 16384 pixels on dithered content) and gives fewer chains.  The bit-exact definition: DESIGN.md "GIF encoder".
+ *  * nq_gif_max_bytes: an upper bound of the file size for any content and any K (pure arithmetic, no device, no handle).
+ *  * nq_encode_gif_device: index maps in DEVICE memory (2-byte aligned pointers suffice), everything else on the host.  The file is
+ *    assembled in device memory and copied to `out` in one copy; *out_size = its size.  The call returns when `out` holds the file.
+ *    h may be a handle of either kind (its stream, scratch and error text are used).  nq_encode_gif: the same with index maps in
+ *    HOST memory (they are uploaded first).
+ *  * NQ_ERR_INVALID before any device work: n < 1, a side outside 1..65535, K outside 1..256, segment_pixels < 0, loop_count
+ *    outside -1..65535, a delay outside 0..65535, NULL or odd index pointers.  After the encoding: an index >= K, or cap smaller
+ *    than the file (then *out_size holds the size and `out` is untouched).  The handle stays usable after any of these. ---- */
+int nq_gif_max_bytes(int n, const int32_t* widths, const int32_t* heights, int K, int segment_pixels, int64_t* out_bytes);
+int nq_encode_gif_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                         const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
+                         uint8_t* out, int64_t cap, int64_t* out_size);
+int nq_encode_gif(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                  const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
+                  uint8_t* out, int64_t cap, int64_t* out_size);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

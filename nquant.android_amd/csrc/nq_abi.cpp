@@ -214,6 +214,15 @@ struct nq_handle {
     bool frames_active = false, reuse_lists = false, lists_built = false;
     nq::ListsView saved_lv;
     unsigned rec_skip = 0;
+    // nq_encode_gif_device: frame table, LZW scratch (bit strings; bit lengths, then bit offsets of the segments), read-back
+    // ({frame bit lengths}[n], bad-index flag), header blob and the file being assembled; nq_encode_gif: the uploaded index maps
+    std::vector<nq::GifFrame> h_gif;
+    DevBuf<nq::GifFrame> d_gif;
+    DevBuf<unsigned> gif_words;
+    DevBuf<unsigned long long> gif_bits, gif_res;
+    DevBuf<unsigned char> gif_blob, gif_file;
+    DevBuf<unsigned short> gif_in;
+    std::vector<uint8_t> h_gif_blob;
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
@@ -1760,6 +1769,186 @@ int nq_palette_from_histograms_device(nq_handle* h, const double* d_hists, int n
     rc = reserve_palette_ws(h, 1);
     if (rc) return rc;
     return palette_from_hist(h, d_hists, n_bands, nMaxColors, out_palette, out_K);
+}
+
+} // extern "C"
+
+// ---- GIF encoding (nq_gif.hip) ----
+namespace {
+
+constexpr int kGifDefaultSegment = 16384;
+
+// most bits a segment of L pixels can take: at most L - 1 codes for misses, a Clear code per table reset (one per >= 3838 new
+// entries), the frame's first Clear, the last code and the terminator, each at most 12 bits wide
+inline long long gif_seg_bits_max(long long L) { return 12 * (L + 3 + L / 3838); }
+inline long long gif_seg_len(long long px, int segment_pixels) { return std::min<long long>(segment_pixels ? segment_pixels : kGifDefaultSegment, px); }
+inline long long gif_stream_len(long long data_bytes) { return data_bytes + (data_bytes + 254) / 255 + 1; }
+constexpr long long kGifHeaderMax = 6 + 7 + 3 * 256 + 19, kGifFrameHeadMax = 8 + 10 + 1;
+
+// the arguments nq_gif_max_bytes takes; false + the reason otherwise
+bool gif_check_shape(int n, const int32_t* widths, const int32_t* heights, int K, int segment_pixels, char* why, size_t len) {
+    if (n < 1) { std::snprintf(why, len, "n = %d: at least one frame", n); return false; }
+    if (!widths || !heights) { std::snprintf(why, len, "widths / heights is NULL"); return false; }
+    if (K < 1 || K > 256) { std::snprintf(why, len, "K = %d: a GIF colour table holds 1..256 entries", K); return false; }
+    if (segment_pixels < 0) { std::snprintf(why, len, "segment_pixels = %d < 0", segment_pixels); return false; }
+    for (int i = 0; i < n; ++i)
+        if (widths[i] < 1 || widths[i] > 65535 || heights[i] < 1 || heights[i] > 65535) {
+            std::snprintf(why, len, "frame %d: %d x %d, sides must be 1..65535", i, widths[i], heights[i]); return false;
+        }
+    return true;
+}
+
+// everything but the index pointers, checked from the host arrays alone (no device work)
+int gif_check(nq_handle* h, int n, const int32_t* widths, const int32_t* heights, const uint32_t* palette, int K, const int32_t* delays_cs,
+              int loop_count, int segment_pixels, const uint8_t* out, int64_t cap, int64_t* out_size) {
+    char why[256];
+    if (!gif_check_shape(n, widths, heights, K, segment_pixels, why, sizeof why)) NQ_FAIL(h, NQ_ERR_INVALID, "%s", why);
+    if (!palette || !out_size) NQ_FAIL(h, NQ_ERR_INVALID, "palette / out_size is NULL");
+    if (loop_count < -1 || loop_count > 65535) NQ_FAIL(h, NQ_ERR_INVALID, "loop_count = %d: must be -1..65535", loop_count);
+    if (delays_cs)
+        for (int i = 0; i < n; ++i)
+            if (delays_cs[i] < 0 || delays_cs[i] > 65535) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: delay %d outside 0..65535", i, delays_cs[i]);
+    if (cap < 0 || (!out && cap > 0)) NQ_FAIL(h, NQ_ERR_INVALID, "out is NULL or cap < 0");
+    return NQ_OK;
+}
+
+int gif_check_index(nq_handle* h, int n, const uint16_t* const* index) {
+    if (!index) NQ_FAIL(h, NQ_ERR_INVALID, "index is NULL");
+    for (int i = 0; i < n; ++i)
+        if (!index[i] || ((uintptr_t) index[i] & 1)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: index pointer NULL or not 2-byte aligned", i);
+    return NQ_OK;
+}
+
+int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights, const uint32_t* palette,
+               int K, const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size) {
+    int N = 0;
+    while ((1 << (N + 1)) < std::max(K, 2)) ++N;
+    const int m = std::max(2, N + 1);
+    int t = -1;                                     // GIF has 1-bit transparency: the first entry with alpha 0, other alphas are dropped
+    for (int i = 0; i < K && t < 0; ++i) if ((palette[i] >> 24) == 0) t = i;
+    // frame table: segments and their scratch
+    h->h_gif.assign(n, nq::GifFrame{});
+    long long segs = 0, words = 0;
+    int W = 0, H = 0;
+    for (int i = 0; i < n; ++i) {
+        nq::GifFrame& F = h->h_gif[i];
+        const long long px = (long long) widths[i] * heights[i], S = gif_seg_len(px, segment_pixels);
+        F.index = d_index[i]; F.npix = px; F.seg_len = (int) S;
+        F.nseg = (px + S - 1) / S; F.seg_base = segs; F.seg_words = gif_seg_bits_max(S) / 32 + 2; F.word_base = words;
+        segs += F.nseg; words += F.nseg * F.seg_words;
+        W = std::max(W, (int) widths[i]); H = std::max(H, (int) heights[i]);
+    }
+    NQ_HIP(h, h->d_gif.reserve(n));
+    NQ_HIP(h, h->gif_words.reserve((size_t) words));
+    NQ_HIP(h, h->gif_bits.reserve(2 * (size_t) segs));
+    NQ_HIP(h, h->gif_res.reserve((size_t) n + 1));
+    NQ_HIP(h, hipMemcpyAsync(h->d_gif.p, h->h_gif.data(), n * sizeof(nq::GifFrame), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemsetAsync(h->gif_res.p + n, 0, sizeof(unsigned long long), h->stream));
+    launch_gif_lzw(h->d_gif.p, n, segs, K, m, h->gif_words.p, h->gif_bits.p, h->gif_res.p + n, h->stream);
+    launch_gif_scan(h->d_gif.p, n, h->gif_bits.p, h->gif_bits.p + segs, h->gif_res.p, h->stream);
+    NQ_HIP(h, launch_status());
+    std::vector<unsigned long long> res((size_t) n + 1);
+    NQ_HIP(h, hipMemcpyAsync(res.data(), h->gif_res.p, res.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    if (res[n]) NQ_FAIL(h, NQ_ERR_INVALID, "an index map holds an index >= K = %d", K);
+    // file layout: header + per frame {extension, descriptor, m, sub-blocks} + trailer; the header bytes go to the device in one blob
+    std::vector<uint8_t>& blob = h->h_gif_blob;
+    blob.clear();
+    auto u16 = [&](int v) { blob.push_back((uint8_t) (v & 255)); blob.push_back((uint8_t) (v >> 8)); };
+    blob.insert(blob.end(), {'G', 'I', 'F', '8', '9', 'a'});
+    u16(W); u16(H);
+    blob.push_back((uint8_t) (0xF0 | N)); blob.push_back((uint8_t) (t >= 0 ? t : 0)); blob.push_back(0);
+    for (int i = 0; i < (1 << (N + 1)); ++i) {
+        const uint32_t c = i < K ? palette[i] : 0;
+        blob.push_back((uint8_t) (c >> 16)); blob.push_back((uint8_t) (c >> 8)); blob.push_back((uint8_t) c);
+    }
+    if (n > 1 && loop_count >= 0) {
+        blob.insert(blob.end(), {0x21, 0xFF, 0x0B, 'N', 'E', 'T', 'S', 'C', 'A', 'P', 'E', '2', '.', '0', 0x03, 0x01});
+        u16(loop_count); blob.push_back(0);
+    }
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        nq::GifFrame& F = h->h_gif[i];
+        const size_t start = i == 0 ? 0 : blob.size();
+        if (n > 1 || t >= 0) {
+            blob.insert(blob.end(), {0x21, 0xF9, 0x04, (uint8_t) ((n > 1 ? 2 << 2 : 0) | (t >= 0 ? 1 : 0))});
+            u16(delays_cs ? delays_cs[i] : 0); blob.push_back((uint8_t) (t >= 0 ? t : 0)); blob.push_back(0);
+        }
+        blob.push_back(0x2C); u16(0); u16(0); u16(widths[i]); u16(heights[i]); blob.push_back(0);
+        blob.push_back((uint8_t) m);
+        F.prefix_off = (long long) start; F.prefix_len = (int) (blob.size() - start);
+        F.data_bytes = (long long) ((res[i] + 7) / 8); F.stream_len = gif_stream_len(F.data_bytes);
+        F.file_off = total;
+        total += F.prefix_len + F.stream_len;
+    }
+    total += 1;                                     // trailer
+    *out_size = total;
+    if (cap < total) NQ_FAIL(h, NQ_ERR_INVALID, "cap = %lld bytes < the file's %lld", (long long) cap, total);
+    NQ_HIP(h, h->gif_blob.reserve(blob.size()));
+    NQ_HIP(h, h->gif_file.reserve((size_t) total));
+    NQ_HIP(h, hipMemcpyAsync(h->gif_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemcpyAsync(h->d_gif.p, h->h_gif.data(), n * sizeof(nq::GifFrame), hipMemcpyHostToDevice, h->stream));
+    launch_gif_gather(h->d_gif.p, n, h->gif_words.p, h->gif_bits.p, h->gif_bits.p + segs, h->gif_blob.p, h->gif_file.p, total, h->stream);
+    NQ_HIP(h, launch_status());
+    NQ_HIP(h, hipMemcpyAsync(out, h->gif_file.p, (size_t) total, hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    return NQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_gif_max_bytes(int n, const int32_t* widths, const int32_t* heights, int K, int segment_pixels, int64_t* out_bytes) {
+    char why[256];
+    if (!out_bytes || !gif_check_shape(n, widths, heights, K, segment_pixels, why, sizeof why)) return NQ_ERR_INVALID;
+    long long total = kGifHeaderMax + 1;
+    for (int i = 0; i < n; ++i) {
+        const long long px = (long long) widths[i] * heights[i], S = gif_seg_len(px, segment_pixels), full = px / S, rest = px % S;
+        const long long bits = full * gif_seg_bits_max(S) + (rest ? gif_seg_bits_max(rest) : 0);
+        total += kGifFrameHeadMax + gif_stream_len((bits + 7) / 8);
+    }
+    *out_bytes = total;
+    return NQ_OK;
+}
+
+int nq_encode_gif_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                         const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
+                         uint8_t* out, int64_t cap, int64_t* out_size) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = gif_check(h, n, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    if (rc) return rc;
+    rc = gif_check_index(h, n, d_index);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return gif_encode(h, n, d_index, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+}
+
+int nq_encode_gif(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                  const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
+                  uint8_t* out, int64_t cap, int64_t* out_size) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = gif_check(h, n, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    if (rc) return rc;
+    rc = gif_check_index(h, n, index);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) total += (size_t) widths[i] * heights[i];
+    NQ_HIP(h, h->gif_in.reserve(total));
+    std::vector<const uint16_t*> dev(n);
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t px = (size_t) widths[i] * heights[i];
+        NQ_HIP(h, hipMemcpyAsync(h->gif_in.p + off, index[i], px * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+        dev[i] = h->gif_in.p + off;
+        off += px;
+    }
+    rc = gif_encode(h, n, dev.data(), widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    if (rc) (void) hipStreamSynchronize(h->stream);     // (no upload from the caller's buffers outlives the call)
+    return rc;
 }
 
 } // extern "C"

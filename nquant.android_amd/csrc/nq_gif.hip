@@ -1,0 +1,235 @@
+// nq_gif.hip -- GIF encoding of palette index maps on gfx950 (include/nquant_abi.h, "GIF encoding"; DESIGN.md "GIF encoder").
+//
+// A frame's indices are cut into segments of S pixels.  Every segment is one LZW chain with a dictionary of its own, so the
+// chains run in parallel; a frame's data is the chains' bit strings one after another (GIF allows a Clear code anywhere).
+//   gif_lzw_kernel     one wave per chain, four chains per workgroup; the dictionary lives in LDS and the indices are staged into
+//                      LDS by the whole wave, 1 KiB ahead of the chain
+//   gif_scan_kernel    per frame: exclusive scan of the segments' bit lengths, the frame's bit length
+//   gif_gather_kernel  one thread per byte of the file: header bytes from the host's blob, sub-block length bytes, and the data
+//                      bytes ORed together from the <= 3 segments each one overlaps
+#include "nq_kernels.h"
+
+namespace nq {
+
+namespace {
+
+constexpr int GIF_CHAINS = 4;            // chains (waves) per workgroup
+constexpr int GIF_SLOTS = 8192;          // open-addressing slots per chain: {key = pre << 8 | c : 20, code : 12}, 0 = empty
+constexpr int GIF_STAGE = 512;           // indices per staging block: 64 lanes x 16 bytes
+
+// every lane's LDS accesses so far are done and visible to the whole wave, and no access moves across this point
+__device__ inline void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// 16 bytes of index map at byte address a (16-byte aligned); the u16 elements outside [lo, hi) read as 0 and are never loaded
+__device__ inline uint4 load_chunk(uintptr_t a, uintptr_t lo, uintptr_t hi) {
+    if (a >= lo && a + 16 <= hi) return *reinterpret_cast<const uint4*>(a);
+    unsigned v[4] = {0, 0, 0, 0};
+    for (int j = 0; j < 8; ++j) {
+        const uintptr_t e = a + 2 * j;
+        if (e >= lo && e < hi) v[j >> 1] |= (unsigned) *reinterpret_cast<const unsigned short*>(e) << (16 * (j & 1));
+    }
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+__device__ inline void clear_table(unsigned* tab, int lane) {
+    uint4* t4 = reinterpret_cast<uint4*>(tab);
+    for (int i = lane; i < GIF_SLOTS / 4; i += 64) t4[i] = make_uint4(0, 0, 0, 0);
+    wave_sync();
+}
+
+// All 64 lanes of a wave run the chain in lockstep on the same values (the LDS reads broadcast); lane 0 alone stores to the
+// dictionary and to global memory.  Every loop is bounded by the segment length or the table size.
+__global__ void __launch_bounds__(64 * GIF_CHAINS) gif_lzw_kernel(const GifFrame* __restrict__ frames, int n_frames, long long n_segs,
+                                                                   int K, int m, unsigned* __restrict__ words,
+                                                                   unsigned long long* __restrict__ seg_bits, unsigned long long* __restrict__ bad) {
+    __shared__ unsigned table[GIF_CHAINS][GIF_SLOTS];
+    __shared__ uint4 stage[GIF_CHAINS][2][GIF_STAGE / 8];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned* tab = table[wv];
+    const unsigned CLEAR = 1u << m, EOI = CLEAR + 1;
+    for (long long g = (long long) blockIdx.x * GIF_CHAINS + wv; g < n_segs; g += (long long) gridDim.x * GIF_CHAINS) {
+        int lo = 0, hi = n_frames - 1;                 // frame of segment g: the last one whose first segment is <= g
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (frames[mid].seg_base <= g) lo = mid; else hi = mid - 1;
+        }
+        const GifFrame& F = frames[lo];
+        const long long s = g - F.seg_base;
+        const long long b = s * F.seg_len;
+        const long long L = min((long long) F.seg_len, F.npix - b);
+        const uintptr_t flo = reinterpret_cast<uintptr_t>(F.index), fhi = flo + 2 * (uintptr_t) F.npix;
+        const uintptr_t a0 = (flo + 2 * (uintptr_t) b) & ~(uintptr_t) 15;        // staging window: 16-byte aligned
+        const long long q0 = (long long) (((flo + 2 * (uintptr_t) b) & 15) >> 1), qend = q0 + L;
+        const long long nblk = (qend + GIF_STAGE - 1) / GIF_STAGE;
+        unsigned* __restrict__ out = words + F.word_base + s * F.seg_words;
+        unsigned long long acc = 0;
+        int nb = 0;
+        long long wpos = 0;
+        auto emit = [&](unsigned code, unsigned w) {
+            acc |= (unsigned long long) code << nb;
+            nb += (int) w;
+            if (nb >= 32) {
+                if (lane == 0) out[wpos] = (unsigned) acc;
+                ++wpos; acc >>= 32; nb -= 32;
+            }
+        };
+        bool badc = false;
+        auto index_at = [&](long long q) -> unsigned {
+            unsigned c = reinterpret_cast<const unsigned short*>(stage[wv][(q / GIF_STAGE) & 1])[q & (GIF_STAGE - 1)];
+            if (c >= (unsigned) K) { badc = true; c &= 255u; }
+            return c;
+        };
+        clear_table(tab, lane);
+        stage[wv][0][lane] = load_chunk(a0 + 16 * (uintptr_t) lane, flo, fhi);
+        wave_sync();
+        unsigned w = m + 1, next = EOI + 1;
+        if (s == 0) emit(CLEAR, w);
+        unsigned pre = index_at(q0);
+        long long q = q0 + 1;
+        for (long long k = 0; k < nblk; ++k) {
+            // the next block's indices are in flight while this block is encoded
+            const uint4 nv = k + 1 < nblk ? load_chunk(a0 + (uintptr_t) (k + 1) * 1024 + 16 * (uintptr_t) lane, flo, fhi) : make_uint4(0, 0, 0, 0);
+            const long long e = min(qend, (k + 1) * GIF_STAGE);
+            for (; q < e; ++q) {
+                const unsigned c = index_at(q);
+                const unsigned key = pre << 8 | c;
+                unsigned h = (key * 0x9E3779B1u) >> 19;
+                unsigned code = 0;
+                for (int probe = 0; probe < GIF_SLOTS; ++probe) {
+                    const unsigned ent = tab[h];
+                    if (ent == 0) break;
+                    if ((ent >> 12) == key) { code = ent & 4095u; break; }
+                    h = (h + 1) & (GIF_SLOTS - 1);
+                }
+                if (code) { pre = code; continue; }
+                emit(pre, w);
+                if (next == 4096) {
+                    emit(CLEAR, w);
+                    wave_sync();
+                    clear_table(tab, lane);
+                    next = EOI + 1; w = m + 1;
+                } else {
+                    if (lane == 0) tab[h] = key << 12 | next;
+                    if (next == (1u << w) && w < 12) ++w;
+                    ++next;
+                }
+                pre = c;
+            }
+            wave_sync();
+            stage[wv][(k + 1) & 1][lane] = nv;
+            wave_sync();
+        }
+        emit(pre, w);
+        if (next == (1u << w) && w < 12) ++w;       // the decoder adds its last entry on reading `pre`
+        emit(s == F.nseg - 1 ? EOI : CLEAR, w);
+        if (lane == 0) {
+            if (nb > 0) out[wpos] = (unsigned) acc;
+            seg_bits[g] = (unsigned long long) wpos * 32 + nb;
+            if (badc) *bad = 1;
+        }
+        wave_sync();
+    }
+}
+
+// one workgroup per frame: seg_off[i] = bits of the frame's segments before i; frame_bits[f] = the frame's total
+__global__ void __launch_bounds__(256) gif_scan_kernel(const GifFrame* __restrict__ frames, const unsigned long long* __restrict__ seg_bits,
+                                                       unsigned long long* __restrict__ seg_off, unsigned long long* __restrict__ frame_bits) {
+    __shared__ unsigned long long part[256];
+    const GifFrame& F = frames[blockIdx.x];
+    unsigned long long carry = 0;
+    for (long long c0 = 0; c0 < F.nseg; c0 += 256) {
+        const long long i = c0 + threadIdx.x;
+        const unsigned long long v = i < F.nseg ? seg_bits[F.seg_base + i] : 0;
+        part[threadIdx.x] = v;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const unsigned long long add = threadIdx.x >= (unsigned) d ? part[threadIdx.x - d] : 0;
+            __syncthreads();
+            part[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (i < F.nseg) seg_off[F.seg_base + i] = carry + part[threadIdx.x] - v;
+        carry += part[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) frame_bits[blockIdx.x] = carry;
+}
+
+// bits [lo, lo + cnt) (cnt <= 8) of a segment's bit string
+__device__ inline unsigned seg_bits_at(const unsigned* __restrict__ sw, unsigned long long lo, int cnt) {
+    const unsigned long long wi = lo >> 5;
+    const unsigned long long v = (unsigned long long) sw[wi] | (unsigned long long) sw[wi + 1] << 32;
+    return (unsigned) (v >> (lo & 31)) & ((1u << cnt) - 1u);
+}
+
+// data byte j of frame F: bits [8j, 8j + 8) of its segments' strings one after another
+__device__ inline unsigned data_byte(const GifFrame& F, long long j, const unsigned* __restrict__ words, const unsigned long long* __restrict__ seg_bits,
+                                     const unsigned long long* __restrict__ seg_off) {
+    const unsigned long long bp = 8ull * (unsigned long long) j;
+    long long lo = 0, hi = F.nseg - 1;                 // the last segment starting at or before bp
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (seg_off[F.seg_base + mid] <= bp) lo = mid; else hi = mid - 1;
+    }
+    unsigned v = 0;
+    for (long long t = lo; t < F.nseg; ++t) {
+        const unsigned long long so = seg_off[F.seg_base + t];
+        if (so >= bp + 8) break;
+        const unsigned long long se = so + seg_bits[F.seg_base + t];
+        const unsigned long long a = so > bp ? so : bp, e = se < bp + 8 ? se : bp + 8;
+        if (a < e) v |= seg_bits_at(words + F.word_base + t * F.seg_words, a - so, (int) (e - a)) << (a - bp);
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(256) gif_gather_kernel(const GifFrame* __restrict__ frames, int n_frames, const unsigned* __restrict__ words,
+                                                         const unsigned long long* __restrict__ seg_bits, const unsigned long long* __restrict__ seg_off,
+                                                         const unsigned char* __restrict__ blob, unsigned char* __restrict__ file, long long total) {
+    for (long long o = (long long) blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (long long) gridDim.x * blockDim.x) {
+        unsigned v = 0x3B;                             // trailer
+        if (o < total - 1) {
+            int lo = 0, hi = n_frames - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (frames[mid].file_off <= o) lo = mid; else hi = mid - 1;
+            }
+            const GifFrame& F = frames[lo];
+            const long long r = o - F.file_off;
+            if (r < F.prefix_len) v = blob[F.prefix_off + r];
+            else {
+                const long long j = r - F.prefix_len;  // sub-block stream: {len, up to 255 data bytes}..., 0
+                const long long blk = j >> 8, rr = j & 255;
+                if (j == F.stream_len - 1) v = 0;
+                else if (rr == 0) v = (unsigned) min(255ll, F.data_bytes - 255 * blk);
+                else v = data_byte(F, 255 * blk + rr - 1, words, seg_bits, seg_off);
+            }
+        }
+        file[o] = (unsigned char) v;
+    }
+}
+
+} // namespace
+
+void launch_gif_lzw(const GifFrame* d_frames, int n_frames, long long n_segs, int K, int m, unsigned* d_words, unsigned long long* d_seg_bits,
+                    unsigned long long* d_bad, hipStream_t s) {
+    long long grid = (n_segs + GIF_CHAINS - 1) / GIF_CHAINS;
+    if (grid > (1 << 20)) grid = 1 << 20;
+    hipLaunchKernelGGL(gif_lzw_kernel, dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, K, m, d_words, d_seg_bits, d_bad);
+}
+
+void launch_gif_scan(const GifFrame* d_frames, int n_frames, const unsigned long long* d_seg_bits, unsigned long long* d_seg_off,
+                     unsigned long long* d_frame_bits, hipStream_t s) {
+    hipLaunchKernelGGL(gif_scan_kernel, dim3((unsigned) n_frames), dim3(256), 0, s, d_frames, d_seg_bits, d_seg_off, d_frame_bits);
+}
+
+void launch_gif_gather(const GifFrame* d_frames, int n_frames, const unsigned* d_words, const unsigned long long* d_seg_bits,
+                       const unsigned long long* d_seg_off, const unsigned char* d_blob, unsigned char* d_file, long long total, hipStream_t s) {
+    long long grid = (total + 255) / 256;
+    if (grid > 256 * 64) grid = 256 * 64;
+    hipLaunchKernelGGL(gif_gather_kernel, dim3((unsigned) grid), dim3(256), 0, s, d_frames, n_frames, d_words, d_seg_bits, d_seg_off, d_blob, d_file, total);
+}
+
+} // namespace nq

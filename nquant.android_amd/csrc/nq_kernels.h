@@ -192,4 +192,22 @@ int merge_team_helpers(int n_jobs, int n_in_flight, int n_cus);
 // first error of a hipFuncSetAttribute issued by a launch_* function on this thread since the last call (hipSuccess: none); cleared
 hipError_t take_launch_error();
 
+// ---- GIF encoding (nq_gif.hip): frame f's indices are cut into segments of seg_len pixels (the last one shorter), segment s of the
+// frame is chain seg_base + s of the call and writes its bit string to words[word_base + s * seg_words ...] (seg_words: the worst case
+// of one segment + 1); file_off .. stream_len place the frame in the file (filled in after the bit lengths are known) ----
+struct GifFrame {
+    const unsigned short* index;   // 2-byte aligned
+    long long npix, seg_base, nseg, word_base, seg_words;
+    int seg_len, prefix_len;       // prefix: the bytes in front of the frame's sub-blocks (file header for frame 0, extension, descriptor, m)
+    long long file_off, prefix_off, data_bytes, stream_len;     // stream: the sub-blocks and their terminator
+};
+// seg_bits[g]: bit length of chain g; *d_bad = 1 when an index >= K was met (zeroed by the caller)
+void launch_gif_lzw(const GifFrame* d_frames, int n_frames, long long n_segs, int K, int m, unsigned* d_words, unsigned long long* d_seg_bits,
+                    unsigned long long* d_bad, hipStream_t s);
+void launch_gif_scan(const GifFrame* d_frames, int n_frames, const unsigned long long* d_seg_bits, unsigned long long* d_seg_off,
+                     unsigned long long* d_frame_bits, hipStream_t s);
+// the whole file (total bytes): frame prefixes from d_blob, sub-block stream of every frame, trailer
+void launch_gif_gather(const GifFrame* d_frames, int n_frames, const unsigned* d_words, const unsigned long long* d_seg_bits,
+                       const unsigned long long* d_seg_off, const unsigned char* d_blob, unsigned char* d_file, long long total, hipStream_t s);
+
 } // namespace nq

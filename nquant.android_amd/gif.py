@@ -1,0 +1,135 @@
+"""GIF89a files from the quantizer's index maps, encoded on the GPU (nq_encode_gif / nq_encode_gif_device, include/nquant_abi.h
+"GIF encoding").  One global colour table for all frames: the palette convert() or convert_frames() returned (K <= 256).  GIF has
+1-bit transparency: the first palette entry whose alpha is 0 becomes the transparent index, other alpha values are dropped.
+There is no CPU fallback: without a HIP device every call raises NqError with status -5 (NQ_ERR_NO_DEVICE)."""
+import ctypes as C
+
+import numpy as np
+
+from .host import MODE_PARALLEL_TILED, NqError, _frame_sizes, convert_frames, load_library
+
+
+def _palette(palette):
+    pal = np.ascontiguousarray(np.asarray(palette).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32).reshape(-1)
+    return pal
+
+
+def _index_maps(indices):
+    if isinstance(indices, np.ndarray) and indices.ndim == 2:
+        indices = [indices]
+    out = []
+    for a in indices:
+        a = np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError("every index map must be a 2-D (height, width) array")
+        if a.dtype != np.uint16:
+            if a.dtype.kind not in "iu":
+                raise TypeError("index maps must hold integers, got %s" % a.dtype)
+            if a.size and (a.min() < 0 or a.max() > 65535):
+                raise ValueError("index out of the uint16 range")
+            a = a.astype(np.uint16)
+        out.append(np.ascontiguousarray(a))
+    if not out:
+        raise ValueError("no frames")
+    return out
+
+
+def _delays(delays_cs, n):
+    if delays_cs is None:
+        return None
+    d = np.ascontiguousarray(delays_cs, np.int32).reshape(-1)
+    if d.size != n:
+        raise ValueError("one delay per frame")
+    return d
+
+
+def gif_max_bytes(widths, heights, K=256, segment_pixels=0):
+    """nq_gif_max_bytes: an upper bound of the file size for frames of these sizes (any content; no device needed)."""
+    L = load_library()
+    w = np.ascontiguousarray(widths, np.int32).reshape(-1)
+    h = np.ascontiguousarray(heights, np.int32).reshape(-1)
+    if w.size != h.size:
+        raise ValueError("one width and one height per frame")
+    out = C.c_int64(0)
+    rc = L.nq_gif_max_bytes(int(w.size), w.ctypes.data, h.ctypes.data, int(K), int(segment_pixels), C.byref(out))
+    if rc != 0:
+        raise NqError(rc, "invalid GIF shape arguments")
+    return out.value
+
+
+def _encode(L, handle, entry, ptrs, w, h, palette, delays_cs, loop, segment_pixels, check):
+    n = len(ptrs)
+    pal = _palette(palette)
+    d = _delays(delays_cs, n)
+    try:
+        cap = gif_max_bytes(w, h, 256, segment_pixels)
+    except NqError:
+        cap = 0                                     # (bad sizes: the encode call below says which)
+    buf = np.empty(max(cap, 1), np.uint8)
+    size = C.c_int64(0)
+    src = (C.c_void_p * n)(*[int(p) for p in ptrs])
+    check(getattr(L, entry)(handle, n, src, w.ctypes.data, h.ctypes.data, pal.ctypes.data, int(pal.size),
+                            d.ctypes.data if d is not None else None, int(loop), int(segment_pixels), buf.ctypes.data, int(cap),
+                            C.byref(size)))
+    return buf[:size.value].tobytes()
+
+
+class _Handle:
+    """A bare library handle (the GIF calls use only its stream, scratch and error text)."""
+
+    def __init__(self, device=0):
+        self._L = load_library()
+        h = C.c_void_p()
+        rc = self._L.nq_create(0, int(device), C.byref(h))
+        if rc != 0:
+            raise NqError(rc, (self._L.nq_last_error(None) or b"").decode())
+        self._h = h
+
+    def _check(self, rc):
+        if rc != 0:
+            raise NqError(rc, (self._L.nq_last_error(self._h) or b"").decode())
+
+    def close(self):
+        if self._h:
+            self._L.nq_destroy(self._h)
+            self._h = None
+
+
+def encode_gif(indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0):
+    """nq_encode_gif: `indices` is one 2-D index map or a sequence of them (sizes may differ), `palette` the ARGB_8888 entries they
+    index (K = len(palette) <= 256).  delays_cs: per-frame delay in hundredths of a second (None: 0); loop: the NETSCAPE2.0 loop
+    count of an animation (0 = for ever, -1 = no loop block); segment_pixels: pixels per LZW chain (0 = 16384).  Returns the file."""
+    maps = _index_maps(indices)
+    w = np.array([a.shape[1] for a in maps], np.int32)
+    h = np.array([a.shape[0] for a in maps], np.int32)
+    hd = _Handle(device)
+    try:
+        return _encode(hd._L, hd._h, "nq_encode_gif", [a.ctypes.data for a in maps], w, h, palette, delays_cs, loop, segment_pixels, hd._check)
+    finally:
+        hd.close()
+
+
+def encode_gif_device(q, d_index_ptrs, widths, heights, palette, delays_cs=None, loop=0, segment_pixels=0):
+    """nq_encode_gif_device on the handle of quantizer `q`: d_index_ptrs[i] is the HIP device address of frame i's uint16 index map
+    (widths[i] x heights[i], 2-byte aligned).  Arguments otherwise as encode_gif.  Returns the file."""
+    n = len(d_index_ptrs)
+    w, h = _frame_sizes(widths, heights, n)
+    return _encode(q._L, q._h, "nq_encode_gif_device", list(d_index_ptrs), w, h, palette, delays_cs, loop, segment_pixels, q._check)
+
+
+def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0):
+    """encode_gif, written to `path`.  Returns the number of bytes written."""
+    data = encode_gif(indices, palette, delays_cs, loop, segment_pixels, device)
+    with open(path, "wb") as f:
+        f.write(data)
+    return len(data)
+
+
+def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
+                          seeds=None, tile=None):
+    """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
+    Returns (file bytes, palette)."""
+    if not 1 <= int(nMaxColors) <= 256:
+        raise ValueError("a GIF colour table holds at most 256 entries")
+    palette, outs = convert_frames(kind, frames, nMaxColors, dither, device=device, mode=mode, seeds=seeds, tile=tile)
+    return encode_gif([o.index for o in outs], palette, delays_cs, loop, segment_pixels, device), palette

@@ -24,7 +24,7 @@ ABI_SYMBOLS = [
     "nq_dither_device", "nq_nearest_index", "nq_closest_tuple", "nq_band_scan_device", "nq_set_scan",
     "nq_band_histogram_device", "nq_palette_from_histograms_device", "nq_band_distinct_device", "nq_set_distinct", "nq_get_stage_ms", "nq_get_merge_stats",
     "nq_get_dither_path", "nq_get_batch_phase_ms", "nq_get_team_stats", "nq_set_band", "nq_band_color_presence_device", "nq_gilbert_dither", "nq_bluenoise_dither", "nq_selftest_ciede",
-    "nq_pnnquan_frames_device", "nq_convert_frames_device", "nq_convert_frames",
+    "nq_pnnquan_frames_device", "nq_convert_frames_device", "nq_convert_frames", "nq_gif_max_bytes", "nq_encode_gif_device", "nq_encode_gif",
 ]
 OPT_CELL_LISTS, OPT_FAST_DITHER, OPT_MERGE_WALL_SECONDS = 1, 2, 3
 
@@ -130,6 +130,9 @@ def load_library():
     L.nq_pnnquan_frames_device.argtypes = [vp, i32, vp, vp, vp, i32, vp, C.POINTER(C.c_int32)]
     L.nq_convert_frames_device.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_int32)]
     L.nq_convert_frames.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_int32)]
+    L.nq_gif_max_bytes.argtypes = [i32, vp, vp, i32, i32, C.POINTER(C.c_int64)]
+    L.nq_encode_gif_device.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, i64, C.POINTER(C.c_int64)]
+    L.nq_encode_gif.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, i64, C.POINTER(C.c_int64)]
     _LIB = L
     return L
 

@@ -88,6 +88,51 @@ public class PnnQuantizer {
 	private static native int[] nqConvertFrames(long h, java.nio.IntBuffer[] in, int[] widths, int[] heights, int nMaxColors,
 			boolean dither, long[] seeds, int mode, java.nio.IntBuffer[] out);
 
+	/** A GIF89a file of index maps (nq_encode_gif, encoded on the GPU): index[i] is a DIRECT buffer of widths[i]*heights[i] palette
+	 *  indices, palette the ARGB entries (at most 256; the first entry with alpha 0 is the transparent index), delaysCs the per-frame
+	 *  delays in hundredths of a second (null: 0), loopCount the NETSCAPE2.0 loop count of an animation (0 = for ever, -1 = none). */
+	public static byte[] encodeGif(java.nio.ShortBuffer[] index, int[] widths, int[] heights, int[] palette, int[] delaysCs, int loopCount) {
+		java.nio.ByteBuffer out = gifBuffer(widths, heights);
+		long h = nqCreate(0, 0);
+		try {
+			return gifBytes(out, nqEncodeGif(h, index, widths, heights, palette, delaysCs, loopCount, out, out.capacity()));
+		} finally {
+			nqDestroy(h);
+		}
+	}
+	private static native long nqEncodeGif(long h, java.nio.ShortBuffer[] index, int[] widths, int[] heights, int[] palette, int[] delaysCs,
+			int loopCount, java.nio.ByteBuffer out, long cap);
+
+	/** convertFrames (one shared palette, every frame dithered with it) followed by encodeGif of the index maps, in one native call;
+	 *  nMaxColors <= 256.  in[i] are DIRECT buffers of widths[i]*heights[i] ARGB ints. */
+	public static byte[] convertFramesToGif(int kind, java.nio.IntBuffer[] in, int[] widths, int[] heights, int nMaxColors, boolean dither,
+			long[] seeds, int[] delaysCs, int loopCount) {
+		java.nio.ByteBuffer out = gifBuffer(widths, heights);
+		long h = nqCreate(kind, 0);
+		try {
+			return gifBytes(out, nqConvertFramesToGif(h, in, widths, heights, nMaxColors, dither, seeds, MODE_PARALLEL_TILED, delaysCs,
+					loopCount, out, out.capacity()));
+		} finally {
+			nqDestroy(h);
+		}
+	}
+	private static native long nqConvertFramesToGif(long h, java.nio.IntBuffer[] in, int[] widths, int[] heights, int nMaxColors,
+			boolean dither, long[] seeds, int mode, int[] delaysCs, int loopCount, java.nio.ByteBuffer out, long cap);
+
+	private static java.nio.ByteBuffer gifBuffer(int[] widths, int[] heights) {
+		long cap = nqGifMaxBytes(widths, heights);
+		if (cap < 0 || cap > Integer.MAX_VALUE)
+			throw new IllegalArgumentException("a GIF of these frames does not fit one byte[]");
+		return java.nio.ByteBuffer.allocateDirect((int) cap);
+	}
+	private static byte[] gifBytes(java.nio.ByteBuffer out, long size) {
+		byte[] gif = new byte[(int) size];
+		out.get(gif);
+		return gif;
+	}
+	/** nq_gif_max_bytes for K = 256 (an upper bound for every K); -1 for invalid sizes */
+	private static native long nqGifMaxBytes(int[] widths, int[] heights);
+
 	@Override
 	protected void finalize() throws Throwable {
 		if (handle != 0) { nqDestroy(handle); handle = 0; }

@@ -133,3 +133,87 @@ JNIEXPORT jintArray JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertFrames
     free(palette); free(dst); free(src);
     return pal;
 }
+
+/* nqGifMaxBytes(): nq_gif_max_bytes for K = 256, the bound for every K; -1 when a size is invalid */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqGifMaxBytes(JNIEnv* env, jclass c, jintArray widths, jintArray heights) {
+    const jsize n = (*env)->GetArrayLength(env, widths);
+    if ((*env)->GetArrayLength(env, heights) != n) return -1;
+    jint* w = (*env)->GetIntArrayElements(env, widths, NULL);
+    jint* hg = (*env)->GetIntArrayElements(env, heights, NULL);
+    int64_t bytes = -1;
+    if (w && hg && nq_gif_max_bytes(n, (const int32_t*) w, (const int32_t*) hg, 256, 0, &bytes) != NQ_OK) bytes = -1;
+    if (hg) (*env)->ReleaseIntArrayElements(env, heights, hg, JNI_ABORT);
+    if (w) (*env)->ReleaseIntArrayElements(env, widths, w, JNI_ABORT);
+    return (jlong) bytes;
+}
+
+/* encodeGif(): direct ShortBuffers of indices in, the file written to the direct ByteBuffer `out` (cap bytes) -> nq_encode_gif.
+ * Returns the file size. */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqEncodeGif(JNIEnv* env, jclass c, jlong hh, jobjectArray index,
+        jintArray widths, jintArray heights, jintArray palette, jintArray delaysCs, jint loopCount, jobject out, jlong cap) {
+    nq_handle* h = (nq_handle*) (intptr_t) hh;
+    const jsize n = (*env)->GetArrayLength(env, index);
+    const uint16_t** src = malloc(sizeof(*src) * (n > 0 ? n : 1));
+    if (!src) { throw_rt(env, "out of memory"); return -1; }
+    for (jsize i = 0; i < n; ++i)
+        src[i] = (const uint16_t*) (*env)->GetDirectBufferAddress(env, (*env)->GetObjectArrayElement(env, index, i));
+    jint* w = (*env)->GetIntArrayElements(env, widths, NULL);
+    jint* hg = (*env)->GetIntArrayElements(env, heights, NULL);
+    jint* pal = (*env)->GetIntArrayElements(env, palette, NULL);
+    jint* d = delaysCs ? (*env)->GetIntArrayElements(env, delaysCs, NULL) : NULL;
+    const jsize K = (*env)->GetArrayLength(env, palette);
+    int64_t size = -1;
+    const int rc = nq_encode_gif(h, n, src, (const int32_t*) w, (const int32_t*) hg, (const uint32_t*) pal, K, (const int32_t*) d, loopCount, 0,
+                                 (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, &size);
+    if (d) (*env)->ReleaseIntArrayElements(env, delaysCs, d, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, palette, pal, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, heights, hg, JNI_ABORT); (*env)->ReleaseIntArrayElements(env, widths, w, JNI_ABORT);
+    free(src);
+    if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
+    return (jlong) size;
+}
+
+/* convertFramesToGif(): nq_convert_frames with index outputs (the ARGB outputs go to scratch), then nq_encode_gif of the index maps
+ * with the shared palette into the direct ByteBuffer `out` (cap bytes).  Returns the file size. */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertFramesToGif(JNIEnv* env, jclass c, jlong hh, jobjectArray in,
+        jintArray widths, jintArray heights, jint nMaxColors, jboolean dither, jlongArray seeds, jint mode, jintArray delaysCs, jint loopCount,
+        jobject out, jlong cap) {
+    nq_handle* h = (nq_handle*) (intptr_t) hh;
+    const jsize n = (*env)->GetArrayLength(env, in);
+    const int pcap = nMaxColors > 2 ? nMaxColors : 2;
+    const uint32_t** src = malloc(sizeof(*src) * (n > 0 ? n : 1));
+    uint32_t** argb = calloc(n > 0 ? n : 1, sizeof(*argb));
+    uint16_t** idx = calloc(n > 0 ? n : 1, sizeof(*idx));
+    uint32_t* palette = malloc(sizeof(uint32_t) * (size_t) pcap);
+    jint* w = (*env)->GetIntArrayElements(env, widths, NULL);
+    jint* hg = (*env)->GetIntArrayElements(env, heights, NULL);
+    jlong* sd = (*env)->GetLongArrayElements(env, seeds, NULL);
+    jint* d = delaysCs ? (*env)->GetIntArrayElements(env, delaysCs, NULL) : NULL;
+    int ok = src && argb && idx && palette && w && hg && sd;
+    for (jsize i = 0; ok && i < n; ++i) {
+        const size_t px = (size_t) (w[i] > 0 ? w[i] : 1) * (size_t) (hg[i] > 0 ? hg[i] : 1);
+        src[i] = (const uint32_t*) (*env)->GetDirectBufferAddress(env, (*env)->GetObjectArrayElement(env, in, i));
+        argb[i] = malloc(px * sizeof(uint32_t));
+        idx[i] = malloc(px * sizeof(uint16_t));
+        ok = argb[i] && idx[i];
+    }
+    int32_t K = 0;
+    int64_t size = -1;
+    int rc = NQ_OK;
+    if (ok) {
+        rc = nq_convert_frames(h, n, src, (const int32_t*) w, (const int32_t*) hg, nMaxColors, dither ? 1 : 0, (const int64_t*) sd, mode,
+                               argb, idx, palette, &K);
+        if (rc == NQ_OK)
+            rc = nq_encode_gif(h, n, (const uint16_t* const*) idx, (const int32_t*) w, (const int32_t*) hg, palette, K, (const int32_t*) d,
+                               loopCount, 0, (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, &size);
+    }
+    for (jsize i = 0; argb && idx && i < n; ++i) { free(argb[i]); free(idx[i]); }
+    if (d) (*env)->ReleaseIntArrayElements(env, delaysCs, d, JNI_ABORT);
+    if (sd) (*env)->ReleaseLongArrayElements(env, seeds, sd, JNI_ABORT);
+    if (hg) (*env)->ReleaseIntArrayElements(env, heights, hg, JNI_ABORT);
+    if (w) (*env)->ReleaseIntArrayElements(env, widths, w, JNI_ABORT);
+    free(palette); free(idx); free(argb); free(src);
+    if (!ok) { throw_rt(env, "out of memory"); return -1; }
+    if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
+    return (jlong) size;
+}

@@ -1,0 +1,121 @@
+"""GIF encoding of 4096x4096 index maps on the GPU (nq_encode_gif_device / nq_encode_gif) against the CPU writers on the same host:
+Pillow's GIF encoder and indexed_png.write_indexed_png.  The maps are what the headline bench converts (gradient_noise,
+PnnLABQuantizer.convert(256, true)).  Times are wall clock around calls that return when the file is in host memory (the GPU calls
+end in a stream synchronise and the copy of the file).
+
+    python tools/gif_bench.py [--size 4096] [--batch 64] [--reps 5] [--out FILE]"""
+import argparse
+import io
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fn, reps):
+    best, out = None, None
+    for _ in range(reps):
+        t = time.perf_counter()
+        out = fn()
+        dt = time.perf_counter() - t
+        best = dt if best is None or dt < best else best
+    return best, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--distinct", type=int, default=4, help="distinct converted maps the batch cycles through")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the Pillow animation timed on the CPU")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from PIL import Image
+    import nquant.android_amd as nq
+    from nquant.android_amd import synth
+    from nquant.android_amd.indexed_png import write_indexed_png
+
+    W = H = args.size
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("GIF encoding of %dx%d index maps (gradient_noise seeds 3.., PnnLABQuantizer.convert(256, true)); best of %d" % (W, H, args.reps))
+    maps, pals = [], []
+    for k in range(args.distinct):
+        q = nq.PnnLABQuantizer(synth.gradient_noise(W, H, 3 + k))
+        o = q.convert(256, True)
+        q.close()
+        maps.append(o.index)
+        pals.append(o.palette)
+    pal = pals[0]
+    dev = [torch.from_numpy(m.view(np.int16).reshape(-1).copy()).cuda() for m in maps]
+    torch.cuda.synchronize()
+    q = nq.PnnQuantizer(np.zeros((1, 1), np.int32))
+
+    # GPU, one frame
+    one = lambda: nq.encode_gif_device(q, [dev[0].data_ptr()], [W], [H], pal)
+    one()
+    t1, gif1 = timed(one, args.reps)
+    say("gpu  encode_gif_device, 1 frame          %9.2f ms/frame  %8.0f Mpx/s  %d bytes" % (t1 * 1e3, W * H / t1 / 1e6, len(gif1)))
+    th, gifh = timed(lambda: nq.encode_gif(maps[0], pal), args.reps)
+    assert gifh == gif1
+    say("gpu  encode_gif (host maps), 1 frame     %9.2f ms/frame  %8.0f Mpx/s" % (th * 1e3, W * H / th / 1e6))
+    # GPU, a batch of frames in one call (one animation)
+    B = args.batch
+    ptrs = [dev[i % len(dev)].data_ptr() for i in range(B)]
+    batch = lambda: nq.encode_gif_device(q, ptrs, [W] * B, [H] * B, pal, [4] * B, 0)
+    batch()
+    tb, gifb = timed(batch, max(2, args.reps // 2))
+    say("gpu  encode_gif_device, %d frames        %9.2f ms/frame  %8.0f Mpx/s  %d bytes (%.1f ms per call)" % (
+        B, tb / B * 1e3, B * W * H / tb / 1e6, len(gifb), tb * 1e3))
+    # CPU writers
+    im = Image.fromarray(maps[0].astype(np.uint8), "P")
+    im.putpalette([v for c in pal for v in ((int(c) >> 16) & 255, (int(c) >> 8) & 255, int(c) & 255)])
+
+    def pillow_one():
+        b = io.BytesIO()
+        im.save(b, "GIF")
+        return b.getvalue()
+    tp, pgif = timed(pillow_one, 2)
+    say("cpu  Pillow GIF, 1 frame                 %9.2f ms/frame  %8.1f Mpx/s  %d bytes" % (tp * 1e3, W * H / tp / 1e6, len(pgif)))
+    F = args.cpu_frames
+    ims = []
+    for i in range(F):
+        x = Image.fromarray(maps[i % len(maps)].astype(np.uint8), "P")
+        x.putpalette(im.getpalette())
+        ims.append(x)
+
+    def pillow_anim():
+        b = io.BytesIO()
+        ims[0].save(b, "GIF", save_all=True, append_images=ims[1:], duration=40, loop=0, optimize=False)
+        return b.getvalue()
+    ta, _ = timed(pillow_anim, 1)
+    say("cpu  Pillow GIF, %d-frame animation       %9.2f ms/frame  %8.1f Mpx/s" % (F, ta / F * 1e3, F * W * H / ta / 1e6))
+    with tempfile.TemporaryDirectory() as d:
+        tn, nbytes = timed(lambda: write_indexed_png(os.path.join(d, "x.png"), maps[0], pal), 2)
+    say("cpu  write_indexed_png, 1 frame          %9.2f ms/frame  %8.1f Mpx/s  %d bytes" % (tn * 1e3, W * H / tn / 1e6, nbytes))
+    say("speed-up vs Pillow: %.0fx (1 frame), %.0fx (batch of %d vs the Pillow animation); size vs Pillow: %.4fx" % (
+        tp / t1, (ta / F) / (tb / B), B, len(gif1) / len(pgif)))
+    # the GPU file decodes to the map
+    dec = Image.open(io.BytesIO(gif1))
+    dec.load()
+    assert (np.array(dec) == maps[0]).all()
+    say("check: Pillow decodes the GPU file to the index map exactly")
+    q.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
