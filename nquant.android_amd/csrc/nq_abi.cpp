@@ -158,7 +158,8 @@ struct nq_handle {
     Scratch own;
     Scratch* sc = &own;
     // device workspace
-    DevBuf<int> d_palette, d_in, d_out_argb, d_colors, d_tuple;
+    DevBuf<int> d_palette, d_colors, d_tuple;
+    DevBuf<uint32_t> d_in, d_out_argb;
     DevBuf<unsigned short> d_out_index;
     DevBuf<short> d_bincache, d_short;
     DevBuf<int> d_seqlog;             // REFERENCE_SEQUENTIAL + LAB + dither=false: colours getLab() saw during the pass (+ 1 counter)
@@ -170,9 +171,6 @@ struct nq_handle {
     int merge_wall_s = 0;             // NQ_OPT_MERGE_WALL_SECONDS: watchdog of a merge loop, seconds of residency (0 = automatic)
     hipStream_t palette_stream = nullptr;   // stream the upload behind dev_palette was enqueued on ...
     bool palette_synced = false;            // ... unless the host has waited for d_palette's content since (then any stream may read it)
-    // nq_gilbert_dither / nq_bluenoise_dither: the static entry points of the reference run the same stages with caller-supplied
-    // saliencies / weight instead of the ones dither() derives
-    struct StageOverride { bool gilbert_only = false, blue_only = false; const float* d_sal = nullptr; bool hasSal = false; double weight = 0; float blueWeight = 1.f; } ov;
     DevBuf<float> d_user_sal;
     int band_y0 = 0, band_image_h = 0; // nq_set_band: this handle dithers a row band of a larger image (0, 0 = a whole image)
     int use_fast_dither = 1;          // NQ_OPT_FAST_DITHER: the specialised dither kernel where the configuration allows it
@@ -252,7 +250,9 @@ static inline hipError_t launch_status() {
 
 namespace {
 
+// the first step of every entry point on a handle (a null handle is NQ_ERR_INVALID)
 int use_device(nq_handle* h) {
+    if (!h) return NQ_ERR_INVALID;
     NQ_HIP(h, hipSetDevice(h->device));
     if (!h->tables_ready) {
         double gamma[256];
@@ -640,18 +640,17 @@ int merge_launch(nq_handle* owner, const PaletteJob* const* jobs, int n) {
 
 // read-back of the palette the merge workgroup wrote (P10): the copies are enqueued by palette_fetch and looked at by palette_check
 // once the stream has been waited for (a batch waits ONCE for all its images, not once per image)
-int palette_fetch(nq_handle* h, const PaletteJob& job, uint32_t* out_palette, int* status) {
+int palette_fetch(nq_handle* h, const PaletteJob& job, uint32_t* out_palette) {
     rec(h, 5);
     NQ_HIP(h, hipMemcpyAsync(out_palette, h->d_palette.p, job.plen * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     h->fetched_palette = out_palette; h->fetched_len = job.plen;
     NQ_HIP(h, hipMemcpyAsync(h->merge_readback, h->d_scalars.p + 4, sizeof h->merge_readback, hipMemcpyDeviceToHost, h->stream));
-    (void) status;
     return NQ_OK;
 }
-int palette_check(nq_handle* h, const PaletteJob& job, int status, int32_t* out_K) {
+int palette_check(nq_handle* h, const PaletteJob& job, int32_t* out_K) {
     std::memcpy(h->merge_stats, h->merge_readback, sizeof h->merge_stats);
     std::memcpy(h->team_stats, h->merge_readback + 20, sizeof h->team_stats);
-    status = (int) (h->merge_readback[36] & 0xFFFFFFFFLL);
+    const int status = (int) (h->merge_readback[36] & 0xFFFFFFFFLL);
     if (h->fetched_palette) { h->dev_palette.assign(h->fetched_palette, h->fetched_palette + h->fetched_len); h->palette_synced = true; }   // (read back and waited for)
     h->fetched_palette = nullptr;
     if (h->merge_stats[14] == 2)
@@ -664,24 +663,58 @@ int palette_check(nq_handle* h, const PaletteJob& job, int status, int32_t* out_
     return NQ_OK;
 }
 int palette_finish(nq_handle* h, const PaletteJob& job, uint32_t* out_palette, int32_t* out_K) {
-    int status = 0;
-    int rc = palette_fetch(h, job, out_palette, &status);
+    int rc = palette_fetch(h, job, out_palette);
     if (rc) return rc;
     NQ_HIP(h, hipStreamSynchronize(h->stream));
     NQ_HIP(h, launch_status());
-    return palette_check(h, job, status, out_K);
+    return palette_check(h, job, out_K);
 }
 
-int palette_from_hist(nq_handle* h, const double* d_hists, int n_bands, int nMaxColors, uint32_t* out_palette, int32_t* out_K,
-                      const uint32_t* d_argb = nullptr, int64_t n_pixels = 0) {
+// the palette of one image: prepare(&job) fills the job, then the merge loop and the read-back
+template <typename Prepare> int palette_of(nq_handle* h, uint32_t* out_palette, int32_t* out_K, Prepare prepare) {
     PaletteJob job;
-    int rc = palette_prepare(h, d_hists, n_bands, nMaxColors, out_palette, out_K, d_argb, n_pixels, &job);
+    int rc = prepare(&job);
     if (rc || !job.merge) return rc;
     const PaletteJob* jp = &job;
     rc = merge_launch(h, &jp, 1);
     if (rc) return rc;
     rec(h, 4);
     return palette_finish(h, job, out_palette, out_K);
+}
+
+// the histogram's parameters (after apply_scan) and its sort workspace on the handle's scratch (after reserve_palette_ws)
+void hist_setup(const nq_handle* h, nq::HistParams* hp, nq::SortWorkspace* ws) {
+    const nq_params& p = h->params;
+    hp->hasSemi = p.hasSemiTransparency; hp->hasTransp = p.nMaxColors < 64 || p.transparentPixelIndex >= 0;
+    hp->transparentColor = p.transparentColor; hp->rewriteTransparent = 0;
+    ws->keys_a = h->sc->keys_a.p; ws->keys_b = h->sc->keys_b.p; ws->vals_a = h->sc->vals_a.p; ws->vals_b = h->sc->vals_b.p;
+    ws->tmp = h->sc->sort_tmp.p; ws->tmp_bytes = h->sc->sort_tmp.n; ws->seg_start = h->sc->seg.p; ws->seg_end = h->sc->seg.p + 65536;
+}
+
+// pnnquan of n pixels once the pre-scan's scalars are back (one image, or the frame table: d_argb == nullptr): apply_scan, the
+// <= 2-colour palette, then the histogram over the keys that keys(hp, ws) lays out in the workspace, and palette_prepare
+template <typename Keys>
+int palette_after_scan(nq_handle* h, const long long* scan3, const uint32_t* d_argb, int64_t n, int nMaxColors, uint32_t* out_palette,
+                       int32_t* out_K, PaletteJob* job, Keys keys) {
+    apply_scan(h, nMaxColors, scan3[0], (uint32_t) scan3[1], scan3[2]);
+    rec(h, 1);
+    nq_params& p = h->params;
+    if (nMaxColors <= 2) {
+        // NQ/PnnQuantizer.java:441-452
+        p.weight = 1;
+        if (p.transparentPixelIndex >= 0) { out_palette[0] = (uint32_t) p.transparentColor; out_palette[1] = 0xFF000000u; }
+        else { out_palette[0] = 0xFF000000u; out_palette[1] = 0xFFFFFFFFu; }
+        p.paletteLength = nMaxColors; *out_K = nMaxColors;
+        rec(h, 2); rec(h, 3); rec(h, 4); rec(h, 5);
+        return NQ_OK;
+    }
+    int rc = reserve_palette_ws(h, n);
+    if (rc) return rc;
+    nq::HistParams hp;
+    nq::SortWorkspace ws;
+    hist_setup(h, &hp, &ws);
+    keys(hp, ws);
+    return palette_prepare(h, h->sc->hist.p, 1, nMaxColors, out_palette, out_K, d_argb, n, job);
 }
 
 // alpha pre-scan + histogram + palette_prepare
@@ -705,45 +738,22 @@ int pnnquan_prepare(nq_handle* h, const uint32_t* d_argb, int width, int height,
     long long scan3[3];
     NQ_HIP(h, hipMemcpyAsync(scan3, d_scan3, sizeof scan3, hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
-    apply_scan(h, nMaxColors, scan3[0], (uint32_t) scan3[1], scan3[2]);
-    rec(h, 1);
-    nq_params& p = h->params;
-    if (nMaxColors <= 2) {
-        // NQ/PnnQuantizer.java:441-452
-        p.weight = 1;
-        if (p.transparentPixelIndex >= 0) { out_palette[0] = (uint32_t) p.transparentColor; out_palette[1] = 0xFF000000u; }
-        else { out_palette[0] = 0xFF000000u; out_palette[1] = 0xFFFFFFFFu; }
-        p.paletteLength = nMaxColors; *out_K = nMaxColors;
-        rec(h, 2); rec(h, 3); rec(h, 4); rec(h, 5);
-        return NQ_OK;
-    }
-    int rc = reserve_palette_ws(h, n);
-    if (rc) return rc;
-    nq::HistParams hp;
-    hp.hasSemi = p.hasSemiTransparency; hp.hasTransp = nMaxColors < 64 || p.transparentPixelIndex >= 0;
-    hp.transparentColor = p.transparentColor; hp.rewriteTransparent = 0;
-    nq::SortWorkspace ws;
-    ws.keys_a = h->sc->keys_a.p; ws.keys_b = h->sc->keys_b.p; ws.vals_a = h->sc->vals_a.p; ws.vals_b = h->sc->vals_b.p;
-    ws.tmp = h->sc->sort_tmp.p; ws.tmp_bytes = h->sc->sort_tmp.n; ws.seg_start = h->sc->seg.p; ws.seg_end = h->sc->seg.p + 65536;
-    // (the speculative words hold 5-6-5 keys and the default transparent colour: right exactly for an image without transparency)
-    const bool words_ready = words && !hp.hasSemi && !hp.hasTransp;
-    launch_histogram(h->kind, (const int*) d_argb, n, hp, ws, h->sc->hist.p, h->stream, words_ready);
-    return palette_prepare(h, h->sc->hist.p, 1, nMaxColors, out_palette, out_K, d_argb, n, job);
+    return palette_after_scan(h, scan3, d_argb, n, nMaxColors, out_palette, out_K, job, [&](const nq::HistParams& hp, const nq::SortWorkspace& ws) {
+        // (the speculative words hold 5-6-5 keys and the default transparent colour: right exactly for an image without transparency)
+        const bool words_ready = words && !hp.hasSemi && !hp.hasTransp;
+        launch_histogram(h->kind, (const int*) d_argb, n, hp, ws, h->sc->hist.p, h->stream, words_ready);
+    });
 }
 
 int pnnquan_device(nq_handle* h, const uint32_t* d_argb, int width, int height, int nMaxColors, uint32_t* out_palette, int32_t* out_K) {
-    PaletteJob job;
-    int rc = pnnquan_prepare(h, d_argb, width, height, nMaxColors, out_palette, out_K, &job);
-    if (rc || !job.merge) return rc;
-    const PaletteJob* jp = &job;
-    rc = merge_launch(h, &jp, 1);
-    if (rc) return rc;
-    rec(h, 4);
-    return palette_finish(h, job, out_palette, out_K);
+    return palette_of(h, out_palette, out_K, [&](PaletteJob* job) {
+        return pnnquan_prepare(h, d_argb, width, height, nMaxColors, out_palette, out_K, job);
+    });
 }
 
 // ---- one palette for a sequence of frames (nq_pnnquan_frames_device / nq_convert_frames_device) ----
 // Arguments of a frames call, checked from the host arrays alone (no device memory is touched): *out_total = pixels of the sequence
+// (when wanted)
 int frames_check(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights, int nMaxColors,
                  bool for_dither, int64_t* out_total) {
     if (n <= 0 || !d_argb || !widths || !heights) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument (n = %d)", n);
@@ -756,7 +766,7 @@ int frames_check(nq_handle* h, int n, const uint32_t* const* d_argb, const int32
         total += (int64_t) widths[i] * heights[i];
         if (total > 2147483647LL) NQ_FAIL(h, NQ_ERR_INVALID, "the sequence holds more pixels than a Java int[] (frame %d)", i);
     }
-    *out_total = total;
+    if (out_total) *out_total = total;
     return NQ_OK;
 }
 
@@ -806,49 +816,27 @@ int pnnquan_frames_prepare(nq_handle* h, int nMaxColors, uint32_t* out_palette, 
     NQ_HIP(h, hipMemcpyAsync(scan3, d_scan3, sizeof scan3, hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
     NQ_HIP(h, launch_status());
-    apply_scan(h, nMaxColors, scan3[0], (uint32_t) scan3[1], scan3[2]);
-    rec(h, 1);
-    nq_params& p = h->params;
-    if (nMaxColors <= 2) {
-        // NQ/PnnQuantizer.java:441-452
-        p.weight = 1;
-        if (p.transparentPixelIndex >= 0) { out_palette[0] = (uint32_t) p.transparentColor; out_palette[1] = 0xFF000000u; }
-        else { out_palette[0] = 0xFF000000u; out_palette[1] = 0xFFFFFFFFu; }
-        p.paletteLength = nMaxColors; *out_K = nMaxColors;
-        rec(h, 2); rec(h, 3); rec(h, 4); rec(h, 5);
-        return NQ_OK;
-    }
-    int rc = reserve_palette_ws(h, n);
-    if (rc) return rc;
-    nq::HistParams hp;
-    hp.hasSemi = p.hasSemiTransparency; hp.hasTransp = nMaxColors < 64 || p.transparentPixelIndex >= 0;
-    hp.transparentColor = p.transparentColor; hp.rewriteTransparent = 0;
-    nq::SortWorkspace ws;
-    ws.keys_a = h->sc->keys_a.p; ws.keys_b = h->sc->keys_b.p; ws.vals_a = h->sc->vals_a.p; ws.vals_b = h->sc->vals_b.p;
-    ws.tmp = h->sc->sort_tmp.p; ws.tmp_bytes = h->sc->sort_tmp.n; ws.seg_start = h->sc->seg.p; ws.seg_end = h->sc->seg.p + 65536;
-    if (!(words && !hp.hasSemi && !hp.hasTransp))
-        launch_frames_pass(FRAMES_KEYS, h->d_frames.p, nf, h->d_items.p, ni, nullptr, reinterpret_cast<unsigned*>(h->sc->vals_a.p), nullptr,
-                           hp.transparentColor, hp.hasSemi ? 2 : hp.hasTransp ? 1 : 0, h->stream);
-    launch_histogram(h->kind, nullptr, n, hp, ws, h->sc->hist.p, h->stream, true);
-    return palette_prepare(h, h->sc->hist.p, 1, nMaxColors, out_palette, out_K, nullptr, n, job);
+    return palette_after_scan(h, scan3, nullptr, n, nMaxColors, out_palette, out_K, job, [&](const nq::HistParams& hp, const nq::SortWorkspace& ws) {
+        if (!(words && !hp.hasSemi && !hp.hasTransp))
+            launch_frames_pass(FRAMES_KEYS, h->d_frames.p, nf, h->d_items.p, ni, nullptr, reinterpret_cast<unsigned*>(h->sc->vals_a.p), nullptr,
+                               hp.transparentColor, hp.hasSemi ? 2 : hp.hasTransp ? 1 : 0, h->stream);
+        launch_histogram(h->kind, nullptr, n, hp, ws, h->sc->hist.p, h->stream, true);
+    });
 }
 
-int pnnquan_frames(nq_handle* h, int nMaxColors, uint32_t* out_palette, int32_t* out_K) {
-    PaletteJob job;
-    int rc = pnnquan_frames_prepare(h, nMaxColors, out_palette, out_K, &job);
-    if (rc || !job.merge) return rc;
-    const PaletteJob* jp = &job;
-    rc = merge_launch(h, &jp, 1);
-    if (rc) return rc;
-    rec(h, 4);
-    return palette_finish(h, job, out_palette, out_K);
+// the dither modes of include/nquant_abi.h (the static GilbertCurve / BlueNoise entry points have no LOOKUP_ONLY form)
+int check_mode(nq_handle* h, int mode, bool lookup_only_ok = true) {
+    if (mode != NQ_MODE_PARALLEL_TILED && mode != NQ_MODE_REFERENCE_SEQUENTIAL && !(lookup_only_ok && mode == NQ_MODE_LOOKUP_ONLY))
+        NQ_FAIL(h, NQ_ERR_INVALID, "unknown mode %d", mode);
+    return NQ_OK;
 }
 
-int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, const uint32_t* palette, int K, int dither,
-                  int64_t seed, int mode, uint32_t* d_out_argb, uint16_t* d_out_index);
+// nq_gilbert_dither / nq_bluenoise_dither: the static entry points of the reference run the same stages with caller-supplied
+// saliencies / weight instead of the ones dither() derives
+struct StageOverride { bool gilbert_only = false, blue_only = false; const float* d_sal = nullptr; bool hasSal = false; double weight = 0; float blueWeight = 1.f; };
 
 int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, const uint32_t* palette, int K, int dither,
-                  int64_t seed, int mode, uint32_t* d_out_argb, uint16_t* d_out_index) {
+                  int64_t seed, int mode, uint32_t* d_out_argb, uint16_t* d_out_index, const StageOverride& ov = StageOverride()) {
     if (!d_argb || width <= 0 || height <= 0 || !palette || K < 1 || !d_out_argb) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
     if (width > 65535 || height > 65535) NQ_FAIL(h, NQ_ERR_INVALID, "image side > 65535");
     if (K > 8192) NQ_FAIL(h, NQ_ERR_UNSUPPORTED, "palettes above 8192 entries do not fit the LDS staging");
@@ -878,14 +866,13 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
         h->dither_events_fresh = true;
         return NQ_OK;
     }
-    if (mode != NQ_MODE_PARALLEL_TILED && mode != NQ_MODE_REFERENCE_SEQUENTIAL) NQ_FAIL(h, NQ_ERR_INVALID, "unknown mode %d", mode);
+    { int rcm = check_mode(h, mode); if (rcm) return rcm; }
     const bool sequential = mode == NQ_MODE_REFERENCE_SEQUENTIAL;
 
     // dither(): RGB NQ/PnnQuantizer.java:393-407, LAB NQ/PnnLABQuantizer.java:493-522
     // The reference negates the field once per convert() (dither() runs once per object); here dither may be called repeatedly on
     // one handle, so the negation holds for this call only and the handle keeps the value pnnquan left.
     struct WeightGuard { double& w; double saved; ~WeightGuard() { w = saved; } } weight_guard{p.weight, p.weight};
-    const nq_handle::StageOverride ov = h->ov;       // (the static entry points GilbertCurve.dither / BlueNoise.dither: nq_gilbert_dither ...)
     const bool staged = ov.gilbert_only || ov.blue_only;
     if (p.hasSemiTransparency && !staged) p.weight = -std::fabs(p.weight);
     bool hasSal = false, salSubst = false;
@@ -1047,6 +1034,137 @@ void finish_batch_timing(nq_handle* h0) {
     h0->batch_phase_ms[3] = tot;
 }
 
+// ---- host forms: the caller's n arrays (px[i] elements each; one image: n = 1) lie end to end in a handle buffer, array i at dev[i] ----
+template <typename T> int stage_room(nq_handle* h, DevBuf<T>& buf, int n, const size_t* px, T** dev) {
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) total += px[i];
+    NQ_HIP(h, buf.reserve(total));
+    for (int i = 0; i < n; ++i) dev[i] = i ? dev[i - 1] + px[i - 1] : buf.p;
+    return NQ_OK;
+}
+// ... uploaded from the caller's arrays
+template <typename T, typename S> int stage_in(nq_handle* h, DevBuf<T>& buf, int n, const size_t* px, const S* const* src, T** dev) {
+    static_assert(sizeof(T) == sizeof(S), "staged element size");
+    int rc = stage_room(h, buf, n, px, dev);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dev[i], src[i], px[i] * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return NQ_OK;
+}
+// ... and read back to them in the same layout (dst[i] == null: not wanted)
+template <typename T, typename S> int stage_out(nq_handle* h, const DevBuf<T>& buf, int n, const size_t* px, S* const* dst) {
+    static_assert(sizeof(T) == sizeof(S), "staged element size");
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        if (dst[i]) NQ_HIP(h, hipMemcpyAsync(dst[i], buf.p + off, px[i] * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+        off += px[i];
+    }
+    return NQ_OK;
+}
+
+// A host form runs its staging and device work in body(); on failure the stream is waited for too, so no copy from or to the
+// caller's buffers outlives the call (on success the body's own read-back wait, or the device form's, has done that)
+template <typename Body> int host_form(nq_handle* h, Body body) {
+    const int rc = body();
+    if (rc) (void) hipStreamSynchronize(h->stream);
+    return rc;
+}
+
+// The host form of an image entry point over n caller images: pixels in d_in; when results are wanted (out_argb or out_index given),
+// room for them in d_out_argb / d_out_index (reserved first: growing a buffer frees the old one, which waits for the device);
+// step(d_in, d_out_argb, d_out_index) on the device copies; then the wanted results read back and waited for
+template <typename Step>
+int host_images(nq_handle* h, int n, const size_t* px, const uint32_t* const* argb, uint32_t* const* out_argb, uint16_t* const* out_index,
+                Step step) {
+    return host_form(h, [&]() -> int {
+        std::vector<uint32_t*> d_in(n), d_out(n);
+        std::vector<uint16_t*> d_index(n);
+        const bool results = out_argb || out_index;
+        int rc = results ? stage_room(h, h->d_out_argb, n, px, d_out.data()) : NQ_OK;
+        if (!rc && results) rc = stage_room(h, h->d_out_index, n, px, d_index.data());
+        if (!rc) rc = stage_in(h, h->d_in, n, px, argb, d_in.data());
+        if (!rc) rc = step(d_in.data(), d_out.data(), d_index.data());
+        if (!rc && out_argb) rc = stage_out(h, h->d_out_argb, n, px, out_argb);
+        if (!rc && out_index) rc = stage_out(h, h->d_out_index, n, px, out_index);
+        if (rc || !results) return rc;
+        NQ_HIP(h, hipStreamSynchronize(h->stream));
+        return NQ_OK;
+    });
+}
+
+// ---- setup shared by the batch entry points ----
+// the batch's arguments, from the host arrays alone (hs[0] is not null); `host`: every image's pointers and size as well
+int batch_check(nq_handle* const* hs, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights, int nMaxColors,
+                const int64_t* rng_seeds, uint32_t* const* out_argb, const uint32_t* out_palettes, int32_t palette_stride, const int32_t* out_K,
+                bool host) {
+    nq_handle* h0 = hs[0];
+    if (!argb || !widths || !heights || !rng_seeds || !out_argb || !out_palettes || !out_K) NQ_FAIL(h0, NQ_ERR_INVALID, "bad argument");
+    if (palette_stride < std::max(nMaxColors, 2)) NQ_FAIL(h0, NQ_ERR_INVALID, "palette_stride < max(nMaxColors, 2)");
+    for (int i = 0; i < n; ++i) {
+        if (host && (!hs[i] || !argb[i] || !out_argb[i] || widths[i] <= 0 || heights[i] <= 0)) NQ_FAIL(h0, NQ_ERR_INVALID, "bad argument for image %d", i);
+        if (!hs[i]) NQ_FAIL(h0, NQ_ERR_INVALID, "null handle in batch");
+        if (hs[i]->device != h0->device) NQ_FAIL(h0, NQ_ERR_INVALID, "handles of a batch must share one device");
+        for (int j = 0; j < i; ++j) if (hs[j] == hs[i]) NQ_FAIL(h0, NQ_ERR_INVALID, "a handle appears twice in the batch");
+    }
+    return NQ_OK;
+}
+
+// a failure on handle h of the batch, reported on the first handle
+int batch_fail(nq_handle* h0, nq_handle* h, int rc) { if (h != h0) h0->err = h->err; return rc; }
+
+// use_device on every handle: tables and events on the handle's own stream, before the batch redirects it
+int batch_use_device(nq_handle* const* hs, int n) {
+    for (int i = 0; i < n; ++i) {
+        int rc = use_device(hs[i]);
+        if (rc) return batch_fail(hs[0], hs[i], rc);
+        if (i) NQ_HIP(hs[0], hipStreamSynchronize(hs[i]->stream));
+    }
+    return NQ_OK;
+}
+
+// what a batch call redirects -- every handle's stream, scratch and light_events -- put back on every way out, and the events handed
+// to it destroyed
+struct BatchGuard {
+    nq_handle* const* hs; int n;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
+    BatchGuard(nq_handle* const* hh, int nn) : hs(hh), n(nn) { for (int i = 0; i < n; ++i) streams.push_back(hs[i]->stream); }
+    ~BatchGuard() {
+        for (int i = 0; i < n; ++i) { hs[i]->stream = streams[i]; hs[i]->sc = &hs[i]->own; hs[i]->light_events = false; }
+        for (hipEvent_t e : events) (void) hipEventDestroy(e);
+    }
+};
+
+// nq_nearest_index (out_index: nearestColorIndex) or nq_closest_tuple (out_closest4: closestColorIndex's four candidates) of M host colours
+int color_lookup(nq_handle* h, const uint32_t* palette, int K, const uint32_t* colors, int64_t M, int16_t* out_index, int32_t* out_closest4) {
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (!palette || K < 1 || K > 8192 || !colors || M < 0 || !(out_index || out_closest4)) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
+    if (M == 0) return NQ_OK;
+    const size_t m = (size_t) M, m4 = 4 * m;
+    return host_form(h, [&]() -> int {
+        int* d_colors = nullptr;
+        int16_t* d_index = nullptr;
+        int32_t* d_tuple = nullptr;
+        rc = upload_palette(h, palette, K);
+        if (!rc) rc = out_index ? stage_room(h, h->d_short, 1, &m, &d_index) : stage_room(h, h->d_tuple, 1, &m4, &d_tuple);
+        if (!rc) rc = stage_in(h, h->d_colors, 1, &m, &colors, &d_colors);
+        DevParams P = dev_params(h, K);
+        nq::ListsView lv;
+        if (!rc) rc = prepare_lists(h, P, &lv);
+        if (rc) return rc;
+        const bool fast = h->use_fast_dither && fast_lookup_eligible(P, lv);
+        if (d_index && fast) launch_fast_nearest_index(P, lv, h->d_palette.p, packed_lists(h), d_colors, M, d_index, h->stream);
+        else if (d_index) launch_nearest_index(P, h->d_palette.p, lv, d_colors, M, d_index, h->stream);
+        else if (fast) launch_fast_closest_tuple(P, lv, h->d_palette.p, packed_lists(h), d_colors, M, d_tuple, h->stream);
+        else launch_closest_tuple(P, h->d_palette.p, lv, d_colors, M, d_tuple, h->stream);
+        NQ_HIP(h, launch_status());
+        rc = out_index ? stage_out(h, h->d_short, 1, &m, &out_index) : stage_out(h, h->d_tuple, 1, &m4, &out_closest4);
+        if (rc) return rc;
+        NQ_HIP(h, hipStreamSynchronize(h->stream));
+        return NQ_OK;
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -1118,7 +1236,6 @@ int nq_set_option(nq_handle* h, int option, int value) {
     NQ_FAIL(h, NQ_ERR_INVALID, "unknown option %d", option);
 }
 int nq_selftest_ciede(nq_handle* h, const float* lab_pairs, int64_t n, uint32_t* out9) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!lab_pairs || n <= 0 || !out9) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
@@ -1186,26 +1303,23 @@ int nq_get_stage_ms(const nq_handle* h, float* out8) {
 
 int nq_pnnquan_device(nq_handle* h, const uint32_t* d_argb, int width, int height, int nMaxColors,
                       uint32_t* out_palette, int32_t* out_K) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     return pnnquan_device(h, d_argb, width, height, nMaxColors, out_palette, out_K);
 }
 
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors, uint32_t* out_palette, int32_t* out_K) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!argb || width <= 0 || height <= 0) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
-    const size_t n = (size_t) width * height;
-    NQ_HIP(h, h->d_in.reserve(n));
-    NQ_HIP(h, hipMemcpyAsync(h->d_in.p, argb, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    return pnnquan_device(h, (const uint32_t*) h->d_in.p, width, height, nMaxColors, out_palette, out_K);
+    const size_t px = (size_t) width * height;
+    return host_images(h, 1, &px, &argb, nullptr, nullptr, [&](auto in, auto, auto) {
+        return pnnquan_device(h, in[0], width, height, nMaxColors, out_palette, out_K);
+    });
 }
 
 int nq_dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, const uint32_t* palette, int K,
                      int dither, int64_t rng_seed, int mode, uint32_t* d_out_argb, uint16_t* d_out_index) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     return dither_device(h, d_argb, width, height, palette, K, dither, rng_seed, mode, d_out_argb, d_out_index);
@@ -1213,49 +1327,40 @@ int nq_dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height
 
 int nq_dither(nq_handle* h, const uint32_t* argb, int width, int height, const uint32_t* palette, int K,
               int dither, int64_t rng_seed, int mode, uint32_t* out_argb, uint16_t* out_index) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!argb || !out_argb || width <= 0 || height <= 0) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
-    const size_t n = (size_t) width * height;
-    NQ_HIP(h, h->d_in.reserve(n)); NQ_HIP(h, h->d_out_argb.reserve(n)); NQ_HIP(h, h->d_out_index.reserve(n));
-    NQ_HIP(h, hipMemcpyAsync(h->d_in.p, argb, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    rc = dither_device(h, (const uint32_t*) h->d_in.p, width, height, palette, K, dither, rng_seed, mode,
-                       (uint32_t*) h->d_out_argb.p, h->d_out_index.p);
-    if (rc) return rc;
-    NQ_HIP(h, hipMemcpyAsync(out_argb, h->d_out_argb.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (out_index) NQ_HIP(h, hipMemcpyAsync(out_index, h->d_out_index.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
-    NQ_HIP(h, hipStreamSynchronize(h->stream));
-    return NQ_OK;
+    const size_t px = (size_t) width * height;
+    return host_images(h, 1, &px, &argb, &out_argb, &out_index, [&](auto in, auto out, auto index) {
+        return dither_device(h, in[0], width, height, palette, K, dither, rng_seed, mode, out[0], index[0]);
+    });
 }
 
 // GilbertCurve.dither(width, height, pixels, palette, ditherable, saliencies, weight, dither) (NQ/GilbertCurve.java:367-373)
 int nq_gilbert_dither(nq_handle* h, int width, int height, const uint32_t* pixels, const uint32_t* palette, int K, const float* saliencies,
                       double weight, int dither, int64_t rng_seed, int mode, int32_t* out_qpixels, uint16_t* out_index) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!pixels || !out_qpixels || width <= 0 || height <= 0) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
-    if (mode != NQ_MODE_PARALLEL_TILED && mode != NQ_MODE_REFERENCE_SEQUENTIAL) NQ_FAIL(h, NQ_ERR_INVALID, "unknown mode %d", mode);
-    const size_t n = (size_t) width * height;
-    NQ_HIP(h, h->d_in.reserve(n)); NQ_HIP(h, h->d_out_argb.reserve(n)); NQ_HIP(h, h->d_out_index.reserve(n));
-    NQ_HIP(h, hipMemcpyAsync(h->d_in.p, pixels, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    if (saliencies) {
-        NQ_HIP(h, h->d_user_sal.reserve(n));
-        NQ_HIP(h, hipMemcpyAsync(h->d_user_sal.p, saliencies, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    }
-    h->ov = nq_handle::StageOverride();
-    h->ov.gilbert_only = true; h->ov.hasSal = saliencies != nullptr; h->ov.d_sal = h->d_user_sal.p; h->ov.weight = weight;
-    rc = dither_device(h, (const uint32_t*) h->d_in.p, width, height, palette, K, dither, rng_seed, mode, (uint32_t*) h->d_out_argb.p, h->d_out_index.p);
-    h->ov = nq_handle::StageOverride();
+    rc = check_mode(h, mode, false);
     if (rc) return rc;
-    std::vector<uint16_t> idx(n);
-    NQ_HIP(h, hipMemcpyAsync(idx.data(), h->d_out_index.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
-    const bool argb_out = dither || K <= 32;          // :278-279: qPixels holds ARGB only then, palette indices otherwise
-    if (argb_out) NQ_HIP(h, hipMemcpyAsync(out_qpixels, h->d_out_argb.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    NQ_HIP(h, hipStreamSynchronize(h->stream));
-    if (!argb_out) for (size_t i = 0; i < n; ++i) out_qpixels[i] = idx[i];
-    if (out_index) std::memcpy(out_index, idx.data(), n * sizeof(uint16_t));
+    const size_t px = (size_t) width * height;
+    std::vector<uint16_t> idx(px);
+    uint16_t* const idx_out = idx.data();
+    // :278-279: qPixels holds ARGB only when dithering or K <= 32, palette indices otherwise
+    uint32_t* const argb_out = dither || K <= 32 ? (uint32_t*) out_qpixels : nullptr;
+    rc = host_images(h, 1, &px, &pixels, &argb_out, &idx_out, [&](auto in, auto out, auto index) {
+        StageOverride ov;
+        ov.gilbert_only = true; ov.hasSal = saliencies != nullptr; ov.weight = weight;
+        float* d_sal = nullptr;
+        const int rcs = saliencies ? stage_in(h, h->d_user_sal, 1, &px, &saliencies, &d_sal) : NQ_OK;
+        if (rcs) return rcs;
+        ov.d_sal = d_sal;
+        return dither_device(h, in[0], width, height, palette, K, dither, rng_seed, mode, out[0], index[0], ov);
+    });
+    if (rc) return rc;
+    if (!argb_out) for (size_t i = 0; i < px; ++i) out_qpixels[i] = idx[i];
+    if (out_index) std::memcpy(out_index, idx.data(), px * sizeof(uint16_t));
     return NQ_OK;
 }
 
@@ -1263,36 +1368,32 @@ int nq_gilbert_dither(nq_handle* h, int width, int height, const uint32_t* pixel
 // indices on entry and ARGB on return
 int nq_bluenoise_dither(nq_handle* h, int width, int height, const uint32_t* pixels, const uint32_t* palette, int K, int32_t* io_qpixels,
                         float weight, int64_t rng_seed, int mode, uint16_t* out_index) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!pixels || !io_qpixels || width <= 0 || height <= 0 || !palette || K < 1) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
-    if (mode != NQ_MODE_PARALLEL_TILED && mode != NQ_MODE_REFERENCE_SEQUENTIAL) NQ_FAIL(h, NQ_ERR_INVALID, "unknown mode %d", mode);
-    const size_t n = (size_t) width * height;
-    std::vector<uint16_t> idx(n);
-    for (size_t i = 0; i < n; ++i) {
+    rc = check_mode(h, mode, false);
+    if (rc) return rc;
+    const size_t px = (size_t) width * height;
+    std::vector<uint16_t> idx(px);
+    for (size_t i = 0; i < px; ++i) {
         if (io_qpixels[i] < 0 || io_qpixels[i] >= K) NQ_FAIL(h, NQ_ERR_INVALID, "qPixels[%zu] = %d is not a palette index", i, io_qpixels[i]);
         idx[i] = (uint16_t) io_qpixels[i];
     }
-    NQ_HIP(h, h->d_in.reserve(n)); NQ_HIP(h, h->d_out_argb.reserve(n)); NQ_HIP(h, h->d_out_index.reserve(n));
-    NQ_HIP(h, hipMemcpyAsync(h->d_in.p, pixels, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    NQ_HIP(h, hipMemcpyAsync(h->d_out_index.p, idx.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
-    NQ_HIP(h, hipStreamSynchronize(h->stream));        // idx goes out of scope
-    h->ov = nq_handle::StageOverride();
-    h->ov.blue_only = true; h->ov.blueWeight = weight; h->ov.weight = h->params.weight;
-    rc = dither_device(h, (const uint32_t*) h->d_in.p, width, height, palette, K, 0, rng_seed, mode, (uint32_t*) h->d_out_argb.p, h->d_out_index.p);
-    h->ov = nq_handle::StageOverride();
-    if (rc) return rc;
-    NQ_HIP(h, hipMemcpyAsync(io_qpixels, h->d_out_argb.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (out_index) NQ_HIP(h, hipMemcpyAsync(out_index, h->d_out_index.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
-    NQ_HIP(h, hipStreamSynchronize(h->stream));
-    return NQ_OK;
+    const uint16_t* const idx_in = idx.data();
+    uint32_t* const argb_out = (uint32_t*) io_qpixels;
+    return host_images(h, 1, &px, &pixels, &argb_out, &out_index, [&](auto in, auto out, auto index) -> int {
+        const int rci = stage_in(h, h->d_out_index, 1, &px, &idx_in, index);
+        if (rci) return rci;
+        NQ_HIP(h, hipStreamSynchronize(h->stream));        // (the indices are in place before the pass)
+        StageOverride ov;
+        ov.blue_only = true; ov.blueWeight = weight; ov.weight = h->params.weight;
+        return dither_device(h, in[0], width, height, palette, K, 0, rng_seed, mode, out[0], index[0], ov);
+    });
 }
 
 int nq_convert_device(nq_handle* h, const uint32_t* d_argb, int width, int height, int nMaxColors, int dither,
                       int64_t rng_seed, int mode, uint32_t* d_out_argb, uint16_t* d_out_index,
                       uint32_t* out_palette, int32_t* out_K) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     rc = pnnquan_device(h, d_argb, width, height, nMaxColors, out_palette, out_K);
@@ -1308,8 +1409,7 @@ int nq_convert_device(nq_handle* h, const uint32_t* d_argb, int width, int heigh
 int nq_pnnquan_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
                              int nMaxColors, uint32_t* out_palette, int32_t* out_K) {
     if (!h) return NQ_ERR_INVALID;
-    int64_t total = 0;
-    int rc = frames_check(h, n, d_argb, widths, heights, nMaxColors, false, &total);
+    int rc = frames_check(h, n, d_argb, widths, heights, nMaxColors, false, nullptr);
     if (rc) return rc;
     if (!out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
     rc = use_device(h);
@@ -1317,7 +1417,7 @@ int nq_pnnquan_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb,
     FramesScope scope(h);
     rc = frames_upload(h, n, d_argb, widths, heights);
     if (rc) return rc;
-    return pnnquan_frames(h, nMaxColors, out_palette, out_K);
+    return palette_of(h, out_palette, out_K, [&](PaletteJob* job) { return pnnquan_frames_prepare(h, nMaxColors, out_palette, out_K, job); });
 }
 
 int nq_convert_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
@@ -1329,13 +1429,14 @@ int nq_convert_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb,
     if (rc) return rc;
     if (!rng_seeds || !d_out_argb || !out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
     for (int i = 0; i < n; ++i) if (!d_out_argb[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: null output pointer", i);
-    if (mode != NQ_MODE_REFERENCE_SEQUENTIAL && mode != NQ_MODE_PARALLEL_TILED && mode != NQ_MODE_LOOKUP_ONLY) NQ_FAIL(h, NQ_ERR_INVALID, "unknown mode %d", mode);
+    rc = check_mode(h, mode);
+    if (rc) return rc;
     rc = use_device(h);
     if (rc) return rc;
     FramesScope scope(h);
     rc = frames_upload(h, n, d_argb, widths, heights);
     if (rc) return rc;
-    rc = pnnquan_frames(h, nMaxColors, out_palette, out_K);
+    rc = palette_of(h, out_palette, out_K, [&](PaletteJob* job) { return pnnquan_frames_prepare(h, nMaxColors, out_palette, out_K, job); });
     if (rc) return rc;
     const int K = *out_K;
     nq_params& p = h->params;
@@ -1367,37 +1468,19 @@ int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const in
                       int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
                       uint32_t* const* out_argb, uint16_t* const* out_index, uint32_t* out_palette, int32_t* out_K) {
     if (!h) return NQ_ERR_INVALID;
-    int64_t total = 0;
-    int rc = frames_check(h, n, argb, widths, heights, nMaxColors, true, &total);
+    int rc = frames_check(h, n, argb, widths, heights, nMaxColors, true, nullptr);
     if (rc) return rc;
     if (!out_argb || !rng_seeds || !out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
     for (int i = 0; i < n; ++i) if (!out_argb[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: null output pointer", i);
-    if (mode != NQ_MODE_REFERENCE_SEQUENTIAL && mode != NQ_MODE_PARALLEL_TILED && mode != NQ_MODE_LOOKUP_ONLY) NQ_FAIL(h, NQ_ERR_INVALID, "unknown mode %d", mode);
+    rc = check_mode(h, mode);
+    if (rc) return rc;
     rc = use_device(h);
     if (rc) return rc;
-    NQ_HIP(h, h->d_in.reserve((size_t) total)); NQ_HIP(h, h->d_out_argb.reserve((size_t) total)); NQ_HIP(h, h->d_out_index.reserve((size_t) total));
-    std::vector<const uint32_t*> src(n);
-    std::vector<uint32_t*> dst(n);
-    std::vector<uint16_t*> idx(n);
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t px = (size_t) widths[i] * heights[i];
-        NQ_HIP(h, hipMemcpyAsync(h->d_in.p + off, argb[i], px * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        src[i] = (const uint32_t*) (h->d_in.p + off); dst[i] = (uint32_t*) (h->d_out_argb.p + off); idx[i] = h->d_out_index.p + off;
-        off += px;
-    }
-    rc = nq_convert_frames_device(h, n, src.data(), widths, heights, nMaxColors, dither, rng_seeds, mode, dst.data(), idx.data(), out_palette, out_K);
-    if (rc) return rc;
-    off = 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t px = (size_t) widths[i] * heights[i];
-        NQ_HIP(h, hipMemcpyAsync(out_argb[i], h->d_out_argb.p + off, px * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        if (out_index && out_index[i])
-            NQ_HIP(h, hipMemcpyAsync(out_index[i], h->d_out_index.p + off, px * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
-        off += px;
-    }
-    NQ_HIP(h, hipStreamSynchronize(h->stream));
-    return NQ_OK;
+    std::vector<size_t> px(n);
+    for (int i = 0; i < n; ++i) px[i] = (size_t) widths[i] * heights[i];
+    return host_images(h, n, px.data(), argb, out_argb, out_index, [&](auto in, auto out, auto index) {
+        return nq_convert_frames_device(h, n, in, widths, heights, nMaxColors, dither, rng_seeds, mode, out, index, out_palette, out_K);
+    });
 }
 
 int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
@@ -1406,30 +1489,16 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
                             uint32_t* out_palettes, int32_t palette_stride, int32_t* out_K) {
     if (!hs || n <= 0 || !hs[0]) return NQ_ERR_INVALID;
     nq_handle* h0 = hs[0];
-    if (!d_argb || !widths || !heights || !rng_seeds || !d_out_argb || !out_palettes || !out_K)
-        NQ_FAIL(h0, NQ_ERR_INVALID, "bad argument");
-    if (palette_stride < std::max(nMaxColors, 2)) NQ_FAIL(h0, NQ_ERR_INVALID, "palette_stride < max(nMaxColors, 2)");
-    for (int i = 0; i < n; ++i) {
-        if (!hs[i]) NQ_FAIL(h0, NQ_ERR_INVALID, "null handle in batch");
-        if (hs[i]->device != h0->device) NQ_FAIL(h0, NQ_ERR_INVALID, "handles of a batch must share one device");
-        for (int j = 0; j < i; ++j) if (hs[j] == hs[i]) NQ_FAIL(h0, NQ_ERR_INVALID, "a handle appears twice in the batch");
-    }
+    int rc = batch_check(hs, n, d_argb, widths, heights, nMaxColors, rng_seeds, d_out_argb, out_palettes, palette_stride, out_K, false);
+    if (rc) return rc;
     // The per-image stages in front of the merge loops run on FOUR lanes by default, eight at most (image i: stream and per-pixel scratch of
     // lane i % L; the scratch is that of the first L handles): while the host waits for a read-back of one image, and while a kernel with a
     // long tail or a small grid runs (the fullest bin's chain of the histogram, the list compactions), the queued kernels of the
     // other lanes keep the GPU busy (NQ_BATCH_LANES = 1..8 overrides).  The merge launch joins the lanes.
-    struct Restore {
-        nq_handle* const* hs; int n; std::vector<hipStream_t> streams;
-        ~Restore() { for (int i = 0; i < n; ++i) { hs[i]->stream = streams[i]; hs[i]->sc = &hs[i]->own; hs[i]->light_events = false; } }
-    } restore{hs, n, {}};
+    BatchGuard guard(hs, n);
     for (int i = 0; i < n; ++i) hs[i]->light_events = i >= 16;
-    for (int i = 0; i < n; ++i) restore.streams.push_back(hs[i]->stream);
-    auto fail_from = [&](nq_handle* h, int rc) { if (h != h0) h0->err = h->err; return rc; };
-    for (int i = 0; i < n; ++i) {
-        int rc = use_device(hs[i]);            // tables / events on the handle's own stream, before it is redirected
-        if (rc) return fail_from(hs[i], rc);
-        if (i) NQ_HIP(h0, hipStreamSynchronize(hs[i]->stream));
-    }
+    rc = batch_use_device(hs, n);
+    if (rc) return rc;
     if (n > 1 && !h0->lane_stream) NQ_HIP(h0, hipStreamCreateWithFlags(&h0->lane_stream, hipStreamNonBlocking));
     int L = std::min(n, 4);          // (measured on 1024 images of 4096^2, ONE issuing thread: prepare phase 640 / 557 / 552 / 543 us per image with 1 / 2 / 3 / 4 lanes)
     if (const char* f = std::getenv("NQ_BATCH_LANES")) { const int t = std::atoi(f); if (t >= 1 && t <= 8) L = std::min(t, n); }
@@ -1460,6 +1529,12 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
                     if (rc) { lane_rc[k] = rc; lane_bad[k] = i; return; }
                     jp[i] = &jobs[i];
                 }
+                // the launch errors of this lane's prepares are kept on this thread: only it can see them
+                const hipError_t e = launch_status();
+                if (e != hipSuccess) {
+                    lane_rc[k] = NQ_ERR_HIP; lane_bad[k] = at;
+                    hs[at]->err = std::string("launch_status() failed in a batch lane: ") + hipGetErrorString(e);
+                }
             } catch (const std::exception& e) {
                 lane_rc[k] = NQ_ERR_HIP; lane_bad[k] = at;
                 try { hs[at]->err = std::string("exception in a batch lane: ") + e.what(); } catch (...) {}
@@ -1474,11 +1549,11 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
         for (int k : inline_lanes) lane_work(k);
         for (auto& t : workers) t.join();
         for (int k = 0; k < L; ++k)
-            if (lane_rc[k]) return fail_from(hs[lane_bad[k] >= 0 && lane_bad[k] < n ? lane_bad[k] : 0], lane_rc[k]);
+            if (lane_rc[k]) return batch_fail(h0, hs[lane_bad[k] >= 0 && lane_bad[k] < n ? lane_bad[k] : 0], lane_rc[k]);
     }
     for (int k = 1; k < L; ++k) NQ_HIP(h0, hipStreamSynchronize(lane_s[k]));          // every prepare has been issued: join before the merge launch
     (void) hipEventRecord(h0->bev[1], lane_s[0]);
-    int rc = merge_launch(h0, jp.data(), n);
+    rc = merge_launch(h0, jp.data(), n);
     if (rc) return rc;
     (void) hipEventRecord(h0->bev[2], lane_s[0]);
     // behind the merge launch everything runs on lane 0 again: two dither kernels side by side would only slow each other down
@@ -1486,24 +1561,23 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
     for (int i = 0; i < n; ++i) if (jobs[i].merge) rec(hs[i], 4);
     // every palette of the batch comes back behind ONE wait; the per-image passes then follow each other on the stream with no
     // host round trip in between (a wait per image left the GPU idle for ~0.1 ms of every image's ~1 ms)
-    std::vector<int> pal_status(n, 0);
     for (int i = 0; i < n; ++i)
         if (jobs[i].merge) {
-            rc = palette_fetch(hs[i], jobs[i], out_palettes + (size_t) i * palette_stride, &pal_status[i]);
-            if (rc) return fail_from(hs[i], rc);
+            rc = palette_fetch(hs[i], jobs[i], out_palettes + (size_t) i * palette_stride);
+            if (rc) return batch_fail(h0, hs[i], rc);
         }
     NQ_HIP(h0, hipStreamSynchronize(lane_s[0]));
     NQ_HIP(h0, launch_status());
     for (int i = 0; i < n; ++i)
         if (jobs[i].merge) {
-            rc = palette_check(hs[i], jobs[i], pal_status[i], out_K + i);
-            if (rc) return fail_from(hs[i], rc);
+            rc = palette_check(hs[i], jobs[i], out_K + i);
+            if (rc) return batch_fail(h0, hs[i], rc);
         }
     for (int i = 0; i < n; ++i) {
         uint32_t* pal = out_palettes + (size_t) i * palette_stride;
         rc = dither_device(hs[i], d_argb[i], widths[i], heights[i], pal, out_K[i], dither, rng_seeds[i], mode, d_out_argb[i],
                            d_out_index ? d_out_index[i] : nullptr);
-        if (rc) return fail_from(hs[i], rc);
+        if (rc) return batch_fail(h0, hs[i], rc);
     }
     (void) hipEventRecord(h0->bev[3], lane_s[0]);
     NQ_HIP(h0, hipStreamSynchronize(lane_s[0]));
@@ -1521,29 +1595,14 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
                      uint32_t* out_palettes, int32_t palette_stride, int32_t* out_K) {
     if (!hs || n <= 0 || !hs[0]) return NQ_ERR_INVALID;
     nq_handle* h0 = hs[0];
-    if (!argb || !widths || !heights || !rng_seeds || !out_argb || !out_palettes || !out_K)
-        NQ_FAIL(h0, NQ_ERR_INVALID, "bad argument");
-    if (palette_stride < std::max(nMaxColors, 2)) NQ_FAIL(h0, NQ_ERR_INVALID, "palette_stride < max(nMaxColors, 2)");
+    int rc = batch_check(hs, n, argb, widths, heights, nMaxColors, rng_seeds, out_argb, out_palettes, palette_stride, out_K, true);
+    if (rc) return rc;
+    BatchGuard guard(hs, n);
+    rc = batch_use_device(hs, n);
+    if (rc) return rc;
     size_t max_px = 0;
     for (int i = 0; i < n; ++i) {
-        if (!hs[i] || !argb[i] || !out_argb[i] || widths[i] <= 0 || heights[i] <= 0) NQ_FAIL(h0, NQ_ERR_INVALID, "bad argument for image %d", i);
-        if (hs[i]->device != h0->device) NQ_FAIL(h0, NQ_ERR_INVALID, "handles of a batch must share one device");
-        for (int j = 0; j < i; ++j) if (hs[j] == hs[i]) NQ_FAIL(h0, NQ_ERR_INVALID, "a handle appears twice in the batch");
         max_px = std::max(max_px, (size_t) widths[i] * heights[i]);
-    }
-    struct Restore {
-        nq_handle* const* hs; int n; std::vector<hipStream_t> streams; std::vector<hipEvent_t> events;
-        ~Restore() {
-            for (int i = 0; i < n; ++i) { hs[i]->stream = streams[i]; hs[i]->sc = &hs[i]->own; }
-            for (hipEvent_t e : events) (void) hipEventDestroy(e);
-        }
-    } restore{hs, n, {}, {}};
-    for (int i = 0; i < n; ++i) restore.streams.push_back(hs[i]->stream);
-    auto fail_from = [&](nq_handle* h, int rc) { if (h != h0) h0->err = h->err; return rc; };
-    for (int i = 0; i < n; ++i) {
-        int rc = use_device(hs[i]);
-        if (rc) return fail_from(hs[i], rc);
-        if (i) NQ_HIP(h0, hipStreamSynchronize(hs[i]->stream));
         NQ_HIP(h0, hs[i]->d_in.reserve((size_t) widths[i] * heights[i]));
         hs[i]->stream = h0->stream; hs[i]->sc = &h0->own;
     }
@@ -1553,7 +1612,7 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
     hipStream_t cs = h0->copy_stream;
     auto new_event = [&](hipEvent_t* e) -> hipError_t {
         hipError_t rc = hipEventCreateWithFlags(e, hipEventDisableTiming);
-        if (rc == hipSuccess) restore.events.push_back(*e);
+        if (rc == hipSuccess) guard.events.push_back(*e);
         return rc;
     };
     std::vector<hipEvent_t> ev_up(n), ev_done(n), ev_dl(n);
@@ -1571,16 +1630,16 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
     std::vector<const PaletteJob*> jp(n);
     (void) hipEventRecord(h0->bev[0], h0->stream);
     for (int i = 0; i < n; ++i) {
-        int rc = upload_until(i + 2);
+        rc = upload_until(i + 2);
         if (rc) return rc;
         NQ_HIP(h0, hipStreamWaitEvent(h0->stream, ev_up[i], 0));
-        rc = pnnquan_prepare(hs[i], (const uint32_t*) hs[i]->d_in.p, widths[i], heights[i], nMaxColors,
+        rc = pnnquan_prepare(hs[i], hs[i]->d_in.p, widths[i], heights[i], nMaxColors,
                              out_palettes + (size_t) i * palette_stride, out_K + i, &jobs[i]);
-        if (rc) return fail_from(hs[i], rc);
+        if (rc) return batch_fail(h0, hs[i], rc);
         jp[i] = &jobs[i];
     }
     (void) hipEventRecord(h0->bev[1], h0->stream);
-    int rc = merge_launch(h0, jp.data(), n);
+    rc = merge_launch(h0, jp.data(), n);
     if (rc) return rc;
     (void) hipEventRecord(h0->bev[2], h0->stream);
     for (int i = 0; i < n; ++i) if (jobs[i].merge) rec(hs[i], 4);
@@ -1588,13 +1647,13 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
         uint32_t* pal = out_palettes + (size_t) i * palette_stride;
         if (jobs[i].merge) {
             rc = palette_finish(hs[i], jobs[i], pal, out_K + i);
-            if (rc) return fail_from(hs[i], rc);
+            if (rc) return batch_fail(h0, hs[i], rc);
         }
         const int r = i % RING;
         if (i >= RING) NQ_HIP(h0, hipStreamWaitEvent(h0->stream, ev_dl[i - RING], 0));     // the slot's previous result has left
-        rc = dither_device(hs[i], (const uint32_t*) hs[i]->d_in.p, widths[i], heights[i], pal, out_K[i], dither, rng_seeds[i], mode,
+        rc = dither_device(hs[i], hs[i]->d_in.p, widths[i], heights[i], pal, out_K[i], dither, rng_seeds[i], mode,
                            (uint32_t*) h0->ring_argb[r].p, h0->ring_index[r].p);
-        if (rc) return fail_from(hs[i], rc);
+        if (rc) return batch_fail(h0, hs[i], rc);
         NQ_HIP(h0, hipEventRecord(ev_done[i], h0->stream));
         NQ_HIP(h0, hipStreamWaitEvent(cs, ev_done[i], 0));
         const size_t px = (size_t) widths[i] * heights[i];
@@ -1613,70 +1672,24 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
 
 int nq_convert(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors, int dither,
                int64_t rng_seed, int mode, uint32_t* out_argb, uint16_t* out_index, uint32_t* out_palette, int32_t* out_K) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!argb || !out_argb || width <= 0 || height <= 0) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
-    const size_t n = (size_t) width * height;
-    NQ_HIP(h, h->d_in.reserve(n)); NQ_HIP(h, h->d_out_argb.reserve(n)); NQ_HIP(h, h->d_out_index.reserve(n));
-    NQ_HIP(h, hipMemcpyAsync(h->d_in.p, argb, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    rc = nq_convert_device(h, (const uint32_t*) h->d_in.p, width, height, nMaxColors, dither, rng_seed, mode,
-                           (uint32_t*) h->d_out_argb.p, h->d_out_index.p, out_palette, out_K);
-    if (rc) return rc;
-    NQ_HIP(h, hipMemcpyAsync(out_argb, h->d_out_argb.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (out_index) NQ_HIP(h, hipMemcpyAsync(out_index, h->d_out_index.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
-    NQ_HIP(h, hipStreamSynchronize(h->stream));
-    return NQ_OK;
+    const size_t px = (size_t) width * height;
+    return host_images(h, 1, &px, &argb, &out_argb, &out_index, [&](auto in, auto out, auto index) {
+        return nq_convert_device(h, in[0], width, height, nMaxColors, dither, rng_seed, mode, out[0], index[0], out_palette, out_K);
+    });
 }
 
 int nq_nearest_index(nq_handle* h, const uint32_t* palette, int K, const uint32_t* colors, int64_t M, int16_t* out_index) {
-    if (!h) return NQ_ERR_INVALID;
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!palette || K < 1 || K > 8192 || !colors || M < 0 || !out_index) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
-    if (M == 0) return NQ_OK;
-    { int rcp = upload_palette(h, palette, K); if (rcp) return rcp; }
-    NQ_HIP(h, h->d_colors.reserve((size_t) M)); NQ_HIP(h, h->d_short.reserve((size_t) M));
-    NQ_HIP(h, hipMemcpyAsync(h->d_colors.p, colors, (size_t) M * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    DevParams P = dev_params(h, K);
-    nq::ListsView lv;
-    rc = prepare_lists(h, P, &lv);
-    if (rc) return rc;
-    if (h->use_fast_dither && fast_lookup_eligible(P, lv))
-        launch_fast_nearest_index(P, lv, h->d_palette.p, packed_lists(h), h->d_colors.p, M, h->d_short.p, h->stream);
-    else
-        launch_nearest_index(P, h->d_palette.p, lv, h->d_colors.p, M, h->d_short.p, h->stream);
-    NQ_HIP(h, launch_status());
-    NQ_HIP(h, hipMemcpyAsync(out_index, h->d_short.p, (size_t) M * sizeof(short), hipMemcpyDeviceToHost, h->stream));
-    NQ_HIP(h, hipStreamSynchronize(h->stream));
-    return NQ_OK;
+    return color_lookup(h, palette, K, colors, M, out_index, nullptr);
 }
 
 int nq_closest_tuple(nq_handle* h, const uint32_t* palette, int K, const uint32_t* colors, int64_t M, int32_t* out_closest4) {
-    if (!h) return NQ_ERR_INVALID;
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!palette || K < 1 || K > 8192 || !colors || M < 0 || !out_closest4) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
-    if (M == 0) return NQ_OK;
-    { int rcp = upload_palette(h, palette, K); if (rcp) return rcp; }
-    NQ_HIP(h, h->d_colors.reserve((size_t) M)); NQ_HIP(h, h->d_tuple.reserve((size_t) 4 * M));
-    NQ_HIP(h, hipMemcpyAsync(h->d_colors.p, colors, (size_t) M * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    DevParams P = dev_params(h, K);
-    nq::ListsView lv;
-    rc = prepare_lists(h, P, &lv);
-    if (rc) return rc;
-    if (h->use_fast_dither && fast_lookup_eligible(P, lv))
-        launch_fast_closest_tuple(P, lv, h->d_palette.p, packed_lists(h), h->d_colors.p, M, h->d_tuple.p, h->stream);
-    else
-        launch_closest_tuple(P, h->d_palette.p, lv, h->d_colors.p, M, h->d_tuple.p, h->stream);
-    NQ_HIP(h, launch_status());
-    NQ_HIP(h, hipMemcpyAsync(out_closest4, h->d_tuple.p, (size_t) 4 * M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    NQ_HIP(h, hipStreamSynchronize(h->stream));
-    return NQ_OK;
+    return color_lookup(h, palette, K, colors, M, nullptr, out_closest4);
 }
 
 int nq_band_scan_device(nq_handle* h, const uint32_t* d_argb, int64_t n_pixels, int64_t index_offset, int nMaxColors, int64_t* d_scan3) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!d_argb || n_pixels <= 0 || !d_scan3) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
@@ -1693,7 +1706,6 @@ int nq_set_scan(nq_handle* h, int nMaxColors, int64_t transparent_index, uint32_
 }
 
 int nq_band_distinct_device(nq_handle* h, const uint32_t* d_argb, int64_t n_pixels, int cap, int64_t* out_count, uint32_t* out_colors) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!d_argb || n_pixels <= 0 || cap < 1 || !out_count || !out_colors) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
@@ -1706,7 +1718,6 @@ int nq_band_distinct_device(nq_handle* h, const uint32_t* d_argb, int64_t n_pixe
 
 int nq_band_color_presence_device(nq_handle* h, const uint32_t* d_argb, int64_t n_pixels, uint8_t* d_presence, int cap_other,
                                   int64_t* out_other_count, uint32_t* out_other) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!d_argb || n_pixels <= 0 || !d_presence || cap_other < 1 || !out_other_count || !out_other) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
@@ -1742,19 +1753,14 @@ int nq_set_distinct(nq_handle* h, int64_t count, const uint32_t* colors) {
 }
 
 int nq_band_histogram_device(nq_handle* h, const uint32_t* d_argb, int64_t n_pixels, double* d_hist) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!d_argb || n_pixels <= 0 || !d_hist) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
     rc = reserve_palette_ws(h, n_pixels);
     if (rc) return rc;
-    const nq_params& p = h->params;
     nq::HistParams hp;
-    hp.hasSemi = p.hasSemiTransparency; hp.hasTransp = p.nMaxColors < 64 || p.transparentPixelIndex >= 0;
-    hp.transparentColor = p.transparentColor; hp.rewriteTransparent = 0;
     nq::SortWorkspace ws;
-    ws.keys_a = h->sc->keys_a.p; ws.keys_b = h->sc->keys_b.p; ws.vals_a = h->sc->vals_a.p; ws.vals_b = h->sc->vals_b.p;
-    ws.tmp = h->sc->sort_tmp.p; ws.tmp_bytes = h->sc->sort_tmp.n; ws.seg_start = h->sc->seg.p; ws.seg_end = h->sc->seg.p + 65536;
+    hist_setup(h, &hp, &ws);
     launch_histogram(h->kind, (const int*) d_argb, n_pixels, hp, ws, d_hist, h->stream);
     NQ_HIP(h, launch_status());
     return NQ_OK;
@@ -1762,13 +1768,14 @@ int nq_band_histogram_device(nq_handle* h, const uint32_t* d_argb, int64_t n_pix
 
 int nq_palette_from_histograms_device(nq_handle* h, const double* d_hists, int n_bands, int nMaxColors,
                                       uint32_t* out_palette, int32_t* out_K) {
-    if (!h) return NQ_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
     if (!d_hists || n_bands < 1 || !out_palette || !out_K || nMaxColors < 3) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
     rc = reserve_palette_ws(h, 1);
     if (rc) return rc;
-    return palette_from_hist(h, d_hists, n_bands, nMaxColors, out_palette, out_K);
+    return palette_of(h, out_palette, out_K, [&](PaletteJob* job) {
+        return palette_prepare(h, d_hists, n_bands, nMaxColors, out_palette, out_K, nullptr, 0, job);
+    });
 }
 
 } // extern "C"
@@ -1935,20 +1942,13 @@ int nq_encode_gif(nq_handle* h, int n, const uint16_t* const* index, const int32
     if (rc) return rc;
     rc = use_device(h);
     if (rc) return rc;
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) total += (size_t) widths[i] * heights[i];
-    NQ_HIP(h, h->gif_in.reserve(total));
-    std::vector<const uint16_t*> dev(n);
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t px = (size_t) widths[i] * heights[i];
-        NQ_HIP(h, hipMemcpyAsync(h->gif_in.p + off, index[i], px * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
-        dev[i] = h->gif_in.p + off;
-        off += px;
-    }
-    rc = gif_encode(h, n, dev.data(), widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
-    if (rc) (void) hipStreamSynchronize(h->stream);     // (no upload from the caller's buffers outlives the call)
-    return rc;
+    std::vector<size_t> px(n);
+    for (int i = 0; i < n; ++i) px[i] = (size_t) widths[i] * heights[i];
+    std::vector<uint16_t*> dev(n);
+    return host_form(h, [&]() {
+        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
+        return rc ? rc : gif_encode(h, n, dev.data(), widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    });
 }
 
 } // extern "C"

@@ -18,19 +18,7 @@ MODE_REFERENCE_SEQUENTIAL, MODE_PARALLEL_TILED, MODE_LOOKUP_ONLY = 0, 1, 2
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-ABI_SYMBOLS = [
-    "nq_abi_version", "nq_create", "nq_destroy", "nq_last_error", "nq_set_stream", "nq_set_tile", "nq_set_option", "nq_get_list_counts", "nq_get_params",
-    "nq_set_params", "nq_convert", "nq_convert_device", "nq_convert_batch_device", "nq_convert_batch", "nq_pnnquan", "nq_pnnquan_device", "nq_dither",
-    "nq_dither_device", "nq_nearest_index", "nq_closest_tuple", "nq_band_scan_device", "nq_set_scan",
-    "nq_band_histogram_device", "nq_palette_from_histograms_device", "nq_band_distinct_device", "nq_set_distinct", "nq_get_stage_ms", "nq_get_merge_stats",
-    "nq_get_dither_path", "nq_get_batch_phase_ms", "nq_get_team_stats", "nq_set_band", "nq_band_color_presence_device", "nq_gilbert_dither", "nq_bluenoise_dither", "nq_selftest_ciede",
-    "nq_pnnquan_frames_device", "nq_convert_frames_device", "nq_convert_frames", "nq_gif_max_bytes", "nq_encode_gif_device", "nq_encode_gif",
-]
 OPT_CELL_LISTS, OPT_FAST_DITHER, OPT_MERGE_WALL_SECONDS = 1, 2, 3
-
-
-def abi_symbols():
-    return list(ABI_SYMBOLS)
 
 
 class NqError(RuntimeError):
@@ -49,6 +37,59 @@ class Params(C.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+_vp, _i32, _i64 = C.c_void_p, C.c_int, C.c_int64
+_pi32, _pi64, _pf32 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float)
+# The C ABI (include/nquant_abi.h): name -> (restype, argtypes).  load_library applies it; abi_symbols() lists it.
+_ABI = {
+    "nq_abi_version": (_i32, []),
+    "nq_create": (_i32, [_i32, _i32, C.POINTER(_vp)]),
+    "nq_destroy": (None, [_vp]),
+    "nq_last_error": (C.c_char_p, [_vp]),
+    "nq_set_stream": (_i32, [_vp, _vp]),
+    "nq_set_tile": (_i32, [_vp, _i32, _i32]),
+    "nq_set_option": (_i32, [_vp, _i32, _i32]),
+    "nq_get_list_counts": (_i32, [_vp, _vp, _vp]),
+    "nq_get_params": (_i32, [_vp, C.POINTER(Params)]),
+    "nq_set_params": (_i32, [_vp, C.POINTER(Params)]),
+    "nq_convert": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _pi32]),
+    "nq_convert_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _pi32]),
+    "nq_convert_batch_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "nq_convert_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "nq_pnnquan": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _pi32]),
+    "nq_pnnquan_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _pi32]),
+    "nq_dither": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _i64, _i32, _vp, _vp]),
+    "nq_dither_device": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _i64, _i32, _vp, _vp]),
+    "nq_nearest_index": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp]),
+    "nq_closest_tuple": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp]),
+    "nq_band_scan_device": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp]),
+    "nq_set_scan": (_i32, [_vp, _i32, _i64, C.c_uint32, _i64]),
+    "nq_band_histogram_device": (_i32, [_vp, _vp, _i64, _vp]),
+    "nq_palette_from_histograms_device": (_i32, [_vp, _vp, _i32, _i32, _vp, _pi32]),
+    "nq_band_distinct_device": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "nq_set_distinct": (_i32, [_vp, _i64, _vp]),
+    "nq_get_stage_ms": (_i32, [_vp, _pf32]),
+    "nq_get_merge_stats": (_i32, [_vp, _pi64]),
+    "nq_get_batch_phase_ms": (_i32, [_vp, _pf32]),
+    "nq_get_team_stats": (_i32, [_vp, _pi64]),
+    "nq_get_dither_path": (_i32, [_vp, _pi32, _pi32]),
+    "nq_set_band": (_i32, [_vp, _i32, _i32]),
+    "nq_selftest_ciede": (_i32, [_vp, _vp, _i64, _vp]),
+    "nq_gilbert_dither": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, C.c_double, _i32, _i64, _i32, _vp, _vp]),
+    "nq_bluenoise_dither": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, C.c_float, _i64, _i32, _vp]),
+    "nq_band_color_presence_device": (_i32, [_vp, _vp, _i64, _vp, _i32, _pi64, _vp]),
+    "nq_pnnquan_frames_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _pi32]),
+    "nq_convert_frames_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pi32]),
+    "nq_convert_frames": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pi32]),
+    "nq_gif_max_bytes": (_i32, [_i32, _vp, _vp, _i32, _i32, _pi64]),
+    "nq_encode_gif_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _pi64]),
+    "nq_encode_gif": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _pi64]),
+}
+
+
+def abi_symbols():
+    return list(_ABI)
 
 
 def library_path():
@@ -88,51 +129,9 @@ def load_library():
         raise FileNotFoundError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'`" % path)
     _preload_hip_runtime()
     L = C.CDLL(path)
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    L.nq_abi_version.restype = i32
-    L.nq_create.argtypes = [i32, i32, C.POINTER(vp)]
-    L.nq_destroy.argtypes = [vp]
-    L.nq_destroy.restype = None
-    L.nq_last_error.argtypes = [vp]
-    L.nq_last_error.restype = C.c_char_p
-    L.nq_set_stream.argtypes = [vp, vp]
-    L.nq_set_tile.argtypes = [vp, i32, i32]
-    L.nq_set_option.argtypes = [vp, i32, i32]
-    L.nq_get_list_counts.argtypes = [vp, vp, vp]
-    L.nq_get_params.argtypes = [vp, C.POINTER(Params)]
-    L.nq_set_params.argtypes = [vp, C.POINTER(Params)]
-    L.nq_convert.argtypes = [vp, vp, i32, i32, i32, i32, i64, i32, vp, vp, vp, C.POINTER(C.c_int32)]
-    L.nq_convert_device.argtypes = [vp, vp, i32, i32, i32, i32, i64, i32, vp, vp, vp, C.POINTER(C.c_int32)]
-    L.nq_convert_batch_device.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp]
-    L.nq_convert_batch.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp]
-    L.nq_pnnquan.argtypes = [vp, vp, i32, i32, i32, vp, C.POINTER(C.c_int32)]
-    L.nq_pnnquan_device.argtypes = [vp, vp, i32, i32, i32, vp, C.POINTER(C.c_int32)]
-    L.nq_dither.argtypes = [vp, vp, i32, i32, vp, i32, i32, i64, i32, vp, vp]
-    L.nq_dither_device.argtypes = [vp, vp, i32, i32, vp, i32, i32, i64, i32, vp, vp]
-    L.nq_nearest_index.argtypes = [vp, vp, i32, vp, i64, vp]
-    L.nq_closest_tuple.argtypes = [vp, vp, i32, vp, i64, vp]
-    L.nq_band_scan_device.argtypes = [vp, vp, i64, i64, i32, vp]
-    L.nq_set_scan.argtypes = [vp, i32, i64, C.c_uint32, i64]
-    L.nq_band_histogram_device.argtypes = [vp, vp, i64, vp]
-    L.nq_palette_from_histograms_device.argtypes = [vp, vp, i32, i32, vp, C.POINTER(C.c_int32)]
-    L.nq_band_distinct_device.argtypes = [vp, vp, i64, i32, vp, vp]
-    L.nq_set_distinct.argtypes = [vp, i64, vp]
-    L.nq_get_stage_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    L.nq_get_merge_stats.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.nq_get_batch_phase_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    L.nq_get_team_stats.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.nq_get_dither_path.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.nq_set_band.argtypes = [vp, i32, i32]
-    L.nq_selftest_ciede.argtypes = [vp, vp, i64, vp]
-    L.nq_gilbert_dither.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.c_double, i32, i64, i32, vp, vp]
-    L.nq_bluenoise_dither.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.c_float, i64, i32, vp]
-    L.nq_band_color_presence_device.argtypes = [vp, vp, i64, vp, i32, C.POINTER(C.c_int64), vp]
-    L.nq_pnnquan_frames_device.argtypes = [vp, i32, vp, vp, vp, i32, vp, C.POINTER(C.c_int32)]
-    L.nq_convert_frames_device.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_int32)]
-    L.nq_convert_frames.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_int32)]
-    L.nq_gif_max_bytes.argtypes = [i32, vp, vp, i32, i32, C.POINTER(C.c_int64)]
-    L.nq_encode_gif_device.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, i64, C.POINTER(C.c_int64)]
-    L.nq_encode_gif.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, i64, C.POINTER(C.c_int64)]
+    for name, (restype, argtypes) in _ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
 
