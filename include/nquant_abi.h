@@ -236,6 +236,38 @@ int nq_encode_gif(nq_handle* h, int n, const uint16_t* const* index, const int32
                   const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
                   uint8_t* out, int64_t cap, int64_t* out_size);
 
+/* ---- PNG encoding: palette index maps (what the convert calls write to out_index) to indexed PNG files, on the GPU.  One call encodes
+ *      n independent images into n files (n = 1 is the plain case; a batch fills the chip).  Image i is a uint16 index map, row-major,
+ *      widths[i] x heights[i], with its own K[i] <= 256 and its own palette: the K[i] ARGB entries at palettes[i * palette_stride]
+ *      (host memory; the layout nq_convert_batch returns).  The files are standard: every PNG decoder reads them.
+ *  * Chunks: IHDR (colour type 3, no interlace), PLTE (K RGB entries), tRNS only when some entry's alpha is not 255 (the alpha bytes of
+ *    entries 0 .. the last such entry: all 8 bits of alpha are kept), one IDAT, IEND.
+ *  * Bit depth d: the smallest of 1, 2, 4, 8 with 2^d >= max(K, 2).  Every scanline has filter type 0; its indices are packed most
+ *    significant bits first and padded to a byte.  The raw stream is heights[i] * (1 + ceil(widths[i] * d / 8)) bytes.
+ *  * IDAT holds a zlib stream (header 78 01, deflate data, Adler-32).  The raw stream is cut into segments of segment_bytes bytes (0:
+ *    the default 32768; at most 65535; the last segment may be shorter).  Every segment is one chain that sees only its own bytes
+ *    (no match reaches before its start) and emits one dynamic-Huffman block; BFINAL is set on the last.  The chains run in parallel
+ *    on the GPU.  A longer segment compresses a little better and gives fewer chains: on a dithered 256-colour map the default gives
+ *    0.997x the bytes of zlib level 1 and 1.05x those of level 6.  The bit-exact definition (hash, parse, code lengths): DESIGN.md
+ *    "PNG encoder".
+ *  * nq_png_max_bytes: an upper bound of the n files' total size for any content (pure arithmetic, no device, no handle); K NULL
+ *    stands for 256 everywhere.
+ *  * nq_encode_png_device: index maps in DEVICE memory (2-byte aligned pointers suffice), everything else on the host.  The files are
+ *    assembled back to back in device memory and copied to `out` in one copy: file i is out[out_offsets[i] .. out_offsets[i + 1]).
+ *    The call returns when `out` holds them.  h may be a handle of either kind (its stream, scratch and error text are used).
+ *    nq_encode_png: the same with index maps in HOST memory (they are uploaded first).
+ *  * NQ_ERR_INVALID before any device work: n < 1, a side outside 1..65535, a K outside 1..256, palette_stride smaller than a K,
+ *    segment_bytes outside 0..65535, NULL or odd index pointers, an image whose size bound exceeds 2^31 - 1 bytes.  After the
+ *    encoding: an index >= its image's K (nq_last_error names the image), or cap smaller than the files (then out_offsets[n] holds
+ *    the size needed and `out` is untouched).  The handle stays usable after any of these. ---- */
+int nq_png_max_bytes(int n, const int32_t* widths, const int32_t* heights, const int32_t* K, int segment_bytes, int64_t* out_bytes);
+int nq_encode_png_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                         const uint32_t* palettes, int32_t palette_stride, const int32_t* K, int segment_bytes,
+                         uint8_t* out, int64_t cap, int64_t* out_offsets);
+int nq_encode_png(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                  const uint32_t* palettes, int32_t palette_stride, const int32_t* K, int segment_bytes,
+                  uint8_t* out, int64_t cap, int64_t* out_offsets);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

@@ -22,6 +22,7 @@ UNITS = {
                                   os.path.join(INC, "nq_blue_noise_64x64.inc")]),
     "nq_dither_fast.hip": ("device", ["nq_dither_fast.hip", "nq_device.h", "nq_kernels.h", os.path.join(INC, "nq_blue_noise_64x64.inc")]),
     "nq_gif.hip": ("device", ["nq_gif.hip", "nq_kernels.h"]),
+    "nq_png.hip": ("device", ["nq_png.hip", "nq_kernels.h"]),
     "nq_abi.cpp": ("host", ["nq_abi.cpp", "nq_kernels.h", os.path.join(INC, "nquant_abi.h")]),
 }
 
@@ -53,6 +54,10 @@ def build(force=False, verbose=False):
         same_flags = False            # objects of unknown origin (if any): rebuild
     if not same_flags:
         force = True
+    # a library newer than every source is current even where the objects did not travel with the tree
+    sources = {os.path.join(CSRC, d) for _, deps in UNITS.values() for d in deps}
+    if not force and not _newer(LIB, sorted(sources) + [me]):
+        return LIB
     for src, (kind, deps) in UNITS.items():
         o = os.path.join(CSRC, src + (".%s.o" % TAG if TAG else ".o"))
         objs.append(o)

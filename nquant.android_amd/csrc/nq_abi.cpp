@@ -221,6 +221,12 @@ struct nq_handle {
     DevBuf<unsigned char> gif_blob, gif_file;
     DevBuf<unsigned short> gif_in;
     std::vector<uint8_t> h_gif_blob;
+    // nq_encode_png_device: image table, token scratch of the resident chains, IDAT CRC registers; bit strings, bit lengths / offsets,
+    // read-back, header blob, files and uploaded index maps live in the GIF buffers above (one encoder runs at a time on a handle)
+    std::vector<nq::PngImage> h_png;
+    DevBuf<nq::PngImage> d_png;
+    DevBuf<unsigned> png_tokens, png_crc;
+    DevBuf<unsigned long long> png_adler;
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
@@ -1948,6 +1954,197 @@ int nq_encode_gif(nq_handle* h, int n, const uint16_t* const* index, const int32
     return host_form(h, [&]() {
         rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
         return rc ? rc : gif_encode(h, n, dev.data(), widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    });
+}
+
+} // extern "C"
+
+// ---- PNG encoding (nq_png.hip) ----
+namespace {
+
+constexpr int kPngDefaultSegment = 32768, kPngMaxSegment = 65535;
+
+// most bits the block of a segment of L bytes can take: 17 bits of block header, 19 x 3 bits of code-length-code lengths, at most
+// 286 + 30 code-length symbols of <= 7 + 7 bits, an end-of-block code of <= 15 bits (4513 in all), and per token a literal of <= 15
+// bits for one byte or a match of <= 15 + 5 + 15 + 13 bits for at least three: <= 16 bits per byte
+inline long long png_seg_bits_max(long long L) { return 4544 + 16 * L; }
+inline int png_depth(int K) { return K <= 2 ? 1 : K <= 4 ? 2 : K <= 16 ? 4 : 8; }
+inline long long png_row_bytes(int w, int K) { return 1 + ((long long) w * png_depth(K) + 7) / 8; }
+inline long long png_seg_len(long long raw, int segment_bytes) { return std::min<long long>(segment_bytes ? segment_bytes : kPngDefaultSegment, raw); }
+// signature, IHDR, PLTE, tRNS, IDAT length + type, zlib header | Adler-32, IDAT CRC, IEND
+inline long long png_prefix_max(int K) { return 8 + 25 + (12 + 3 * K) + (12 + K) + 8 + 2; }
+constexpr long long kPngSuffix = 4 + 4 + 12;
+
+inline long long png_image_max(int w, int h, int K, int segment_bytes) {
+    const long long raw = (long long) h * png_row_bytes(w, K), S = png_seg_len(raw, segment_bytes), full = raw / S, rest = raw % S;
+    const long long bits = full * png_seg_bits_max(S) + (rest ? png_seg_bits_max(rest) : 0);
+    return png_prefix_max(K) + (bits + 7) / 8 + kPngSuffix;
+}
+
+// the arguments nq_png_max_bytes takes; false + the reason otherwise
+bool png_check_shape(int n, const int32_t* widths, const int32_t* heights, const int32_t* K, int segment_bytes, char* why, size_t len) {
+    if (n < 1) { std::snprintf(why, len, "n = %d: at least one image", n); return false; }
+    if (!widths || !heights) { std::snprintf(why, len, "widths / heights is NULL"); return false; }
+    if (segment_bytes < 0 || segment_bytes > kPngMaxSegment) { std::snprintf(why, len, "segment_bytes = %d: must be 0..%d", segment_bytes, kPngMaxSegment); return false; }
+    for (int i = 0; i < n; ++i) {
+        if (widths[i] < 1 || widths[i] > 65535 || heights[i] < 1 || heights[i] > 65535) {
+            std::snprintf(why, len, "image %d: %d x %d, sides must be 1..65535", i, widths[i], heights[i]); return false;
+        }
+        const int k = K ? K[i] : 256;
+        if (k < 1 || k > 256) { std::snprintf(why, len, "image %d: K = %d, a PNG palette holds 1..256 entries", i, k); return false; }
+        if (png_image_max(widths[i], heights[i], k, segment_bytes) > 2147483647ll) {
+            std::snprintf(why, len, "image %d: %d x %d, the file's bound exceeds 2^31 - 1 bytes", i, widths[i], heights[i]); return false;
+        }
+    }
+    return true;
+}
+
+int png_check(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights, const uint32_t* palettes,
+              int32_t palette_stride, const int32_t* K, int segment_bytes, const uint8_t* out, int64_t cap, int64_t* out_offsets) {
+    char why[256];
+    if (!K) NQ_FAIL(h, NQ_ERR_INVALID, "K is NULL");
+    if (!png_check_shape(n, widths, heights, K, segment_bytes, why, sizeof why)) NQ_FAIL(h, NQ_ERR_INVALID, "%s", why);
+    if (!palettes || !out_offsets) NQ_FAIL(h, NQ_ERR_INVALID, "palettes / out_offsets is NULL");
+    for (int i = 0; i < n; ++i)
+        if (palette_stride < K[i]) NQ_FAIL(h, NQ_ERR_INVALID, "palette_stride = %d < K = %d of image %d", palette_stride, K[i], i);
+    if (cap < 0 || (!out && cap > 0)) NQ_FAIL(h, NQ_ERR_INVALID, "out is NULL or cap < 0");
+    if (!index) NQ_FAIL(h, NQ_ERR_INVALID, "index is NULL");
+    for (int i = 0; i < n; ++i)
+        if (!index[i] || ((uintptr_t) index[i] & 1)) NQ_FAIL(h, NQ_ERR_INVALID, "image %d: index pointer NULL or not 2-byte aligned", i);
+    return NQ_OK;
+}
+
+uint32_t png_crc32(const uint8_t* p, size_t n) {
+    uint32_t c = 0xFFFFFFFFu;
+    for (size_t i = 0; i < n; ++i) {
+        c ^= p[i];
+        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
+    }
+    return ~c;
+}
+
+int png_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights, const uint32_t* palettes,
+               int32_t palette_stride, const int32_t* K, int segment_bytes, uint8_t* out, int64_t cap, int64_t* out_offsets) {
+    // image table: segments and their scratch
+    h->h_png.assign(n, nq::PngImage{});
+    long long segs = 0, words = 0;
+    int max_seg = 1;
+    for (int i = 0; i < n; ++i) {
+        nq::PngImage& F = h->h_png[i];
+        F.index = d_index[i]; F.width = widths[i]; F.height = heights[i]; F.K = K[i]; F.depth = png_depth(K[i]);
+        F.row_bytes = (int) png_row_bytes(widths[i], K[i]);
+        F.raw_len = (long long) heights[i] * F.row_bytes;
+        F.seg_len = (int) png_seg_len(F.raw_len, segment_bytes);
+        F.nseg = (F.raw_len + F.seg_len - 1) / F.seg_len; F.seg_base = segs; F.seg_words = png_seg_bits_max(F.seg_len) / 32 + 2; F.word_base = words;
+        segs += F.nseg; words += F.nseg * F.seg_words;
+        max_seg = std::max(max_seg, F.seg_len);
+    }
+    const int grid = (int) std::min<long long>(segs, 4ll * std::max(h->n_cus, 1));
+    NQ_HIP(h, h->d_png.reserve(n));
+    NQ_HIP(h, h->gif_words.reserve((size_t) words));
+    NQ_HIP(h, h->gif_bits.reserve(2 * (size_t) segs));
+    NQ_HIP(h, h->png_adler.reserve((size_t) segs));
+    NQ_HIP(h, h->gif_res.reserve(3 * (size_t) n));
+    NQ_HIP(h, h->png_tokens.reserve((size_t) grid * max_seg));
+    NQ_HIP(h, h->png_crc.reserve(n));
+    NQ_HIP(h, hipMemcpyAsync(h->d_png.p, h->h_png.data(), n * sizeof(nq::PngImage), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemsetAsync(h->gif_res.p + 2 * n, 0, n * sizeof(unsigned long long), h->stream));
+    NQ_HIP(h, launch_png_deflate(h->d_png.p, n, segs, max_seg, grid, h->gif_words.p, h->gif_bits.p, h->png_adler.p, h->png_tokens.p,
+                                 h->gif_res.p + 2 * n, h->stream));
+    launch_png_scan(h->d_png.p, n, h->gif_bits.p, h->png_adler.p, h->gif_bits.p + segs, h->gif_res.p, h->stream);
+    NQ_HIP(h, launch_status());
+    std::vector<unsigned long long> res(3 * (size_t) n);
+    NQ_HIP(h, hipMemcpyAsync(res.data(), h->gif_res.p, res.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n; ++i)
+        if (res[2 * n + i]) NQ_FAIL(h, NQ_ERR_INVALID, "image %d: the index map holds an index >= K = %d", i, K[i]);
+    // per image the bytes in front of the deflate data, in one blob: signature, IHDR, PLTE, tRNS, IDAT length and type, zlib header
+    std::vector<uint8_t>& blob = h->h_gif_blob;
+    blob.clear();
+    auto u32 = [&](uint32_t v) { for (int k = 3; k >= 0; --k) blob.push_back((uint8_t) (v >> (8 * k))); };
+    size_t chunk_at = 0;
+    auto begin = [&](uint32_t len, const char* type) { u32(len); chunk_at = blob.size(); blob.insert(blob.end(), type, type + 4); };
+    auto end = [&]() { u32(png_crc32(blob.data() + chunk_at, blob.size() - chunk_at)); };
+    long long total = 0, crc_chunks = 0;
+    for (int i = 0; i < n; ++i) {
+        nq::PngImage& F = h->h_png[i];
+        const uint32_t* pal = palettes + (size_t) i * palette_stride;
+        const size_t start = blob.size();
+        blob.insert(blob.end(), {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A});
+        begin(13, "IHDR"); u32((uint32_t) widths[i]); u32((uint32_t) heights[i]);
+        blob.insert(blob.end(), {(uint8_t) F.depth, 3, 0, 0, 0}); end();
+        begin((uint32_t) (3 * K[i]), "PLTE");
+        for (int k = 0; k < K[i]; ++k) { blob.push_back((uint8_t) (pal[k] >> 16)); blob.push_back((uint8_t) (pal[k] >> 8)); blob.push_back((uint8_t) pal[k]); }
+        end();
+        int nt = 0;
+        for (int k = 0; k < K[i]; ++k) if ((pal[k] >> 24) != 255) nt = k + 1;
+        if (nt) {
+            begin((uint32_t) nt, "tRNS");
+            for (int k = 0; k < nt; ++k) blob.push_back((uint8_t) (pal[k] >> 24));
+            end();
+        }
+        F.data_bytes = (long long) ((res[2 * i] + 7) / 8);
+        begin((uint32_t) (2 + F.data_bytes + 4), "IDAT");
+        blob.push_back(0x78); blob.push_back(0x01);  // deflate, 32 KiB window; no dictionary, fastest; 0x7801 is a multiple of 31
+        F.prefix_off = (long long) start; F.prefix_len = (int) (blob.size() - start);
+        F.file_off = total; F.crc_base = crc_chunks;
+        out_offsets[i] = total;
+        total += F.prefix_len + F.data_bytes + kPngSuffix;
+        crc_chunks += (10 + F.data_bytes + 127) / 128;
+    }
+    out_offsets[n] = total;
+    if (cap < total) NQ_FAIL(h, NQ_ERR_INVALID, "cap = %lld bytes < the files' %lld", (long long) cap, total);
+    NQ_HIP(h, h->gif_blob.reserve(blob.size()));
+    NQ_HIP(h, h->gif_file.reserve((size_t) total));
+    NQ_HIP(h, hipMemcpyAsync(h->gif_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemcpyAsync(h->d_png.p, h->h_png.data(), n * sizeof(nq::PngImage), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemsetAsync(h->png_crc.p, 0, n * sizeof(unsigned), h->stream));
+    launch_png_gather(h->d_png.p, n, h->gif_words.p, h->gif_bits.p, h->gif_bits.p + segs, h->gif_res.p, h->gif_blob.p, h->gif_file.p, total,
+                      crc_chunks, h->png_crc.p, h->stream);
+    NQ_HIP(h, launch_status());
+    NQ_HIP(h, hipMemcpyAsync(out, h->gif_file.p, (size_t) total, hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    return NQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_png_max_bytes(int n, const int32_t* widths, const int32_t* heights, const int32_t* K, int segment_bytes, int64_t* out_bytes) {
+    char why[256];
+    if (!out_bytes || !png_check_shape(n, widths, heights, K, segment_bytes, why, sizeof why)) return NQ_ERR_INVALID;
+    long long total = 0;
+    for (int i = 0; i < n; ++i) total += png_image_max(widths[i], heights[i], K ? K[i] : 256, segment_bytes);
+    *out_bytes = total;
+    return NQ_OK;
+}
+
+int nq_encode_png_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                         const uint32_t* palettes, int32_t palette_stride, const int32_t* K, int segment_bytes,
+                         uint8_t* out, int64_t cap, int64_t* out_offsets) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = png_check(h, n, d_index, widths, heights, palettes, palette_stride, K, segment_bytes, out, cap, out_offsets);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return png_encode(h, n, d_index, widths, heights, palettes, palette_stride, K, segment_bytes, out, cap, out_offsets);
+}
+
+int nq_encode_png(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                  const uint32_t* palettes, int32_t palette_stride, const int32_t* K, int segment_bytes,
+                  uint8_t* out, int64_t cap, int64_t* out_offsets) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = png_check(h, n, index, widths, heights, palettes, palette_stride, K, segment_bytes, out, cap, out_offsets);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    std::vector<size_t> px(n);
+    for (int i = 0; i < n; ++i) px[i] = (size_t) widths[i] * heights[i];
+    std::vector<uint16_t*> dev(n);
+    return host_form(h, [&]() {
+        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
+        return rc ? rc : png_encode(h, n, dev.data(), widths, heights, palettes, palette_stride, K, segment_bytes, out, cap, out_offsets);
     });
 }
 

@@ -133,6 +133,43 @@ public class PnnQuantizer {
 	/** nq_gif_max_bytes for K = 256 (an upper bound for every K); -1 for invalid sizes */
 	private static native long nqGifMaxBytes(int[] widths, int[] heights);
 
+	/** An indexed PNG file of one index map (nq_encode_png, encoded on the GPU): index is a DIRECT buffer of width*height palette
+	 *  indices, palette the ARGB entries (at most 256; alpha values other than 255 go to a tRNS chunk, all 8 bits). */
+	public static byte[] encodePng(java.nio.ShortBuffer index, int width, int height, int[] palette) {
+		java.nio.ByteBuffer out = pngBuffer(width, height);
+		long h = nqCreate(0, 0);
+		try {
+			return gifBytes(out, nqEncodePng(h, index, width, height, palette, out, out.capacity()));
+		} finally {
+			nqDestroy(h);
+		}
+	}
+	private static native long nqEncodePng(long h, java.nio.ShortBuffer index, int width, int height, int[] palette, java.nio.ByteBuffer out,
+			long cap);
+
+	/** convert(nMaxColors, dither) of the kind's quantizer followed by encodePng of the index map, in one native call; nMaxColors <= 256.
+	 *  in is a DIRECT buffer of width*height ARGB ints. */
+	public static byte[] convertToPng(int kind, java.nio.IntBuffer in, int width, int height, int nMaxColors, boolean dither, long seed) {
+		java.nio.ByteBuffer out = pngBuffer(width, height);
+		long h = nqCreate(kind, 0);
+		try {
+			return gifBytes(out, nqConvertToPng(h, in, width, height, nMaxColors, dither, seed, MODE_PARALLEL_TILED, out, out.capacity()));
+		} finally {
+			nqDestroy(h);
+		}
+	}
+	private static native long nqConvertToPng(long h, java.nio.IntBuffer in, int width, int height, int nMaxColors, boolean dither, long seed,
+			int mode, java.nio.ByteBuffer out, long cap);
+
+	private static java.nio.ByteBuffer pngBuffer(int width, int height) {
+		long cap = nqPngMaxBytes(width, height);
+		if (cap < 0 || cap > Integer.MAX_VALUE)
+			throw new IllegalArgumentException("a PNG of this image does not fit one byte[]");
+		return java.nio.ByteBuffer.allocateDirect((int) cap);
+	}
+	/** nq_png_max_bytes of one image for K = 256 (an upper bound for every K); -1 for an invalid size */
+	private static native long nqPngMaxBytes(int width, int height);
+
 	@Override
 	protected void finalize() throws Throwable {
 		if (handle != 0) { nqDestroy(handle); handle = 0; }

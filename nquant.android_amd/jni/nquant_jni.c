@@ -217,3 +217,55 @@ JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertFramesToGi
     if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
     return (jlong) size;
 }
+
+/* nqPngMaxBytes(): nq_png_max_bytes of one image for K = 256, the bound for every K; -1 when the size is invalid */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqPngMaxBytes(JNIEnv* env, jclass c, jint width, jint height) {
+    const int32_t w = width, hg = height;
+    int64_t bytes = -1;
+    if (nq_png_max_bytes(1, &w, &hg, NULL, 0, &bytes) != NQ_OK) bytes = -1;
+    return (jlong) bytes;
+}
+
+/* encodePng(): a direct ShortBuffer of indices in, the file written to the direct ByteBuffer `out` (cap bytes) -> nq_encode_png.
+ * Returns the file size. */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqEncodePng(JNIEnv* env, jclass c, jlong hh, jobject index, jint width,
+        jint height, jintArray palette, jobject out, jlong cap) {
+    nq_handle* h = (nq_handle*) (intptr_t) hh;
+    const uint16_t* src = (const uint16_t*) (*env)->GetDirectBufferAddress(env, index);
+    const int32_t w = width, hg = height, K = (*env)->GetArrayLength(env, palette);
+    jint* pal = (*env)->GetIntArrayElements(env, palette, NULL);
+    if (!pal) { throw_rt(env, "out of memory"); return -1; }
+    int64_t offs[2] = {0, -1};
+    const int rc = nq_encode_png(h, 1, &src, &w, &hg, (const uint32_t*) pal, K, &K, 0, (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, offs);
+    (*env)->ReleaseIntArrayElements(env, palette, pal, JNI_ABORT);
+    if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
+    return (jlong) offs[1];
+}
+
+/* convertToPng(): nq_convert with the index output (the ARGB output goes to scratch), then nq_encode_png of the index map with the
+ * image's palette into the direct ByteBuffer `out` (cap bytes).  Returns the file size. */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertToPng(JNIEnv* env, jclass c, jlong hh, jobject in, jint width,
+        jint height, jint nMaxColors, jboolean dither, jlong seed, jint mode, jobject out, jlong cap) {
+    nq_handle* h = (nq_handle*) (intptr_t) hh;
+    const size_t px = (size_t) (width > 0 ? width : 1) * (size_t) (height > 0 ? height : 1);
+    const int pcap = nMaxColors > 2 ? nMaxColors : 2;
+    uint32_t* argb = malloc(px * sizeof(uint32_t));
+    uint16_t* idx = malloc(px * sizeof(uint16_t));
+    uint32_t* palette = malloc(sizeof(uint32_t) * (size_t) pcap);
+    const int32_t w = width, hg = height;
+    int32_t K = 0;
+    int64_t offs[2] = {0, -1};
+    int rc = NQ_OK;
+    const int ok = argb && idx && palette;
+    if (ok) {
+        rc = nq_convert(h, (const uint32_t*) (*env)->GetDirectBufferAddress(env, in), width, height, nMaxColors, dither ? 1 : 0, seed, mode,
+                        argb, idx, palette, &K);
+        const uint16_t* src = idx;
+        if (rc == NQ_OK)
+            rc = nq_encode_png(h, 1, &src, &w, &hg, palette, K, &K, 0, (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, offs);
+    }
+    free(palette); free(idx); free(argb);
+    if (!ok) { throw_rt(env, "out of memory"); return -1; }
+    if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
+    return (jlong) offs[1];
+}
