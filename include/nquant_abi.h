@@ -355,6 +355,12 @@ int nq_get_merge_stats(const nq_handle* h, int64_t* out16);
  * popped, ticks in the find_nn epilogues, ticks spent choosing work records, results a helper declined (RGB), times the loop gave up
  * on its helpers for a while}.  Diagnostics. */
 int nq_get_team_stats(const nq_handle* h, int64_t* out16);
+/* Which merge kernel the last merge launch ran for THIS handle's job (a host-side record, no device traffic): *out_threads = the
+ * workgroup-size code as NQ_MERGE_THREADS spells it -- 512, 256, 128, or 127 for the dense 128-thread variant (csrc/nq_kernels.hip:
+ * chosen from the number of merge jobs of the whole call) --, *out_helpers = helper workgroups per loop of the handle's kind in that
+ * launch (0 unless 512 threads).  Both are 0 when the handle's last palette needed no merge loop (few colours, nMaxColors <= 2) or
+ * none has run yet.  Diagnostics. */
+int nq_get_merge_variant(const nq_handle* h, int32_t* out_threads, int32_t* out_helpers);
 /* Phases of the last nq_convert_batch[_device] call, as seen by its FIRST handle: HIP-event spans on the launch stream, ms:
  * {every image's pre-scan + histogram + initial find_nn pass, the merge launch (all merge loops side by side + palette fill),
  *  every image's palette read-back + candidate lists + dither pass, whole call}.  Divided by the batch size these are the

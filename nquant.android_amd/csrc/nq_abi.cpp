@@ -191,6 +191,7 @@ struct nq_handle {
     std::vector<uint32_t> dev_palette;  // what d_palette holds, as far as the host knows (empty: unknown): an upload of the same entries is skipped
     uint32_t* fetched_palette = nullptr; int fetched_len = 0;      // palette_fetch -> palette_check
     long long merge_readback[37] = {0}; // d_scalars[4..41) as the merge kernel left it: one copy per image ([36] = status word)
+    int merge_variant[2] = {0, 0};     // nq_get_merge_variant: {workgroup-size code, helpers} launch_merge picked for this handle's last merge job
     long long team_stats[16] = {0};    // merge teams: {work records published, results used, timed-out waits, ticks waited, helpers, still speculating}
     DevBuf<unsigned long long> team;  // 256 u64 of hand-off words of this handle's merge team
     bool light_events = false;        // batch entry points: this image records only the stage events 0, 5, 6 (see rec)
@@ -479,6 +480,7 @@ void rec(nq_handle* h, int i) {
 // what palette_prepare leaves for the merge launch and palette_finish; merge == false: the palette is already final
 struct PaletteJob {
     bool merge = false;
+    nq_handle* h = nullptr;           // the handle the job was prepared on (merge_launch records the variant there)
     nq::MergeJob mj;
     int plen = 0;
 };
@@ -486,7 +488,8 @@ struct PaletteJob {
 // pnnquan after the histogram(s) exist on the device, up to the initial find_nn pass (P4..P8)
 int palette_prepare(nq_handle* h, const double* d_hists, int n_bands, int nMaxColors, uint32_t* out_palette, int32_t* out_K,
                     const uint32_t* d_argb, int64_t n_pixels, PaletteJob* job) {
-    job->merge = false;
+    job->merge = false; job->h = h;
+    h->merge_variant[0] = h->merge_variant[1] = 0;      // (no merge job yet: an early return leaves it that way)
     nq_params& p = h->params;
     const int kind = h->kind;
     nq::Bins B = bins_of(h);
@@ -612,10 +615,11 @@ int palette_prepare(nq_handle* h, const double* d_hists, int n_bands, int nMaxCo
 // the merge loops (P9) of n prepared images in one launch per kind, on the stream of `owner`
 int merge_launch(nq_handle* owner, const PaletteJob* const* jobs, int n) {
     std::vector<nq::MergeJob> host;
+    std::vector<nq_handle*> of;                             // host[i] is the job of handle of[i]
     int n_lab = 0;
     for (int pass = 1; pass >= 0; --pass) {                 // LAB jobs first, then RGB
         for (int i = 0; i < n; ++i)
-            if (jobs[i]->merge && jobs[i]->mj.np.kind == pass) host.push_back(jobs[i]->mj);
+            if (jobs[i]->merge && jobs[i]->mj.np.kind == pass) { host.push_back(jobs[i]->mj); of.push_back(jobs[i]->h); }
         if (pass == 1) n_lab = (int) host.size();
     }
     if (host.empty()) return NQ_OK;
@@ -638,9 +642,12 @@ int merge_launch(nq_handle* owner, const PaletteJob* const* jobs, int n) {
     NQ_HIP(owner, owner->d_jobs.reserve(host.size()));
     NQ_HIP(owner, hipMemcpyAsync(owner->d_jobs.p, host.data(), host.size() * sizeof(nq::MergeJob), hipMemcpyHostToDevice, owner->stream));
     NQ_HIP(owner, hipStreamSynchronize(owner->stream));    // `host` goes out of scope
-    NQ_HIP(owner, launch_merge(1, owner->d_jobs.p, n_lab, (int) host.size(), owner->n_cus, helpers_lab, owner->stream));
-    NQ_HIP(owner, launch_merge(0, owner->d_jobs.p + n_lab, n_rgb, (int) host.size(), owner->n_cus, helpers_rgb, owner->stream));
+    int variant_lab[2] = {0, 0}, variant_rgb[2] = {0, 0};
+    NQ_HIP(owner, launch_merge(1, owner->d_jobs.p, n_lab, (int) host.size(), owner->n_cus, helpers_lab, owner->stream, variant_lab));
+    NQ_HIP(owner, launch_merge(0, owner->d_jobs.p + n_lab, n_rgb, (int) host.size(), owner->n_cus, helpers_rgb, owner->stream, variant_rgb));
     NQ_HIP(owner, launch_status());
+    for (int i = 0; i < (int) host.size(); ++i)
+        if (of[i]) std::memcpy(of[i]->merge_variant, i < n_lab ? variant_lab : variant_rgb, sizeof of[i]->merge_variant);
     return NQ_OK;
 }
 
@@ -703,6 +710,7 @@ template <typename Keys>
 int palette_after_scan(nq_handle* h, const long long* scan3, const uint32_t* d_argb, int64_t n, int nMaxColors, uint32_t* out_palette,
                        int32_t* out_K, PaletteJob* job, Keys keys) {
     apply_scan(h, nMaxColors, scan3[0], (uint32_t) scan3[1], scan3[2]);
+    h->merge_variant[0] = h->merge_variant[1] = 0;
     rec(h, 1);
     nq_params& p = h->params;
     if (nMaxColors <= 2) {
@@ -1290,6 +1298,11 @@ int nq_get_team_stats(const nq_handle* h, int64_t* out16) {
     std::memcpy(out16, h->team_stats, sizeof h->team_stats);
     return NQ_OK;
 }
+int nq_get_merge_variant(const nq_handle* h, int32_t* out_threads, int32_t* out_helpers) {
+    if (!h || !out_threads || !out_helpers) return NQ_ERR_INVALID;
+    *out_threads = h->merge_variant[0]; *out_helpers = h->merge_variant[1];
+    return NQ_OK;
+}
 int nq_get_batch_phase_ms(const nq_handle* h0, float* out4) {
     if (!h0 || !out4) return NQ_ERR_INVALID;
     std::memcpy(out4, h0->batch_phase_ms, sizeof h0->batch_phase_ms);
@@ -1554,6 +1567,10 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
         lane_work(0);
         for (int k : inline_lanes) lane_work(k);
         for (auto& t : workers) t.join();
+        // a failed lane ends the call: the kernels the other lanes have queued write their handles' buffers and the lane scratch, and the
+        // lane streams do not synchronise with the handles' own streams -- nothing of this call may still run when the handles are used again
+        if (std::any_of(lane_rc.begin(), lane_rc.end(), [](int r) { return r != NQ_OK; }))
+            for (int k = 0; k < L; ++k) (void) hipStreamSynchronize(lane_s[k]);
         for (int k = 0; k < L; ++k)
             if (lane_rc[k]) return batch_fail(h0, hs[lane_bad[k] >= 0 && lane_bad[k] < n ? lane_bad[k] : 0], lane_rc[k]);
     }

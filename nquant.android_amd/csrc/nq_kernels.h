@@ -183,8 +183,9 @@ struct MergeJob {
 // unpartitioned MI355X): <= n_cus -> 512-thread workgroups, one per CU; <= 2 n_cus -> 256 threads, two per CU; more -> 128 threads, four
 // per CU.  helpers > 0 (either kind, 512-thread variant only; every job's `team` area zeroed and `helpers` set to
 // the same number): the grid holds 1 + helpers workgroups per job (merge teams, nq_merge.inc).  Returns the first HIP error of the
-// attribute call / launch.
-hipError_t launch_merge(int kind, const MergeJob* d_jobs, int n, int n_in_flight, int n_cus, int helpers, hipStream_t s);
+// attribute call / launch.  out_variant (nullable; untouched when n <= 0): {the workgroup-size code as NQ_MERGE_THREADS spells it -- 512, 256,
+// 128, or 127 for the dense variant --, helper workgroups per job} of the kernel that was launched.
+hipError_t launch_merge(int kind, const MergeJob* d_jobs, int n, int n_in_flight, int n_cus, int helpers, hipStream_t s, int* out_variant = nullptr);
 // helpers launch_merge would use for n jobs of one kind when n_in_flight loops share a device of n_cus compute units (0..7;
 // NQ_MERGE_HELPERS overrides).  Sized on THIS call's jobs: merge launches of other handles / threads on the same device are not
 // counted -- correctness does not depend on it (every wait of a team is bounded, nq_merge.inc), only the speed-up does.

@@ -333,9 +333,10 @@ int merge_team_helpers(int n_jobs, int n_in_flight, int n_cus) {
     }
     return h;
 }
-hipError_t launch_merge(int kind, const MergeJob* d_jobs, int n, int n_in_flight, int n_cus, int helpers, hipStream_t s) {
+hipError_t launch_merge(int kind, const MergeJob* d_jobs, int n, int n_in_flight, int n_cus, int helpers, hipStream_t s, int* out_variant) {
     if (n <= 0) return hipSuccess;
     const int threads = merge_threads_for(n_in_flight, n_cus);
+    if (out_variant) { out_variant[0] = threads; out_variant[1] = threads == 512 && helpers > 0 ? helpers : 0; }
     // Phase stamps (nq_merge.inc, STATS) cost ~20 scalar-cache round trips per find_nn event: every variant runs without them unless
     // NQ_MERGE_STATS=1 asks for the stamped build (tools/latency.py, tools/batch_rate.py: the tick fields of nq_get_merge_stats /
     // nq_get_team_stats are 0 otherwise; the event counters are always there)

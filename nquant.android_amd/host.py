@@ -73,6 +73,7 @@ _ABI = {
     "nq_get_merge_stats": (_i32, [_vp, _pi64]),
     "nq_get_batch_phase_ms": (_i32, [_vp, _pf32]),
     "nq_get_team_stats": (_i32, [_vp, _pi64]),
+    "nq_get_merge_variant": (_i32, [_vp, _pi32, _pi32]),
     "nq_get_dither_path": (_i32, [_vp, _pi32, _pi32]),
     "nq_set_band": (_i32, [_vp, _i32, _i32]),
     "nq_selftest_ciede": (_i32, [_vp, _vp, _i64, _vp]),
@@ -241,6 +242,13 @@ class PnnQuantizer:
         self._check(self._L.nq_get_team_stats(self._h, a))
         return dict(zip(["published", "used", "timeouts", "wait_ticks_100MHz", "helpers", "speculating_at_end", "cache_hits_top", "virtual_merges_used",
                          "sift_ticks", "merge_ticks", "top_fetch_ticks", "pops", "epilogue_ticks", "select_ticks", "declined", "gave_up"], list(a)))
+
+    def merge_variant(self):
+        """(workgroup-size code, helpers per loop) of the merge kernel the last merge launch ran for this quantizer's job
+        (nq_get_merge_variant): 512 / 256 / 128, or 127 for the dense variant; (0, 0) when the last palette needed no merge loop."""
+        threads, helpers = C.c_int32(0), C.c_int32(0)
+        self._check(self._L.nq_get_merge_variant(self._h, C.byref(threads), C.byref(helpers)))
+        return threads.value, helpers.value
 
     def batch_phase_ms(self):
         """Phases of the last batch call this quantizer was the FIRST handle of: {prepare, merge, finish, total} in ms (nq_get_batch_phase_ms)."""
