@@ -236,6 +236,34 @@ int nq_encode_gif(nq_handle* h, int n, const uint16_t* const* index, const int32
                   const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
                   uint8_t* out, int64_t cap, int64_t* out_size);
 
+/* ---- GIF encoding, delta mode: an animation whose frames store only what changed.  All n frames are width x height.  Frame 0 is
+ *      written whole; frame i >= 1 is the bounding rectangle of the pixels where index map i differs from index map i - 1, and the
+ *      unchanged pixels inside it are transparent.  Every frame has disposal 1 ("keep"), so the canvas after frame i - 1 is frame i - 1
+ *      and a decoder composes frame i exactly.  What makes static regions repeat from frame to frame is the caller's business: with
+ *      NQ_MODE_PARALLEL_TILED and equal seeds a tile whose input pixels did not change gives the same indices again.
+ *  * n = 1: the file is byte for byte nq_encode_gif's, out_rects = {0, 0, width, height}.  The rest of this list is n > 1.
+ *  * A palette entry with alpha 0 is NQ_ERR_INVALID before any device work: real transparency cannot be un-painted under "keep";
+ *    use nq_encode_gif.  Other alpha values are dropped.
+ *  * u, the "unchanged" index: u = K when K <= 255; none when K = 256, then frames are cropped only.  Kt = K + 1 when u exists, else K.
+ *    N and m follow nq_encode_gif's rules applied to Kt.  Colour table as there (entry u is 0, 0, 0), background index 0, loop block
+ *    as there.
+ *  * Every frame has a graphic control extension: packed = 1 << 2 | (u exists), delays_cs[i], transparent index u (none: 0).
+ *  * Frame i >= 1: D = the pixels with index_i != index_(i-1); the rectangle is D's bounding box, 1 x 1 at (0, 0) when D is empty.
+ *    The body is the rectangle row-major: index_i, with every pixel outside D replaced by u when u exists.  The body is cut into
+ *    segment_pixels segments and LZW-coded exactly as nq_encode_gif does with a frame.
+ *  * nq_gif_max_bytes(n, widths, heights, 256, segment_pixels) with every width / height equal to width / height bounds the file:
+ *    no rectangle is larger than its frame and Kt <= 256.
+ *  * out_rects (NULL: not wanted): 4 ints per frame, x, y, w, h of its rectangle, written on success.
+ *  * Checks, cap / *out_size and the two memory forms as for nq_encode_gif; an index >= K in any frame is reported after the
+ *    difference pass.  The index maps are never written.  The handle stays usable after any error.
+ *  The bit-exact definition and the kernels: DESIGN.md "GIF encoder, delta mode". ---- */
+int nq_encode_gif_delta_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height,
+                               const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
+                               uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
+int nq_encode_gif_delta(nq_handle* h, int n, const uint16_t* const* index, int width, int height,
+                        const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
+                        uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
+
 /* ---- PNG encoding: palette index maps (what the convert calls write to out_index) to indexed PNG files, on the GPU.  One call encodes
  *      n independent images into n files (n = 1 is the plain case; a batch fills the chip).  Image i is a uint16 index map, row-major,
  *      widths[i] x heights[i], with its own K[i] <= 256 and its own palette: the K[i] ARGB entries at palettes[i * palette_stride]

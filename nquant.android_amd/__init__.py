@@ -8,7 +8,8 @@ from .host import (NQ_KIND_RGB, NQ_KIND_LAB, MODE_REFERENCE_SEQUENTIAL, MODE_PAR
                    NqError, Params, PnnQuantizer, PnnLABQuantizer, QuantizedImage, load_library, library_path,
                    abi_symbols, convert_batch_device, convert_batch_host, convert_frames, convert_frames_device,
                    pnnquan_frames_device)
-from .gif import convert_frames_to_gif, encode_gif, encode_gif_device, gif_max_bytes, write_gif
+from .gif import (convert_frames_to_gif, encode_gif, encode_gif_delta, encode_gif_delta_device, encode_gif_device, gif_max_bytes,
+                  write_gif)
 from .png import convert_to_png, encode_png, encode_png_device, png_max_bytes, write_png
 from .build import build as build_library
 
@@ -16,4 +17,5 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "NqError", "Params", "PnnQuantizer", "PnnLABQuantizer", "QuantizedImage", "load_library", "library_path",
            "abi_symbols", "build_library", "convert_batch_device", "convert_batch_host", "convert_frames",
            "convert_frames_device", "pnnquan_frames_device", "encode_gif", "encode_gif_device", "write_gif", "convert_frames_to_gif",
-           "gif_max_bytes", "encode_png", "encode_png_device", "write_png", "convert_to_png", "png_max_bytes"]
+           "encode_gif_delta", "encode_gif_delta_device", "gif_max_bytes", "encode_png", "encode_png_device", "write_png",
+           "convert_to_png", "png_max_bytes"]

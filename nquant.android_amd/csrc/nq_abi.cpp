@@ -6,6 +6,7 @@
 #include "../../include/nquant_abi.h"
 #include "nq_kernels.h"
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -222,6 +223,14 @@ struct nq_handle {
     DevBuf<unsigned char> gif_blob, gif_file;
     DevBuf<unsigned short> gif_in;
     std::vector<uint8_t> h_gif_blob;
+    // nq_encode_gif_delta_device: the frames' pointers, the changed pixels' boxes ({min x, min y, max x, max y}[n - 1], bad-index flag),
+    // the body table and the cropped bodies the LZW chains read
+    std::vector<int> h_gif_box;
+    std::vector<nq::GifDelta> h_gif_delta;
+    DevBuf<const unsigned short*> gif_ptrs;
+    DevBuf<int> gif_box;
+    DevBuf<nq::GifDelta> d_gif_delta;
+    DevBuf<unsigned short> gif_body;
     // nq_encode_png_device: image table, token scratch of the resident chains, IDAT CRC registers; bit strings, bit lengths / offsets,
     // read-back, header blob, files and uploaded index maps live in the GIF buffers above (one encoder runs at a time on a handle)
     std::vector<nq::PngImage> h_png;
@@ -1849,24 +1858,28 @@ int gif_check_index(nq_handle* h, int n, const uint16_t* const* index) {
     return NQ_OK;
 }
 
-int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights, const uint32_t* palette,
-               int K, const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size) {
+// where a frame sits on the screen
+struct GifRect { int x, y, w, h; };
+
+// The file of n index maps (device memory, map i is rects[i].w x rects[i].h and drawn at rects[i].x, rects[i].y) on a W x H screen.
+// Kt sizes the colour table and the code size (K palette entries + the delta mode's unchanged index); gce < 0: no graphic control
+// extensions, else their packed byte; tr: their transparent index byte and the screen's background index.  The caller has zeroed
+// nothing: the bad-index flag is this function's own.
+int gif_encode_maps(nq_handle* h, int n, const uint16_t* const* d_index, const GifRect* rects, int W, int H, const uint32_t* palette, int K,
+                    int Kt, int gce, int tr, int bg, const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap,
+                    int64_t* out_size) {
     int N = 0;
-    while ((1 << (N + 1)) < std::max(K, 2)) ++N;
+    while ((1 << (N + 1)) < std::max(Kt, 2)) ++N;
     const int m = std::max(2, N + 1);
-    int t = -1;                                     // GIF has 1-bit transparency: the first entry with alpha 0, other alphas are dropped
-    for (int i = 0; i < K && t < 0; ++i) if ((palette[i] >> 24) == 0) t = i;
     // frame table: segments and their scratch
     h->h_gif.assign(n, nq::GifFrame{});
     long long segs = 0, words = 0;
-    int W = 0, H = 0;
     for (int i = 0; i < n; ++i) {
         nq::GifFrame& F = h->h_gif[i];
-        const long long px = (long long) widths[i] * heights[i], S = gif_seg_len(px, segment_pixels);
+        const long long px = (long long) rects[i].w * rects[i].h, S = gif_seg_len(px, segment_pixels);
         F.index = d_index[i]; F.npix = px; F.seg_len = (int) S;
         F.nseg = (px + S - 1) / S; F.seg_base = segs; F.seg_words = gif_seg_bits_max(S) / 32 + 2; F.word_base = words;
         segs += F.nseg; words += F.nseg * F.seg_words;
-        W = std::max(W, (int) widths[i]); H = std::max(H, (int) heights[i]);
     }
     NQ_HIP(h, h->d_gif.reserve(n));
     NQ_HIP(h, h->gif_words.reserve((size_t) words));
@@ -1874,7 +1887,7 @@ int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
     NQ_HIP(h, h->gif_res.reserve((size_t) n + 1));
     NQ_HIP(h, hipMemcpyAsync(h->d_gif.p, h->h_gif.data(), n * sizeof(nq::GifFrame), hipMemcpyHostToDevice, h->stream));
     NQ_HIP(h, hipMemsetAsync(h->gif_res.p + n, 0, sizeof(unsigned long long), h->stream));
-    launch_gif_lzw(h->d_gif.p, n, segs, K, m, h->gif_words.p, h->gif_bits.p, h->gif_res.p + n, h->stream);
+    launch_gif_lzw(h->d_gif.p, n, segs, Kt, m, h->gif_words.p, h->gif_bits.p, h->gif_res.p + n, h->stream);
     launch_gif_scan(h->d_gif.p, n, h->gif_bits.p, h->gif_bits.p + segs, h->gif_res.p, h->stream);
     NQ_HIP(h, launch_status());
     std::vector<unsigned long long> res((size_t) n + 1);
@@ -1887,7 +1900,7 @@ int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
     auto u16 = [&](int v) { blob.push_back((uint8_t) (v & 255)); blob.push_back((uint8_t) (v >> 8)); };
     blob.insert(blob.end(), {'G', 'I', 'F', '8', '9', 'a'});
     u16(W); u16(H);
-    blob.push_back((uint8_t) (0xF0 | N)); blob.push_back((uint8_t) (t >= 0 ? t : 0)); blob.push_back(0);
+    blob.push_back((uint8_t) (0xF0 | N)); blob.push_back((uint8_t) bg); blob.push_back(0);
     for (int i = 0; i < (1 << (N + 1)); ++i) {
         const uint32_t c = i < K ? palette[i] : 0;
         blob.push_back((uint8_t) (c >> 16)); blob.push_back((uint8_t) (c >> 8)); blob.push_back((uint8_t) c);
@@ -1900,11 +1913,11 @@ int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
     for (int i = 0; i < n; ++i) {
         nq::GifFrame& F = h->h_gif[i];
         const size_t start = i == 0 ? 0 : blob.size();
-        if (n > 1 || t >= 0) {
-            blob.insert(blob.end(), {0x21, 0xF9, 0x04, (uint8_t) ((n > 1 ? 2 << 2 : 0) | (t >= 0 ? 1 : 0))});
-            u16(delays_cs ? delays_cs[i] : 0); blob.push_back((uint8_t) (t >= 0 ? t : 0)); blob.push_back(0);
+        if (gce >= 0) {
+            blob.insert(blob.end(), {0x21, 0xF9, 0x04, (uint8_t) gce});
+            u16(delays_cs ? delays_cs[i] : 0); blob.push_back((uint8_t) tr); blob.push_back(0);
         }
-        blob.push_back(0x2C); u16(0); u16(0); u16(widths[i]); u16(heights[i]); blob.push_back(0);
+        blob.push_back(0x2C); u16(rects[i].x); u16(rects[i].y); u16(rects[i].w); u16(rects[i].h); blob.push_back(0);
         blob.push_back((uint8_t) m);
         F.prefix_off = (long long) start; F.prefix_len = (int) (blob.size() - start);
         F.data_bytes = (long long) ((res[i] + 7) / 8); F.stream_len = gif_stream_len(F.data_bytes);
@@ -1923,6 +1936,100 @@ int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
     NQ_HIP(h, hipMemcpyAsync(out, h->gif_file.p, (size_t) total, hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
     return NQ_OK;
+}
+
+// nq_encode_gif_device: whole frames at (0, 0), disposal 2
+int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights, const uint32_t* palette,
+               int K, const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size) {
+    int t = -1;                                     // GIF has 1-bit transparency: the first entry with alpha 0, other alphas are dropped
+    for (int i = 0; i < K && t < 0; ++i) if ((palette[i] >> 24) == 0) t = i;
+    std::vector<GifRect> rects(n);
+    int W = 0, H = 0;
+    for (int i = 0; i < n; ++i) {
+        rects[i] = {0, 0, (int) widths[i], (int) heights[i]};
+        W = std::max(W, (int) widths[i]); H = std::max(H, (int) heights[i]);
+    }
+    const int gce = n > 1 || t >= 0 ? (n > 1 ? 2 << 2 : 0) | (t >= 0 ? 1 : 0) : -1;
+    return gif_encode_maps(h, n, d_index, rects.data(), W, H, palette, K, K, gce, t >= 0 ? t : 0, t >= 0 ? t : 0, delays_cs, loop_count,
+                           segment_pixels, out, cap, out_size);
+}
+
+// nq_encode_gif_delta_device after the argument checks (n >= 2): difference pass, one read-back of the boxes, body pass, then the
+// bodies are encoded like any index maps
+int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, const uint32_t* palette, int K,
+                     const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size,
+                     int32_t* out_rects) {
+    const int u = K <= 255 ? K : -1;                // the "unchanged" index, transparent in every frame
+    std::vector<int>& box = h->h_gif_box;
+    box.assign(4 * (size_t) (n - 1) + 1, 0);
+    for (int i = 0; i < n - 1; ++i) { box[4 * i] = box[4 * i + 1] = INT_MAX; box[4 * i + 2] = box[4 * i + 3] = -1; }
+    NQ_HIP(h, h->gif_ptrs.reserve(n));
+    NQ_HIP(h, h->gif_box.reserve(box.size()));
+    NQ_HIP(h, hipMemcpyAsync(h->gif_ptrs.p, d_index, n * sizeof(*d_index), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemcpyAsync(h->gif_box.p, box.data(), box.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    launch_gif_diff(h->gif_ptrs.p, n, W, H, K, h->gif_box.p, h->gif_box.p + 4 * (size_t) (n - 1), h->stream);
+    NQ_HIP(h, launch_status());
+    NQ_HIP(h, hipMemcpyAsync(box.data(), h->gif_box.p, box.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    if (box[4 * (size_t) (n - 1)]) NQ_FAIL(h, NQ_ERR_INVALID, "an index map holds an index >= K = %d", K);
+    std::vector<GifRect> rects(n);
+    rects[0] = {0, 0, W, H};
+    size_t room = 0;
+    long long max_area = 1;
+    for (int i = 1; i < n; ++i) {
+        const int* b = &box[4 * (size_t) (i - 1)];
+        GifRect& r = rects[i];
+        if (b[2] < 0) r = {0, 0, 1, 1};             // nothing changed
+        else r = {b[0], b[1], b[2] - b[0] + 1, b[3] - b[1] + 1};
+        if (r.x < 0 || r.y < 0 || r.w < 1 || r.h < 1 || r.x + r.w > W || r.y + r.h > H)
+            NQ_FAIL(h, NQ_ERR_HIP, "frame %d: the difference pass returned the box %d %d %d %d", i, b[0], b[1], b[2], b[3]);
+        const long long area = (long long) r.w * r.h;
+        room += (size_t) ((area + 7) & ~7ll);
+        max_area = std::max(max_area, area);
+    }
+    NQ_HIP(h, h->gif_body.reserve(room));
+    NQ_HIP(h, h->d_gif_delta.reserve(n - 1));
+    h->h_gif_delta.assign(n - 1, nq::GifDelta{});
+    std::vector<const uint16_t*> maps(n);
+    maps[0] = d_index[0];
+    size_t at = 0;
+    for (int i = 1; i < n; ++i) {
+        const GifRect& r = rects[i];
+        h->h_gif_delta[i - 1] = {d_index[i], d_index[i - 1], h->gif_body.p + at, r.x, r.y, r.w, r.h};
+        maps[i] = h->gif_body.p + at;
+        at += (size_t) (((long long) r.w * r.h + 7) & ~7ll);
+    }
+    NQ_HIP(h, hipMemcpyAsync(h->d_gif_delta.p, h->h_gif_delta.data(), (n - 1) * sizeof(nq::GifDelta), hipMemcpyHostToDevice, h->stream));
+    launch_gif_body(h->d_gif_delta.p, n - 1, W, u, max_area, h->stream);
+    NQ_HIP(h, launch_status());
+    // The chains below check against Kt, so an index == K in frame 0 (read in place, not through a body) passes them: it is the
+    // difference pass above that has checked frame 0, as the predecessor of frame 1, and every other frame against K.
+    const int rc = gif_encode_maps(h, n, maps.data(), rects.data(), W, H, palette, K, K + (u >= 0 ? 1 : 0), 1 << 2 | (u >= 0 ? 1 : 0),
+                                   u >= 0 ? u : 0, 0, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    if (rc) return rc;
+    if (out_rects)
+        for (int i = 0; i < n; ++i) { out_rects[4 * i] = rects[i].x; out_rects[4 * i + 1] = rects[i].y; out_rects[4 * i + 2] = rects[i].w; out_rects[4 * i + 3] = rects[i].h; }
+    return NQ_OK;
+}
+
+// the checks both delta forms share, done from the host arguments alone; ws / hs: the size repeated per frame for the shared checks
+int gif_delta_check(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
+                    const int32_t* delays_cs, int loop_count, int segment_pixels, const uint8_t* out, int64_t cap, int64_t* out_size,
+                    std::vector<int32_t>* ws, std::vector<int32_t>* hs) {
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    ws->assign(n, width); hs->assign(n, height);
+    int rc = gif_check(h, n, ws->data(), hs->data(), palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    if (rc) return rc;
+    if (n > 1)
+        for (int i = 0; i < K; ++i)
+            if ((palette[i] >> 24) == 0)
+                NQ_FAIL(h, NQ_ERR_INVALID, "palette entry %d is transparent (alpha 0): frames that keep the canvas cannot un-paint a pixel, "
+                        "use nq_encode_gif", i);
+    return gif_check_index(h, n, index);
+}
+
+void gif_whole_rect(int32_t* out_rects, int width, int height) {
+    if (out_rects) { out_rects[0] = out_rects[1] = 0; out_rects[2] = width; out_rects[3] = height; }
 }
 
 } // namespace
@@ -1971,6 +2078,45 @@ int nq_encode_gif(nq_handle* h, int n, const uint16_t* const* index, const int32
     return host_form(h, [&]() {
         rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
         return rc ? rc : gif_encode(h, n, dev.data(), widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    });
+}
+
+int nq_encode_gif_delta_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height, const uint32_t* palette, int K,
+                               const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size,
+                               int32_t* out_rects) {
+    if (!h) return NQ_ERR_INVALID;
+    std::vector<int32_t> ws, hs;
+    int rc = gif_delta_check(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size, &ws, &hs);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    if (n > 1)
+        return gif_encode_delta(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size, out_rects);
+    rc = gif_encode(h, n, d_index, ws.data(), hs.data(), palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    if (rc == NQ_OK) gif_whole_rect(out_rects, width, height);
+    return rc;
+}
+
+int nq_encode_gif_delta(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
+                        const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size,
+                        int32_t* out_rects) {
+    if (!h) return NQ_ERR_INVALID;
+    std::vector<int32_t> ws, hs;
+    int rc = gif_delta_check(h, n, index, width, height, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size, &ws, &hs);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    std::vector<size_t> px(n, (size_t) width * height);
+    std::vector<uint16_t*> dev(n);
+    return host_form(h, [&]() {
+        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
+        if (rc) return rc;
+        if (n > 1)
+            return gif_encode_delta(h, n, dev.data(), width, height, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size,
+                                    out_rects);
+        rc = gif_encode(h, n, dev.data(), ws.data(), hs.data(), palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+        if (rc == NQ_OK) gif_whole_rect(out_rects, width, height);
+        return rc;
     });
 }
 

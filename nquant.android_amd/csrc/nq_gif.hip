@@ -7,6 +7,10 @@
 //   gif_scan_kernel    per frame: exclusive scan of the segments' bit lengths, the frame's bit length
 //   gif_gather_kernel  one thread per byte of the file: header bytes from the host's blob, sub-block length bytes, and the data
 //                      bytes ORed together from the <= 3 segments each one overlaps
+// Delta mode (nq_encode_gif_delta_device) puts two passes in front: the frames after the first become cropped bodies in scratch, and
+// the three kernels above run on those as on any index map.
+//   gif_diff_kernel    frame f against frame f - 1: bounding box of the changed pixels (and the index >= K check of all frames)
+//   gif_body_kernel    the box's pixels, row-major, the unchanged ones replaced by the transparent index
 #include "nq_kernels.h"
 
 namespace nq {
@@ -211,7 +215,120 @@ __global__ void __launch_bounds__(256) gif_gather_kernel(const GifFrame* __restr
     }
 }
 
+// ---- delta mode ----
+
+// the 16 bytes at byte address addr (2-byte aligned, no more), put together from the two aligned chunks around them; the elements
+// outside [lo, hi) read as 0 and are never loaded.  addr is the same in every lane modulo 16, so the branches are uniform.
+__device__ inline uint4 load_chunk_at(uintptr_t addr, uintptr_t lo, uintptr_t hi) {
+    const uintptr_t a = addr & ~(uintptr_t) 15;
+    const unsigned sh = (unsigned) (addr & 15);
+    const uint4 A = load_chunk(a, lo, hi);
+    if (sh == 0) return A;
+    const uint4 B = load_chunk(a + 16, lo, hi);
+    const unsigned v[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
+    const unsigned d = sh >> 2;
+    const bool half = (sh & 2) != 0;
+    unsigned r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        unsigned l = v[k], u = v[k + 1];
+#pragma unroll
+        for (int t = 1; t < 4; ++t)
+            if (d == (unsigned) t) { l = v[k + t]; u = v[k + t + 1]; }
+        r[k] = half ? (l >> 16 | u << 16) : l;
+    }
+    return make_uint4(r[0], r[1], r[2], r[3]);
+}
+
+__device__ inline bool pair_bad(unsigned v, unsigned K) { return (v & 0xFFFFu) >= K || (v >> 16) >= K; }
+
+// Frame f >= 1 against frame f - 1, eight pixels (one aligned 16-byte chunk of frame f) per thread and step: the bounding box of the
+// pixels that differ, reduced over the wave and added to box[4 * (f - 1) ..] with one atomic min / max per wave that saw a difference.
+// blockIdx.y strides over the frames, blockIdx.x over a frame's chunks.  W * H < 2^32, so pixel numbers fit an unsigned.
+__global__ void __launch_bounds__(256) gif_diff_kernel(const unsigned short* const* __restrict__ index, int n_frames, int W, long long npix,
+                                                       int K, int* __restrict__ box, int* __restrict__ bad) {
+    bool badc = false;
+    for (int f = (int) blockIdx.y + 1; f < n_frames; f += (int) gridDim.y) {
+        const uintptr_t clo = reinterpret_cast<uintptr_t>(index[f]), chi = clo + 2 * (uintptr_t) npix;
+        const uintptr_t plo = reinterpret_cast<uintptr_t>(index[f - 1]), phi = plo + 2 * (uintptr_t) npix;
+        const uintptr_t a0 = clo & ~(uintptr_t) 15;
+        const long long nchunk = (long long) ((chi - a0 + 15) >> 4);
+        int x0 = 0x7FFFFFFF, y0 = 0x7FFFFFFF, x1 = -1, y1 = -1;
+        for (long long c = (long long) blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (long long) gridDim.x * blockDim.x) {
+            const uintptr_t a = a0 + 16 * (uintptr_t) c;
+            const long long p0 = ((long long) a - (long long) clo) / 2;          // pixel of the chunk's first element: -7 .. npix - 1
+            const uint4 cu = load_chunk(a, clo, chi);
+            const uint4 pv = load_chunk_at(plo + (uintptr_t) (2 * p0), plo, phi);
+            badc = badc || pair_bad(cu.x, K) || pair_bad(cu.y, K) || pair_bad(cu.z, K) || pair_bad(cu.w, K)
+                        || pair_bad(pv.x, K) || pair_bad(pv.y, K) || pair_bad(pv.z, K) || pair_bad(pv.w, K);
+            const unsigned dx[4] = {cu.x ^ pv.x, cu.y ^ pv.y, cu.z ^ pv.z, cu.w ^ pv.w};
+            if ((dx[0] | dx[1] | dx[2] | dx[3]) == 0) continue;                  // (elements outside the frames are 0 in both)
+            const unsigned first = p0 > 0 ? (unsigned) p0 : 0u;
+            int y = (int) (first / (unsigned) W), x = (int) (first % (unsigned) W);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (p0 + j < 0) continue;
+                if ((dx[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) {
+                    x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
+                }
+                if (++x == W) { x = 0; ++y; }
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            x0 = min(x0, __shfl_xor(x0, d)); y0 = min(y0, __shfl_xor(y0, d));
+            x1 = max(x1, __shfl_xor(x1, d)); y1 = max(y1, __shfl_xor(y1, d));
+        }
+        if ((threadIdx.x & 63) == 0 && x1 >= 0) {
+            int* b = box + 4 * (f - 1);
+            atomicMin(b + 0, x0); atomicMin(b + 1, y0); atomicMax(b + 2, x1); atomicMax(b + 3, y1);
+        }
+    }
+    if (badc) *bad = 1;                            // (every thread that stores, stores the same value)
+}
+
+// Body of frame f's rectangle: eight consecutive body pixels per thread, one 16-byte store.  The sources are read element by element
+// (a rectangle's rows start anywhere); both reads stay inside the frame because the rectangle does.
+__global__ void __launch_bounds__(256) gif_body_kernel(const GifDelta* __restrict__ delta, int n_bodies, int W, int u) {
+    for (int f = (int) blockIdx.y; f < n_bodies; f += (int) gridDim.y) {
+        const GifDelta D = delta[f];
+        const unsigned area = (unsigned) D.w * (unsigned) D.h;                   // <= W * H < 2^32
+        const long long nchunk = ((long long) area + 7) >> 3;
+        for (long long c = (long long) blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (long long) gridDim.x * blockDim.x) {
+            const unsigned e0 = (unsigned) (8 * c);
+            unsigned r = e0 / (unsigned) D.w, col = e0 % (unsigned) D.w;
+            unsigned v[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if ((long long) e0 + j < (long long) area) {
+                    const size_t src = (size_t) (D.y + (int) r) * (size_t) W + (size_t) (D.x + (int) col);
+                    const unsigned cv = D.cur[src], pv = D.prev[src];
+                    v[j >> 1] |= (u >= 0 && cv == pv ? (unsigned) u : cv) << (16 * (j & 1));
+                }
+                if (++col == (unsigned) D.w) { col = 0; ++r; }
+            }
+            reinterpret_cast<uint4*>(D.body)[c] = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+    }
+}
+
 } // namespace
+
+void launch_gif_diff(const unsigned short* const* d_index, int n_frames, int W, int H, int K, int* d_box, int* d_bad, hipStream_t s) {
+    const long long npix = (long long) W * H;
+    long long gx = ((npix + 7) / 8 + 1 + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    const int gy = n_frames - 1 < 65535 ? n_frames - 1 : 65535;
+    hipLaunchKernelGGL(gif_diff_kernel, dim3((unsigned) gx, (unsigned) gy), dim3(256), 0, s, d_index, n_frames, W, npix, K, d_box, d_bad);
+}
+
+void launch_gif_body(const GifDelta* d_delta, int n_bodies, int W, int u, long long max_area, hipStream_t s) {
+    long long gx = ((max_area + 7) / 8 + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    if (gx < 1) gx = 1;
+    const int gy = n_bodies < 65535 ? n_bodies : 65535;
+    hipLaunchKernelGGL(gif_body_kernel, dim3((unsigned) gx, (unsigned) gy), dim3(256), 0, s, d_delta, n_bodies, W, u);
+}
 
 void launch_gif_lzw(const GifFrame* d_frames, int n_frames, long long n_segs, int K, int m, unsigned* d_words, unsigned long long* d_seg_bits,
                     unsigned long long* d_bad, hipStream_t s) {

@@ -211,6 +211,20 @@ void launch_gif_scan(const GifFrame* d_frames, int n_frames, const unsigned long
 void launch_gif_gather(const GifFrame* d_frames, int n_frames, const unsigned* d_words, const unsigned long long* d_seg_bits,
                        const unsigned long long* d_seg_off, const unsigned char* d_blob, unsigned char* d_file, long long total, hipStream_t s);
 
+// ---- GIF delta mode (nq_gif.hip): n frames of one size W x H.  Frame f >= 1 is compared with frame f - 1; its body is the changed
+// pixels' bounding rectangle, row-major, with the unchanged pixels replaced by the index u (u < 0: kept) ----
+struct GifDelta {
+    const unsigned short* cur;     // frame f and frame f - 1, 2-byte aligned
+    const unsigned short* prev;
+    unsigned short* body;          // 16-byte aligned, room for w * h rounded up to a multiple of 8 elements
+    int x, y, w, h;                // the rectangle, inside the frame
+};
+// box[4 * (f - 1) ..] = {min x, min y, max x, max y} of the pixels where frame f differs from frame f - 1, reduced with atomic min /
+// max into what the caller put there ({INT_MAX, INT_MAX, -1, -1}); *d_bad = 1 when an index >= K was met in any frame (n >= 2)
+void launch_gif_diff(const unsigned short* const* d_index, int n_frames, int W, int H, int K, int* d_box, int* d_bad, hipStream_t s);
+// bodies of the n_bodies rectangles in d_delta (max_area: the largest w * h among them)
+void launch_gif_body(const GifDelta* d_delta, int n_bodies, int W, int u, long long max_area, hipStream_t s);
+
 // ---- PNG encoding (nq_png.hip): image i's raw stream (per row a filter byte 0 + the indices packed at `depth` bits) is cut into
 // segments of seg_len bytes (the last one shorter); segment s of the image is chain seg_base + s of the call and writes its deflate
 // block to words[word_base + s * seg_words ...].  file_off .. crc_base place the image's file in the output (filled in after the bit

@@ -1,6 +1,10 @@
 """GIF89a files from the quantizer's index maps, encoded on the GPU (nq_encode_gif / nq_encode_gif_device, include/nquant_abi.h
 "GIF encoding").  One global colour table for all frames: the palette convert() or convert_frames() returned (K <= 256).  GIF has
 1-bit transparency: the first palette entry whose alpha is 0 becomes the transparent index, other alpha values are dropped.
+Delta mode (nq_encode_gif_delta / nq_encode_gif_delta_device, "GIF encoding, delta mode"): frames of one size, each after the first
+stored as the rectangle that changed with the unchanged pixels transparent.  Static regions repeat from frame to frame only when the
+dither makes them repeat: MODE_PARALLEL_TILED with equal seeds for all frames does (a tile's chain depends on its pixels, its
+position and the seed alone).
 There is no CPU fallback: without a HIP device every call raises NqError with status -5 (NQ_ERR_NO_DEVICE)."""
 import ctypes as C
 
@@ -74,6 +78,31 @@ def _encode(L, handle, entry, ptrs, w, h, palette, delays_cs, loop, segment_pixe
     return buf[:size.value].tobytes()
 
 
+def _encode_delta(L, handle, entry, ptrs, width, height, palette, delays_cs, loop, segment_pixels, check):
+    """The delta entry points: one size for all frames.  Returns (file bytes, rectangles as an (n, 4) int32 array of x, y, w, h)."""
+    n = len(ptrs)
+    pal = _palette(palette)
+    d = _delays(delays_cs, n)
+    try:
+        cap = gif_max_bytes([width] * n, [height] * n, 256, segment_pixels)
+    except NqError:
+        cap = 0                                     # (bad sizes: the encode call below says which)
+    buf = np.empty(max(cap, 1), np.uint8)
+    rects = np.zeros((max(n, 1), 4), np.int32)
+    size = C.c_int64(0)
+    src = (C.c_void_p * max(n, 1))(*[int(p) for p in ptrs])
+    check(getattr(L, entry)(handle, n, src, int(width), int(height), pal.ctypes.data, int(pal.size), d.ctypes.data if d is not None else None,
+                            int(loop), int(segment_pixels), buf.ctypes.data, int(cap), C.byref(size), rects.ctypes.data))
+    return buf[:size.value].tobytes(), rects[:n]
+
+
+def _one_size(maps):
+    shapes = {a.shape for a in maps}
+    if len(shapes) != 1:
+        raise ValueError("delta mode: all frames must have one size, got %s" % sorted(shapes))
+    return maps[0].shape
+
+
 class _Handle:
     """A bare library handle (the GIF calls use only its stream, scratch and error text)."""
 
@@ -117,19 +146,49 @@ def encode_gif_device(q, d_index_ptrs, widths, heights, palette, delays_cs=None,
     return _encode(q._L, q._h, "nq_encode_gif_device", list(d_index_ptrs), w, h, palette, delays_cs, loop, segment_pixels, q._check)
 
 
-def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0):
-    """encode_gif, written to `path`.  Returns the number of bytes written."""
-    data = encode_gif(indices, palette, delays_cs, loop, segment_pixels, device)
+def encode_gif_delta(indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0, return_rects=False):
+    """nq_encode_gif_delta: as encode_gif, but all frames have one size, every frame after the first stores only the bounding rectangle
+    of the pixels that differ from the frame before, and the unchanged pixels in it are transparent (index K; K = 256: cropped only).
+    A palette entry with alpha 0 is an error when there are two frames or more.  Returns the file; with return_rects=True the pair
+    (file, (n, 4) int32 array of every frame's x, y, w, h)."""
+    maps = _index_maps(indices)
+    height, width = _one_size(maps)
+    hd = _Handle(device)
+    try:
+        data, rects = _encode_delta(hd._L, hd._h, "nq_encode_gif_delta", [a.ctypes.data for a in maps], width, height, palette, delays_cs,
+                                    loop, segment_pixels, hd._check)
+    finally:
+        hd.close()
+    return (data, rects) if return_rects else data
+
+
+def encode_gif_delta_device(q, d_index_ptrs, width, height, palette, delays_cs=None, loop=0, segment_pixels=0, return_rects=False):
+    """nq_encode_gif_delta_device on the handle of quantizer `q`: d_index_ptrs[i] is the HIP device address of frame i's uint16 index
+    map (width x height, 2-byte aligned; never written).  Arguments and result otherwise as encode_gif_delta."""
+    if len(d_index_ptrs) == 0:
+        raise ValueError("no frames")
+    data, rects = _encode_delta(q._L, q._h, "nq_encode_gif_delta_device", list(d_index_ptrs), width, height, palette, delays_cs, loop,
+                                segment_pixels, q._check)
+    return (data, rects) if return_rects else data
+
+
+def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0, delta=False):
+    """encode_gif (delta=True: encode_gif_delta), written to `path`.  Returns the number of bytes written."""
+    data = (encode_gif_delta if delta else encode_gif)(indices, palette, delays_cs, loop, segment_pixels, device)
     with open(path, "wb") as f:
         f.write(data)
     return len(data)
 
 
 def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
-                          seeds=None, tile=None):
+                          seeds=None, tile=None, delta=False):
     """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
+    delta=True: encode_gif_delta instead; the frames must have one size.  Seeds are passed on as given: regions that do not move repeat
+    in the index maps, and so drop out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.
     Returns (file bytes, palette)."""
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
+    if delta and len({np.asarray(f).shape for f in frames}) > 1:
+        raise ValueError("delta mode: all frames must have one size")
     palette, outs = convert_frames(kind, frames, nMaxColors, dither, device=device, mode=mode, seeds=seeds, tile=tile)
-    return encode_gif([o.index for o in outs], palette, delays_cs, loop, segment_pixels, device), palette
+    return (encode_gif_delta if delta else encode_gif)([o.index for o in outs], palette, delays_cs, loop, segment_pixels, device), palette

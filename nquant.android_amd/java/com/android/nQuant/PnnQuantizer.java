@@ -103,21 +103,45 @@ public class PnnQuantizer {
 	private static native long nqEncodeGif(long h, java.nio.ShortBuffer[] index, int[] widths, int[] heights, int[] palette, int[] delaysCs,
 			int loopCount, java.nio.ByteBuffer out, long cap);
 
+	/** encodeGif in delta mode (nq_encode_gif_delta): all frames are width x height; every frame after the first stores only the
+	 *  rectangle that differs from the frame before, its unchanged pixels transparent, and keeps the canvas.  With two frames or more
+	 *  the palette must not hold an entry with alpha 0. */
+	public static byte[] encodeGifDelta(java.nio.ShortBuffer[] index, int width, int height, int[] palette, int[] delaysCs, int loopCount) {
+		int[] widths = new int[index.length], heights = new int[index.length];
+		java.util.Arrays.fill(widths, width);
+		java.util.Arrays.fill(heights, height);
+		java.nio.ByteBuffer out = gifBuffer(widths, heights);
+		long h = nqCreate(0, 0);
+		try {
+			return gifBytes(out, nqEncodeGifDelta(h, index, width, height, palette, delaysCs, loopCount, out, out.capacity()));
+		} finally {
+			nqDestroy(h);
+		}
+	}
+	private static native long nqEncodeGifDelta(long h, java.nio.ShortBuffer[] index, int width, int height, int[] palette, int[] delaysCs,
+			int loopCount, java.nio.ByteBuffer out, long cap);
+
 	/** convertFrames (one shared palette, every frame dithered with it) followed by encodeGif of the index maps, in one native call;
 	 *  nMaxColors <= 256.  in[i] are DIRECT buffers of widths[i]*heights[i] ARGB ints. */
 	public static byte[] convertFramesToGif(int kind, java.nio.IntBuffer[] in, int[] widths, int[] heights, int nMaxColors, boolean dither,
 			long[] seeds, int[] delaysCs, int loopCount) {
+		return convertFramesToGif(kind, in, widths, heights, nMaxColors, dither, seeds, delaysCs, loopCount, false);
+	}
+	/** The same with delta = true: encodeGifDelta of the index maps; the frames must have one size.  Regions that do not move drop out
+	 *  of the file when the seeds are equal (the tiled dither then repeats their indices from frame to frame). */
+	public static byte[] convertFramesToGif(int kind, java.nio.IntBuffer[] in, int[] widths, int[] heights, int nMaxColors, boolean dither,
+			long[] seeds, int[] delaysCs, int loopCount, boolean delta) {
 		java.nio.ByteBuffer out = gifBuffer(widths, heights);
 		long h = nqCreate(kind, 0);
 		try {
 			return gifBytes(out, nqConvertFramesToGif(h, in, widths, heights, nMaxColors, dither, seeds, MODE_PARALLEL_TILED, delaysCs,
-					loopCount, out, out.capacity()));
+					loopCount, delta, out, out.capacity()));
 		} finally {
 			nqDestroy(h);
 		}
 	}
 	private static native long nqConvertFramesToGif(long h, java.nio.IntBuffer[] in, int[] widths, int[] heights, int nMaxColors,
-			boolean dither, long[] seeds, int mode, int[] delaysCs, int loopCount, java.nio.ByteBuffer out, long cap);
+			boolean dither, long[] seeds, int mode, int[] delaysCs, int loopCount, boolean delta, java.nio.ByteBuffer out, long cap);
 
 	private static java.nio.ByteBuffer gifBuffer(int[] widths, int[] heights) {
 		long cap = nqGifMaxBytes(widths, heights);

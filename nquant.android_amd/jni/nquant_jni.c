@@ -173,11 +173,35 @@ JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqEncodeGif(JNIEnv*
     return (jlong) size;
 }
 
+/* encodeGifDelta(): as encodeGif for frames of one size, every frame after the first stored as the rectangle that changed ->
+ * nq_encode_gif_delta.  Returns the file size. */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqEncodeGifDelta(JNIEnv* env, jclass c, jlong hh, jobjectArray index,
+        jint width, jint height, jintArray palette, jintArray delaysCs, jint loopCount, jobject out, jlong cap) {
+    nq_handle* h = (nq_handle*) (intptr_t) hh;
+    const jsize n = (*env)->GetArrayLength(env, index);
+    const uint16_t** src = malloc(sizeof(*src) * (n > 0 ? n : 1));
+    if (!src) { throw_rt(env, "out of memory"); return -1; }
+    for (jsize i = 0; i < n; ++i)
+        src[i] = (const uint16_t*) (*env)->GetDirectBufferAddress(env, (*env)->GetObjectArrayElement(env, index, i));
+    jint* pal = (*env)->GetIntArrayElements(env, palette, NULL);
+    jint* d = delaysCs ? (*env)->GetIntArrayElements(env, delaysCs, NULL) : NULL;
+    const jsize K = (*env)->GetArrayLength(env, palette);
+    int64_t size = -1;
+    const int rc = nq_encode_gif_delta(h, n, src, width, height, (const uint32_t*) pal, K, (const int32_t*) d, loopCount, 0,
+                                       (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, &size, NULL);
+    if (d) (*env)->ReleaseIntArrayElements(env, delaysCs, d, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, palette, pal, JNI_ABORT);
+    free(src);
+    if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
+    return (jlong) size;
+}
+
 /* convertFramesToGif(): nq_convert_frames with index outputs (the ARGB outputs go to scratch), then nq_encode_gif of the index maps
- * with the shared palette into the direct ByteBuffer `out` (cap bytes).  Returns the file size. */
+ * with the shared palette into the direct ByteBuffer `out` (cap bytes); delta: nq_encode_gif_delta instead, the frames must have one
+ * size.  Returns the file size. */
 JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertFramesToGif(JNIEnv* env, jclass c, jlong hh, jobjectArray in,
         jintArray widths, jintArray heights, jint nMaxColors, jboolean dither, jlongArray seeds, jint mode, jintArray delaysCs, jint loopCount,
-        jobject out, jlong cap) {
+        jboolean delta, jobject out, jlong cap) {
     nq_handle* h = (nq_handle*) (intptr_t) hh;
     const jsize n = (*env)->GetArrayLength(env, in);
     const int pcap = nMaxColors > 2 ? nMaxColors : 2;
@@ -200,10 +224,15 @@ JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertFramesToGi
     int32_t K = 0;
     int64_t size = -1;
     int rc = NQ_OK;
-    if (ok) {
+    int one_size = 1;
+    for (jsize i = 1; ok && delta && i < n; ++i) one_size = one_size && w[i] == w[0] && hg[i] == hg[0];
+    if (ok && one_size) {
         rc = nq_convert_frames(h, n, src, (const int32_t*) w, (const int32_t*) hg, nMaxColors, dither ? 1 : 0, (const int64_t*) sd, mode,
                                argb, idx, palette, &K);
-        if (rc == NQ_OK)
+        if (rc == NQ_OK && delta)
+            rc = nq_encode_gif_delta(h, n, (const uint16_t* const*) idx, n > 0 ? w[0] : 0, n > 0 ? hg[0] : 0, palette, K, (const int32_t*) d,
+                                     loopCount, 0, (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, &size, NULL);
+        else if (rc == NQ_OK)
             rc = nq_encode_gif(h, n, (const uint16_t* const*) idx, (const int32_t*) w, (const int32_t*) hg, palette, K, (const int32_t*) d,
                                loopCount, 0, (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, &size);
     }
@@ -214,6 +243,7 @@ JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertFramesToGi
     if (w) (*env)->ReleaseIntArrayElements(env, widths, w, JNI_ABORT);
     free(palette); free(idx); free(argb); free(src);
     if (!ok) { throw_rt(env, "out of memory"); return -1; }
+    if (!one_size) { throw_rt(env, "delta mode: all frames must have one size"); return -1; }
     if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
     return (jlong) size;
 }

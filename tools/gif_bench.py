@@ -3,7 +3,12 @@ Pillow's GIF encoder and indexed_png.write_indexed_png.  The maps are what the h
 PnnLABQuantizer.convert(256, true)).  Times are wall clock around calls that return when the file is in host memory (the GPU calls
 end in a stream synchronise and the copy of the file).
 
-    python tools/gif_bench.py [--size 4096] [--batch 64] [--reps 5] [--out FILE]"""
+    python tools/gif_bench.py [--size 4096] [--batch 64] [--reps 5] [--out FILE]
+
+--delta measures the delta mode instead (nq_encode_gif_delta_device next to nq_encode_gif_device on the same maps): --batch frames from
+nq_convert_frames_device with equal seeds, once a sprite moving over a still background and once unrelated images.
+
+    python tools/gif_bench.py --delta [--size 4096] [--batch 64] [--reps 3] [--out profiles/r07/gif_delta_bench.txt]"""
 import argparse
 import io
 import os
@@ -27,6 +32,56 @@ def timed(fn, reps):
     return best, out
 
 
+def delta_bench(args, say):
+    """Bytes and ms per call of the delta encoder and of the full-frame encoder on the same device-resident index maps."""
+    import torch
+    import nquant.android_amd as nq
+    from nquant.android_amd import synth
+
+    W = H = args.size
+    n, K = args.batch, 255
+    side = max(16, W // 16)                          # the sprite: a square of unrelated pixels, moved 3/4 of its side per frame
+    say("delta-mode GIF encoding of %d frames of %dx%d (PnnLABQuantizer, convert_frames_device(%d, true), equal seeds, tiled mode); "
+        "best of %d" % (n, W, H, K, args.reps))
+    outs = [torch.empty(W * H, dtype=torch.int32, device="cuda") for _ in range(n)]
+    idxs = [torch.empty(W * H, dtype=torch.int16, device="cuda") for _ in range(n)]
+
+    def run(name, frames):
+        q = nq.PnnLABQuantizer(np.zeros((1, 1), np.int32))
+        t = time.perf_counter()
+        pal = nq.convert_frames_device(q, [f.data_ptr() for f in frames], [W] * n, [H] * n, K, True, [o.data_ptr() for o in outs],
+                                       [i.data_ptr() for i in idxs], seeds=[0] * n)
+        torch.cuda.synchronize()
+        say("%s: convert_frames_device %.0f ms, K = %d" % (name, (time.perf_counter() - t) * 1e3, len(pal)))
+        ptrs = [i.data_ptr() for i in idxs]
+        full = lambda: nq.encode_gif_device(q, ptrs, [W] * n, [H] * n, pal, [4] * n, 0)
+        delta = lambda: nq.encode_gif_delta_device(q, ptrs, W, H, pal, [4] * n, 0, return_rects=True)
+        full()
+        delta()
+        tf, gf = timed(full, args.reps)
+        td, (gd, rects) = timed(delta, args.reps)
+        area = int((rects[:, 2].astype(np.int64) * rects[:, 3]).sum())
+        say("%s: encode_gif_device        %9.1f ms per call  %12d bytes" % (name, tf * 1e3, len(gf)))
+        say("%s: encode_gif_delta_device  %9.1f ms per call  %12d bytes  (%.3fx the time, %.3fx the bytes; rectangles cover %.3f of the "
+            "pixels)" % (name, td * 1e3, len(gd), td / tf, len(gd) / len(gf), area / (n * W * H)))
+        q.close()
+
+    back = synth.gradient_noise_torch(W, H, 3).reshape(H, W)
+    sprite = synth.uniform_rgb(side, side, 1)
+    sprite = torch.from_numpy(sprite).cuda()
+    frames = []
+    for i in range(n):
+        f = back.clone()
+        x = (i * 3 * side // 4) % (W - side)
+        y = (i * side // 2) % (H - side)
+        f[y:y + side, x:x + side] = sprite
+        frames.append(f.reshape(-1).contiguous())
+    run("moving sprite   ", frames)
+    del frames, back
+    frames = [synth.gradient_noise_torch(W, H, 3 + k) for k in range(n)]
+    run("unrelated images", frames)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -35,7 +90,20 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the Pillow animation timed on the CPU")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--delta", action="store_true", help="measure the delta mode against the full-frame call instead")
     args = ap.parse_args()
+    if args.delta:
+        lines = []
+
+        def say(s):
+            print(s, flush=True)
+            lines.append(s)
+        delta_bench(args, say)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     import torch
     from PIL import Image
     import nquant.android_amd as nq
