@@ -296,6 +296,49 @@ int nq_encode_png(nq_handle* h, int n, const uint16_t* const* index, const int32
                   const uint32_t* palettes, int32_t palette_stride, const int32_t* K, int segment_bytes,
                   uint8_t* out, int64_t cap, int64_t* out_offsets);
 
+/* ---- APNG encoding: n index maps of one size over one palette to ONE animated PNG file whose frames store only what changed, with
+ *      all 8 bits of the palette's alpha (what delta GIF cannot do: it refuses alpha 0 and drops every other alpha).  All n frames are
+ *      width x height uint16 index maps over the K <= 256 ARGB entries of `palette` (what nq_convert_frames returns).  A frame's data
+ *      is the zlib stream nq_encode_png writes, so the same chains encode it; every APNG decoder composes the file back to the frames,
+ *      and a plain PNG decoder shows frame 0.
+ *  * n = 1: the file is byte for byte nq_encode_png's (no acTL, no fcTL), out_rects = {0, 0, width, height}.  The rest is n > 1.
+ *  * One mode per file, decided from the palette alone.  Mark mode: every alpha is 255 and K <= 255; then u = K is the "unchanged"
+ *    index, Kt = K + 1, palette entry u is (0, 0, 0) with alpha 0, and frames >= 1 have blend_op 1 (OVER).  Crop mode otherwise: no
+ *    u, Kt = K, every frame has blend_op 0 (SOURCE), which replaces the region whatever the alpha is.  (In mark mode the bit depth
+ *    grows when K is 2, 4 or 16.)
+ *  * Header: signature; IHDR (depth: the smallest of 1, 2, 4, 8 with 2^d >= max(Kt, 2); colour type 3); PLTE (Kt RGB entries); tRNS by
+ *    nq_encode_png's rule applied to the Kt entries (mark mode: K bytes 255, then 0); acTL (num_frames = n, num_plays = loop_count,
+ *    0 = for ever).
+ *  * Frame i: fcTL {sequence_number, the rectangle's width, height, x, y, delay_num = delays_cs[i] (NULL: 0), delay_den = 100,
+ *    dispose_op 0, blend_op as above (frame 0: always 0)}, then its data: frame 0 one IDAT, frame i >= 1 one fdAT (its sequence number,
+ *    then the zlib stream).  fcTL and fdAT share one sequence counter that starts at 0.  IEND follows the last frame.
+ *  * Rectangle: frame 0 whole.  Frame i >= 1: D = the pixels with index_i != index_(i-1); the rectangle is D's bounding box, 1 x 1 at
+ *    (0, 0) when D is empty.  The body is the rectangle row-major: index_i, in mark mode with every pixel outside D replaced by u.
+ *  * A frame's zlib stream is exactly what nq_encode_png puts into IDAT for an image that is the body, with Kt colours and the same
+ *    segment_bytes: header 78 01, the raw stream (per row a filter byte 0, then the indices packed most significant bits first) cut
+ *    into segments, one dynamic-Huffman chain each, BFINAL on the last, Adler-32.  The bodies are never materialised: the chains read
+ *    the rectangle out of the two index maps.
+ *  * nq_apng_max_bytes: an upper bound of the file size for any content and any K (pure arithmetic, no device, no handle): n times
+ *    nq_png_max_bytes of one width x height image at K = 256, plus 58 bytes (acTL and frame 0's fcTL) -- no rectangle exceeds its
+ *    frame, Kt <= 256, and a later frame's fcTL and sequence number are smaller than the still-image header it does not repeat.
+ *  * out_rects (NULL: not wanted): 4 ints per frame, x, y, w, h of its rectangle, written on success.
+ *  * nq_encode_apng_device: index maps in DEVICE memory (2-byte aligned pointers suffice; never written), everything else on the host;
+ *    h may be a handle of either kind.  The file is assembled in device memory and copied to `out` in one copy; *out_size = its size.
+ *    nq_encode_apng: the same with index maps in HOST memory (they are uploaded first).
+ *  * NQ_ERR_INVALID before any device work (*out_size and out_rects stay untouched): n < 1, a side outside 1..65535, K outside
+ *    1..256, segment_bytes outside 0..65535, loop_count < 0, a delay outside 0..65535, NULL or odd index pointers, a frame whose size
+ *    bound (K = 256) exceeds 2^31 - 1 bytes.  After the encoding: an index >= K anywhere in any frame (n >= 2: reported after the
+ *    difference pass, also outside the rectangle), or cap smaller than the file (then *out_size holds the size and `out` is
+ *    untouched).  The handle stays usable after any of these.
+ *  The bit-exact definition and the kernels: DESIGN.md "PNG encoder, animated (APNG)". ---- */
+int nq_apng_max_bytes(int n, int width, int height, int segment_bytes, int64_t* out_bytes);
+int nq_encode_apng_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height,
+                          const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_bytes,
+                          uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
+int nq_encode_apng(nq_handle* h, int n, const uint16_t* const* index, int width, int height,
+                   const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_bytes,
+                   uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

@@ -1954,12 +1954,10 @@ int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
                            segment_pixels, out, cap, out_size);
 }
 
-// nq_encode_gif_delta_device after the argument checks (n >= 2): difference pass, one read-back of the boxes, body pass, then the
-// bodies are encoded like any index maps
-int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, const uint32_t* palette, int K,
-                     const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size,
-                     int32_t* out_rects) {
-    const int u = K <= 255 ? K : -1;                // the "unchanged" index, transparent in every frame
+// The rectangles of n >= 2 frames of one size (device memory): frame 0 whole, frame i >= 1 the bounding box of the pixels that differ
+// from frame i - 1 (1 x 1 at (0, 0) when none does).  One difference pass over all frames and one small read-back; an index >= K
+// anywhere in any frame is NQ_ERR_INVALID.  Shared by the delta GIF and the APNG encoder.
+int changed_rects(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, int K, std::vector<GifRect>* out) {
     std::vector<int>& box = h->h_gif_box;
     box.assign(4 * (size_t) (n - 1) + 1, 0);
     for (int i = 0; i < n - 1; ++i) { box[4 * i] = box[4 * i + 1] = INT_MAX; box[4 * i + 2] = box[4 * i + 3] = -1; }
@@ -1972,10 +1970,9 @@ int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W,
     NQ_HIP(h, hipMemcpyAsync(box.data(), h->gif_box.p, box.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
     if (box[4 * (size_t) (n - 1)]) NQ_FAIL(h, NQ_ERR_INVALID, "an index map holds an index >= K = %d", K);
-    std::vector<GifRect> rects(n);
+    std::vector<GifRect>& rects = *out;
+    rects.assign(n, GifRect{});
     rects[0] = {0, 0, W, H};
-    size_t room = 0;
-    long long max_area = 1;
     for (int i = 1; i < n; ++i) {
         const int* b = &box[4 * (size_t) (i - 1)];
         GifRect& r = rects[i];
@@ -1983,7 +1980,23 @@ int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W,
         else r = {b[0], b[1], b[2] - b[0] + 1, b[3] - b[1] + 1};
         if (r.x < 0 || r.y < 0 || r.w < 1 || r.h < 1 || r.x + r.w > W || r.y + r.h > H)
             NQ_FAIL(h, NQ_ERR_HIP, "frame %d: the difference pass returned the box %d %d %d %d", i, b[0], b[1], b[2], b[3]);
-        const long long area = (long long) r.w * r.h;
+    }
+    return NQ_OK;
+}
+
+// nq_encode_gif_delta_device after the argument checks (n >= 2): difference pass, one read-back of the boxes, body pass, then the
+// bodies are encoded like any index maps
+int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, const uint32_t* palette, int K,
+                     const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size,
+                     int32_t* out_rects) {
+    const int u = K <= 255 ? K : -1;                // the "unchanged" index, transparent in every frame
+    std::vector<GifRect> rects;
+    const int rc0 = changed_rects(h, n, d_index, W, H, K, &rects);
+    if (rc0) return rc0;
+    size_t room = 0;
+    long long max_area = 1;
+    for (int i = 1; i < n; ++i) {
+        const long long area = (long long) rects[i].w * rects[i].h;
         room += (size_t) ((area + 7) & ~7ll);
         max_area = std::max(max_area, area);
     }
@@ -2132,7 +2145,8 @@ constexpr int kPngDefaultSegment = 32768, kPngMaxSegment = 65535;
 // bits for one byte or a match of <= 15 + 5 + 15 + 13 bits for at least three: <= 16 bits per byte
 inline long long png_seg_bits_max(long long L) { return 4544 + 16 * L; }
 inline int png_depth(int K) { return K <= 2 ? 1 : K <= 4 ? 2 : K <= 16 ? 4 : 8; }
-inline long long png_row_bytes(int w, int K) { return 1 + ((long long) w * png_depth(K) + 7) / 8; }
+inline long long png_row_bytes_at(int w, int depth) { return 1 + ((long long) w * depth + 7) / 8; }
+inline long long png_row_bytes(int w, int K) { return png_row_bytes_at(w, png_depth(K)); }
 inline long long png_seg_len(long long raw, int segment_bytes) { return std::min<long long>(segment_bytes ? segment_bytes : kPngDefaultSegment, raw); }
 // signature, IHDR, PLTE, tRNS, IDAT length + type, zlib header | Adler-32, IDAT CRC, IEND
 inline long long png_prefix_max(int K) { return 8 + 25 + (12 + 3 * K) + (12 + K) + 8 + 2; }
@@ -2186,17 +2200,18 @@ uint32_t png_crc32(const uint8_t* p, size_t n) {
     return ~c;
 }
 
-int png_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights, const uint32_t* palettes,
-               int32_t palette_stride, const int32_t* K, int segment_bytes, uint8_t* out, int64_t cap, int64_t* out_offsets) {
-    // image table: segments and their scratch
-    h->h_png.assign(n, nq::PngImage{});
+// The chains of the n images in h->h_png (index, prev, width, height, pitch, K, depth, u filled in by the caller): segments and their
+// scratch, one deflate launch and one scan for all of them, one read-back.  res[2 i] = image i's deflate bit length, res[2 n + i] != 0:
+// image i holds an index >= its K.  *out_segs: chains of the call.
+int png_chains(nq_handle* h, int n, int segment_bytes, std::vector<unsigned long long>* out_res, long long* out_segs) {
     long long segs = 0, words = 0;
     int max_seg = 1;
+    bool rect = false;                              // any image that is a rectangle of a larger map or a delta frame
     for (int i = 0; i < n; ++i) {
         nq::PngImage& F = h->h_png[i];
-        F.index = d_index[i]; F.width = widths[i]; F.height = heights[i]; F.K = K[i]; F.depth = png_depth(K[i]);
-        F.row_bytes = (int) png_row_bytes(widths[i], K[i]);
-        F.raw_len = (long long) heights[i] * F.row_bytes;
+        rect = rect || F.prev != nullptr || F.pitch != F.width;
+        F.row_bytes = (int) png_row_bytes_at(F.width, F.depth);
+        F.raw_len = (long long) F.height * F.row_bytes;
         F.seg_len = (int) png_seg_len(F.raw_len, segment_bytes);
         F.nseg = (F.raw_len + F.seg_len - 1) / F.seg_len; F.seg_base = segs; F.seg_words = png_seg_bits_max(F.seg_len) / 32 + 2; F.word_base = words;
         segs += F.nseg; words += F.nseg * F.seg_words;
@@ -2212,51 +2227,65 @@ int png_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
     NQ_HIP(h, h->png_crc.reserve(n));
     NQ_HIP(h, hipMemcpyAsync(h->d_png.p, h->h_png.data(), n * sizeof(nq::PngImage), hipMemcpyHostToDevice, h->stream));
     NQ_HIP(h, hipMemsetAsync(h->gif_res.p + 2 * n, 0, n * sizeof(unsigned long long), h->stream));
-    NQ_HIP(h, launch_png_deflate(h->d_png.p, n, segs, max_seg, grid, h->gif_words.p, h->gif_bits.p, h->png_adler.p, h->png_tokens.p,
+    NQ_HIP(h, launch_png_deflate(h->d_png.p, n, segs, max_seg, grid, rect, h->gif_words.p, h->gif_bits.p, h->png_adler.p, h->png_tokens.p,
                                  h->gif_res.p + 2 * n, h->stream));
     launch_png_scan(h->d_png.p, n, h->gif_bits.p, h->png_adler.p, h->gif_bits.p + segs, h->gif_res.p, h->stream);
     NQ_HIP(h, launch_status());
-    std::vector<unsigned long long> res(3 * (size_t) n);
-    NQ_HIP(h, hipMemcpyAsync(res.data(), h->gif_res.p, res.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    out_res->assign(3 * (size_t) n, 0);
+    NQ_HIP(h, hipMemcpyAsync(out_res->data(), h->gif_res.p, out_res->size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n; ++i)
-        if (res[2 * n + i]) NQ_FAIL(h, NQ_ERR_INVALID, "image %d: the index map holds an index >= K = %d", i, K[i]);
-    // per image the bytes in front of the deflate data, in one blob: signature, IHDR, PLTE, tRNS, IDAT length and type, zlib header
-    std::vector<uint8_t>& blob = h->h_gif_blob;
-    blob.clear();
-    auto u32 = [&](uint32_t v) { for (int k = 3; k >= 0; --k) blob.push_back((uint8_t) (v >> (8 * k))); };
+    *out_segs = segs;
+    return NQ_OK;
+}
+
+// the bytes the host writes, in one blob: chunks with their CRC, and the head of a data chunk (its CRC is the device's)
+struct PngBlob {
+    std::vector<uint8_t>& b;
     size_t chunk_at = 0;
-    auto begin = [&](uint32_t len, const char* type) { u32(len); chunk_at = blob.size(); blob.insert(blob.end(), type, type + 4); };
-    auto end = [&]() { u32(png_crc32(blob.data() + chunk_at, blob.size() - chunk_at)); };
-    long long total = 0, crc_chunks = 0;
-    for (int i = 0; i < n; ++i) {
-        nq::PngImage& F = h->h_png[i];
-        const uint32_t* pal = palettes + (size_t) i * palette_stride;
-        const size_t start = blob.size();
-        blob.insert(blob.end(), {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A});
-        begin(13, "IHDR"); u32((uint32_t) widths[i]); u32((uint32_t) heights[i]);
-        blob.insert(blob.end(), {(uint8_t) F.depth, 3, 0, 0, 0}); end();
-        begin((uint32_t) (3 * K[i]), "PLTE");
-        for (int k = 0; k < K[i]; ++k) { blob.push_back((uint8_t) (pal[k] >> 16)); blob.push_back((uint8_t) (pal[k] >> 8)); blob.push_back((uint8_t) pal[k]); }
+    void u16(uint32_t v) { b.push_back((uint8_t) (v >> 8)); b.push_back((uint8_t) v); }
+    void u32(uint32_t v) { for (int k = 3; k >= 0; --k) b.push_back((uint8_t) (v >> (8 * k))); }
+    void begin(uint32_t len, const char* type) { u32(len); chunk_at = b.size(); b.insert(b.end(), type, type + 4); }
+    void end() { u32(png_crc32(b.data() + chunk_at, b.size() - chunk_at)); }
+    // signature, IHDR, PLTE, tRNS (only when some entry's alpha is not 255: the alpha bytes up to the last such entry)
+    void head(int w, int hgt, int depth, const uint32_t* pal, int K) {
+        b.insert(b.end(), {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A});
+        begin(13, "IHDR"); u32((uint32_t) w); u32((uint32_t) hgt);
+        b.insert(b.end(), {(uint8_t) depth, 3, 0, 0, 0}); end();
+        begin((uint32_t) (3 * K), "PLTE");
+        for (int k = 0; k < K; ++k) { b.push_back((uint8_t) (pal[k] >> 16)); b.push_back((uint8_t) (pal[k] >> 8)); b.push_back((uint8_t) pal[k]); }
         end();
         int nt = 0;
-        for (int k = 0; k < K[i]; ++k) if ((pal[k] >> 24) != 255) nt = k + 1;
+        for (int k = 0; k < K; ++k) if ((pal[k] >> 24) != 255) nt = k + 1;
         if (nt) {
             begin((uint32_t) nt, "tRNS");
-            for (int k = 0; k < nt; ++k) blob.push_back((uint8_t) (pal[k] >> 24));
+            for (int k = 0; k < nt; ++k) b.push_back((uint8_t) (pal[k] >> 24));
             end();
         }
-        F.data_bytes = (long long) ((res[2 * i] + 7) / 8);
-        begin((uint32_t) (2 + F.data_bytes + 4), "IDAT");
-        blob.push_back(0x78); blob.push_back(0x01);  // deflate, 32 KiB window; no dictionary, fastest; 0x7801 is a multiple of 31
-        F.prefix_off = (long long) start; F.prefix_len = (int) (blob.size() - start);
-        F.file_off = total; F.crc_base = crc_chunks;
-        out_offsets[i] = total;
-        total += F.prefix_len + F.data_bytes + kPngSuffix;
-        crc_chunks += (10 + F.data_bytes + 127) / 128;
     }
-    out_offsets[n] = total;
-    if (cap < total) NQ_FAIL(h, NQ_ERR_INVALID, "cap = %lld bytes < the files' %lld", (long long) cap, total);
+    // length, type and (seq >= 0: an fdAT's sequence number) of the data chunk around data_bytes of deflate data, then the zlib header:
+    // deflate, 32 KiB window; no dictionary, fastest; 0x7801 is a multiple of 31.  Returns crc_lead.
+    int data_head(long long data_bytes, long long seq) {
+        u32((uint32_t) ((seq >= 0 ? 4 : 0) + 2 + data_bytes + 4));
+        const char* type = seq >= 0 ? "fdAT" : "IDAT";
+        b.insert(b.end(), type, type + 4);
+        if (seq >= 0) u32((uint32_t) seq);
+        b.push_back(0x78); b.push_back(0x01);
+        return seq >= 0 ? 10 : 6;
+    }
+};
+
+// place image i (its prefix is blob[start ..)) at *total; the CRC and, with iend, the IEND chunk follow its data
+void png_place(nq::PngImage& F, const std::vector<uint8_t>& blob, size_t start, int crc_lead, bool iend, long long* total, long long* crc_chunks) {
+    F.prefix_off = (long long) start; F.prefix_len = (int) (blob.size() - start);
+    F.crc_lead = crc_lead; F.iend = iend ? 1 : 0;
+    F.file_off = *total; F.crc_base = *crc_chunks;
+    *total += F.prefix_len + F.data_bytes + 8 + (iend ? 12 : 0);
+    *crc_chunks += (crc_lead + 4 + F.data_bytes + 127) / 128;
+}
+
+// blob and placed image table -> the `total` bytes of the files in `out`
+int png_assemble(nq_handle* h, int n, long long segs, long long total, long long crc_chunks, uint8_t* out) {
+    const std::vector<uint8_t>& blob = h->h_gif_blob;
     NQ_HIP(h, h->gif_blob.reserve(blob.size()));
     NQ_HIP(h, h->gif_file.reserve((size_t) total));
     NQ_HIP(h, hipMemcpyAsync(h->gif_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
@@ -2267,6 +2296,128 @@ int png_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
     NQ_HIP(h, launch_status());
     NQ_HIP(h, hipMemcpyAsync(out, h->gif_file.p, (size_t) total, hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
+    return NQ_OK;
+}
+
+int png_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights, const uint32_t* palettes,
+               int32_t palette_stride, const int32_t* K, int segment_bytes, uint8_t* out, int64_t cap, int64_t* out_offsets) {
+    h->h_png.assign(n, nq::PngImage{});
+    for (int i = 0; i < n; ++i) {
+        nq::PngImage& F = h->h_png[i];
+        F.index = d_index[i]; F.width = F.pitch = widths[i]; F.height = heights[i]; F.K = K[i]; F.depth = png_depth(K[i]); F.u = -1;
+    }
+    std::vector<unsigned long long> res;
+    long long segs = 0;
+    const int rc = png_chains(h, n, segment_bytes, &res, &segs);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i)
+        if (res[2 * n + i]) NQ_FAIL(h, NQ_ERR_INVALID, "image %d: the index map holds an index >= K = %d", i, K[i]);
+    // per image the bytes in front of the deflate data: signature, IHDR, PLTE, tRNS, IDAT length and type, zlib header
+    h->h_gif_blob.clear();
+    PngBlob blob{h->h_gif_blob};
+    long long total = 0, crc_chunks = 0;
+    for (int i = 0; i < n; ++i) {
+        nq::PngImage& F = h->h_png[i];
+        const size_t start = blob.b.size();
+        blob.head(widths[i], heights[i], F.depth, palettes + (size_t) i * palette_stride, K[i]);
+        F.data_bytes = (long long) ((res[2 * i] + 7) / 8);
+        const int lead = blob.data_head(F.data_bytes, -1);
+        out_offsets[i] = total;
+        png_place(F, blob.b, start, lead, true, &total, &crc_chunks);
+    }
+    out_offsets[n] = total;
+    if (cap < total) NQ_FAIL(h, NQ_ERR_INVALID, "cap = %lld bytes < the files' %lld", (long long) cap, total);
+    return png_assemble(h, n, segs, total, crc_chunks, out);
+}
+
+// ---- APNG: one file of n frames of one size over one palette (include/nquant_abi.h "APNG encoding") ----
+// signature .. tRNS + acTL + frame 0's fcTL; every later frame an fcTL more than a still image's IDAT; an fdAT's sequence number
+constexpr long long kApngExtra = 20 + 38;
+
+// the arguments nq_apng_max_bytes takes; false + the reason otherwise
+bool apng_check_shape(int n, int width, int height, int segment_bytes, char* why, size_t len) {
+    if (n < 1) { std::snprintf(why, len, "n = %d: at least one frame", n); return false; }
+    const int32_t w = width, hg = height;
+    return png_check_shape(1, &w, &hg, nullptr, segment_bytes, why, len);
+}
+
+int apng_check(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
+               const int32_t* delays_cs, int loop_count, int segment_bytes, const uint8_t* out, int64_t cap, int64_t* out_size) {
+    char why[256];
+    if (!apng_check_shape(n, width, height, segment_bytes, why, sizeof why)) NQ_FAIL(h, NQ_ERR_INVALID, "%s", why);
+    if (K < 1 || K > 256) NQ_FAIL(h, NQ_ERR_INVALID, "K = %d: a PNG palette holds 1..256 entries", K);
+    if (!palette || !out_size) NQ_FAIL(h, NQ_ERR_INVALID, "palette / out_size is NULL");
+    if (loop_count < 0) NQ_FAIL(h, NQ_ERR_INVALID, "loop_count = %d: must be >= 0 (0 = for ever)", loop_count);
+    if (delays_cs)
+        for (int i = 0; i < n; ++i)
+            if (delays_cs[i] < 0 || delays_cs[i] > 65535) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: delay %d outside 0..65535", i, delays_cs[i]);
+    if (cap < 0 || (!out && cap > 0)) NQ_FAIL(h, NQ_ERR_INVALID, "out is NULL or cap < 0");
+    return gif_check_index(h, n, index);
+}
+
+// nq_encode_apng_device after the argument checks
+int apng_encode(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, const uint32_t* palette, int K, const int32_t* delays_cs,
+                int loop_count, int segment_bytes, uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects) {
+    if (n == 1) {                                   // a still image: nq_encode_png's file
+        const int32_t w = W, hg = H, k = K;
+        int64_t offs[2] = {0, -1};
+        const int rc = png_encode(h, 1, d_index, &w, &hg, palette, K, &k, segment_bytes, out, cap, offs);
+        if (offs[1] >= 0) *out_size = offs[1];
+        if (rc == NQ_OK) gif_whole_rect(out_rects, W, H);
+        return rc;
+    }
+    // one mode per file, from the palette alone: mark (opaque palette with room for u: unchanged pixels are index u, alpha 0, blended
+    // OVER) or crop (the rectangle replaces what was there)
+    bool opaque = true;
+    for (int i = 0; i < K; ++i) opaque = opaque && (palette[i] >> 24) == 255;
+    const int u = opaque && K <= 255 ? K : -1, Kt = K + (u >= 0 ? 1 : 0), depth = png_depth(Kt);
+    std::vector<uint32_t> pal(palette, palette + K);
+    if (u >= 0) pal.push_back(0);
+    std::vector<GifRect> rects;
+    int rc = changed_rects(h, n, d_index, W, H, K, &rects);      // (also the index >= K check of every frame)
+    if (rc) return rc;
+    h->h_png.assign(n, nq::PngImage{});
+    for (int i = 0; i < n; ++i) {
+        nq::PngImage& F = h->h_png[i];
+        const GifRect& r = rects[i];
+        const size_t first = (size_t) r.y * W + r.x;
+        F.index = d_index[i] + first;
+        F.prev = u >= 0 && i > 0 ? d_index[i - 1] + first : nullptr;
+        F.width = r.w; F.height = r.h; F.pitch = W; F.K = K; F.depth = depth; F.u = u;
+    }
+    std::vector<unsigned long long> res;
+    long long segs = 0;
+    rc = png_chains(h, n, segment_bytes, &res, &segs);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i)
+        if (res[2 * n + i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: the index map holds an index >= K = %d", i, K);
+    h->h_gif_blob.clear();
+    PngBlob blob{h->h_gif_blob};
+    long long total = 0, crc_chunks = 0;
+    uint32_t seq = 0;
+    for (int i = 0; i < n; ++i) {
+        nq::PngImage& F = h->h_png[i];
+        const GifRect& r = rects[i];
+        const size_t start = blob.b.size();
+        if (i == 0) {
+            blob.head(W, H, depth, pal.data(), Kt);
+            blob.begin(8, "acTL"); blob.u32((uint32_t) n); blob.u32((uint32_t) loop_count); blob.end();
+        }
+        blob.begin(26, "fcTL");
+        blob.u32(seq++); blob.u32((uint32_t) r.w); blob.u32((uint32_t) r.h); blob.u32((uint32_t) r.x); blob.u32((uint32_t) r.y);
+        blob.u16((uint32_t) (delays_cs ? delays_cs[i] : 0)); blob.u16(100);
+        blob.b.push_back(0); blob.b.push_back((uint8_t) (u >= 0 && i > 0 ? 1 : 0));      // dispose NONE; blend SOURCE / OVER
+        blob.end();
+        F.data_bytes = (long long) ((res[2 * i] + 7) / 8);
+        const int lead = blob.data_head(F.data_bytes, i == 0 ? -1 : (long long) seq++);
+        png_place(F, blob.b, start, lead, i == n - 1, &total, &crc_chunks);
+    }
+    *out_size = total;
+    if (cap < total) NQ_FAIL(h, NQ_ERR_INVALID, "cap = %lld bytes < the file's %lld", (long long) cap, total);
+    rc = png_assemble(h, n, segs, total, crc_chunks, out);
+    if (rc) return rc;
+    if (out_rects)
+        for (int i = 0; i < n; ++i) { out_rects[4 * i] = rects[i].x; out_rects[4 * i + 1] = rects[i].y; out_rects[4 * i + 2] = rects[i].w; out_rects[4 * i + 3] = rects[i].h; }
     return NQ_OK;
 }
 
@@ -2308,6 +2459,41 @@ int nq_encode_png(nq_handle* h, int n, const uint16_t* const* index, const int32
     return host_form(h, [&]() {
         rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
         return rc ? rc : png_encode(h, n, dev.data(), widths, heights, palettes, palette_stride, K, segment_bytes, out, cap, out_offsets);
+    });
+}
+
+int nq_apng_max_bytes(int n, int width, int height, int segment_bytes, int64_t* out_bytes) {
+    char why[256];
+    if (!out_bytes || !apng_check_shape(n, width, height, segment_bytes, why, sizeof why)) return NQ_ERR_INVALID;
+    *out_bytes = (long long) n * png_image_max(width, height, 256, segment_bytes) + kApngExtra;
+    return NQ_OK;
+}
+
+int nq_encode_apng_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height, const uint32_t* palette, int K,
+                          const int32_t* delays_cs, int loop_count, int segment_bytes, uint8_t* out, int64_t cap, int64_t* out_size,
+                          int32_t* out_rects) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = apng_check(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_bytes, out, cap, out_size);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return apng_encode(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_bytes, out, cap, out_size, out_rects);
+}
+
+int nq_encode_apng(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
+                   const int32_t* delays_cs, int loop_count, int segment_bytes, uint8_t* out, int64_t cap, int64_t* out_size,
+                   int32_t* out_rects) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = apng_check(h, n, index, width, height, palette, K, delays_cs, loop_count, segment_bytes, out, cap, out_size);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    std::vector<size_t> px(n, (size_t) width * height);
+    std::vector<uint16_t*> dev(n);
+    return host_form(h, [&]() {
+        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
+        return rc ? rc : apng_encode(h, n, dev.data(), width, height, palette, K, delays_cs, loop_count, segment_bytes, out, cap, out_size,
+                                     out_rects);
     });
 }
 

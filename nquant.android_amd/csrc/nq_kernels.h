@@ -227,11 +227,17 @@ void launch_gif_body(const GifDelta* d_delta, int n_bodies, int W, int u, long l
 
 // ---- PNG encoding (nq_png.hip): image i's raw stream (per row a filter byte 0 + the indices packed at `depth` bits) is cut into
 // segments of seg_len bytes (the last one shorter); segment s of the image is chain seg_base + s of the call and writes its deflate
-// block to words[word_base + s * seg_words ...].  file_off .. crc_base place the image's file in the output (filled in after the bit
-// lengths are known): prefix (signature .. zlib header, from the blob), data_bytes of deflate data, Adler-32, IDAT CRC, IEND ----
+// block to words[word_base + s * seg_words ...].  An image is width x height pixels whose rows lie `pitch` elements apart, so it may be
+// a rectangle inside a larger map (index points at its first pixel); with `prev` set (the same rectangle of another map of that
+// pitch) a pixel equal to prev's is packed as the index u instead.  file_off .. crc_base place the image's data chunk in the output
+// (filled in after the bit lengths are known): prefix (everything in front of the deflate data, from the blob: for a still image
+// signature .. IDAT header + zlib header), data_bytes of deflate data, Adler-32, the chunk's CRC, and the IEND chunk when `iend` is
+// set.  The CRC covers the last crc_lead bytes of the prefix (chunk type .. zlib header: 6 for IDAT, 10 for an APNG frame's fdAT with
+// its sequence number), the data and the Adler-32.  Several images may so make up one file (an APNG: one per frame). ----
 struct PngImage {
     const unsigned short* index;   // 2-byte aligned
-    int width, height, K, depth, row_bytes, seg_len, prefix_len;
+    const unsigned short* prev;    // NULL: every pixel is packed as it is
+    int width, height, pitch, K, depth, u, row_bytes, seg_len, prefix_len, crc_lead, iend;
     long long raw_len, seg_base, nseg, word_base, seg_words;
     long long file_off, prefix_off, data_bytes, crc_base;      // crc_base: first of the image's 128-byte pieces in png_crc_kernel
 };
@@ -239,15 +245,16 @@ struct PngImage {
 inline int png_buf_bytes(int seg_len) { return (seg_len + 16 + 15) & ~15; }
 // dynamic LDS of one chain (= one workgroup of 64) at this largest segment length
 size_t png_deflate_lds_bytes(int max_seg_len);
-// `grid` chains at a time; d_tokens: grid * max_seg_len words; seg_bits[g] / seg_adler[g]: bit length and Adler-32 partial
+// `grid` chains at a time; rect: some image of the call has prev set or pitch != width (then the kernel that honours them runs;
+// without it every image is a whole map and the still-image kernel runs); d_tokens: grid * max_seg_len words; seg_bits[g] / seg_adler[g]: bit length and Adler-32 partial
 // (A | B << 32) of chain g; *d_bad = 1 when an index >= its image's K was met (zeroed by the caller)
-hipError_t launch_png_deflate(const PngImage* d_images, int n_images, long long n_segs, int max_seg_len, int grid, unsigned* d_words,
+hipError_t launch_png_deflate(const PngImage* d_images, int n_images, long long n_segs, int max_seg_len, int grid, bool rect, unsigned* d_words,
                               unsigned long long* d_seg_bits, unsigned long long* d_seg_adler, unsigned* d_tokens, unsigned long long* d_bad,
                               hipStream_t s);
 // d_res[2 i] = image i's deflate bit length, d_res[2 i + 1] = the Adler-32 of its raw stream
 void launch_png_scan(const PngImage* d_images, int n_images, const unsigned long long* d_seg_bits, const unsigned long long* d_seg_adler,
                      unsigned long long* d_seg_off, unsigned long long* d_res, hipStream_t s);
-// all files (total bytes) and the IDAT CRCs (d_crc[n_images], zeroed by the caller; n_crc_chunks 128-byte pieces over all images)
+// all files (total bytes) and the data chunks' CRCs (d_crc[n_images], zeroed by the caller; n_crc_chunks 128-byte pieces over all images)
 void launch_png_gather(const PngImage* d_images, int n_images, const unsigned* d_words, const unsigned long long* d_seg_bits,
                        const unsigned long long* d_seg_off, const unsigned long long* d_res, const unsigned char* d_blob, unsigned char* d_file,
                        long long total, long long n_crc_chunks, unsigned* d_crc, hipStream_t s);

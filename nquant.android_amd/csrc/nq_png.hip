@@ -8,8 +8,11 @@
 //   png_scan_kernel     per image: exclusive scan of the segments' bit lengths, Adler-32 of the raw stream from the segments' partials
 //   png_gather_kernel   one thread per byte of the files: header bytes from the host's blob, data bytes ORed from the <= 2 segments
 //                       each overlaps (a block is longer than 8 bits), Adler-32, IEND
-//   png_crc_kernel      CRC-32 of every IDAT chunk: per-thread partials moved to the chunk's end by x^n mod P and XORed together
+//   png_crc_kernel      CRC-32 of every data chunk (IDAT, or an APNG frame's fdAT): per-thread partials moved to the chunk's end by
+//                       x^n mod P and XORed together
 //   png_crc_store_kernel  the four CRC bytes into the files
+// An "image" of a call is whatever one zlib stream encodes: a whole index map, or (APNG) a frame's changed rectangle read in place
+// from two maps, with the unchanged pixels packed as one index.  Several images may lie in one file, each in a data chunk of its own.
 #include "nq_kernels.h"
 
 namespace nq {
@@ -174,7 +177,10 @@ __device__ inline void emit_items(PngTables& T, BitOut& B, unsigned long long va
 extern __shared__ uint4 png_lds[];
 
 // All 64 lanes of the wave work on one segment; what is sequential (greedy selection, tree construction) runs on uniform values
-// or in lane 0.  Every loop is bounded by the segment length, a table size or a symbol count.
+// or in lane 0.  Every loop is bounded by the segment length, a table size or a symbol count.  RECT = false: every
+// image is a whole map, rows width elements apart -- the still-image encoder as it was before rectangles existed.  RECT = true: an
+// image may be a rectangle inside a larger map (rows pitch elements apart) and a delta frame (prev, u).
+template <bool RECT>
 __global__ void __launch_bounds__(64) png_deflate_kernel(const PngImage* __restrict__ images, int n_images, long long n_segs, int buf_bytes,
                                                          unsigned* __restrict__ words, unsigned long long* __restrict__ seg_bits,
                                                          unsigned long long* __restrict__ seg_adler, unsigned* __restrict__ tokens,
@@ -213,13 +219,18 @@ __global__ void __launch_bounds__(64) png_deflate_kernel(const PngImage* __restr
                 const unsigned t = col0 + (unsigned) o, r = t / rowb, c = t - r * rowb;
                 unsigned v = 0;
                 if (c) {
-                    const unsigned short* __restrict__ rowp = F.index + (row0 + r) * (long long) W;
+                    // the maps are read element by element: a rectangle's rows start at any x, nothing wider than 2 bytes is aligned
+                    const long long ro = (row0 + r) * (RECT ? (long long) F.pitch : (long long) W);
+                    const unsigned short* __restrict__ rowp = F.index + ro;
                     const unsigned x0 = (c - 1) * per;
                     for (unsigned k = 0; k < per; ++k) {
                         const unsigned x = x0 + k;
                         if (x >= W) break;
                         unsigned idx = rowp[x];
                         if (idx >= K) { badc = true; idx &= (1u << d) - 1u; }
+                        else if constexpr (RECT) {            // a delta frame: a pixel equal to prev's packs as u (prev is uniform)
+                            if (F.prev && F.prev[ro + x] == idx) idx = (unsigned) F.u;
+                        }
                         v |= idx << (8 - d * (k + 1));
                     }
                 }
@@ -473,8 +484,8 @@ __device__ inline unsigned data_byte(const PngImage& F, long long j, const unsig
     return v;
 }
 
-// file layout of an image: prefix (signature .. zlib header, from the blob), data_bytes of deflate data, Adler-32, the IDAT chunk's
-// CRC (png_crc_store_kernel), the IEND chunk
+// file layout of an image: prefix (.. zlib header, from the blob), data_bytes of deflate data, Adler-32, the data chunk's CRC
+// (png_crc_store_kernel), the IEND chunk when the image ends a file
 __global__ void __launch_bounds__(256) png_gather_kernel(const PngImage* __restrict__ images, int n_images, const unsigned* __restrict__ words,
                                                          const unsigned long long* __restrict__ seg_bits, const unsigned long long* __restrict__ seg_off,
                                                          const unsigned long long* __restrict__ res, const unsigned char* __restrict__ blob,
@@ -493,7 +504,8 @@ __global__ void __launch_bounds__(256) png_gather_kernel(const PngImage* __restr
         else if (j < F.data_bytes) v = data_byte(F, j, words, seg_bits, seg_off);
         else if (j < F.data_bytes + 4) v = (unsigned) (res[2 * lo + 1] >> (8 * (3 - (j - F.data_bytes)))) & 255u;
         else if (j < F.data_bytes + 8) continue;
-        else v = iend[j - F.data_bytes - 8];
+        else if (F.iend) v = iend[j - F.data_bytes - 8];
+        else continue;
         file[o] = (unsigned char) v;
     }
 }
@@ -516,7 +528,8 @@ __device__ inline unsigned crc_x_pow_8n(unsigned long long n) {       // x^(8n) 
     return r;
 }
 
-// The IDAT chunk's CRC covers its type and data: bytes [file_off + prefix_len - 6, + 10 + data_bytes).  Thread c of an image takes
+// The data chunk's CRC covers its type and data: bytes [file_off + prefix_len - crc_lead, + crc_lead + data_bytes + 4) (crc_lead: type,
+// an fdAT's sequence number, zlib header; + 4: the Adler-32).  Thread c of an image takes
 // bytes [128c, 128c + 128) of that range: their remainder with a zero register, times x^(8 * bytes after them); thread 0 adds the
 // initial register 0xFFFFFFFF times x^(8 * all bytes).  The XOR of all of these is the register at the end.
 __global__ void __launch_bounds__(256) png_crc_kernel(const PngImage* __restrict__ images, int n_images, const unsigned char* __restrict__ file,
@@ -535,8 +548,8 @@ __global__ void __launch_bounds__(256) png_crc_kernel(const PngImage* __restrict
             if (images[mid].crc_base <= t) lo = mid; else hi = mid - 1;
         }
         const PngImage& F = images[lo];
-        const long long len = 10 + F.data_bytes, c = t - F.crc_base, a = c * PNG_CRC_CHUNK, e = min(len, a + PNG_CRC_CHUNK);
-        const unsigned char* __restrict__ src = file + F.file_off + F.prefix_len - 6;
+        const long long len = F.crc_lead + 4 + F.data_bytes, c = t - F.crc_base, a = c * PNG_CRC_CHUNK, e = min(len, a + PNG_CRC_CHUNK);
+        const unsigned char* __restrict__ src = file + F.file_off + F.prefix_len - F.crc_lead;
         unsigned reg = 0;
         for (long long i = a; i < e; ++i) reg = table[(reg ^ src[i]) & 255u] ^ (reg >> 8);
         reg = crc_mul(reg, crc_x_pow_8n((unsigned long long) (len - e)));
@@ -559,15 +572,16 @@ __global__ void __launch_bounds__(64) png_crc_store_kernel(const PngImage* __res
 
 size_t png_deflate_lds_bytes(int max_seg_len) { return (size_t) png_buf_bytes(max_seg_len) + 2 * (1 << PNG_HASH_BITS) + sizeof(PngTables); }
 
-hipError_t launch_png_deflate(const PngImage* d_images, int n_images, long long n_segs, int max_seg_len, int grid, unsigned* d_words,
+hipError_t launch_png_deflate(const PngImage* d_images, int n_images, long long n_segs, int max_seg_len, int grid, bool rect, unsigned* d_words,
                               unsigned long long* d_seg_bits, unsigned long long* d_seg_adler, unsigned* d_tokens, unsigned long long* d_bad,
                               hipStream_t s) {
     const size_t lds = png_deflate_lds_bytes(max_seg_len);
+    const auto kernel = rect ? png_deflate_kernel<true> : png_deflate_kernel<false>;
     if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*) png_deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+        const hipError_t e = hipFuncSetAttribute((const void*) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(png_deflate_kernel, dim3((unsigned) grid), dim3(64), lds, s, d_images, n_images, n_segs, png_buf_bytes(max_seg_len), d_words,
+    hipLaunchKernelGGL(kernel, dim3((unsigned) grid), dim3(64), lds, s, d_images, n_images, n_segs, png_buf_bytes(max_seg_len), d_words,
                        d_seg_bits, d_seg_adler, d_tokens, (long long) max_seg_len, d_bad);
     return hipSuccess;
 }

@@ -91,6 +91,9 @@ _ABI = {
     "nq_png_max_bytes": (_i32, [_i32, _vp, _vp, _vp, _i32, _pi64]),
     "nq_encode_png_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
     "nq_encode_png": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
+    "nq_apng_max_bytes": (_i32, [_i32, _i32, _i32, _i32, _pi64]),
+    "nq_encode_apng_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _pi64, _vp]),
+    "nq_encode_apng": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _pi64, _vp]),
 }
 
 
@@ -442,19 +445,21 @@ def convert_frames_device(q, d_pixels, widths, heights, nMaxColors, dither, d_ou
     return pal[:K.value].copy()
 
 
-def convert_frames(kind, frames, nMaxColors, dither, device=0, mode=MODE_PARALLEL_TILED, seeds=None, tile=None):
-    """nq_convert_frames on host arrays: `frames` is a sequence of 2-D int32/uint32 ARGB_8888 arrays (sizes may differ).  Returns
-    (palette, [QuantizedImage per frame]) -- one palette shared by all frames (include/nquant_abi.h, "one palette for a sequence of
-    frames").  seeds[i] defaults to 0 for every frame; tile as for the quantizer objects (None = automatic)."""
+def _frames_quantizer(kind, frames, device, mode, tile):
+    """(the frames as int32 arrays, a quantizer of `kind` whose handle runs the frame-sequence calls)."""
     frames = [_as_i32(f) for f in frames]
-    n = len(frames)
-    if n == 0:
+    if len(frames) == 0:
         raise ValueError("no frames")
     for f in frames:
         if f.ndim != 2:
             raise ValueError("every frame must be a 2-D (height, width) array")
     cls = PnnLABQuantizer if int(kind) == NQ_KIND_LAB else PnnQuantizer
-    q = cls(frames[0], device=device, mode=mode, tile=tile)
+    return frames, cls(frames[0], device=device, mode=mode, tile=tile)
+
+
+def _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds):
+    """nq_convert_frames of the int32 frames on the handle of quantizer `q`, which stays open."""
+    n = len(frames)
     hs = np.array([f.shape[0] for f in frames], np.int32)
     ws = np.array([f.shape[1] for f in frames], np.int32)
     sd = np.array([0] * n if seeds is None else list(seeds), np.int64)
@@ -467,11 +472,19 @@ def convert_frames(kind, frames, nMaxColors, dither, device=0, mode=MODE_PARALLE
     idx = (C.c_void_p * n)(*[o.ctypes.data for o in idxs])
     pal = np.zeros(max(int(nMaxColors), 2), np.int32)
     K = C.c_int32(0)
+    q._check(q._L.nq_convert_frames(q._h, n, src, ws.ctypes.data, hs.ctypes.data, int(nMaxColors), int(bool(dither)), sd.ctypes.data,
+                                    int(mode), dst, idx, pal.ctypes.data, C.byref(K)))
+    palette = pal[:K.value].copy()
+    return palette, [QuantizedImage(o, i, palette) for o, i in zip(outs, idxs)]
+
+
+def convert_frames(kind, frames, nMaxColors, dither, device=0, mode=MODE_PARALLEL_TILED, seeds=None, tile=None):
+    """nq_convert_frames on host arrays: `frames` is a sequence of 2-D int32/uint32 ARGB_8888 arrays (sizes may differ).  Returns
+    (palette, [QuantizedImage per frame]) -- one palette shared by all frames (include/nquant_abi.h, "one palette for a sequence of
+    frames").  seeds[i] defaults to 0 for every frame; tile as for the quantizer objects (None = automatic)."""
+    frames, q = _frames_quantizer(kind, frames, device, mode, tile)
     try:
-        q._check(q._L.nq_convert_frames(q._h, n, src, ws.ctypes.data, hs.ctypes.data, int(nMaxColors), int(bool(dither)), sd.ctypes.data,
-                                        int(mode), dst, idx, pal.ctypes.data, C.byref(K)))
-        palette = pal[:K.value].copy()
-        return palette, [QuantizedImage(o, i, palette) for o, i in zip(outs, idxs)]
+        return _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds)
     finally:
         q.close()
 

@@ -194,6 +194,48 @@ public class PnnQuantizer {
 	/** nq_png_max_bytes of one image for K = 256 (an upper bound for every K); -1 for an invalid size */
 	private static native long nqPngMaxBytes(int width, int height);
 
+	/** An animated PNG (APNG) of index maps of one size over one palette (nq_encode_apng, encoded on the GPU): every frame after the
+	 *  first stores only the rectangle that differs from the frame before, and all 8 bits of the palette's alpha are kept, so --
+	 *  unlike encodeGifDelta -- the palette may hold transparent and translucent entries.  index[i] are DIRECT buffers of width*height
+	 *  palette indices; delaysCs in hundredths of a second (null: 0); loopCount 0 plays for ever. */
+	public static byte[] encodeApng(java.nio.ShortBuffer[] index, int width, int height, int[] palette, int[] delaysCs, int loopCount) {
+		java.nio.ByteBuffer out = apngBuffer(index.length, width, height);
+		long h = nqCreate(0, 0);
+		try {
+			return gifBytes(out, nqEncodeApng(h, index, width, height, palette, delaysCs, loopCount, out, out.capacity()));
+		} finally {
+			nqDestroy(h);
+		}
+	}
+	private static native long nqEncodeApng(long h, java.nio.ShortBuffer[] index, int width, int height, int[] palette, int[] delaysCs,
+			int loopCount, java.nio.ByteBuffer out, long cap);
+
+	/** convertFrames (one shared palette, every frame dithered with it) followed by encodeApng of the index maps, in one native call on
+	 *  one handle; nMaxColors <= 256.  in[i] are DIRECT buffers of width*height ARGB ints.  Regions that do not move drop out of the
+	 *  file when the seeds are equal (the tiled dither then repeats their indices from frame to frame). */
+	public static byte[] convertFramesToApng(int kind, java.nio.IntBuffer[] in, int width, int height, int nMaxColors, boolean dither,
+			long[] seeds, int[] delaysCs, int loopCount) {
+		java.nio.ByteBuffer out = apngBuffer(in.length, width, height);
+		long h = nqCreate(kind, 0);
+		try {
+			return gifBytes(out, nqConvertFramesToApng(h, in, width, height, nMaxColors, dither, seeds, MODE_PARALLEL_TILED, delaysCs,
+					loopCount, out, out.capacity()));
+		} finally {
+			nqDestroy(h);
+		}
+	}
+	private static native long nqConvertFramesToApng(long h, java.nio.IntBuffer[] in, int width, int height, int nMaxColors,
+			boolean dither, long[] seeds, int mode, int[] delaysCs, int loopCount, java.nio.ByteBuffer out, long cap);
+
+	private static java.nio.ByteBuffer apngBuffer(int n, int width, int height) {
+		long cap = nqApngMaxBytes(n, width, height);
+		if (cap < 0 || cap > Integer.MAX_VALUE)
+			throw new IllegalArgumentException("an APNG of these frames does not fit one byte[]");
+		return java.nio.ByteBuffer.allocateDirect((int) cap);
+	}
+	/** nq_apng_max_bytes (an upper bound for every K and any content); -1 for invalid sizes */
+	private static native long nqApngMaxBytes(int n, int width, int height);
+
 	@Override
 	protected void finalize() throws Throwable {
 		if (handle != 0) { nqDestroy(handle); handle = 0; }

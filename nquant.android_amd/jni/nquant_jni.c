@@ -299,3 +299,79 @@ JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertToPng(JNIE
     if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
     return (jlong) offs[1];
 }
+
+/* nqApngMaxBytes(): nq_apng_max_bytes, the bound for every K; -1 when a size is invalid */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqApngMaxBytes(JNIEnv* env, jclass c, jint n, jint width, jint height) {
+    int64_t bytes = -1;
+    if (nq_apng_max_bytes(n, width, height, 0, &bytes) != NQ_OK) bytes = -1;
+    return (jlong) bytes;
+}
+
+/* encodeApng(): direct ShortBuffers of indices in (frames of one size), the file written to the direct ByteBuffer `out` (cap bytes)
+ * -> nq_encode_apng.  Returns the file size. */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqEncodeApng(JNIEnv* env, jclass c, jlong hh, jobjectArray index,
+        jint width, jint height, jintArray palette, jintArray delaysCs, jint loopCount, jobject out, jlong cap) {
+    nq_handle* h = (nq_handle*) (intptr_t) hh;
+    const jsize n = (*env)->GetArrayLength(env, index);
+    const uint16_t** src = malloc(sizeof(*src) * (n > 0 ? n : 1));
+    if (!src) { throw_rt(env, "out of memory"); return -1; }
+    for (jsize i = 0; i < n; ++i)
+        src[i] = (const uint16_t*) (*env)->GetDirectBufferAddress(env, (*env)->GetObjectArrayElement(env, index, i));
+    jint* pal = (*env)->GetIntArrayElements(env, palette, NULL);
+    jint* d = delaysCs ? (*env)->GetIntArrayElements(env, delaysCs, NULL) : NULL;
+    const jsize K = (*env)->GetArrayLength(env, palette);
+    int64_t size = -1;
+    const int rc = nq_encode_apng(h, n, src, width, height, (const uint32_t*) pal, K, (const int32_t*) d, loopCount, 0,
+                                  (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, &size, NULL);
+    if (d) (*env)->ReleaseIntArrayElements(env, delaysCs, d, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, palette, pal, JNI_ABORT);
+    free(src);
+    if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
+    return (jlong) size;
+}
+
+/* convertFramesToApng(): nq_convert_frames of frames of one size with index outputs (the ARGB outputs go to scratch), then
+ * nq_encode_apng of the index maps with the shared palette, on the same handle, into the direct ByteBuffer `out` (cap bytes).
+ * Returns the file size. */
+JNIEXPORT jlong JNICALL Java_com_android_nQuant_PnnQuantizer_nqConvertFramesToApng(JNIEnv* env, jclass c, jlong hh, jobjectArray in,
+        jint width, jint height, jint nMaxColors, jboolean dither, jlongArray seeds, jint mode, jintArray delaysCs, jint loopCount,
+        jobject out, jlong cap) {
+    nq_handle* h = (nq_handle*) (intptr_t) hh;
+    const jsize n = (*env)->GetArrayLength(env, in);
+    const jsize m = n > 0 ? n : 1;
+    const int pcap = nMaxColors > 2 ? nMaxColors : 2;
+    const size_t px = (size_t) (width > 0 ? width : 1) * (size_t) (height > 0 ? height : 1);
+    const uint32_t** src = malloc(sizeof(*src) * m);
+    uint32_t** argb = calloc(m, sizeof(*argb));
+    uint16_t** idx = calloc(m, sizeof(*idx));
+    int32_t* w = malloc(sizeof(int32_t) * m);
+    int32_t* hg = malloc(sizeof(int32_t) * m);
+    uint32_t* palette = malloc(sizeof(uint32_t) * (size_t) pcap);
+    jlong* sd = seeds ? (*env)->GetLongArrayElements(env, seeds, NULL) : NULL;
+    jint* d = delaysCs ? (*env)->GetIntArrayElements(env, delaysCs, NULL) : NULL;
+    int ok = src && argb && idx && w && hg && palette && sd;
+    for (jsize i = 0; ok && i < n; ++i) {
+        src[i] = (const uint32_t*) (*env)->GetDirectBufferAddress(env, (*env)->GetObjectArrayElement(env, in, i));
+        argb[i] = malloc(px * sizeof(uint32_t));
+        idx[i] = malloc(px * sizeof(uint16_t));
+        w[i] = width; hg[i] = height;
+        ok = argb[i] && idx[i];
+    }
+    int32_t K = 0;
+    int64_t size = -1;
+    int rc = NQ_OK;
+    if (ok) {
+        rc = nq_convert_frames(h, n, src, w, hg, nMaxColors, dither ? 1 : 0, (const int64_t*) sd, mode, argb, idx, palette, &K);
+        if (rc == NQ_OK)
+            rc = nq_encode_apng(h, n, (const uint16_t* const*) idx, width, height, palette, K, (const int32_t*) d, loopCount, 0,
+                                (uint8_t*) (*env)->GetDirectBufferAddress(env, out), cap, &size, NULL);
+    }
+    for (jsize i = 0; argb && idx && i < n; ++i) { free(argb[i]); free(idx[i]); }
+    if (d) (*env)->ReleaseIntArrayElements(env, delaysCs, d, JNI_ABORT);
+    if (sd) (*env)->ReleaseLongArrayElements(env, seeds, sd, JNI_ABORT);
+    free(palette); free(hg); free(w); free(idx); free(argb); free(src);
+    if (!seeds) { throw_rt(env, "seeds is null"); return -1; }
+    if (!ok) { throw_rt(env, "out of memory"); return -1; }
+    if (rc != NQ_OK) { throw_rt(env, nq_last_error(h)); return -1; }
+    return (jlong) size;
+}
