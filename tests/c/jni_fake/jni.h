@@ -1,34 +1,50 @@
-/* tests/c/jni_syntax/jni.h -- NOT a JDK header: the handful of JNI declarations (names and signatures as in the public JNI
- * specification) that nquant.android_amd/jni/nquant_jni.c uses, so that `gcc -fsyntax-only` can check the shim's calls into
- * include/nquant_abi.h in an image without a JDK (tests/test_abi_cpu.py).  Never linked, never shipped; a real build uses
- * $JAVA_HOME/include/jni.h (see the shim's header comment). */
-#ifndef NQ_JNI_SYNTAX_STUB_H
-#define NQ_JNI_SYNTAX_STUB_H
+/* tests/c/jni_fake/jni.h -- NOT a JDK header.  Our own declarations of the JNI types and of a JNINativeInterface_ function table, names
+ * and signatures as in the public JNI specification, for the part of JNI that nquant.android_amd/jni/nquant_jni.c uses.  With
+ * fake_jni.c it forms a small fake JNI runtime under which the tests EXECUTE the shim (tests/jni_fake.py); the order of the table's
+ * slots is our own, so nothing compiled against this header can be loaded into a real JVM.  Test infrastructure, never shipped; a
+ * real build uses $JAVA_HOME/include/jni.h (see the shim's header comment). */
+#ifndef NQ_FAKE_JNI_H
+#define NQ_FAKE_JNI_H
 #include <stdint.h>
-#define JNIEXPORT
+
+#define JNIEXPORT __attribute__((visibility("default")))
 #define JNICALL
 #define JNI_FALSE 0
 #define JNI_TRUE 1
+#define JNI_OK 0
+#define JNI_ERR (-1)
+#define JNI_COMMIT 1
 #define JNI_ABORT 2
+
+typedef int8_t jbyte;
+typedef int16_t jshort;
 typedef int32_t jint;
 typedef int64_t jlong;
-typedef int16_t jshort;
 typedef uint8_t jboolean;
 typedef jint jsize;
+
 typedef struct _jobject* jobject;
 typedef jobject jclass;
+typedef jobject jthrowable;
 typedef jobject jarray;
 typedef jarray jintArray;
 typedef jarray jlongArray;
 typedef jarray jshortArray;
 typedef jarray jobjectArray;
+
 struct JNINativeInterface_;
 typedef const struct JNINativeInterface_* JNIEnv;
+
 struct JNINativeInterface_ {
     jclass (*FindClass)(JNIEnv*, const char*);
     jint (*ThrowNew)(JNIEnv*, jclass, const char*);
+    jthrowable (*ExceptionOccurred)(JNIEnv*);
+    void (*ExceptionClear)(JNIEnv*);
     jboolean (*ExceptionCheck)(JNIEnv*);
+    jint (*PushLocalFrame)(JNIEnv*, jint);
+    jobject (*PopLocalFrame)(JNIEnv*, jobject);
     void (*DeleteLocalRef)(JNIEnv*, jobject);
+    jint (*EnsureLocalCapacity)(JNIEnv*, jint);
     jsize (*GetArrayLength)(JNIEnv*, jarray);
     jobjectArray (*NewObjectArray)(JNIEnv*, jsize, jclass, jobject);
     jobject (*GetObjectArrayElement)(JNIEnv*, jobjectArray, jsize);
