@@ -339,6 +339,43 @@ int nq_encode_apng(nq_handle* h, int n, const uint16_t* const* index, int width,
                    const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_bytes,
                    uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
 
+/* ---- temporal hold: what makes still regions of REAL footage repeat from frame to frame, so that the delta GIF and APNG encoders above
+ *      find something to drop.  One least-significant bit of sensor or codec noise in a tile changes that tile's whole error-diffusion
+ *      chain; after this pass a pixel whose SOURCE colour has not moved by more than `threshold` keeps the PALETTE INDEX (and the ARGB
+ *      output) it had in the frame before (gifski, ffmpeg paletteuse diff_mode).  It runs between nq_convert_frames_device and the
+ *      encoder, on the buffers those calls share; no palette is needed.
+ *  * Inputs: n ARGB frames d_argb[i] (never written), their n uint16 index maps d_index[i] and, optionally, their n ARGB outputs
+ *    d_out_argb[i], both updated in place; all are width x height.  threshold is 0..255.
+ *  * For every pixel position p, independently of every other:
+ *        anchor = argb[0][p]
+ *        for i = 1 .. n-1:
+ *            d = the largest |difference| of the four 8-bit channels (a, r, g, b) of argb[i][p] and anchor
+ *            d <= threshold: index[i][p] = index[i-1][p], out_argb[i][p] = out_argb[i-1][p] (the values AFTER frame i-1 was processed),
+ *                            held[i] += 1
+ *            otherwise:      anchor = argb[i][p]; index[i][p] and out_argb[i][p] stay as they are
+ *    The anchor moves only when a pixel is released: a slow fade accumulates until it exceeds the threshold and is then taken over, it
+ *    never drifts without bound.  threshold 0 holds exactly the pixels whose source equals the anchor bit for bit.  Frame 0 is never
+ *    written and held[0] = 0; n = 1 checks its arguments and does nothing else.  Nothing outside the n * width * height elements of
+ *    each array is read or written.
+ *  * The trade: a held pixel does not diffuse its quantisation error again -- it shows the colour it was given when its anchor was
+ *    set, not the nearest rendering of its present source.  With a threshold near the noise floor (2..6) that is invisible and the
+ *    background stops shimmering; a large threshold posterises slow gradients in time.
+ *  * nq_hold_frames_device: the frames in DEVICE memory; pointer arrays are host arrays of n pointers.  Index pointers need 2-byte,
+ *    ARGB pointers 4-byte alignment; when every pointer is 16-byte aligned the kernel moves 16 bytes per access, otherwise one pixel per
+ *    access (same results).  No index map or output may overlap any other buffer of the call.  out_held (host, n values; NULL: not wanted) receives held[];
+ *    the call returns when it is there.  With out_held == NULL the call is asynchronous on the handle's stream.  h may be a handle of
+ *    either kind: its stream, scratch and error text are used, its params are neither read nor changed.
+ *    nq_hold_frames: the same with HOST buffers (all frames are uploaded, the device form runs, index maps and outputs 1 .. n-1 are
+ *    copied back).
+ *  * NQ_ERR_INVALID before any device work, every buffer untouched: n < 1, a side outside 1..65535, threshold outside 0..255, a NULL
+ *    pointer array or entry (d_out_argb may be NULL as a whole, not in part), an odd index pointer, an ARGB pointer that is not 4-byte
+ *    aligned, n * width * height above 2^31 - 1.  The handle stays usable after any of these.
+ *  The kernel: DESIGN.md 5b "temporal hold". ---- */
+int nq_hold_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, uint16_t* const* d_index, uint32_t* const* d_out_argb,
+                          int width, int height, int threshold, int64_t* out_held);
+int nq_hold_frames(nq_handle* h, int n, const uint32_t* const* argb, uint16_t* const* index, uint32_t* const* out_argb,
+                   int width, int height, int threshold, int64_t* out_held);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

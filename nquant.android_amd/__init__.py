@@ -12,6 +12,7 @@ from .gif import (convert_frames_to_gif, encode_gif, encode_gif_delta, encode_gi
                   write_gif)
 from .png import convert_to_png, encode_png, encode_png_device, png_max_bytes, write_png
 from .apng import apng_max_bytes, convert_frames_to_apng, encode_apng, encode_apng_device, write_apng
+from .hold import hold_frames, hold_frames_device
 from .build import build as build_library
 
 __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARALLEL_TILED", "MODE_LOOKUP_ONLY",
@@ -20,4 +21,4 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "convert_frames_device", "pnnquan_frames_device", "encode_gif", "encode_gif_device", "write_gif", "convert_frames_to_gif",
            "encode_gif_delta", "encode_gif_delta_device", "gif_max_bytes", "encode_png", "encode_png_device", "write_png",
            "convert_to_png", "png_max_bytes", "apng_max_bytes", "encode_apng", "encode_apng_device", "write_apng",
-           "convert_frames_to_apng"]
+           "convert_frames_to_apng", "hold_frames", "hold_frames_device"]

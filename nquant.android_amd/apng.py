@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from .gif import _Handle, _delays, _index_maps, _palette
+from .hold import _hold_host, _threshold
 from .host import MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frames_quantizer, load_library
 
 
@@ -83,20 +84,26 @@ def write_apng(path, frames, palette, delays_cs=None, loop=0, segment_bytes=0, d
 
 
 def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, seeds=None, tile=None, segment_bytes=0, device=0,
-                           mode=MODE_PARALLEL_TILED, return_rects=False):
+                           mode=MODE_PARALLEL_TILED, return_rects=False, hold=None):
     """convert_frames (one shared palette for the ARGB frames, which must have one size) followed by encode_apng of the index maps on
     the same handle.  nMaxColors <= 256.  Seeds are passed on as given: regions that do not move repeat in the index maps, and so drop
-    out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.  Returns (file bytes, palette); with
-    return_rects=True (file bytes, palette, rectangles)."""
+    out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.  hold (None: no such pass): an integer
+    0..255 runs the temporal hold (hold.py) with that threshold between the two steps, on the same handle, so that pixels whose source
+    moved by no more than it keep their index (footage with sensor or codec noise); the index maps pass through host memory in between.
+    Returns (file bytes, palette); with return_rects=True (file bytes, palette, rectangles)."""
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a PNG palette holds at most 256 entries")
     if len({np.asarray(f).shape for f in frames}) > 1:
         raise ValueError("APNG: all frames must have one size")
+    if hold is not None:
+        hold = _threshold(hold)
     frames, q = _frames_quantizer(kind, frames, device, mode, tile)
     try:
         palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds)
         maps = _index_maps([o.index for o in outs])
         height, width = _one_size(maps)
+        if hold is not None:
+            _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
         data, rects = _encode(q._L, q._h, "nq_encode_apng", [a.ctypes.data for a in maps], width, height, palette, delays_cs, loop,
                               segment_bytes, q._check)
     finally:

@@ -23,6 +23,7 @@ UNITS = {
     "nq_dither_fast.hip": ("device", ["nq_dither_fast.hip", "nq_device.h", "nq_kernels.h", os.path.join(INC, "nq_blue_noise_64x64.inc")]),
     "nq_gif.hip": ("device", ["nq_gif.hip", "nq_kernels.h"]),
     "nq_png.hip": ("device", ["nq_png.hip", "nq_kernels.h"]),
+    "nq_hold.hip": ("device", ["nq_hold.hip", "nq_kernels.h"]),
     "nq_abi.cpp": ("host", ["nq_abi.cpp", "nq_kernels.h", os.path.join(INC, "nquant_abi.h")]),
 }
 

@@ -237,6 +237,11 @@ struct nq_handle {
     DevBuf<nq::PngImage> d_png;
     DevBuf<unsigned> png_tokens, png_crc;
     DevBuf<unsigned long long> png_adler;
+    // nq_hold_frames_device: the tables of frame pointers (source, index, output: n each; the host copy stays alive for the asynchronous
+    // upload) and the per-frame held counters; nq_hold_frames stages its frames in d_in / d_out_index / d_out_argb
+    std::vector<void*> h_hold_ptrs;
+    DevBuf<void*> hold_ptrs;
+    DevBuf<unsigned long long> hold_held;
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
@@ -2494,6 +2499,110 @@ int nq_encode_apng(nq_handle* h, int n, const uint16_t* const* index, int width,
         rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
         return rc ? rc : apng_encode(h, n, dev.data(), width, height, palette, K, delays_cs, loop_count, segment_bytes, out, cap, out_size,
                                      out_rects);
+    });
+}
+
+} // extern "C"
+
+// ---- temporal hold (nq_hold.hip) ----
+namespace {
+
+// every argument of both forms, from the host arrays alone (no device work)
+int hold_check(nq_handle* h, int n, const uint32_t* const* argb, uint16_t* const* index, uint32_t* const* out_argb, int width, int height,
+               int threshold) {
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    if (width < 1 || width > 65535 || height < 1 || height > 65535) NQ_FAIL(h, NQ_ERR_INVALID, "%d x %d: sides must be 1..65535", width, height);
+    if (threshold < 0 || threshold > 255) NQ_FAIL(h, NQ_ERR_INVALID, "threshold = %d: must be 0..255", threshold);
+    if ((long long) n * width * height > 2147483647ll)
+        NQ_FAIL(h, NQ_ERR_INVALID, "%d frames of %d x %d: more than 2^31 - 1 pixels", n, width, height);
+    if (!argb || !index) NQ_FAIL(h, NQ_ERR_INVALID, "the array of frame / index pointers is NULL");
+    for (int i = 0; i < n; ++i) {
+        if (!argb[i] || ((uintptr_t) argb[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: pixel pointer NULL or not 4-byte aligned", i);
+        if (!index[i] || ((uintptr_t) index[i] & 1)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: index pointer NULL or not 2-byte aligned", i);
+        if (out_argb && (!out_argb[i] || ((uintptr_t) out_argb[i] & 3)))
+            NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: output pointer NULL or not 4-byte aligned", i);
+    }
+    return NQ_OK;
+}
+
+// nq_hold_frames_device after the checks: the pointer tables go up, one launch walks the sequence, the counters come back when wanted
+int hold_device(nq_handle* h, int n, const uint32_t* const* d_argb, uint16_t* const* d_index, uint32_t* const* d_out_argb, int width,
+                int height, int threshold, int64_t* out_held) {
+    if (n == 1) {                                   // frame 0 is never written
+        if (out_held) out_held[0] = 0;
+        return NQ_OK;
+    }
+    std::vector<void*>& t = h->h_hold_ptrs;
+    t.assign(3 * (size_t) n, nullptr);
+    bool vec = true;                                // the 16-byte path needs every frame of every stream aligned to it
+    for (int i = 0; i < n; ++i) {
+        t[i] = const_cast<uint32_t*>(d_argb[i]); t[n + (size_t) i] = d_index[i];   // (the kernel reads the sources only)
+        if (d_out_argb) t[2 * (size_t) n + i] = d_out_argb[i];
+        vec = vec && !(((uintptr_t) d_argb[i] | (uintptr_t) d_index[i] | (uintptr_t) (d_out_argb ? d_out_argb[i] : nullptr)) & 15);
+    }
+    NQ_HIP(h, h->hold_ptrs.reserve(t.size()));
+    if (out_held) NQ_HIP(h, h->hold_held.reserve(n));
+    // With out_held == NULL the call returns with this upload only enqueued, and the next call on the handle rewrites `t` and may
+    // regrow hold_ptrs.  Both are safe for the reason the encoders' table uploads are: the runtime copies a small pageable source
+    // into its own staging memory before hipMemcpyAsync returns, and DevBuf::reserve frees through hipFree, which waits for the device.
+    NQ_HIP(h, hipMemcpyAsync(h->hold_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+    if (out_held) NQ_HIP(h, hipMemsetAsync(h->hold_held.p, 0, n * sizeof(unsigned long long), h->stream));
+    launch_hold(reinterpret_cast<const unsigned* const*>(h->hold_ptrs.p), reinterpret_cast<unsigned short* const*>(h->hold_ptrs.p + n),
+                d_out_argb ? reinterpret_cast<unsigned* const*>(h->hold_ptrs.p + 2 * (size_t) n) : nullptr, n, (long long) width * height,
+                threshold, vec, out_held ? h->hold_held.p : nullptr, h->stream);
+    NQ_HIP(h, launch_status());
+    if (!out_held) return NQ_OK;
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "held counters");
+    NQ_HIP(h, hipMemcpyAsync(out_held, h->hold_held.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    return NQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_hold_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, uint16_t* const* d_index, uint32_t* const* d_out_argb,
+                          int width, int height, int threshold, int64_t* out_held) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = hold_check(h, n, d_argb, d_index, d_out_argb, width, height, threshold);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return hold_device(h, n, d_argb, d_index, d_out_argb, width, height, threshold, out_held);
+}
+
+int nq_hold_frames(nq_handle* h, int n, const uint32_t* const* argb, uint16_t* const* index, uint32_t* const* out_argb, int width, int height,
+                   int threshold, int64_t* out_held) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = hold_check(h, n, argb, index, out_argb, width, height, threshold);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    if (n == 1) return hold_device(h, n, argb, index, out_argb, width, height, threshold, out_held);
+    // frames lie `pitch` elements apart in the staging buffers, so that every one starts 16-byte aligned (the vector path)
+    const size_t px = (size_t) width * height, pitch = (px + 7) & ~(size_t) 7;
+    return host_form(h, [&]() -> int {
+        NQ_HIP(h, h->d_in.reserve(n * pitch));
+        NQ_HIP(h, h->d_out_index.reserve(n * pitch));
+        if (out_argb) NQ_HIP(h, h->d_out_argb.reserve(n * pitch));
+        std::vector<const uint32_t*> d_src(n);
+        std::vector<uint16_t*> d_idx(n);
+        std::vector<uint32_t*> d_out(n);
+        for (int i = 0; i < n; ++i) {
+            d_src[i] = h->d_in.p + i * pitch; d_idx[i] = h->d_out_index.p + i * pitch; d_out[i] = out_argb ? h->d_out_argb.p + i * pitch : nullptr;
+            NQ_HIP(h, hipMemcpyAsync(h->d_in.p + i * pitch, argb[i], px * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            NQ_HIP(h, hipMemcpyAsync(d_idx[i], index[i], px * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+            if (out_argb) NQ_HIP(h, hipMemcpyAsync(d_out[i], out_argb[i], px * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        }
+        const int rc2 = hold_device(h, n, d_src.data(), d_idx.data(), out_argb ? d_out.data() : nullptr, width, height, threshold, out_held);
+        if (rc2) return rc2;
+        for (int i = 1; i < n; ++i) {
+            NQ_HIP(h, hipMemcpyAsync(index[i], d_idx[i], px * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+            if (out_argb) NQ_HIP(h, hipMemcpyAsync(out_argb[i], d_out[i], px * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        }
+        NQ_HIP(h, hipStreamSynchronize(h->stream));
+        return NQ_OK;
     });
 }
 

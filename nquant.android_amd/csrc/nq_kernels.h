@@ -259,4 +259,11 @@ void launch_png_gather(const PngImage* d_images, int n_images, const unsigned* d
                        const unsigned long long* d_seg_off, const unsigned long long* d_res, const unsigned char* d_blob, unsigned char* d_file,
                        long long total, long long n_crc_chunks, unsigned* d_crc, hipStream_t s);
 
+// ---- temporal hold (nq_hold.hip): d_src / d_idx / d_out are device arrays of n frame pointers (npix elements per frame; d_out null: no
+// ARGB stream), d_held n counters the caller zeroed (null: not counted).  Frames 1 .. n - 1 of idx (and out) are updated in place in one
+// launch.  vec: the 16-byte path -- the caller has checked that EVERY frame pointer of every stream is 16-byte aligned; otherwise the
+// one-pixel-per-thread path, which needs 2-byte (idx) and 4-byte (src, out) alignment only.  No idx / out frame may overlap another frame. ----
+void launch_hold(const unsigned* const* d_src, unsigned short* const* d_idx, unsigned* const* d_out, int n, long long npix, int threshold,
+                 bool vec, unsigned long long* d_held, hipStream_t s);
+
 } // namespace nq

@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .host import MODE_PARALLEL_TILED, NqError, _frame_sizes, convert_frames, load_library
+from .host import MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frame_sizes, _frames_quantizer, convert_frames, load_library
 
 
 def _palette(palette):
@@ -181,14 +181,33 @@ def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, 
 
 
 def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
-                          seeds=None, tile=None, delta=False):
+                          seeds=None, tile=None, hold=None, delta=False):
     """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
     delta=True: encode_gif_delta instead; the frames must have one size.  Seeds are passed on as given: regions that do not move repeat
     in the index maps, and so drop out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.
+    hold (delta=True only; None: no such pass): an integer 0..255 runs the temporal hold (hold.py) with that threshold between the
+    two steps, so that pixels whose source moved by no more than it keep their index -- what footage with sensor or codec noise needs
+    for its still regions to drop out.  All three steps then run on one handle; the index maps pass through host memory in between.
     Returns (file bytes, palette)."""
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
+    if hold is not None and not delta:
+        raise ValueError("hold needs delta=True: full frames store every pixel whether it repeats or not")
     if delta and len({np.asarray(f).shape for f in frames}) > 1:
         raise ValueError("delta mode: all frames must have one size")
+    if hold is not None:
+        from .hold import _hold_host, _threshold
+        hold = _threshold(hold)
+        frames, q = _frames_quantizer(kind, frames, device, mode, tile)
+        try:
+            palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds)
+            maps = [o.index for o in outs]
+            height, width = _one_size(maps)
+            _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
+            data, _ = _encode_delta(q._L, q._h, "nq_encode_gif_delta", [a.ctypes.data for a in maps], width, height, palette, delays_cs, loop,
+                                    segment_pixels, q._check)
+        finally:
+            q.close()
+        return data, palette
     palette, outs = convert_frames(kind, frames, nMaxColors, dither, device=device, mode=mode, seeds=seeds, tile=tile)
     return (encode_gif_delta if delta else encode_gif)([o.index for o in outs], palette, delays_cs, loop, segment_pixels, device), palette

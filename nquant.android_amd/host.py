@@ -94,6 +94,8 @@ _ABI = {
     "nq_apng_max_bytes": (_i32, [_i32, _i32, _i32, _i32, _pi64]),
     "nq_encode_apng_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _pi64, _vp]),
     "nq_encode_apng": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _pi64, _vp]),
+    "nq_hold_frames_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "nq_hold_frames": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
 }
 
 
