@@ -264,6 +264,46 @@ int nq_encode_gif_delta(nq_handle* h, int n, const uint16_t* const* index, int w
                         const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
                         uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
 
+/* ---- GIF encoding, lossy mode: the four GIF calls above with one more argument, `lossy` (0..255), after segment_pixels.  What decides
+ *      the size of a GIF once the still pixels are gone is how well the rest compresses, and a dithered index map is close to the worst
+ *      case for LZW: neighbouring pixels flip between two or three near palette colours and almost no string repeats.  In lossy mode
+ *      (gifsicle --lossy, gifski's quality) the encoder may, where the exact next index does not continue the current dictionary
+ *      string, take a near colour that does: matches get longer, there are fewer codes.  The file is a standard GIF.
+ *  * Everything about the file is as nq_encode_gif / nq_encode_gif_delta define it: header, colour table, extensions, rectangles, bodies,
+ *    segmentation, Clear and End-of-Information placement, code widths, sub-blocks.  The one change is inside a segment's chain, at the
+ *    step "is (pre, c) in the dictionary?" (pre: the code of the current string, c: the next pixel's index):
+ *      rgb[i] = the 8-bit r, g, b of entry i of the Kt-entry colour table as written to the file (alpha is ignored; delta mode's
+ *               entry u is 0, 0, 0);  T = the file's transparent index: t for the full-frame calls, u for delta mode, -1 when none
+ *      (pre, c) is in the dictionary:  proceed as without lossy (the exact index always wins, also among duplicate colours)
+ *      otherwise, when lossy > 0 and c != T:  the candidates are all c' in 0..Kt-1 with c' != c, c' != T, (pre, c') in the dictionary
+ *               and max(|dr|, |dg|, |db|) <= lossy between rgb[c'] and rgb[c].  If there is one, take the c' with the smallest
+ *               (dr^2 + dg^2 + db^2, c') in lexicographic order: pre = the code of (pre, c'), go on with the next pixel; this pixel
+ *               decodes as c'
+ *      no candidate:  exactly the miss of the lossless call: emit pre, add (pre, c) with the EXACT c (or Clear at 4096), pre = c
+ *    A segment's first pixel is always exact.
+ *  * lossy = 0 gives the bytes of the call without `lossy`, byte for byte.
+ *  * Every decoded pixel is the source index or a colour within `lossy` per channel of the source index's colour.  The metric is that
+ *    of nq_hold_frames' threshold, on purpose: the two knobs read alike.
+ *  * A transparent pixel is never replaced, and no pixel is replaced by the transparent index.
+ *  * Delta mode: rectangles and bodies come from the index maps as given, so out_rects equals the lossless call's, and the bound holds
+ *    for the composed canvas: a kept pixel shows a colour within `lossy` of an index that has not changed since.
+ *  * nq_gif_max_bytes bounds the file as before: a chain still emits at most one code per pixel.
+ *  * lossy outside 0..255 is NQ_ERR_INVALID before any device work (*out_size and out_rects untouched).  All other checks, cap /
+ *    *out_size, out_rects and the two memory forms are as for the counterparts; an index >= K is reported after the encoding.
+ *  The kernel and why the exact c is what enters the dictionary: DESIGN.md 5b "lossy mode". ---- */
+int nq_encode_gif_lossy_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                               const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                               uint8_t* out, int64_t cap, int64_t* out_size);
+int nq_encode_gif_lossy(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                        const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                        uint8_t* out, int64_t cap, int64_t* out_size);
+int nq_encode_gif_delta_lossy_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height,
+                                     const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                                     uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
+int nq_encode_gif_delta_lossy(nq_handle* h, int n, const uint16_t* const* index, int width, int height,
+                              const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                              uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
+
 /* ---- PNG encoding: palette index maps (what the convert calls write to out_index) to indexed PNG files, on the GPU.  One call encodes
  *      n independent images into n files (n = 1 is the plain case; a batch fills the chip).  Image i is a uint16 index map, row-major,
  *      widths[i] x heights[i], with its own K[i] <= 256 and its own palette: the K[i] ARGB entries at palettes[i * palette_stride]

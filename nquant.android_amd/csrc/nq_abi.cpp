@@ -223,6 +223,9 @@ struct nq_handle {
     DevBuf<unsigned char> gif_blob, gif_file;
     DevBuf<unsigned short> gif_in;
     std::vector<uint8_t> h_gif_blob;
+    // lossy mode: the file's colour table as the chains read it (256 entries 0x00RRGGBB)
+    std::vector<unsigned> h_gif_rgb;
+    DevBuf<unsigned> gif_rgb;
     // nq_encode_gif_delta_device: the frames' pointers, the changed pixels' boxes ({min x, min y, max x, max y}[n - 1], bad-index flag),
     // the body table and the cropped bodies the LZW chains read
     std::vector<int> h_gif_box;
@@ -1844,9 +1847,10 @@ bool gif_check_shape(int n, const int32_t* widths, const int32_t* heights, int K
 
 // everything but the index pointers, checked from the host arrays alone (no device work)
 int gif_check(nq_handle* h, int n, const int32_t* widths, const int32_t* heights, const uint32_t* palette, int K, const int32_t* delays_cs,
-              int loop_count, int segment_pixels, const uint8_t* out, int64_t cap, int64_t* out_size) {
+              int loop_count, int segment_pixels, int lossy, const uint8_t* out, int64_t cap, int64_t* out_size) {
     char why[256];
     if (!gif_check_shape(n, widths, heights, K, segment_pixels, why, sizeof why)) NQ_FAIL(h, NQ_ERR_INVALID, "%s", why);
+    if (lossy < 0 || lossy > 255) NQ_FAIL(h, NQ_ERR_INVALID, "lossy = %d: must be 0..255", lossy);
     if (!palette || !out_size) NQ_FAIL(h, NQ_ERR_INVALID, "palette / out_size is NULL");
     if (loop_count < -1 || loop_count > 65535) NQ_FAIL(h, NQ_ERR_INVALID, "loop_count = %d: must be -1..65535", loop_count);
     if (delays_cs)
@@ -1869,13 +1873,20 @@ struct GifRect { int x, y, w, h; };
 // The file of n index maps (device memory, map i is rects[i].w x rects[i].h and drawn at rects[i].x, rects[i].y) on a W x H screen.
 // Kt sizes the colour table and the code size (K palette entries + the delta mode's unchanged index); gce < 0: no graphic control
 // extensions, else their packed byte; tr: their transparent index byte and the screen's background index.  The caller has zeroed
-// nothing: the bad-index flag is this function's own.
+// nothing: the bad-index flag is this function's own.  lossy > 0: the chains may take a colour within `lossy` of a pixel's own
+// ("GIF encoding, lossy mode"); T: the index they neither replace nor substitute, -1 when the file has no transparent index.
 int gif_encode_maps(nq_handle* h, int n, const uint16_t* const* d_index, const GifRect* rects, int W, int H, const uint32_t* palette, int K,
-                    int Kt, int gce, int tr, int bg, const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap,
-                    int64_t* out_size) {
+                    int Kt, int gce, int tr, int bg, const int32_t* delays_cs, int loop_count, int segment_pixels, int T, int lossy,
+                    uint8_t* out, int64_t cap, int64_t* out_size) {
     int N = 0;
     while ((1 << (N + 1)) < std::max(Kt, 2)) ++N;
     const int m = std::max(2, N + 1);
+    if (lossy > 0) {                                // the colour table as the file holds it: alpha dropped, zeros from entry K on
+        h->h_gif_rgb.assign(256, 0u);
+        for (int i = 0; i < K; ++i) h->h_gif_rgb[i] = palette[i] & 0xFFFFFFu;
+        NQ_HIP(h, h->gif_rgb.reserve(256));
+        NQ_HIP(h, hipMemcpyAsync(h->gif_rgb.p, h->h_gif_rgb.data(), 256 * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    }
     // frame table: segments and their scratch
     h->h_gif.assign(n, nq::GifFrame{});
     long long segs = 0, words = 0;
@@ -1892,7 +1903,8 @@ int gif_encode_maps(nq_handle* h, int n, const uint16_t* const* d_index, const G
     NQ_HIP(h, h->gif_res.reserve((size_t) n + 1));
     NQ_HIP(h, hipMemcpyAsync(h->d_gif.p, h->h_gif.data(), n * sizeof(nq::GifFrame), hipMemcpyHostToDevice, h->stream));
     NQ_HIP(h, hipMemsetAsync(h->gif_res.p + n, 0, sizeof(unsigned long long), h->stream));
-    launch_gif_lzw(h->d_gif.p, n, segs, Kt, m, h->gif_words.p, h->gif_bits.p, h->gif_res.p + n, h->stream);
+    launch_gif_lzw(h->d_gif.p, n, segs, Kt, m, h->gif_words.p, h->gif_bits.p, h->gif_res.p + n, lossy > 0 ? h->gif_rgb.p : nullptr, T, lossy,
+                   h->stream);
     launch_gif_scan(h->d_gif.p, n, h->gif_bits.p, h->gif_bits.p + segs, h->gif_res.p, h->stream);
     NQ_HIP(h, launch_status());
     std::vector<unsigned long long> res((size_t) n + 1);
@@ -1945,7 +1957,7 @@ int gif_encode_maps(nq_handle* h, int n, const uint16_t* const* d_index, const G
 
 // nq_encode_gif_device: whole frames at (0, 0), disposal 2
 int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights, const uint32_t* palette,
-               int K, const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size) {
+               int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size) {
     int t = -1;                                     // GIF has 1-bit transparency: the first entry with alpha 0, other alphas are dropped
     for (int i = 0; i < K && t < 0; ++i) if ((palette[i] >> 24) == 0) t = i;
     std::vector<GifRect> rects(n);
@@ -1956,7 +1968,7 @@ int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
     }
     const int gce = n > 1 || t >= 0 ? (n > 1 ? 2 << 2 : 0) | (t >= 0 ? 1 : 0) : -1;
     return gif_encode_maps(h, n, d_index, rects.data(), W, H, palette, K, K, gce, t >= 0 ? t : 0, t >= 0 ? t : 0, delays_cs, loop_count,
-                           segment_pixels, out, cap, out_size);
+                           segment_pixels, t, lossy, out, cap, out_size);
 }
 
 // The rectangles of n >= 2 frames of one size (device memory): frame 0 whole, frame i >= 1 the bounding box of the pixels that differ
@@ -1992,7 +2004,7 @@ int changed_rects(nq_handle* h, int n, const uint16_t* const* d_index, int W, in
 // nq_encode_gif_delta_device after the argument checks (n >= 2): difference pass, one read-back of the boxes, body pass, then the
 // bodies are encoded like any index maps
 int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, const uint32_t* palette, int K,
-                     const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size,
+                     const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size,
                      int32_t* out_rects) {
     const int u = K <= 255 ? K : -1;                // the "unchanged" index, transparent in every frame
     std::vector<GifRect> rects;
@@ -2023,7 +2035,7 @@ int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W,
     // The chains below check against Kt, so an index == K in frame 0 (read in place, not through a body) passes them: it is the
     // difference pass above that has checked frame 0, as the predecessor of frame 1, and every other frame against K.
     const int rc = gif_encode_maps(h, n, maps.data(), rects.data(), W, H, palette, K, K + (u >= 0 ? 1 : 0), 1 << 2 | (u >= 0 ? 1 : 0),
-                                   u >= 0 ? u : 0, 0, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+                                   u >= 0 ? u : 0, 0, delays_cs, loop_count, segment_pixels, u, lossy, out, cap, out_size);
     if (rc) return rc;
     if (out_rects)
         for (int i = 0; i < n; ++i) { out_rects[4 * i] = rects[i].x; out_rects[4 * i + 1] = rects[i].y; out_rects[4 * i + 2] = rects[i].w; out_rects[4 * i + 3] = rects[i].h; }
@@ -2032,11 +2044,11 @@ int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W,
 
 // the checks both delta forms share, done from the host arguments alone; ws / hs: the size repeated per frame for the shared checks
 int gif_delta_check(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
-                    const int32_t* delays_cs, int loop_count, int segment_pixels, const uint8_t* out, int64_t cap, int64_t* out_size,
-                    std::vector<int32_t>* ws, std::vector<int32_t>* hs) {
+                    const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, const uint8_t* out, int64_t cap,
+                    int64_t* out_size, std::vector<int32_t>* ws, std::vector<int32_t>* hs) {
     if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
     ws->assign(n, width); hs->assign(n, height);
-    int rc = gif_check(h, n, ws->data(), hs->data(), palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    int rc = gif_check(h, n, ws->data(), hs->data(), palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
     if (rc) return rc;
     if (n > 1)
         for (int i = 0; i < K; ++i)
@@ -2048,6 +2060,78 @@ int gif_delta_check(nq_handle* h, int n, const uint16_t* const* index, int width
 
 void gif_whole_rect(int32_t* out_rects, int width, int height) {
     if (out_rects) { out_rects[0] = out_rects[1] = 0; out_rects[2] = width; out_rects[3] = height; }
+}
+
+// The four memory forms behind the exports; lossy = 0 is the lossless call ("GIF encoding, lossy mode").
+int gif_device_call(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                    const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                    uint8_t* out, int64_t cap, int64_t* out_size) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = gif_check(h, n, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+    if (rc) return rc;
+    rc = gif_check_index(h, n, d_index);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return gif_encode(h, n, d_index, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+}
+
+int gif_host_call(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                  const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                  uint8_t* out, int64_t cap, int64_t* out_size) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = gif_check(h, n, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+    if (rc) return rc;
+    rc = gif_check_index(h, n, index);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    std::vector<size_t> px(n);
+    for (int i = 0; i < n; ++i) px[i] = (size_t) widths[i] * heights[i];
+    std::vector<uint16_t*> dev(n);
+    return host_form(h, [&]() {
+        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
+        return rc ? rc : gif_encode(h, n, dev.data(), widths, heights, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+    });
+}
+
+int gif_delta_device_call(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height, const uint32_t* palette, int K,
+                          const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap,
+                          int64_t* out_size, int32_t* out_rects) {
+    if (!h) return NQ_ERR_INVALID;
+    std::vector<int32_t> ws, hs;
+    int rc = gif_delta_check(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size, &ws, &hs);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    if (n > 1)
+        return gif_encode_delta(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size, out_rects);
+    rc = gif_encode(h, n, d_index, ws.data(), hs.data(), palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+    if (rc == NQ_OK) gif_whole_rect(out_rects, width, height);
+    return rc;
+}
+
+int gif_delta_host_call(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
+                        const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap,
+                        int64_t* out_size, int32_t* out_rects) {
+    if (!h) return NQ_ERR_INVALID;
+    std::vector<int32_t> ws, hs;
+    int rc = gif_delta_check(h, n, index, width, height, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size, &ws, &hs);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    std::vector<size_t> px(n, (size_t) width * height);
+    std::vector<uint16_t*> dev(n);
+    return host_form(h, [&]() {
+        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
+        if (rc) return rc;
+        if (n > 1)
+            return gif_encode_delta(h, n, dev.data(), width, height, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size,
+                                    out_rects);
+        rc = gif_encode(h, n, dev.data(), ws.data(), hs.data(), palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+        if (rc == NQ_OK) gif_whole_rect(out_rects, width, height);
+        return rc;
+    });
 }
 
 } // namespace
@@ -2070,72 +2154,51 @@ int nq_gif_max_bytes(int n, const int32_t* widths, const int32_t* heights, int K
 int nq_encode_gif_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
                          const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
                          uint8_t* out, int64_t cap, int64_t* out_size) {
-    if (!h) return NQ_ERR_INVALID;
-    int rc = gif_check(h, n, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
-    if (rc) return rc;
-    rc = gif_check_index(h, n, d_index);
-    if (rc) return rc;
-    rc = use_device(h);
-    if (rc) return rc;
-    return gif_encode(h, n, d_index, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
+    return gif_device_call(h, n, d_index, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, 0, out, cap, out_size);
 }
 
 int nq_encode_gif(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
                   const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels,
                   uint8_t* out, int64_t cap, int64_t* out_size) {
-    if (!h) return NQ_ERR_INVALID;
-    int rc = gif_check(h, n, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
-    if (rc) return rc;
-    rc = gif_check_index(h, n, index);
-    if (rc) return rc;
-    rc = use_device(h);
-    if (rc) return rc;
-    std::vector<size_t> px(n);
-    for (int i = 0; i < n; ++i) px[i] = (size_t) widths[i] * heights[i];
-    std::vector<uint16_t*> dev(n);
-    return host_form(h, [&]() {
-        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
-        return rc ? rc : gif_encode(h, n, dev.data(), widths, heights, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
-    });
+    return gif_host_call(h, n, index, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, 0, out, cap, out_size);
 }
 
 int nq_encode_gif_delta_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height, const uint32_t* palette, int K,
                                const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size,
                                int32_t* out_rects) {
-    if (!h) return NQ_ERR_INVALID;
-    std::vector<int32_t> ws, hs;
-    int rc = gif_delta_check(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size, &ws, &hs);
-    if (rc) return rc;
-    rc = use_device(h);
-    if (rc) return rc;
-    if (n > 1)
-        return gif_encode_delta(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size, out_rects);
-    rc = gif_encode(h, n, d_index, ws.data(), hs.data(), palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
-    if (rc == NQ_OK) gif_whole_rect(out_rects, width, height);
-    return rc;
+    return gif_delta_device_call(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_pixels, 0, out, cap, out_size, out_rects);
 }
 
 int nq_encode_gif_delta(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
                         const int32_t* delays_cs, int loop_count, int segment_pixels, uint8_t* out, int64_t cap, int64_t* out_size,
                         int32_t* out_rects) {
-    if (!h) return NQ_ERR_INVALID;
-    std::vector<int32_t> ws, hs;
-    int rc = gif_delta_check(h, n, index, width, height, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size, &ws, &hs);
-    if (rc) return rc;
-    rc = use_device(h);
-    if (rc) return rc;
-    std::vector<size_t> px(n, (size_t) width * height);
-    std::vector<uint16_t*> dev(n);
-    return host_form(h, [&]() {
-        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
-        if (rc) return rc;
-        if (n > 1)
-            return gif_encode_delta(h, n, dev.data(), width, height, palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size,
-                                    out_rects);
-        rc = gif_encode(h, n, dev.data(), ws.data(), hs.data(), palette, K, delays_cs, loop_count, segment_pixels, out, cap, out_size);
-        if (rc == NQ_OK) gif_whole_rect(out_rects, width, height);
-        return rc;
-    });
+    return gif_delta_host_call(h, n, index, width, height, palette, K, delays_cs, loop_count, segment_pixels, 0, out, cap, out_size, out_rects);
+}
+
+int nq_encode_gif_lossy_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                               const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                               uint8_t* out, int64_t cap, int64_t* out_size) {
+    return gif_device_call(h, n, d_index, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+}
+
+int nq_encode_gif_lossy(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                        const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                        uint8_t* out, int64_t cap, int64_t* out_size) {
+    return gif_host_call(h, n, index, widths, heights, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+}
+
+int nq_encode_gif_delta_lossy_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height, const uint32_t* palette,
+                                     int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap,
+                                     int64_t* out_size, int32_t* out_rects) {
+    return gif_delta_device_call(h, n, d_index, width, height, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size,
+                                 out_rects);
+}
+
+int nq_encode_gif_delta_lossy(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
+                              const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap,
+                              int64_t* out_size, int32_t* out_rects) {
+    return gif_delta_host_call(h, n, index, width, height, palette, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size,
+                               out_rects);
 }
 
 } // extern "C"

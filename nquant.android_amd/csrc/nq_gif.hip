@@ -3,7 +3,8 @@
 // A frame's indices are cut into segments of S pixels.  Every segment is one LZW chain with a dictionary of its own, so the
 // chains run in parallel; a frame's data is the chains' bit strings one after another (GIF allows a Clear code anywhere).
 //   gif_lzw_kernel     one wave per chain, four chains per workgroup; the dictionary lives in LDS and the indices are staged into
-//                      LDS by the whole wave, 1 KiB ahead of the chain
+//                      LDS by the whole wave, 1 KiB ahead of the chain.  <true> is the lossy mode ("GIF encoding, lossy mode"): on a
+//                      miss the 64 lanes try the near colours that would continue the string, four candidates each
 //   gif_scan_kernel    per frame: exclusive scan of the segments' bit lengths, the frame's bit length
 //   gif_gather_kernel  one thread per byte of the file: header bytes from the host's blob, sub-block length bytes, and the data
 //                      bytes ORed together from the <= 3 segments each one overlaps
@@ -44,15 +45,49 @@ __device__ inline void clear_table(unsigned* tab, int lane) {
     wave_sync();
 }
 
+// the code of `key` (pre << 8 | c) in a chain's dictionary, 0 when it is not there; *slot: where it is, or the empty slot it would take
+__device__ inline unsigned find_code(const unsigned* tab, unsigned key, unsigned* slot) {
+    unsigned h = (key * 0x9E3779B1u) >> 19;
+    unsigned code = 0;
+    for (int probe = 0; probe < GIF_SLOTS; ++probe) {
+        const unsigned ent = tab[h];
+        if (ent == 0) break;
+        if ((ent >> 12) == key) { code = ent & 4095u; break; }
+        h = (h + 1) & (GIF_SLOTS - 1);
+    }
+    *slot = h;
+    return code;
+}
+
+// largest channel difference (.x) and squared distance (.y) of two packed 0x00RRGGBB colours
+__device__ inline uint2 rgb_apart(unsigned a, unsigned b) {
+    const int dr = (int) (a >> 16 & 255u) - (int) (b >> 16 & 255u), dg = (int) (a >> 8 & 255u) - (int) (b >> 8 & 255u),
+              db = (int) (a & 255u) - (int) (b & 255u);
+    return make_uint2((unsigned) max(max(abs(dr), abs(dg)), abs(db)), (unsigned) (dr * dr + dg * dg + db * db));
+}
+
 // All 64 lanes of a wave run the chain in lockstep on the same values (the LDS reads broadcast); lane 0 alone stores to the
 // dictionary and to global memory.  Every loop is bounded by the segment length or the table size.
+// LOSSY: `rgb` is the file's colour table (256 entries 0x00RRGGBB, zeros from entry K on; here K is the table's Kt), T its transparent
+// index (-1: none), lossy the threshold 1..255.  Where the exact index misses, lane l looks up (pre, c') for c' = l, l + 64, l + 128,
+// l + 192, a wave minimum over d^2 << 8 | c' picks the winner, and its code is handed to every lane: all lanes hold the same `pre` again.
+template <bool LOSSY>
 __global__ void __launch_bounds__(64 * GIF_CHAINS) gif_lzw_kernel(const GifFrame* __restrict__ frames, int n_frames, long long n_segs,
                                                                    int K, int m, unsigned* __restrict__ words,
-                                                                   unsigned long long* __restrict__ seg_bits, unsigned long long* __restrict__ bad) {
+                                                                   unsigned long long* __restrict__ seg_bits, unsigned long long* __restrict__ bad,
+                                                                   const unsigned* __restrict__ rgb, int T, int lossy) {
     __shared__ unsigned table[GIF_CHAINS][GIF_SLOTS];
     __shared__ uint4 stage[GIF_CHAINS][2][GIF_STAGE / 8];
+    __shared__ unsigned pal[LOSSY ? 256 : 1];      // the colour of the index at hand is read from here (a broadcast)
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned* tab = table[wv];
+    unsigned mine[4] = {0, 0, 0, 0};               // this lane's four candidates' colours
+    if constexpr (LOSSY) {
+        static_assert(64 * GIF_CHAINS == 256, "one thread per colour table entry");
+        pal[threadIdx.x] = rgb[threadIdx.x];
+        for (int j = 0; j < 4; ++j) mine[j] = rgb[lane + 64 * j];
+        __syncthreads();
+    }
     const unsigned CLEAR = 1u << m, EOI = CLEAR + 1;
     for (long long g = (long long) blockIdx.x * GIF_CHAINS + wv; g < n_segs; g += (long long) gridDim.x * GIF_CHAINS) {
         int lo = 0, hi = n_frames - 1;                 // frame of segment g: the last one whose first segment is <= g
@@ -100,15 +135,35 @@ __global__ void __launch_bounds__(64 * GIF_CHAINS) gif_lzw_kernel(const GifFrame
             for (; q < e; ++q) {
                 const unsigned c = index_at(q);
                 const unsigned key = pre << 8 | c;
-                unsigned h = (key * 0x9E3779B1u) >> 19;
-                unsigned code = 0;
-                for (int probe = 0; probe < GIF_SLOTS; ++probe) {
-                    const unsigned ent = tab[h];
-                    if (ent == 0) break;
-                    if ((ent >> 12) == key) { code = ent & 4095u; break; }
-                    h = (h + 1) & (GIF_SLOTS - 1);
-                }
+                unsigned h;
+                unsigned code = find_code(tab, key, &h);
                 if (code) { pre = code; continue; }
+                if constexpr (LOSSY) {
+                    if (c != (unsigned) T) {
+                        wave_sync();                                            // lane 0's dictionary stores, read by every lane below
+                        const unsigned want = pal[c];
+                        unsigned best = ~0u, best_code = 0;                     // this lane's smallest d^2 << 8 | c' and its code
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const unsigned cc = (unsigned) lane + 64u * j;
+                            const uint2 d = rgb_apart(mine[j], want);
+                            if (cc < (unsigned) K && cc != c && cc != (unsigned) T && d.x <= (unsigned) lossy) {
+                                unsigned at;
+                                const unsigned cd = find_code(tab, pre << 8 | cc, &at);
+                                const unsigned v = d.y << 8 | cc;
+                                if (cd && v < best) { best = v; best_code = cd; }
+                            }
+                        }
+                        unsigned win = best;
+#pragma unroll
+                        for (int d = 32; d >= 1; d >>= 1) win = min(win, (unsigned) __shfl_xor((int) win, d));
+                        if (win != ~0u) {
+                            // the winner's lane is the only one whose `best` names that c'
+                            pre = (unsigned) __shfl((int) best_code, (int) (win & 63u));
+                            continue;
+                        }
+                    }
+                }
                 emit(pre, w);
                 if (next == 4096) {
                     emit(CLEAR, w);
@@ -331,10 +386,15 @@ void launch_gif_body(const GifDelta* d_delta, int n_bodies, int W, int u, long l
 }
 
 void launch_gif_lzw(const GifFrame* d_frames, int n_frames, long long n_segs, int K, int m, unsigned* d_words, unsigned long long* d_seg_bits,
-                    unsigned long long* d_bad, hipStream_t s) {
+                    unsigned long long* d_bad, const unsigned* d_rgb, int T, int lossy, hipStream_t s) {
     long long grid = (n_segs + GIF_CHAINS - 1) / GIF_CHAINS;
     if (grid > (1 << 20)) grid = 1 << 20;
-    hipLaunchKernelGGL(gif_lzw_kernel, dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, K, m, d_words, d_seg_bits, d_bad);
+    if (lossy > 0)
+        hipLaunchKernelGGL(gif_lzw_kernel<true>, dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, K, m, d_words,
+                           d_seg_bits, d_bad, d_rgb, T, lossy);
+    else
+        hipLaunchKernelGGL(gif_lzw_kernel<false>, dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, K, m, d_words,
+                           d_seg_bits, d_bad, (const unsigned*) nullptr, -1, 0);
 }
 
 void launch_gif_scan(const GifFrame* d_frames, int n_frames, const unsigned long long* d_seg_bits, unsigned long long* d_seg_off,

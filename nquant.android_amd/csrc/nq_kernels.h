@@ -203,8 +203,10 @@ struct GifFrame {
     long long file_off, prefix_off, data_bytes, stream_len;     // stream: the sub-blocks and their terminator
 };
 // seg_bits[g]: bit length of chain g; *d_bad = 1 when an index >= K was met (zeroed by the caller)
+// lossy > 0 ("GIF encoding, lossy mode"): d_rgb = the file's colour table, 256 entries 0x00RRGGBB (zeros from entry K on), T = its
+// transparent index or -1; lossy == 0 runs the lossless chains and reads neither
 void launch_gif_lzw(const GifFrame* d_frames, int n_frames, long long n_segs, int K, int m, unsigned* d_words, unsigned long long* d_seg_bits,
-                    unsigned long long* d_bad, hipStream_t s);
+                    unsigned long long* d_bad, const unsigned* d_rgb, int T, int lossy, hipStream_t s);
 void launch_gif_scan(const GifFrame* d_frames, int n_frames, const unsigned long long* d_seg_bits, unsigned long long* d_seg_off,
                      unsigned long long* d_frame_bits, hipStream_t s);
 // the whole file (total bytes): frame prefixes from d_blob, sub-block stream of every frame, trailer

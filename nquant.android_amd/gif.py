@@ -5,6 +5,9 @@ Delta mode (nq_encode_gif_delta / nq_encode_gif_delta_device, "GIF encoding, del
 stored as the rectangle that changed with the unchanged pixels transparent.  Static regions repeat from frame to frame only when the
 dither makes them repeat: MODE_PARALLEL_TILED with equal seeds for all frames does (a tile's chain depends on its pixels, its
 position and the seed alone).
+Lossy mode (the nq_encode_gif*_lossy* calls, "GIF encoding, lossy mode"): every encoder here takes a trailing lossy=0..255.  Above 0 the
+LZW chains may write a palette colour within `lossy` per channel of a pixel's own where that continues the current dictionary string,
+which is what shrinks dithered content; 0 calls the lossless entry points.
 There is no CPU fallback: without a HIP device every call raises NqError with status -5 (NQ_ERR_NO_DEVICE)."""
 import ctypes as C
 
@@ -61,7 +64,19 @@ def gif_max_bytes(widths, heights, K=256, segment_pixels=0):
     return out.value
 
 
-def _encode(L, handle, entry, ptrs, w, h, palette, delays_cs, loop, segment_pixels, check):
+# the lossy counterpart of every encoder entry point (include/nquant_abi.h, "GIF encoding, lossy mode")
+_LOSSY = {"nq_encode_gif": "nq_encode_gif_lossy", "nq_encode_gif_device": "nq_encode_gif_lossy_device",
+          "nq_encode_gif_delta": "nq_encode_gif_delta_lossy", "nq_encode_gif_delta_device": "nq_encode_gif_delta_lossy_device"}
+
+
+def _entry(L, entry, segment_pixels, lossy):
+    """(the function to call, its arguments from segment_pixels on up to the output buffer): lossy 0 is the lossless export."""
+    if int(lossy) == 0:
+        return getattr(L, entry), (int(segment_pixels),)
+    return getattr(L, _LOSSY[entry]), (int(segment_pixels), int(lossy))
+
+
+def _encode(L, handle, entry, ptrs, w, h, palette, delays_cs, loop, segment_pixels, check, lossy=0):
     n = len(ptrs)
     pal = _palette(palette)
     d = _delays(delays_cs, n)
@@ -72,13 +87,13 @@ def _encode(L, handle, entry, ptrs, w, h, palette, delays_cs, loop, segment_pixe
     buf = np.empty(max(cap, 1), np.uint8)
     size = C.c_int64(0)
     src = (C.c_void_p * n)(*[int(p) for p in ptrs])
-    check(getattr(L, entry)(handle, n, src, w.ctypes.data, h.ctypes.data, pal.ctypes.data, int(pal.size),
-                            d.ctypes.data if d is not None else None, int(loop), int(segment_pixels), buf.ctypes.data, int(cap),
-                            C.byref(size)))
+    fn, seg = _entry(L, entry, segment_pixels, lossy)
+    check(fn(handle, n, src, w.ctypes.data, h.ctypes.data, pal.ctypes.data, int(pal.size), d.ctypes.data if d is not None else None,
+             int(loop), *seg, buf.ctypes.data, int(cap), C.byref(size)))
     return buf[:size.value].tobytes()
 
 
-def _encode_delta(L, handle, entry, ptrs, width, height, palette, delays_cs, loop, segment_pixels, check):
+def _encode_delta(L, handle, entry, ptrs, width, height, palette, delays_cs, loop, segment_pixels, check, lossy=0):
     """The delta entry points: one size for all frames.  Returns (file bytes, rectangles as an (n, 4) int32 array of x, y, w, h)."""
     n = len(ptrs)
     pal = _palette(palette)
@@ -91,8 +106,9 @@ def _encode_delta(L, handle, entry, ptrs, width, height, palette, delays_cs, loo
     rects = np.zeros((max(n, 1), 4), np.int32)
     size = C.c_int64(0)
     src = (C.c_void_p * max(n, 1))(*[int(p) for p in ptrs])
-    check(getattr(L, entry)(handle, n, src, int(width), int(height), pal.ctypes.data, int(pal.size), d.ctypes.data if d is not None else None,
-                            int(loop), int(segment_pixels), buf.ctypes.data, int(cap), C.byref(size), rects.ctypes.data))
+    fn, seg = _entry(L, entry, segment_pixels, lossy)
+    check(fn(handle, n, src, int(width), int(height), pal.ctypes.data, int(pal.size), d.ctypes.data if d is not None else None, int(loop),
+             *seg, buf.ctypes.data, int(cap), C.byref(size), rects.ctypes.data))
     return buf[:size.value].tobytes(), rects[:n]
 
 
@@ -124,71 +140,86 @@ class _Handle:
             self._h = None
 
 
-def encode_gif(indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0):
+def encode_gif(indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0, lossy=0):
     """nq_encode_gif: `indices` is one 2-D index map or a sequence of them (sizes may differ), `palette` the ARGB_8888 entries they
     index (K = len(palette) <= 256).  delays_cs: per-frame delay in hundredths of a second (None: 0); loop: the NETSCAPE2.0 loop
-    count of an animation (0 = for ever, -1 = no loop block); segment_pixels: pixels per LZW chain (0 = 16384).  Returns the file."""
+    count of an animation (0 = for ever, -1 = no loop block); segment_pixels: pixels per LZW chain (0 = 16384); lossy: 0..255, the
+    largest per-channel colour error a chain may trade for a longer match (0: none, nq_encode_gif_lossy otherwise).  Returns the file."""
     maps = _index_maps(indices)
     w = np.array([a.shape[1] for a in maps], np.int32)
     h = np.array([a.shape[0] for a in maps], np.int32)
     hd = _Handle(device)
     try:
-        return _encode(hd._L, hd._h, "nq_encode_gif", [a.ctypes.data for a in maps], w, h, palette, delays_cs, loop, segment_pixels, hd._check)
+        return _encode(hd._L, hd._h, "nq_encode_gif", [a.ctypes.data for a in maps], w, h, palette, delays_cs, loop, segment_pixels, hd._check,
+                       lossy)
     finally:
         hd.close()
 
 
-def encode_gif_device(q, d_index_ptrs, widths, heights, palette, delays_cs=None, loop=0, segment_pixels=0):
+def encode_gif_device(q, d_index_ptrs, widths, heights, palette, delays_cs=None, loop=0, segment_pixels=0, lossy=0):
     """nq_encode_gif_device on the handle of quantizer `q`: d_index_ptrs[i] is the HIP device address of frame i's uint16 index map
     (widths[i] x heights[i], 2-byte aligned).  Arguments otherwise as encode_gif.  Returns the file."""
     n = len(d_index_ptrs)
     w, h = _frame_sizes(widths, heights, n)
-    return _encode(q._L, q._h, "nq_encode_gif_device", list(d_index_ptrs), w, h, palette, delays_cs, loop, segment_pixels, q._check)
+    return _encode(q._L, q._h, "nq_encode_gif_device", list(d_index_ptrs), w, h, palette, delays_cs, loop, segment_pixels, q._check,
+                   lossy)
 
 
-def encode_gif_delta(indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0, return_rects=False):
+def encode_gif_delta(indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0, return_rects=False, lossy=0):
     """nq_encode_gif_delta: as encode_gif, but all frames have one size, every frame after the first stores only the bounding rectangle
     of the pixels that differ from the frame before, and the unchanged pixels in it are transparent (index K; K = 256: cropped only).
-    A palette entry with alpha 0 is an error when there are two frames or more.  Returns the file; with return_rects=True the pair
+    A palette entry with alpha 0 is an error when there are two frames or more.  lossy as for encode_gif (the rectangles do not
+    depend on it).  Returns the file; with return_rects=True the pair
     (file, (n, 4) int32 array of every frame's x, y, w, h)."""
     maps = _index_maps(indices)
     height, width = _one_size(maps)
     hd = _Handle(device)
     try:
         data, rects = _encode_delta(hd._L, hd._h, "nq_encode_gif_delta", [a.ctypes.data for a in maps], width, height, palette, delays_cs,
-                                    loop, segment_pixels, hd._check)
+                                    loop, segment_pixels, hd._check, lossy)
     finally:
         hd.close()
     return (data, rects) if return_rects else data
 
 
-def encode_gif_delta_device(q, d_index_ptrs, width, height, palette, delays_cs=None, loop=0, segment_pixels=0, return_rects=False):
+def encode_gif_delta_device(q, d_index_ptrs, width, height, palette, delays_cs=None, loop=0, segment_pixels=0, return_rects=False, lossy=0):
     """nq_encode_gif_delta_device on the handle of quantizer `q`: d_index_ptrs[i] is the HIP device address of frame i's uint16 index
     map (width x height, 2-byte aligned; never written).  Arguments and result otherwise as encode_gif_delta."""
     if len(d_index_ptrs) == 0:
         raise ValueError("no frames")
     data, rects = _encode_delta(q._L, q._h, "nq_encode_gif_delta_device", list(d_index_ptrs), width, height, palette, delays_cs, loop,
-                                segment_pixels, q._check)
+                                segment_pixels, q._check, lossy)
     return (data, rects) if return_rects else data
 
 
-def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0, delta=False):
-    """encode_gif (delta=True: encode_gif_delta), written to `path`.  Returns the number of bytes written."""
-    data = (encode_gif_delta if delta else encode_gif)(indices, palette, delays_cs, loop, segment_pixels, device)
+def _lossy_keyword(lossy):
+    """write_gif and convert_frames_to_gif keep `delta` as their last parameter, so `lossy` sits where an older positional call put
+    delta: a bool there is that call, not a threshold."""
+    if isinstance(lossy, (bool, np.bool_)):
+        raise TypeError("lossy is an integer 0..255; pass delta by keyword")
+    return int(lossy)
+
+
+def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, device=0, lossy=0, delta=False):
+    """encode_gif (delta=True: encode_gif_delta), written to `path`; lossy as there.  Returns the number of bytes written."""
+    lossy = _lossy_keyword(lossy)
+    data = (encode_gif_delta if delta else encode_gif)(indices, palette, delays_cs, loop, segment_pixels, device, lossy=lossy)
     with open(path, "wb") as f:
         f.write(data)
     return len(data)
 
 
 def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
-                          seeds=None, tile=None, hold=None, delta=False):
+                          seeds=None, tile=None, hold=None, lossy=0, delta=False):
     """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
     delta=True: encode_gif_delta instead; the frames must have one size.  Seeds are passed on as given: regions that do not move repeat
     in the index maps, and so drop out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.
     hold (delta=True only; None: no such pass): an integer 0..255 runs the temporal hold (hold.py) with that threshold between the
     two steps, so that pixels whose source moved by no more than it keep their index -- what footage with sensor or codec noise needs
     for its still regions to drop out.  All three steps then run on one handle; the index maps pass through host memory in between.
+    lossy: as for encode_gif, applied to whichever encoder runs (with hold: on that same handle).
     Returns (file bytes, palette)."""
+    lossy = _lossy_keyword(lossy)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
     if hold is not None and not delta:
@@ -205,9 +236,10 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
             height, width = _one_size(maps)
             _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
             data, _ = _encode_delta(q._L, q._h, "nq_encode_gif_delta", [a.ctypes.data for a in maps], width, height, palette, delays_cs, loop,
-                                    segment_pixels, q._check)
+                                    segment_pixels, q._check, lossy)
         finally:
             q.close()
         return data, palette
     palette, outs = convert_frames(kind, frames, nMaxColors, dither, device=device, mode=mode, seeds=seeds, tile=tile)
-    return (encode_gif_delta if delta else encode_gif)([o.index for o in outs], palette, delays_cs, loop, segment_pixels, device), palette
+    data = (encode_gif_delta if delta else encode_gif)([o.index for o in outs], palette, delays_cs, loop, segment_pixels, device, lossy=lossy)
+    return data, palette

@@ -8,7 +8,13 @@ end in a stream synchronise and the copy of the file).
 --delta measures the delta mode instead (nq_encode_gif_delta_device next to nq_encode_gif_device on the same maps): --batch frames from
 nq_convert_frames_device with equal seeds, once a sprite moving over a still background and once unrelated images.
 
-    python tools/gif_bench.py --delta [--size 4096] [--batch 64] [--reps 3] [--out profiles/r07/gif_delta_bench.txt]"""
+    python tools/gif_bench.py --delta [--size 4096] [--batch 64] [--reps 3] [--out profiles/r07/gif_delta_bench.txt]
+
+--lossy N (repeatable) measures the lossy mode instead (nq_encode_gif_lossy_device): one index map from convert_frames, encoded without
+and with every threshold N; per call the file bytes, their ratio to the lossless file, the ms per call, and the share of pixels that
+decode to another index than the source's, found by decoding each file with the decoder below.
+
+    python tools/gif_bench.py --lossy 8 --lossy 16 --lossy 32 [--size 4096] [--reps 5] [--out profiles/r09/gif_lossy_bench.txt]"""
 import argparse
 import io
 import os
@@ -82,6 +88,106 @@ def delta_bench(args, say):
     run("unrelated images", frames)
 
 
+def lzw_indices(data, m, count):
+    """The first `count` indices of a GIF frame's LZW data (sub-blocks already joined).  The codes between two Clear codes have
+    widths that depend only on how many codes came since the Clear, so each such run is cut out of the bit string in one numpy
+    gather; the strings are then put together code by code."""
+    clear, eoi = 1 << m, (1 << m) + 1
+    bits = np.unpackbits(np.frombuffer(data, np.uint8), bitorder="little")
+    nbits = bits.size
+    run = 4096 + 64
+    size = eoi + 1 + np.maximum(np.arange(run) - 1, 0)
+    w = np.minimum(12, np.maximum(m + 1, np.floor(np.log2(np.minimum(size, 4096))).astype(np.int64) + 1))
+    off = np.concatenate([[0], np.cumsum(w)])
+    bits = np.concatenate([bits, np.zeros(12 * run + 64, np.uint8)])
+    lane, weight = np.arange(12), 1 << np.arange(12)
+    base = [bytes([i]) for i in range(clear)] + [None, None]
+    out, have, pos = [], 0, 0
+    while pos + m + 1 <= nbits and have < count:
+        codes = ((bits[(pos + off[:run])[:, None] + lane] * (lane < w[:, None])) @ weight)
+        stop = np.nonzero((codes == clear) | (codes == eoi) | (pos + off[1:] > nbits))[0]
+        n = int(stop[0]) if stop.size else run
+        if n == run:                                 # (a table that stays full for longer than the margin: not met with this encoder)
+            raise ValueError("no Clear code within %d codes" % run)
+        table = list(base)
+        prev = None
+        for code in codes[:n].tolist():
+            if prev is None:
+                e = table[code]
+            elif code < len(table):
+                e = table[code]
+                if len(table) < 4096:
+                    table.append(prev + e[:1])
+            else:
+                e = prev + prev[:1]
+                table.append(e)
+            out.append(e)
+            have += len(e)
+            prev = e
+        if pos + off[n + 1] > nbits or codes[n] == eoi:
+            break
+        pos += int(off[n + 1])
+    return np.frombuffer(b"".join(out), np.uint8)[:count]
+
+
+def first_frame_indices(gif):
+    """The index map (flat) of the first frame of a GIF file written by this library."""
+    assert gif[:6] == b"GIF89a"
+    pos = 13 + (3 << ((gif[10] & 7) + 1))
+    while gif[pos] == 0x21:                          # extensions
+        pos += 2
+        while gif[pos]:
+            pos += 1 + gif[pos]
+        pos += 1
+    assert gif[pos] == 0x2C
+    w, h = gif[pos + 5] | gif[pos + 6] << 8, gif[pos + 7] | gif[pos + 8] << 8
+    m = gif[pos + 10]
+    pos += 11
+    data = bytearray()
+    while gif[pos]:
+        data += gif[pos + 1:pos + 1 + gif[pos]]
+        pos += 1 + gif[pos]
+    return lzw_indices(bytes(data), m, w * h)
+
+
+def lossy_bench(args, say):
+    """Bytes, ms per call and substituted pixels of the lossy encoder next to the lossless call on the same device-resident index map."""
+    import torch
+    import nquant.android_amd as nq
+    from nquant.android_amd import synth
+
+    W = H = args.size
+    say("lossy GIF encoding of one %dx%d index map (gradient_noise seed 3, PnnLABQuantizer, convert_frames(256, true)); best of %d"
+        % (W, H, args.reps))
+    frame = synth.gradient_noise(W, H, 3)
+    nq.convert_frames(nq.NQ_KIND_LAB, [frame], 256, True)
+    tc, (pal, outs) = timed(lambda: nq.convert_frames(nq.NQ_KIND_LAB, [frame], 256, True), 2)
+    say("convert_frames (host frames, upload and read-back included)  %9.2f ms per call, K = %d" % (tc * 1e3, len(pal)))
+    src = outs[0].index.reshape(-1)
+    dev = torch.from_numpy(outs[0].index.view(np.int16).reshape(-1).copy()).cuda()
+    torch.cuda.synchronize()
+    q = nq.PnnQuantizer(np.zeros((1, 1), np.int32))
+    t0 = n0 = None
+    for lossy in [0] + list(args.lossy):
+        call = lambda: nq.encode_gif_device(q, [dev.data_ptr()], [W], [H], pal, lossy=lossy)
+        call()
+        t, gif = timed(call, args.reps)
+        if lossy == 0:
+            t0, n0 = t, len(gif)
+        dec = first_frame_indices(gif)
+        assert dec.size == src.size
+        changed = int((dec != src).sum())
+        assert lossy > 0 or changed == 0
+        say("%-22s %9.2f ms per call (%.3fx lossless)  %10d bytes (%.4fx lossless)  %.4f of the pixels substituted" % (
+            "encode_gif_device" if lossy == 0 else "  lossy = %d" % lossy, t * 1e3, t / t0, len(gif), len(gif) / n0, changed / src.size))
+        if lossy > 0:
+            rgb = np.stack([(pal.astype(np.int64) >> s) & 255 for s in (16, 8, 0)], -1)
+            worst = int(np.abs(rgb[dec] - rgb[src]).max())
+            say("%-22s largest channel error of a decoded pixel: %d" % ("", worst))
+            assert worst <= lossy
+    q.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -91,14 +197,16 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the Pillow animation timed on the CPU")
     ap.add_argument("--out", default=None)
     ap.add_argument("--delta", action="store_true", help="measure the delta mode against the full-frame call instead")
+    ap.add_argument("--lossy", type=int, action="append", default=[], metavar="N",
+                    help="measure the lossy mode at threshold N (1..255; repeatable) against the lossless call instead")
     args = ap.parse_args()
-    if args.delta:
+    if args.delta or args.lossy:
         lines = []
 
         def say(s):
             print(s, flush=True)
             lines.append(s)
-        delta_bench(args, say)
+        (lossy_bench if args.lossy else delta_bench)(args, say)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
