@@ -304,6 +304,61 @@ int nq_encode_gif_delta_lossy(nq_handle* h, int n, const uint16_t* const* index,
                               const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
                               uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
 
+/* ---- GIF encoding, local colour tables: one palette per frame instead of one per file.  An animation with a scene cut, or a slide
+ *      show of unrelated pictures, is not tied to 256 colours for its whole length: frames of one shot share a palette, the next shot
+ *      brings its own.  The palettes use the layout nq_convert_batch returns and nq_encode_png takes: frame i has K[i] <= 256 ARGB
+ *      entries at palettes[i * palette_stride] (host memory).  `lossy` is an argument of these calls from the start; 0 is lossless.
+ *      Everything not restated here is as nq_encode_gif / nq_encode_gif_delta / "lossy mode" define it: segmentation, the chain
+ *      listing, Clear and End-of-Information placement, sub-blocks, the NETSCAPE2.0 block, cap / *out_size, that the call returns
+ *      when `out` holds the file, that the index maps are never written, the _device form with 2-byte aligned device pointers and the
+ *      host form that uploads first.
+ *  Full frames (nq_encode_gif_local):
+ *  * "GIF89a", then the screen descriptor: the largest width and height, packed 0x70 (NO global table), background 0, aspect 0.  The
+ *    loop block as before (n > 1 and loop_count >= 0).
+ *  * Per frame i: N_i, m_i and t_i follow nq_encode_gif's rules applied to frame i's own K[i] and palette (t_i: its first entry
+ *    with alpha 0, -1: none).
+ *  * A graphic control extension when n > 1 or t_i >= 0: packed = (n > 1 ? 2 << 2 : 0) | (t_i >= 0), delays_cs[i], then t_i or 0.
+ *  * The image descriptor at (0, 0) with packed 0x80 | N_i, then 2^(N_i+1) RGB entries (zeros after entry K[i] - 1), the byte m_i and
+ *    the sub-blocks.
+ *  * n = 1 is this same form.  It is NOT byte-equal to nq_encode_gif's file, which has a global table and no local one.
+ *  Delta mode (nq_encode_gif_local_delta), all frames width x height:
+ *  * rgb_i[j] = the 24-bit RGB of entry j of frame i's palette (alpha is not part of it).
+ *  * n > 1: an alpha-0 entry in ANY frame's palette is NQ_ERR_INVALID before any device work, for delta mode's reason.
+ *  * u_i = K[i] when K[i] <= 255; a frame with K[i] = 256 has no u_i and is cropped only.  Kt_i = K[i] + (u_i exists); N_i and m_i
+ *    come from Kt_i; table entry u_i is 0, 0, 0.
+ *  * Every frame, frame 0 included, uses Kt_i and has an extension: packed = 1 << 2 | (u_i exists), delays_cs[i], then u_i or 0.
+ *  * Frame 0 is written whole.
+ *  * Frame i >= 1: D = the pixels p with rgb_i[index_i[p]] != rgb_(i-1)[index_(i-1)[p]] -- "unchanged" is judged on the colour shown,
+ *    not on the index, since index 7 of frame i and index 7 of frame i - 1 are unrelated once the tables differ.  The rectangle is D's
+ *    bounding box, 1 x 1 at (0, 0) when D is empty.  The body is index_i over the rectangle, with the pixels outside D replaced by u_i
+ *    where it exists.  With equal palettes in consecutive frames this is nq_encode_gif_delta's D, up to duplicate colours.
+ *  * n = 1 is the full-frame local file, out_rects = {0, 0, width, height}.
+ *  Lossy mode (both calls): the loop body of "lossy mode" per frame, with rgb = that frame's written table and Kt = that frame's Kt_i;
+ *    T = t_i for full frames, u_i for delta mode, -1 when there is none.  Rectangles and bodies come from the maps and palettes as
+ *    given, so out_rects does not depend on `lossy`.
+ *  * nq_gif_local_max_bytes = nq_gif_max_bytes(n, widths, heights, 256, segment_pixels) + 768 * n bounds either file (delta mode: pass
+ *    n copies of width / height): it drops one global table and adds at most one 768-byte table per frame.
+ *  * NQ_ERR_INVALID before any device work, *out_size and out_rects untouched: nq_encode_gif's list (nq_encode_gif_delta's for delta
+ *    mode), a K[i] outside 1..256, palette_stride smaller than a K[i], K or palettes NULL, lossy outside 0..255.  An index >= its own
+ *    frame's K[i] is reported after the encoding (delta mode: after the difference pass, anywhere in any frame); nq_last_error names the
+ *    frame.  The handle stays usable after every error.
+ *  The kernels, and why no canvas is composed: DESIGN.md 5b "Local colour tables". ---- */
+int nq_gif_local_max_bytes(int n, const int32_t* widths, const int32_t* heights, int segment_pixels, int64_t* out_bytes);
+int nq_encode_gif_local_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                               const uint32_t* palettes, int32_t palette_stride, const int32_t* K, const int32_t* delays_cs, int loop_count,
+                               int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size);
+int nq_encode_gif_local(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                        const uint32_t* palettes, int32_t palette_stride, const int32_t* K, const int32_t* delays_cs, int loop_count,
+                        int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size);
+int nq_encode_gif_local_delta_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height,
+                                     const uint32_t* palettes, int32_t palette_stride, const int32_t* K, const int32_t* delays_cs,
+                                     int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size,
+                                     int32_t* out_rects);
+int nq_encode_gif_local_delta(nq_handle* h, int n, const uint16_t* const* index, int width, int height,
+                              const uint32_t* palettes, int32_t palette_stride, const int32_t* K, const int32_t* delays_cs,
+                              int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size,
+                              int32_t* out_rects);
+
 /* ---- PNG encoding: palette index maps (what the convert calls write to out_index) to indexed PNG files, on the GPU.  One call encodes
  *      n independent images into n files (n = 1 is the plain case; a batch fills the chip).  Image i is a uint16 index map, row-major,
  *      widths[i] x heights[i], with its own K[i] <= 256 and its own palette: the K[i] ARGB entries at palettes[i * palette_stride]

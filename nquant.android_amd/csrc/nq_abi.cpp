@@ -234,6 +234,9 @@ struct nq_handle {
     DevBuf<int> gif_box;
     DevBuf<nq::GifDelta> d_gif_delta;
     DevBuf<unsigned short> gif_body;
+    // nq_encode_gif_local*: one record per frame (K, Kt, m, T and the written colour table)
+    std::vector<nq::GifLocal> h_gif_local;
+    DevBuf<nq::GifLocal> d_gif_local;
     // nq_encode_png_device: image table, token scratch of the resident chains, IDAT CRC registers; bit strings, bit lengths / offsets,
     // read-back, header blob, files and uploaded index maps live in the GIF buffers above (one encoder runs at a time on a handle)
     std::vector<nq::PngImage> h_png;
@@ -1870,18 +1873,30 @@ int gif_check_index(nq_handle* h, int n, const uint16_t* const* index) {
 // where a frame sits on the screen
 struct GifRect { int x, y, w, h; };
 
+// Local colour tables ("GIF encoding, local colour tables"): what frame i's header takes from its own palette instead of from the
+// call: its graphic control extension's packed byte (< 0: no extension) and transparent index byte.  Its K, Kt, m, T and written
+// table are h->h_gif_local[i], which the chains and the two delta passes read from h->d_gif_local.
+struct GifLocalHead { int gce, tr; };
+
+inline int gif_color_bits(int Kt) {
+    int N = 0;
+    while ((1 << (N + 1)) < std::max(Kt, 2)) ++N;
+    return N;
+}
+
 // The file of n index maps (device memory, map i is rects[i].w x rects[i].h and drawn at rects[i].x, rects[i].y) on a W x H screen.
 // Kt sizes the colour table and the code size (K palette entries + the delta mode's unchanged index); gce < 0: no graphic control
 // extensions, else their packed byte; tr: their transparent index byte and the screen's background index.  The caller has zeroed
 // nothing: the bad-index flag is this function's own.  lossy > 0: the chains may take a colour within `lossy` of a pixel's own
 // ("GIF encoding, lossy mode"); T: the index they neither replace nor substitute, -1 when the file has no transparent index.
+// loc (NULL: one global table): one entry per frame; the file has no global table, every frame has a local one, and palette .. tr and T
+// are not read: the caller has filled h->h_gif_local and copied it to h->d_gif_local.
 int gif_encode_maps(nq_handle* h, int n, const uint16_t* const* d_index, const GifRect* rects, int W, int H, const uint32_t* palette, int K,
                     int Kt, int gce, int tr, int bg, const int32_t* delays_cs, int loop_count, int segment_pixels, int T, int lossy,
-                    uint8_t* out, int64_t cap, int64_t* out_size) {
-    int N = 0;
-    while ((1 << (N + 1)) < std::max(Kt, 2)) ++N;
+                    uint8_t* out, int64_t cap, int64_t* out_size, const GifLocalHead* loc = nullptr) {
+    const int N = gif_color_bits(Kt);
     const int m = std::max(2, N + 1);
-    if (lossy > 0) {                                // the colour table as the file holds it: alpha dropped, zeros from entry K on
+    if (lossy > 0 && !loc) {                              // the colour table as the file holds it: alpha dropped, zeros from entry K on
         h->h_gif_rgb.assign(256, 0u);
         for (int i = 0; i < K; ++i) h->h_gif_rgb[i] = palette[i] & 0xFFFFFFu;
         NQ_HIP(h, h->gif_rgb.reserve(256));
@@ -1902,23 +1917,30 @@ int gif_encode_maps(nq_handle* h, int n, const uint16_t* const* d_index, const G
     NQ_HIP(h, h->gif_bits.reserve(2 * (size_t) segs));
     NQ_HIP(h, h->gif_res.reserve((size_t) n + 1));
     NQ_HIP(h, hipMemcpyAsync(h->d_gif.p, h->h_gif.data(), n * sizeof(nq::GifFrame), hipMemcpyHostToDevice, h->stream));
-    NQ_HIP(h, hipMemsetAsync(h->gif_res.p + n, 0, sizeof(unsigned long long), h->stream));
-    launch_gif_lzw(h->d_gif.p, n, segs, Kt, m, h->gif_words.p, h->gif_bits.p, h->gif_res.p + n, lossy > 0 ? h->gif_rgb.p : nullptr, T, lossy,
-                   h->stream);
+    NQ_HIP(h, hipMemsetAsync(h->gif_res.p + n, loc ? 0xFF : 0, sizeof(unsigned long long), h->stream));
+    if (loc)
+        launch_gif_lzw_local(h->d_gif.p, n, segs, h->d_gif_local.p, h->gif_words.p, h->gif_bits.p, h->gif_res.p + n, lossy, h->stream);
+    else
+        launch_gif_lzw(h->d_gif.p, n, segs, Kt, m, h->gif_words.p, h->gif_bits.p, h->gif_res.p + n, lossy > 0 ? h->gif_rgb.p : nullptr, T, lossy,
+                       h->stream);
     launch_gif_scan(h->d_gif.p, n, h->gif_bits.p, h->gif_bits.p + segs, h->gif_res.p, h->stream);
     NQ_HIP(h, launch_status());
     std::vector<unsigned long long> res((size_t) n + 1);
     NQ_HIP(h, hipMemcpyAsync(res.data(), h->gif_res.p, res.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
-    if (res[n]) NQ_FAIL(h, NQ_ERR_INVALID, "an index map holds an index >= K = %d", K);
+    if (loc && res[n] != ~0ull) {
+        const int f = (int) std::min<unsigned long long>(res[n], (unsigned long long) n - 1);
+        NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: the index map holds an index >= its K = %d", f, h->h_gif_local[f].K);
+    }
+    if (!loc && res[n]) NQ_FAIL(h, NQ_ERR_INVALID, "an index map holds an index >= K = %d", K);
     // file layout: header + per frame {extension, descriptor, m, sub-blocks} + trailer; the header bytes go to the device in one blob
     std::vector<uint8_t>& blob = h->h_gif_blob;
     blob.clear();
     auto u16 = [&](int v) { blob.push_back((uint8_t) (v & 255)); blob.push_back((uint8_t) (v >> 8)); };
     blob.insert(blob.end(), {'G', 'I', 'F', '8', '9', 'a'});
     u16(W); u16(H);
-    blob.push_back((uint8_t) (0xF0 | N)); blob.push_back((uint8_t) bg); blob.push_back(0);
-    for (int i = 0; i < (1 << (N + 1)); ++i) {
+    blob.push_back((uint8_t) (loc ? 0x70 : 0xF0 | N)); blob.push_back((uint8_t) bg); blob.push_back(0);
+    for (int i = 0; !loc && i < (1 << (N + 1)); ++i) {
         const uint32_t c = i < K ? palette[i] : 0;
         blob.push_back((uint8_t) (c >> 16)); blob.push_back((uint8_t) (c >> 8)); blob.push_back((uint8_t) c);
     }
@@ -1930,12 +1952,25 @@ int gif_encode_maps(nq_handle* h, int n, const uint16_t* const* d_index, const G
     for (int i = 0; i < n; ++i) {
         nq::GifFrame& F = h->h_gif[i];
         const size_t start = i == 0 ? 0 : blob.size();
-        if (gce >= 0) {
-            blob.insert(blob.end(), {0x21, 0xF9, 0x04, (uint8_t) gce});
-            u16(delays_cs ? delays_cs[i] : 0); blob.push_back((uint8_t) tr); blob.push_back(0);
+        const int gce_i = loc ? loc[i].gce : gce, tr_i = loc ? loc[i].tr : tr;
+        if (gce_i >= 0) {
+            blob.insert(blob.end(), {0x21, 0xF9, 0x04, (uint8_t) gce_i});
+            u16(delays_cs ? delays_cs[i] : 0); blob.push_back((uint8_t) tr_i); blob.push_back(0);
         }
-        blob.push_back(0x2C); u16(rects[i].x); u16(rects[i].y); u16(rects[i].w); u16(rects[i].h); blob.push_back(0);
-        blob.push_back((uint8_t) m);
+        blob.push_back(0x2C); u16(rects[i].x); u16(rects[i].y); u16(rects[i].w); u16(rects[i].h);
+        if (loc) {                                  // the frame's own table, then its own m
+            const nq::GifLocal& P = h->h_gif_local[i];
+            const int Ni = gif_color_bits(P.Kt);
+            blob.push_back((uint8_t) (0x80 | Ni));
+            for (int j = 0; j < (1 << (Ni + 1)); ++j) {
+                const unsigned c = P.rgb[j];
+                blob.push_back((uint8_t) (c >> 16)); blob.push_back((uint8_t) (c >> 8)); blob.push_back((uint8_t) c);
+            }
+            blob.push_back((uint8_t) P.m);
+        } else {
+            blob.push_back(0);
+            blob.push_back((uint8_t) m);
+        }
         F.prefix_off = (long long) start; F.prefix_len = (int) (blob.size() - start);
         F.data_bytes = (long long) ((res[i] + 7) / 8); F.stream_len = gif_stream_len(F.data_bytes);
         F.file_off = total;
@@ -1973,20 +2008,28 @@ int gif_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_
 
 // The rectangles of n >= 2 frames of one size (device memory): frame 0 whole, frame i >= 1 the bounding box of the pixels that differ
 // from frame i - 1 (1 x 1 at (0, 0) when none does).  One difference pass over all frames and one small read-back; an index >= K
-// anywhere in any frame is NQ_ERR_INVALID.  Shared by the delta GIF and the APNG encoder.
-int changed_rects(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, int K, std::vector<GifRect>* out) {
+// anywhere in any frame is NQ_ERR_INVALID.  Shared by the delta GIF and the APNG encoder.  local: "differ" is judged on the colours
+// h->d_gif_local gives the indices and every frame is checked against its own K (K is not read).
+int changed_rects(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, int K, std::vector<GifRect>* out, bool local = false) {
     std::vector<int>& box = h->h_gif_box;
-    box.assign(4 * (size_t) (n - 1) + 1, 0);
+    box.assign(4 * (size_t) (n - 1) + 1, local ? INT_MAX : 0);
     for (int i = 0; i < n - 1; ++i) { box[4 * i] = box[4 * i + 1] = INT_MAX; box[4 * i + 2] = box[4 * i + 3] = -1; }
     NQ_HIP(h, h->gif_ptrs.reserve(n));
     NQ_HIP(h, h->gif_box.reserve(box.size()));
     NQ_HIP(h, hipMemcpyAsync(h->gif_ptrs.p, d_index, n * sizeof(*d_index), hipMemcpyHostToDevice, h->stream));
     NQ_HIP(h, hipMemcpyAsync(h->gif_box.p, box.data(), box.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    launch_gif_diff(h->gif_ptrs.p, n, W, H, K, h->gif_box.p, h->gif_box.p + 4 * (size_t) (n - 1), h->stream);
+    if (local)
+        launch_gif_diff_local(h->gif_ptrs.p, n, W, H, h->d_gif_local.p, h->gif_box.p, h->gif_box.p + 4 * (size_t) (n - 1), h->stream);
+    else
+        launch_gif_diff(h->gif_ptrs.p, n, W, H, K, h->gif_box.p, h->gif_box.p + 4 * (size_t) (n - 1), h->stream);
     NQ_HIP(h, launch_status());
     NQ_HIP(h, hipMemcpyAsync(box.data(), h->gif_box.p, box.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
-    if (box[4 * (size_t) (n - 1)]) NQ_FAIL(h, NQ_ERR_INVALID, "an index map holds an index >= K = %d", K);
+    if (local && box[4 * (size_t) (n - 1)] != INT_MAX) {
+        const int f = std::min(std::max(box[4 * (size_t) (n - 1)], 0), n - 1);
+        NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: the index map holds an index >= its K = %d", f, h->h_gif_local[f].K);
+    }
+    if (!local && box[4 * (size_t) (n - 1)]) NQ_FAIL(h, NQ_ERR_INVALID, "an index map holds an index >= K = %d", K);
     std::vector<GifRect>& rects = *out;
     rects.assign(n, GifRect{});
     rects[0] = {0, 0, W, H};
@@ -2002,13 +2045,14 @@ int changed_rects(nq_handle* h, int n, const uint16_t* const* d_index, int W, in
 }
 
 // nq_encode_gif_delta_device after the argument checks (n >= 2): difference pass, one read-back of the boxes, body pass, then the
-// bodies are encoded like any index maps
+// bodies are encoded like any index maps.  loc (NULL: one global table): both passes compare colours and every frame has its own u,
+// from h->h_gif_local / h->d_gif_local; palette and K are not read.
 int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W, int H, const uint32_t* palette, int K,
                      const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size,
-                     int32_t* out_rects) {
+                     int32_t* out_rects, const GifLocalHead* loc = nullptr) {
     const int u = K <= 255 ? K : -1;                // the "unchanged" index, transparent in every frame
     std::vector<GifRect> rects;
-    const int rc0 = changed_rects(h, n, d_index, W, H, K, &rects);
+    const int rc0 = changed_rects(h, n, d_index, W, H, K, &rects, loc != nullptr);
     if (rc0) return rc0;
     size_t room = 0;
     long long max_area = 1;
@@ -2030,12 +2074,13 @@ int gif_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int W,
         at += (size_t) (((long long) r.w * r.h + 7) & ~7ll);
     }
     NQ_HIP(h, hipMemcpyAsync(h->d_gif_delta.p, h->h_gif_delta.data(), (n - 1) * sizeof(nq::GifDelta), hipMemcpyHostToDevice, h->stream));
-    launch_gif_body(h->d_gif_delta.p, n - 1, W, u, max_area, h->stream);
+    if (loc) launch_gif_body_local(h->d_gif_delta.p, n - 1, W, h->d_gif_local.p, max_area, h->stream);
+    else launch_gif_body(h->d_gif_delta.p, n - 1, W, u, max_area, h->stream);
     NQ_HIP(h, launch_status());
     // The chains below check against Kt, so an index == K in frame 0 (read in place, not through a body) passes them: it is the
     // difference pass above that has checked frame 0, as the predecessor of frame 1, and every other frame against K.
     const int rc = gif_encode_maps(h, n, maps.data(), rects.data(), W, H, palette, K, K + (u >= 0 ? 1 : 0), 1 << 2 | (u >= 0 ? 1 : 0),
-                                   u >= 0 ? u : 0, 0, delays_cs, loop_count, segment_pixels, u, lossy, out, cap, out_size);
+                                   u >= 0 ? u : 0, 0, delays_cs, loop_count, segment_pixels, u, lossy, out, cap, out_size, loc);
     if (rc) return rc;
     if (out_rects)
         for (int i = 0; i < n; ++i) { out_rects[4 * i] = rects[i].x; out_rects[4 * i + 1] = rects[i].y; out_rects[4 * i + 2] = rects[i].w; out_rects[4 * i + 3] = rects[i].h; }
@@ -2134,9 +2179,180 @@ int gif_delta_host_call(nq_handle* h, int n, const uint16_t* const* index, int w
     });
 }
 
+// ---- local colour tables ----
+
+// the checks of both local calls, from the host arguments alone: gif_check's list, then K and the palettes
+int gif_local_check(nq_handle* h, int n, const int32_t* widths, const int32_t* heights, const uint32_t* palettes, int32_t palette_stride,
+                    const int32_t* K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy, const uint8_t* out, int64_t cap,
+                    int64_t* out_size, bool delta) {
+    int rc = gif_check(h, n, widths, heights, palettes, 256, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size);
+    if (rc) return rc;
+    if (!K) NQ_FAIL(h, NQ_ERR_INVALID, "K is NULL");
+    for (int i = 0; i < n; ++i) {
+        if (K[i] < 1 || K[i] > 256) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: K = %d: a GIF colour table holds 1..256 entries", i, K[i]);
+        if (palette_stride < K[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: palette_stride = %d < K = %d", i, palette_stride, K[i]);
+    }
+    if (delta && n > 1)
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < K[i]; ++j)
+                if ((palettes[(size_t) i * palette_stride + j] >> 24) == 0)
+                    NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: palette entry %d is transparent (alpha 0): frames that keep the canvas cannot "
+                            "un-paint a pixel, use nq_encode_gif_local", i, j);
+    return NQ_OK;
+}
+
+// h->h_gif_local and the frames' header values from the palettes, copied to h->d_gif_local.  delta: Kt and T follow u, else t.
+int gif_local_tables(nq_handle* h, int n, const uint32_t* palettes, int32_t palette_stride, const int32_t* K, bool delta,
+                     std::vector<GifLocalHead>* heads) {
+    h->h_gif_local.assign(n, nq::GifLocal{});
+    heads->assign(n, GifLocalHead{});
+    for (int i = 0; i < n; ++i) {
+        nq::GifLocal& P = h->h_gif_local[i];
+        const uint32_t* pal = palettes + (size_t) i * palette_stride;
+        P.K = K[i];
+        for (int j = 0; j < P.K; ++j) P.rgb[j] = pal[j] & 0xFFFFFFu;
+        if (delta) {
+            P.T = P.K <= 255 ? P.K : -1;            // u
+            P.Kt = P.K + (P.T >= 0 ? 1 : 0);
+            (*heads)[i] = {1 << 2 | (P.T >= 0 ? 1 : 0), P.T >= 0 ? P.T : 0};
+        } else {
+            P.T = -1;                               // t
+            for (int j = 0; j < P.K && P.T < 0; ++j) if ((pal[j] >> 24) == 0) P.T = j;
+            P.Kt = P.K;
+            (*heads)[i] = {n > 1 || P.T >= 0 ? (n > 1 ? 2 << 2 : 0) | (P.T >= 0 ? 1 : 0) : -1, P.T >= 0 ? P.T : 0};
+        }
+        P.m = std::max(2, gif_color_bits(P.Kt) + 1);
+    }
+    NQ_HIP(h, h->d_gif_local.reserve(n));
+    NQ_HIP(h, hipMemcpyAsync(h->d_gif_local.p, h->h_gif_local.data(), n * sizeof(nq::GifLocal), hipMemcpyHostToDevice, h->stream));
+    return NQ_OK;
+}
+
+// nq_encode_gif_local_device after the checks: whole frames at (0, 0), disposal 2, every frame under its own table
+int gif_local_encode(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                     const uint32_t* palettes, int32_t palette_stride, const int32_t* K, const int32_t* delays_cs, int loop_count,
+                     int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size) {
+    std::vector<GifLocalHead> heads;
+    const int rc = gif_local_tables(h, n, palettes, palette_stride, K, false, &heads);
+    if (rc) return rc;
+    std::vector<GifRect> rects(n);
+    int W = 0, H = 0;
+    for (int i = 0; i < n; ++i) {
+        rects[i] = {0, 0, (int) widths[i], (int) heights[i]};
+        W = std::max(W, (int) widths[i]); H = std::max(H, (int) heights[i]);
+    }
+    return gif_encode_maps(h, n, d_index, rects.data(), W, H, nullptr, 0, 0, -1, 0, 0, delays_cs, loop_count, segment_pixels, -1, lossy, out, cap,
+                           out_size, heads.data());
+}
+
+// nq_encode_gif_local_delta_device after the checks; n = 1 is the full-frame file
+int gif_local_encode_delta(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height, const uint32_t* palettes,
+                           int32_t palette_stride, const int32_t* K, const int32_t* delays_cs, int loop_count, int segment_pixels, int lossy,
+                           uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects) {
+    if (n == 1) {
+        const int32_t w = width, ht = height;
+        const int rc = gif_local_encode(h, 1, d_index, &w, &ht, palettes, palette_stride, K, delays_cs, loop_count, segment_pixels, lossy, out,
+                                        cap, out_size);
+        if (rc == NQ_OK) gif_whole_rect(out_rects, width, height);
+        return rc;
+    }
+    std::vector<GifLocalHead> heads;
+    const int rc = gif_local_tables(h, n, palettes, palette_stride, K, true, &heads);
+    if (rc) return rc;
+    return gif_encode_delta(h, n, d_index, width, height, nullptr, 0, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size, out_rects,
+                            heads.data());
+}
+
 } // namespace
 
 extern "C" {
+
+// The bound of the same frames under one global table, nq_gif_max_bytes(.., 256, ..), counts
+//   6 + 7 + 768 (global table) + 19 (loop block) + 1 (trailer)  and per frame  8 (extension) + 10 (descriptor) + 1 (m) + the stream's bound,
+// the extension and the loop block for every n, n = 1 included, and the stream's bound for any K.  A file with local tables is
+//   6 + 7 + (n > 1: 19) + 1  and per frame  (0 or 8) + 10 + 3 * 2^(N_i+1) <= 768 + 1 + the same stream,
+// so it is at most that bound - 768 + 768 * n.  Adding 768 * n without taking the global table off keeps the arithmetic in one place
+// and is 768 bytes loose (787 for n = 1 without an extension).
+int nq_gif_local_max_bytes(int n, const int32_t* widths, const int32_t* heights, int segment_pixels, int64_t* out_bytes) {
+    const int rc = nq_gif_max_bytes(n, widths, heights, 256, segment_pixels, out_bytes);
+    if (rc == NQ_OK) *out_bytes += 768ll * n;
+    return rc;
+}
+
+int nq_encode_gif_local_device(nq_handle* h, int n, const uint16_t* const* d_index, const int32_t* widths, const int32_t* heights,
+                               const uint32_t* palettes, int32_t palette_stride, const int32_t* K, const int32_t* delays_cs, int loop_count,
+                               int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = gif_local_check(h, n, widths, heights, palettes, palette_stride, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size,
+                             false);
+    if (rc) return rc;
+    rc = gif_check_index(h, n, d_index);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return gif_local_encode(h, n, d_index, widths, heights, palettes, palette_stride, K, delays_cs, loop_count, segment_pixels, lossy, out, cap,
+                            out_size);
+}
+
+int nq_encode_gif_local(nq_handle* h, int n, const uint16_t* const* index, const int32_t* widths, const int32_t* heights,
+                        const uint32_t* palettes, int32_t palette_stride, const int32_t* K, const int32_t* delays_cs, int loop_count,
+                        int segment_pixels, int lossy, uint8_t* out, int64_t cap, int64_t* out_size) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = gif_local_check(h, n, widths, heights, palettes, palette_stride, K, delays_cs, loop_count, segment_pixels, lossy, out, cap, out_size,
+                             false);
+    if (rc) return rc;
+    rc = gif_check_index(h, n, index);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    std::vector<size_t> px(n);
+    for (int i = 0; i < n; ++i) px[i] = (size_t) widths[i] * heights[i];
+    std::vector<uint16_t*> dev(n);
+    return host_form(h, [&]() {
+        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
+        return rc ? rc : gif_local_encode(h, n, dev.data(), widths, heights, palettes, palette_stride, K, delays_cs, loop_count, segment_pixels,
+                                          lossy, out, cap, out_size);
+    });
+}
+
+int nq_encode_gif_local_delta_device(nq_handle* h, int n, const uint16_t* const* d_index, int width, int height, const uint32_t* palettes,
+                                     int32_t palette_stride, const int32_t* K, const int32_t* delays_cs, int loop_count, int segment_pixels,
+                                     int lossy, uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects) {
+    if (!h) return NQ_ERR_INVALID;
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    const std::vector<int32_t> ws(n, width), hs(n, height);
+    int rc = gif_local_check(h, n, ws.data(), hs.data(), palettes, palette_stride, K, delays_cs, loop_count, segment_pixels, lossy, out, cap,
+                             out_size, true);
+    if (rc) return rc;
+    rc = gif_check_index(h, n, d_index);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return gif_local_encode_delta(h, n, d_index, width, height, palettes, palette_stride, K, delays_cs, loop_count, segment_pixels, lossy, out,
+                                  cap, out_size, out_rects);
+}
+
+int nq_encode_gif_local_delta(nq_handle* h, int n, const uint16_t* const* index, int width, int height, const uint32_t* palettes,
+                              int32_t palette_stride, const int32_t* K, const int32_t* delays_cs, int loop_count, int segment_pixels,
+                              int lossy, uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects) {
+    if (!h) return NQ_ERR_INVALID;
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    const std::vector<int32_t> ws(n, width), hs(n, height);
+    int rc = gif_local_check(h, n, ws.data(), hs.data(), palettes, palette_stride, K, delays_cs, loop_count, segment_pixels, lossy, out, cap,
+                             out_size, true);
+    if (rc) return rc;
+    rc = gif_check_index(h, n, index);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    std::vector<size_t> px(n, (size_t) width * height);
+    std::vector<uint16_t*> dev(n);
+    return host_form(h, [&]() {
+        rc = stage_in(h, h->gif_in, n, px.data(), index, dev.data());
+        return rc ? rc : gif_local_encode_delta(h, n, dev.data(), width, height, palettes, palette_stride, K, delays_cs, loop_count,
+                                                segment_pixels, lossy, out, cap, out_size, out_rects);
+    });
+}
 
 int nq_gif_max_bytes(int n, const int32_t* widths, const int32_t* heights, int K, int segment_pixels, int64_t* out_bytes) {
     char why[256];

@@ -12,7 +12,12 @@
 // the three kernels above run on those as on any index map.
 //   gif_diff_kernel    frame f against frame f - 1: bounding box of the changed pixels (and the index >= K check of all frames)
 //   gif_body_kernel    the box's pixels, row-major, the unchanged ones replaced by the transparent index
+// Local colour tables (nq_encode_gif_local*): one GifLocal record per frame (K, Kt, m, T and the written table) replaces the per-call
+// values.  gif_lzw_kernel<.., true> takes them per chain; gif_diff_local_kernel and gif_body_local_kernel are the two delta passes with
+// "differs" judged on the colours the two frames' tables give the indices (the tables sit in LDS).  Scan and gather are shared.
 #include "nq_kernels.h"
+
+#include <type_traits>
 
 namespace nq {
 
@@ -71,29 +76,53 @@ __device__ inline uint2 rgb_apart(unsigned a, unsigned b) {
 // LOSSY: `rgb` is the file's colour table (256 entries 0x00RRGGBB, zeros from entry K on; here K is the table's Kt), T its transparent
 // index (-1: none), lossy the threshold 1..255.  Where the exact index misses, lane l looks up (pre, c') for c' = l, l + 64, l + 128,
 // l + 192, a wave minimum over d^2 << 8 | c' picks the winner, and its code is handed to every lane: all lanes hold the same `pre` again.
-template <bool LOSSY>
+// LOCAL ("GIF encoding, local colour tables"): `rgb` is the per-frame records instead, and K, m, T and the colour table are those of
+// the chain's frame, rgb[frame] (the arguments K, m and T are not read).  The four chains of a workgroup may sit in four frames, so
+// every wave has an LDS palette of its own and fills it, and `mine`, when its frame changes from one chain to the next.  *bad is
+// lowered to the frame's number.  The parameter list is the same for both forms: the code of <.., false> is what it was without LOCAL.
+template <bool LOSSY, bool LOCAL>
 __global__ void __launch_bounds__(64 * GIF_CHAINS) gif_lzw_kernel(const GifFrame* __restrict__ frames, int n_frames, long long n_segs,
                                                                    int K, int m, unsigned* __restrict__ words,
                                                                    unsigned long long* __restrict__ seg_bits, unsigned long long* __restrict__ bad,
-                                                                   const unsigned* __restrict__ rgb, int T, int lossy) {
+                                                                   std::conditional_t<LOCAL, const GifLocal*, const unsigned*> __restrict__ rgb,
+                                                                   int T, int lossy) {
     __shared__ unsigned table[GIF_CHAINS][GIF_SLOTS];
     __shared__ uint4 stage[GIF_CHAINS][2][GIF_STAGE / 8];
-    __shared__ unsigned pal[LOSSY ? 256 : 1];      // the colour of the index at hand is read from here (a broadcast)
+    __shared__ unsigned pal[LOSSY ? (LOCAL ? 256 * GIF_CHAINS : 256) : 1];     // the colour of the index at hand is read from here (a broadcast)
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned* tab = table[wv];
+    unsigned* wpal = pal + (LOSSY && LOCAL ? 256 * wv : 0);                      // LOCAL: this wave's palette
     unsigned mine[4] = {0, 0, 0, 0};               // this lane's four candidates' colours
-    if constexpr (LOSSY) {
+    if constexpr (LOSSY && !LOCAL) {
         static_assert(64 * GIF_CHAINS == 256, "one thread per colour table entry");
         pal[threadIdx.x] = rgb[threadIdx.x];
         for (int j = 0; j < 4; ++j) mine[j] = rgb[lane + 64 * j];
         __syncthreads();
     }
-    const unsigned CLEAR = 1u << m, EOI = CLEAR + 1;
+    unsigned CLEAR = 1u << m, EOI = CLEAR + 1;
+    int held = -1;                                 // LOCAL: the frame whose K, m, T and colours this wave holds
     for (long long g = (long long) blockIdx.x * GIF_CHAINS + wv; g < n_segs; g += (long long) gridDim.x * GIF_CHAINS) {
         int lo = 0, hi = n_frames - 1;                 // frame of segment g: the last one whose first segment is <= g
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
             if (frames[mid].seg_base <= g) lo = mid; else hi = mid - 1;
+        }
+        if constexpr (LOCAL) {
+            if (lo != held) {                          // (g is the same in every lane of the wave, so is this branch)
+                const GifLocal& P = rgb[lo];
+                K = P.Kt; m = P.m; T = P.T;
+                CLEAR = 1u << m; EOI = CLEAR + 1;
+                if constexpr (LOSSY) {
+                    wave_sync();                       // the chain before has read this wave's palette for the last time
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        mine[j] = P.rgb[lane + 64 * j];
+                        wpal[lane + 64 * j] = mine[j];
+                    }
+                    wave_sync();
+                }
+                held = lo;
+            }
         }
         const GifFrame& F = frames[lo];
         const long long s = g - F.seg_base;
@@ -141,7 +170,7 @@ __global__ void __launch_bounds__(64 * GIF_CHAINS) gif_lzw_kernel(const GifFrame
                 if constexpr (LOSSY) {
                     if (c != (unsigned) T) {
                         wave_sync();                                            // lane 0's dictionary stores, read by every lane below
-                        const unsigned want = pal[c];
+                        const unsigned want = wpal[c];
                         unsigned best = ~0u, best_code = 0;                     // this lane's smallest d^2 << 8 | c' and its code
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
@@ -187,7 +216,11 @@ __global__ void __launch_bounds__(64 * GIF_CHAINS) gif_lzw_kernel(const GifFrame
         if (lane == 0) {
             if (nb > 0) out[wpos] = (unsigned) acc;
             seg_bits[g] = (unsigned long long) wpos * 32 + nb;
-            if (badc) *bad = 1;
+            if constexpr (LOCAL) {
+                if (badc) atomicMin(bad, (unsigned long long) lo);
+            } else {
+                if (badc) *bad = 1;
+            }
         }
         wave_sync();
     }
@@ -367,6 +400,94 @@ __global__ void __launch_bounds__(256) gif_body_kernel(const GifDelta* __restric
     }
 }
 
+// ---- local colour tables ("GIF encoding, local colour tables"): the two delta passes compare colours, not indices ----
+
+// frame f - 1's written table to tab[0], frame f's to tab[1], one entry per thread of the workgroup (256); the barriers keep the
+// readers of the pair before and of this pair apart
+__device__ inline void load_tables(unsigned (*tab)[256], const GifLocal* __restrict__ local, int f) {
+    __syncthreads();
+    tab[0][threadIdx.x] = local[f - 1].rgb[threadIdx.x];
+    tab[1][threadIdx.x] = local[f].rgb[threadIdx.x];
+    __syncthreads();
+}
+
+// gif_diff_kernel with "differs" judged on the colour shown: the same grid, chunk loads, shifted predecessor and wave reduction.  The
+// two tables are refilled whenever blockIdx.y's stride moves on (f is the same in every thread of a workgroup, so are the barriers).
+// An index is checked against its own frame's K and masked to 8 bits before it addresses the table.  An element outside the frame was
+// not loaded and is not compared: equal indices no longer mean equal colours, so the zeros standing for it must not reach the tables.
+__global__ void __launch_bounds__(256) gif_diff_local_kernel(const unsigned short* const* __restrict__ index, int n_frames, int W, long long npix,
+                                                             const GifLocal* __restrict__ local, int* __restrict__ box, int* __restrict__ bad) {
+    __shared__ unsigned tab[2][256];
+    int badf = 0x7FFFFFFF;
+    for (int f = (int) blockIdx.y + 1; f < n_frames; f += (int) gridDim.y) {
+        load_tables(tab, local, f);
+        const unsigned Kp = (unsigned) local[f - 1].K, Kc = (unsigned) local[f].K;
+        const uintptr_t clo = reinterpret_cast<uintptr_t>(index[f]), chi = clo + 2 * (uintptr_t) npix;
+        const uintptr_t plo = reinterpret_cast<uintptr_t>(index[f - 1]), phi = plo + 2 * (uintptr_t) npix;
+        const uintptr_t a0 = clo & ~(uintptr_t) 15;
+        const long long nchunk = (long long) ((chi - a0 + 15) >> 4);
+        int x0 = 0x7FFFFFFF, y0 = 0x7FFFFFFF, x1 = -1, y1 = -1;
+        for (long long c = (long long) blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (long long) gridDim.x * blockDim.x) {
+            const uintptr_t a = a0 + 16 * (uintptr_t) c;
+            const long long p0 = ((long long) a - (long long) clo) / 2;          // pixel of the chunk's first element: -7 .. npix - 1
+            const uint4 cu = load_chunk(a, clo, chi);
+            const uint4 pv = load_chunk_at(plo + (uintptr_t) (2 * p0), plo, phi);
+            if (pair_bad(cu.x, Kc) || pair_bad(cu.y, Kc) || pair_bad(cu.z, Kc) || pair_bad(cu.w, Kc)) badf = min(badf, f);
+            if (pair_bad(pv.x, Kp) || pair_bad(pv.y, Kp) || pair_bad(pv.z, Kp) || pair_bad(pv.w, Kp)) badf = min(badf, f - 1);
+            const unsigned ce[4] = {cu.x, cu.y, cu.z, cu.w}, pe[4] = {pv.x, pv.y, pv.z, pv.w};
+            const unsigned first = p0 > 0 ? (unsigned) p0 : 0u;
+            int y = (int) (first / (unsigned) W), x = (int) (first % (unsigned) W);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if (p0 + j < 0 || p0 + j >= npix) continue;
+                const unsigned ci = (ce[j >> 1] >> (16 * (j & 1))) & 255u, pi = (pe[j >> 1] >> (16 * (j & 1))) & 255u;
+                if (tab[1][ci] != tab[0][pi]) {
+                    x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
+                }
+                if (++x == W) { x = 0; ++y; }
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            x0 = min(x0, __shfl_xor(x0, d)); y0 = min(y0, __shfl_xor(y0, d));
+            x1 = max(x1, __shfl_xor(x1, d)); y1 = max(y1, __shfl_xor(y1, d));
+        }
+        if ((threadIdx.x & 63) == 0 && x1 >= 0) {
+            int* b = box + 4 * (f - 1);
+            atomicMin(b + 0, x0); atomicMin(b + 1, y0); atomicMax(b + 2, x1); atomicMax(b + 3, y1);
+        }
+    }
+    if (badf != 0x7FFFFFFF) atomicMin(bad, badf);
+}
+
+// gif_body_kernel with the same comparison; body b is frame b + 1 against frame b and takes its u from frame b + 1's record
+__global__ void __launch_bounds__(256) gif_body_local_kernel(const GifDelta* __restrict__ delta, int n_bodies, int W,
+                                                             const GifLocal* __restrict__ local) {
+    __shared__ unsigned tab[2][256];
+    for (int f = (int) blockIdx.y; f < n_bodies; f += (int) gridDim.y) {
+        load_tables(tab, local, f + 1);
+        const int u = local[f + 1].T;
+        const GifDelta D = delta[f];
+        const unsigned area = (unsigned) D.w * (unsigned) D.h;                   // <= W * H < 2^32
+        const long long nchunk = ((long long) area + 7) >> 3;
+        for (long long c = (long long) blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (long long) gridDim.x * blockDim.x) {
+            const unsigned e0 = (unsigned) (8 * c);
+            unsigned r = e0 / (unsigned) D.w, col = e0 % (unsigned) D.w;
+            unsigned v[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if ((long long) e0 + j < (long long) area) {
+                    const size_t src = (size_t) (D.y + (int) r) * (size_t) W + (size_t) (D.x + (int) col);
+                    const unsigned cv = D.cur[src], pv = D.prev[src];
+                    v[j >> 1] |= (u >= 0 && tab[1][cv & 255u] == tab[0][pv & 255u] ? (unsigned) u : cv) << (16 * (j & 1));
+                }
+                if (++col == (unsigned) D.w) { col = 0; ++r; }
+            }
+            reinterpret_cast<uint4*>(D.body)[c] = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+    }
+}
+
 } // namespace
 
 void launch_gif_diff(const unsigned short* const* d_index, int n_frames, int W, int H, int K, int* d_box, int* d_bad, hipStream_t s) {
@@ -390,11 +511,40 @@ void launch_gif_lzw(const GifFrame* d_frames, int n_frames, long long n_segs, in
     long long grid = (n_segs + GIF_CHAINS - 1) / GIF_CHAINS;
     if (grid > (1 << 20)) grid = 1 << 20;
     if (lossy > 0)
-        hipLaunchKernelGGL(gif_lzw_kernel<true>, dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, K, m, d_words,
+        hipLaunchKernelGGL((gif_lzw_kernel<true, false>), dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, K, m, d_words,
                            d_seg_bits, d_bad, d_rgb, T, lossy);
     else
-        hipLaunchKernelGGL(gif_lzw_kernel<false>, dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, K, m, d_words,
+        hipLaunchKernelGGL((gif_lzw_kernel<false, false>), dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, K, m, d_words,
                            d_seg_bits, d_bad, (const unsigned*) nullptr, -1, 0);
+}
+
+void launch_gif_lzw_local(const GifFrame* d_frames, int n_frames, long long n_segs, const GifLocal* d_local, unsigned* d_words,
+                          unsigned long long* d_seg_bits, unsigned long long* d_bad, int lossy, hipStream_t s) {
+    long long grid = (n_segs + GIF_CHAINS - 1) / GIF_CHAINS;
+    if (grid > (1 << 20)) grid = 1 << 20;
+    if (lossy > 0)
+        hipLaunchKernelGGL((gif_lzw_kernel<true, true>), dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, 0, 0, d_words,
+                           d_seg_bits, d_bad, d_local, -1, lossy);
+    else
+        hipLaunchKernelGGL((gif_lzw_kernel<false, true>), dim3((unsigned) grid), dim3(64 * GIF_CHAINS), 0, s, d_frames, n_frames, n_segs, 0, 0, d_words,
+                           d_seg_bits, d_bad, d_local, -1, 0);
+}
+
+void launch_gif_diff_local(const unsigned short* const* d_index, int n_frames, int W, int H, const GifLocal* d_local, int* d_box, int* d_bad,
+                           hipStream_t s) {
+    const long long npix = (long long) W * H;
+    long long gx = ((npix + 7) / 8 + 1 + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    const int gy = n_frames - 1 < 65535 ? n_frames - 1 : 65535;
+    hipLaunchKernelGGL(gif_diff_local_kernel, dim3((unsigned) gx, (unsigned) gy), dim3(256), 0, s, d_index, n_frames, W, npix, d_local, d_box, d_bad);
+}
+
+void launch_gif_body_local(const GifDelta* d_delta, int n_bodies, int W, const GifLocal* d_local, long long max_area, hipStream_t s) {
+    long long gx = ((max_area + 7) / 8 + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    if (gx < 1) gx = 1;
+    const int gy = n_bodies < 65535 ? n_bodies : 65535;
+    hipLaunchKernelGGL(gif_body_local_kernel, dim3((unsigned) gx, (unsigned) gy), dim3(256), 0, s, d_delta, n_bodies, W, d_local);
 }
 
 void launch_gif_scan(const GifFrame* d_frames, int n_frames, const unsigned long long* d_seg_bits, unsigned long long* d_seg_off,

@@ -227,6 +227,26 @@ void launch_gif_diff(const unsigned short* const* d_index, int n_frames, int W, 
 // bodies of the n_bodies rectangles in d_delta (max_area: the largest w * h among them)
 void launch_gif_body(const GifDelta* d_delta, int n_bodies, int W, int u, long long max_area, hipStream_t s);
 
+// ---- GIF local colour tables (nq_gif.hip; "GIF encoding, local colour tables"): one record per frame, what the launches above take
+// per call.  The record holds its table (not an offset to it), so a chain finds everything behind one pointer ----
+struct GifLocal {
+    int K;                         // the frame's palette entries: what an index of the caller's map is checked against
+    int Kt;                        // entries of the written table (delta mode: K + 1 when u exists): what a chain checks against
+    int m;                         // minimum code size, from Kt
+    int T;                         // the index the lossy step leaves alone and delta bodies mark unchanged pixels with (t or u); -1: none
+    unsigned rgb[256];             // the written table, 0x00RRGGBB, zeros from entry K on
+};
+// launch_gif_lzw with K, m, T and the colour table taken per chain from d_local[frame of the chain].  *d_bad: the caller puts ~0 there;
+// a chain that meets an index >= its frame's Kt lowers it to the frame's number
+void launch_gif_lzw_local(const GifFrame* d_frames, int n_frames, long long n_segs, const GifLocal* d_local, unsigned* d_words,
+                          unsigned long long* d_seg_bits, unsigned long long* d_bad, int lossy, hipStream_t s);
+// launch_gif_diff by colour: pixel p of frame f differs when d_local[f].rgb[index_f[p]] != d_local[f - 1].rgb[index_(f-1)[p]].  *d_bad: the
+// caller puts INT_MAX there; it is lowered to the number of a frame that holds an index >= its own K
+void launch_gif_diff_local(const unsigned short* const* d_index, int n_frames, int W, int H, const GifLocal* d_local, int* d_box, int* d_bad,
+                           hipStream_t s);
+// launch_gif_body by colour: body b is frame b + 1 against frame b, unchanged pixels replaced by d_local[b + 1].T where that is >= 0
+void launch_gif_body_local(const GifDelta* d_delta, int n_bodies, int W, const GifLocal* d_local, long long max_area, hipStream_t s);
+
 // ---- PNG encoding (nq_png.hip): image i's raw stream (per row a filter byte 0 + the indices packed at `depth` bits) is cut into
 // segments of seg_len bytes (the last one shorter); segment s of the image is chain seg_base + s of the call and writes its deflate
 // block to words[word_base + s * seg_words ...].  An image is width x height pixels whose rows lie `pitch` elements apart, so it may be

@@ -8,6 +8,9 @@ position and the seed alone).
 Lossy mode (the nq_encode_gif*_lossy* calls, "GIF encoding, lossy mode"): every encoder here takes a trailing lossy=0..255.  Above 0 the
 LZW chains may write a palette colour within `lossy` per channel of a pixel's own where that continues the current dictionary string,
 which is what shrinks dithered content; 0 calls the lossless entry points.
+Local colour tables (the nq_encode_gif_local* calls, "GIF encoding, local colour tables"): one palette per frame, so an animation is not
+tied to 256 colours for its whole length.  The practical unit is the shot: convert_shots_to_gif gives every shot its own palette, and
+delta mode there compares the colours shown, not the indices.
 There is no CPU fallback: without a HIP device every call raises NqError with status -5 (NQ_ERR_NO_DEVICE)."""
 import ctypes as C
 
@@ -190,6 +193,156 @@ def encode_gif_delta_device(q, d_index_ptrs, width, height, palette, delays_cs=N
     data, rects = _encode_delta(q._L, q._h, "nq_encode_gif_delta_device", list(d_index_ptrs), width, height, palette, delays_cs, loop,
                                 segment_pixels, q._check, lossy)
     return (data, rects) if return_rects else data
+
+
+# ---- local colour tables: one palette per frame ----
+def gif_local_max_bytes(widths, heights, segment_pixels=0):
+    """nq_gif_local_max_bytes: an upper bound of the size of a file with a local colour table per frame (any content, any K; no device
+    needed).  Delta mode: one width and one height per frame, all equal."""
+    L = load_library()
+    w = np.ascontiguousarray(widths, np.int32).reshape(-1)
+    h = np.ascontiguousarray(heights, np.int32).reshape(-1)
+    if w.size != h.size:
+        raise ValueError("one width and one height per frame")
+    out = C.c_int64(0)
+    rc = L.nq_gif_local_max_bytes(int(w.size), w.ctypes.data, h.ctypes.data, int(segment_pixels), C.byref(out))
+    if rc != 0:
+        raise NqError(rc, "invalid GIF shape arguments")
+    return out.value
+
+
+def _palettes(palettes, n):
+    """(the palettes packed to one stride as a (n, stride) uint32 array, K per frame): ragged lengths are allowed."""
+    pals = [_palette(p) for p in palettes]
+    if len(pals) != n:
+        raise ValueError("one palette per frame: %d palettes for %d frames" % (len(pals), n))
+    K = np.array([p.size for p in pals], np.int32)
+    packed = np.zeros((max(n, 1), max(int(K.max()) if n else 1, 1)), np.uint32)
+    for i, p in enumerate(pals):
+        packed[i, :p.size] = p
+    return packed, K
+
+
+def _encode_local(L, handle, entry, ptrs, w, h, palettes, delays_cs, loop, segment_pixels, lossy, check, delta):
+    """One call of any of the four local exports; delta: w and h are the one size.  Returns (file bytes, rectangles or None)."""
+    n = len(ptrs)
+    if n == 0:
+        raise ValueError("no frames")
+    pal, K = _palettes(palettes, n)
+    d = _delays(delays_cs, n)
+    try:
+        cap = gif_local_max_bytes([w] * n if delta else w, [h] * n if delta else h, segment_pixels)
+    except NqError:
+        cap = 0                                     # (bad sizes: the encode call below says which)
+    buf = np.empty(max(cap, 1), np.uint8)
+    size = C.c_int64(0)
+    src = (C.c_void_p * n)(*[int(p) for p in ptrs])
+    sizes = (int(w), int(h)) if delta else (w.ctypes.data, h.ctypes.data)
+    rects = np.zeros((n, 4), np.int32) if delta else None
+    check(getattr(L, entry)(handle, n, src, *sizes, pal.ctypes.data, int(pal.shape[1]), K.ctypes.data, d.ctypes.data if d is not None else None,
+                            int(loop), int(segment_pixels), int(lossy), buf.ctypes.data, int(cap), C.byref(size),
+                            *((rects.ctypes.data,) if delta else ())))
+    return buf[:size.value].tobytes(), rects
+
+
+def encode_gif_local(indices, palettes, delays_cs=None, loop=0, segment_pixels=0, device=0, lossy=0):
+    """nq_encode_gif_local: as encode_gif, but `palettes` is a sequence of one palette per frame (lengths may differ, each <= 256) and
+    every frame is written with its own local colour table; the file has no global one.  Returns the file."""
+    maps = _index_maps(indices)
+    w = np.array([a.shape[1] for a in maps], np.int32)
+    h = np.array([a.shape[0] for a in maps], np.int32)
+    _palettes(palettes, len(maps))                   # (argument errors come before the device is asked for)
+    hd = _Handle(device)
+    try:
+        return _encode_local(hd._L, hd._h, "nq_encode_gif_local", [a.ctypes.data for a in maps], w, h, palettes, delays_cs, loop,
+                             segment_pixels, lossy, hd._check, False)[0]
+    finally:
+        hd.close()
+
+
+def encode_gif_local_device(q, d_index_ptrs, widths, heights, palettes, delays_cs=None, loop=0, segment_pixels=0, lossy=0):
+    """nq_encode_gif_local_device on the handle of quantizer `q`: as encode_gif_device with one palette per frame."""
+    w, h = _frame_sizes(widths, heights, len(d_index_ptrs))
+    return _encode_local(q._L, q._h, "nq_encode_gif_local_device", list(d_index_ptrs), w, h, palettes, delays_cs, loop, segment_pixels,
+                         lossy, q._check, False)[0]
+
+
+def encode_gif_local_delta(indices, palettes, delays_cs=None, loop=0, segment_pixels=0, device=0, return_rects=False, lossy=0):
+    """nq_encode_gif_local_delta: as encode_gif_delta with one palette per frame.  A pixel is unchanged when the COLOUR it shows is the
+    one the frame before showed there, whatever the two indices are: frames of one shot, which share a palette, drop their still regions
+    as before, and where the palette changes the frame is repainted.  Returns the file; with return_rects=True (file, rectangles)."""
+    maps = _index_maps(indices)
+    height, width = _one_size(maps)
+    _palettes(palettes, len(maps))                   # (argument errors come before the device is asked for)
+    hd = _Handle(device)
+    try:
+        data, rects = _encode_local(hd._L, hd._h, "nq_encode_gif_local_delta", [a.ctypes.data for a in maps], width, height, palettes,
+                                    delays_cs, loop, segment_pixels, lossy, hd._check, True)
+    finally:
+        hd.close()
+    return (data, rects) if return_rects else data
+
+
+def encode_gif_local_delta_device(q, d_index_ptrs, width, height, palettes, delays_cs=None, loop=0, segment_pixels=0, return_rects=False,
+                                  lossy=0):
+    """nq_encode_gif_local_delta_device on the handle of quantizer `q`: as encode_gif_delta_device with one palette per frame."""
+    data, rects = _encode_local(q._L, q._h, "nq_encode_gif_local_delta_device", list(d_index_ptrs), width, height, palettes, delays_cs, loop,
+                                segment_pixels, lossy, q._check, True)
+    return (data, rects) if return_rects else data
+
+
+def _shots(shot_starts, n):
+    """[(first frame, one past the last)] per shot."""
+    starts = [int(s) for s in shot_starts]
+    if not starts or starts[0] != 0 or any(b <= a for a, b in zip(starts[:-1], starts[1:])) or starts[-1] >= n:
+        raise ValueError("shot_starts must be an increasing list of frame numbers below %d that begins with 0, got %r" % (n, starts))
+    return list(zip(starts, starts[1:] + [n]))
+
+
+def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0,
+                         mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, delta=True):
+    """One palette per shot: frames shot_starts[k] .. shot_starts[k + 1] - 1 are shot k and get a convert_frames palette of their own
+    (shot_starts=range(n): one palette per frame), then encode_gif_local_delta (delta=False: encode_gif_local) writes all frames, each
+    with its shot's palette as its local colour table.  hold (delta=True only) runs per shot and never across a cut: a held index means
+    nothing under another table.  seeds, tile, lossy as for convert_frames_to_gif.  Everything runs on one handle.  Cuts are the
+    caller's to find.  Returns (file bytes, list of per-shot palettes)."""
+    lossy = _lossy_keyword(lossy)
+    if not 1 <= int(nMaxColors) <= 256:
+        raise ValueError("a GIF colour table holds at most 256 entries")
+    if hold is not None and not delta:
+        raise ValueError("hold needs delta=True: full frames store every pixel whether it repeats or not")
+    if delta and len({np.asarray(f).shape for f in frames}) > 1:
+        raise ValueError("delta mode: all frames must have one size")
+    shots = _shots(shot_starts, len(frames))
+    if seeds is not None and len(list(seeds)) != len(frames):
+        raise ValueError("one seed per frame")
+    if hold is not None:
+        from .hold import _hold_host, _threshold
+        hold = _threshold(hold)
+    frames, q = _frames_quantizer(kind, frames, device, mode, tile)
+    try:
+        maps, palettes = [], []
+        for a, b in shots:
+            palette, outs = _convert_frames_on(q, frames[a:b], nMaxColors, dither, mode, None if seeds is None else list(seeds)[a:b])
+            shot_maps = [o.index for o in outs]
+            if hold is not None:
+                _hold_host(q._L, q._h, q._check, frames[a:b], shot_maps, None, hold)
+            maps += shot_maps
+            palettes.append(palette)
+        per_frame = [palettes[k] for k, (a, b) in enumerate(shots) for _ in range(a, b)]
+        ptrs = [m.ctypes.data for m in maps]
+        if delta:
+            height, width = _one_size(maps)
+            data, _ = _encode_local(q._L, q._h, "nq_encode_gif_local_delta", ptrs, width, height, per_frame, delays_cs, loop, segment_pixels,
+                                    lossy, q._check, True)
+        else:
+            w = np.array([m.shape[1] for m in maps], np.int32)
+            h = np.array([m.shape[0] for m in maps], np.int32)
+            data, _ = _encode_local(q._L, q._h, "nq_encode_gif_local", ptrs, w, h, per_frame, delays_cs, loop, segment_pixels, lossy,
+                                    q._check, False)
+    finally:
+        q.close()
+    return data, palettes
 
 
 def _lossy_keyword(lossy):

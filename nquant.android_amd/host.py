@@ -92,6 +92,11 @@ _ABI = {
     "nq_encode_gif_lossy": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _pi64]),
     "nq_encode_gif_delta_lossy_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _pi64, _vp]),
     "nq_encode_gif_delta_lossy": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _pi64, _vp]),
+    "nq_gif_local_max_bytes": (_i32, [_i32, _vp, _vp, _i32, _pi64]),
+    "nq_encode_gif_local_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _pi64]),
+    "nq_encode_gif_local": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _pi64]),
+    "nq_encode_gif_local_delta_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _pi64, _vp]),
+    "nq_encode_gif_local_delta": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _pi64, _vp]),
     "nq_png_max_bytes": (_i32, [_i32, _vp, _vp, _vp, _i32, _pi64]),
     "nq_encode_png_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
     "nq_encode_png": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),

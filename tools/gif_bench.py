@@ -14,7 +14,15 @@ nq_convert_frames_device with equal seeds, once a sprite moving over a still bac
 and with every threshold N; per call the file bytes, their ratio to the lossless file, the ms per call, and the share of pixels that
 decode to another index than the source's, found by decoding each file with the decoder below.
 
-    python tools/gif_bench.py --lossy 8 --lossy 16 --lossy 32 [--size 4096] [--reps 5] [--out profiles/r09/gif_lossy_bench.txt]"""
+    python tools/gif_bench.py --lossy 8 --lossy 16 --lossy 32 [--size 4096] [--reps 5] [--out profiles/r09/gif_lossy_bench.txt]
+
+--local measures the local colour tables instead: (a) one --size map through nq_encode_gif_local_device next to nq_encode_gif_device on
+the same map, lossless and at lossy 16; (b) a two-shot sequence of --shot-frames frames of --shot-size pixels a side (each shot a
+gradient_noise background of its own, the second with its channels rotated so that the shots' colours differ, and a moving sprite)
+through convert_shots_to_gif and through convert_frames_to_gif(delta=True) at K = 256 and 64: file bytes and the summed squared RGB error
+of Pillow's canvases against the source frames.
+
+    python tools/gif_bench.py --local [--size 4096] [--shot-size 1024] [--shot-frames 16] [--reps 5] [--out profiles/r10/gif_local_bench.txt]"""
 import argparse
 import io
 import os
@@ -188,6 +196,72 @@ def lossy_bench(args, say):
     q.close()
 
 
+def local_bench(args, say):
+    """(a) ms per call of the local-table encoder next to the global-table one on one device-resident map; (b) bytes and squared error
+    of one palette per shot against one shared palette."""
+    import torch
+    from PIL import Image
+    import nquant.android_amd as nq
+    from nquant.android_amd import synth
+
+    W = H = args.size
+    say("(a) one %dx%d index map (gradient_noise seed 3, PnnLABQuantizer.convert(256, true)), device-resident; best of %d" % (W, H, args.reps))
+    q0 = nq.PnnLABQuantizer(synth.gradient_noise(W, H, 3))
+    o = q0.convert(256, True)
+    q0.close()
+    pal = o.palette
+    dev = torch.from_numpy(o.index.view(np.int16).reshape(-1).copy()).cuda()
+    torch.cuda.synchronize()
+    q = nq.PnnQuantizer(np.zeros((1, 1), np.int32))
+    for lossy in (0, 16):
+        glob = lambda: nq.encode_gif_device(q, [dev.data_ptr()], [W], [H], pal, lossy=lossy)
+        loc = lambda: nq.encode_gif_local_device(q, [dev.data_ptr()], [W], [H], [pal], lossy=lossy)
+        glob()
+        loc()
+        tg, gg = timed(glob, args.reps)
+        tl, gl = timed(loc, args.reps)
+        tg2, _ = timed(glob, args.reps)              # the global call again: what two runs of the same call differ by
+        say("lossy %2d: encode_gif_device       %8.2f ms per call (again: %.2f)  %10d bytes" % (lossy, tg * 1e3, tg2 * 1e3, len(gg)))
+        say("lossy %2d: encode_gif_local_device %8.2f ms per call (%.3fx)        %10d bytes" % (lossy, tl * 1e3, tl / min(tg, tg2), len(gl)))
+        a, b = Image.open(io.BytesIO(gg)), Image.open(io.BytesIO(gl))
+        assert (np.array(a.convert("RGB")) == np.array(b.convert("RGB"))).all()
+    say("check: Pillow decodes both files of either threshold to the same picture")
+    q.close()
+    del dev
+
+    S, n = args.shot_size, args.shot_frames
+    half = n // 2
+    say("(b) %d frames of %dx%d, a cut after frame %d; PnnLABQuantizer, dither, equal seeds, delta mode, host frames" % (n, S, S, half - 1))
+    side = max(16, S // 16)
+    sprite = synth.uniform_rgb(side, side, 1)
+    backs = [synth.gradient_noise(S, S, 3), synth.gradient_noise(S, S, 4)]
+    v = backs[1].view(np.uint32)                     # second shot: R <- G <- B <- R
+    backs[1] = (0xFF000000 | (v & 0xFFFF) << 8 | (v >> 16) & 0xFF).astype(np.uint32).view(np.int32)
+    frames = []
+    for i in range(n):
+        f = backs[i >= half].copy()
+        x, y = (i * 3 * side // 4) % (S - side), (i * side // 2) % (S - side)
+        f[y:y + side, x:x + side] = sprite
+        frames.append(f)
+    src = [np.stack([(f.view(np.uint32) >> s) & 255 for s in (16, 8, 0)], -1).astype(np.int64) for f in frames]
+
+    def sse(gif):
+        im = Image.open(io.BytesIO(gif))
+        total = 0
+        for i in range(im.n_frames):
+            im.seek(i)
+            total += int(((np.array(im.convert("RGB")).astype(np.int64) - src[i]) ** 2).sum())
+        return total
+
+    for K in (256, 64):
+        shots, pals = nq.convert_shots_to_gif(nq.NQ_KIND_LAB, frames, [0, half], K, True, seeds=[0] * n)
+        one, p1 = nq.convert_frames_to_gif(nq.NQ_KIND_LAB, frames, K, True, seeds=[0] * n, delta=True)
+        es, e1 = sse(shots), sse(one)
+        say("K = %3d: one palette per shot (K %s)  %10d bytes  squared error %d" % (K, [len(p) for p in pals], len(shots), es))
+        say("K = %3d: one shared palette (K %d)    %10d bytes  squared error %d  (per shot / shared: %.3fx the bytes, %.3fx the error)"
+            % (K, len(p1), len(one), e1, len(shots) / len(one), es / e1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=4096)
@@ -199,14 +273,17 @@ def main():
     ap.add_argument("--delta", action="store_true", help="measure the delta mode against the full-frame call instead")
     ap.add_argument("--lossy", type=int, action="append", default=[], metavar="N",
                     help="measure the lossy mode at threshold N (1..255; repeatable) against the lossless call instead")
+    ap.add_argument("--local", action="store_true", help="measure the local colour tables against the global-table calls instead")
+    ap.add_argument("--shot-size", type=int, default=1024, help="--local: side of the two-shot sequence's frames")
+    ap.add_argument("--shot-frames", type=int, default=16, help="--local: frames of the two-shot sequence")
     args = ap.parse_args()
-    if args.delta or args.lossy:
+    if args.delta or args.lossy or args.local:
         lines = []
 
         def say(s):
             print(s, flush=True)
             lines.append(s)
-        (lossy_bench if args.lossy else delta_bench)(args, say)
+        (local_bench if args.local else lossy_bench if args.lossy else delta_bench)(args, say)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
