@@ -940,7 +940,9 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
         NQ_FAIL(h, NQ_ERR_INVALID, "nq_set_band: the band [%d, %d) does not fit the image height %d (or REFERENCE_SEQUENTIAL mode)", h->band_y0, h->band_y0 + height, h->band_image_h);
     const int rule_h = banded ? h->band_image_h : height;          // the automatic tile follows the WHOLE image
     if (sequential) { T.tile_w = width; T.tile_h = height; }
-    else if (h->tile_w > 0 && h->tile_h > 0) { T.tile_w = std::min(h->tile_w, width); T.tile_h = std::min(h->tile_h, height); }
+    // (a band clamps the tile to the WHOLE image here, as the automatic rule does: tile_base below counts the image's tile rows, and a
+    // last band lower than the tile would otherwise number its tiles -- their random streams -- by its own height)
+    else if (h->tile_w > 0 && h->tile_h > 0) { T.tile_w = std::min(h->tile_w, width); T.tile_h = std::min(h->tile_h, rule_h); }
     else {
         // automatic: 8x8 when that yields >= 2 wavefronts of chains per SIMD (131072 chains), else 4x4.  The tile size does not change
         // the measured dither quality, it sets how many chains run in parallel and how much LDS a chain's staged indices
@@ -955,7 +957,7 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
         T.tile_w = std::min(tsz, width); T.tile_h = std::min(tsz, rule_h);
     }
     if (banded) {
-        T.tile_h = std::min(T.tile_h, h->band_image_h);
+        // (T.tile_h <= the image height here; the band's own height clamps it only after tile_base is known)
         if (h->band_y0 % T.tile_h != 0 || (h->band_y0 + height != h->band_image_h && height % T.tile_h != 0))
             NQ_FAIL(h, NQ_ERR_INVALID, "nq_set_band: band origin %d / rows %d must be multiples of the tile height %d", h->band_y0, height, T.tile_h);
         T.y_origin = h->band_y0;

@@ -1,8 +1,11 @@
 """Randomised GPU-vs-oracle parity sweep (palette + scalars, tiled dither, lookups) over image kinds, sizes, K and flags.
-python tests/fuzz_parity.py [seconds] [seed] [big|seq|fast]  -- prints every mismatch and a summary; exit code 1 on any mismatch.
+python tests/fuzz_parity.py [seconds] [seed] [big|seq|fast|tiny]  -- prints every mismatch and a summary; exit code 1 on any mismatch.
 fast: the specialised dither kernel (csrc/nq_dither_fast.hip) -- LAB, 33 <= K <= 256, opaque or alpha-0 images, `weight` injected into
 both sides from (.0026, .0149) (the DITHER_MAX = 25 rung needs > 17 000 bins, i.e. large images, by itself), random tiles incl. odd ones,
-dither on / off; output, lookups and the tiles handed back are compared with the oracle and the generic kernel."""
+dither on / off; output, lookups and the tiles handed back are compared with the oracle and the generic kernel.
+tiny: images of 1..16 pixels a side (fewer pixels than a wavefront, one-pixel strips, tiles larger than the image, 1x1 and 7x5 tiles); the
+comparisons of std, and a whole convert() in REFERENCE_SEQUENTIAL mode every other case.  No case is excused there: a throw of the
+oracle is not caught (none was seen at these sizes) and an UNSUPPORTED / REFERENCE_THROWS status of the GPU side counts as a mismatch."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -15,9 +18,9 @@ Ks = [3, 4, 5, 6, 7, 8, 12, 15, 16, 17, 24, 31, 32, 33, 48, 63, 64, 65, 100, 127
 
 
 def run(budget=300.0, seed=1, mode="std", max_cases=None, log=print):
-    """One sweep: mode std | big | fast | seq, until `budget` seconds have passed or `max_cases` cases have run.  Returns (cases,
+    """One sweep: mode std | big | fast | seq | tiny, until `budget` seconds have passed or `max_cases` cases have run.  Returns (cases,
     mismatches).  tests/test_gpu_fuzz_slice.py runs fixed-seed slices of every mode under the driver."""
-    BIG, FAST, SEQ = mode == "big", mode == "fast", mode == "seq"
+    BIG, FAST, SEQ, TINY = mode == "big", mode == "fast", mode == "seq", mode == "tiny"
     # big: 160..360 pixels a side (up to ~60k bins), palette + scalars only; seq: whole convert() in REFERENCE_SEQUENTIAL mode against the oracle's convert()
     rng = np.random.default_rng(int(seed))
     t_end = time.time() + budget
@@ -30,6 +33,8 @@ def run(budget=300.0, seed=1, mode="std", max_cases=None, log=print):
         w, h = (int(rng.integers(160, 360)), int(rng.integers(160, 360))) if BIG else (int(rng.integers(17, 150)), int(rng.integers(17, 150)))
         if SEQ:
             w, h = int(rng.integers(9, 90)), int(rng.integers(9, 90))
+        if TINY:
+            w, h = int(rng.integers(1, 17)), int(rng.integers(1, 17))
         seed = int(rng.integers(1, 1 << 30))
         gen = int(rng.integers(0, 5))
         if gen == 0: img = synth.uniform_rgb(w, h, seed)
@@ -39,9 +44,11 @@ def run(budget=300.0, seed=1, mode="std", max_cases=None, log=print):
         else: img = synth.with_alpha(synth.few_colors(w, h, seed, int(rng.integers(2, 300))), seed)
         K = int(Ks[rng.integers(0, len(Ks))])
         dither = bool(rng.integers(0, 2))
-        tile = (int(rng.choice([4, 8, 16])),) * 2
+        tile = [(4, 4), (8, 8), (16, 16), (1, 1), (7, 5)][int(rng.integers(0, 5))] if TINY else (int(rng.choice([4, 8, 16])),) * 2
         rseed = int(rng.integers(0, 1 << 20))
         tag = "kind %d %dx%d gen %d seed %d K %d dither %d tile %d" % (kind, w, h, gen, seed, K, dither, tile[0])
+        if TINY:
+            tag = "TINY " + tag + "x%d rseed %d" % (tile[1], rseed)
         try:
             if FAST:
                 K = int(rng.integers(33, 257))
@@ -103,7 +110,7 @@ def run(budget=300.0, seed=1, mode="std", max_cases=None, log=print):
                 continue
             oq = oracle_lib.OracleQuantizer(kind, img, seed=rseed)
             oq.prescan(K)
-            want_pal = oq.pnnquan(K)
+            want_pal = oq.pnnquan(K)          # (a throw of the oracle is not caught here: it ends the sweep)
             gq = (nq.PnnLABQuantizer if kind else nq.PnnQuantizer)(img, mode=nq.MODE_PARALLEL_TILED, seed=rseed, tile=tile)
             got_pal = gq.pnnquan(K)
             n_cases += 1
@@ -129,8 +136,16 @@ def run(budget=300.0, seed=1, mode="std", max_cases=None, log=print):
                 n_bad += 1; print("NEAREST MISMATCH:", tag, flush=True)
             if (gq.closestTuple(got_pal, cols) != oq.closest_tuple(want_pal, cols)).any():
                 n_bad += 1; print("CLOSEST MISMATCH:", tag, flush=True)
+            if TINY and n_cases % 2 == 0:
+                oq = oracle_lib.OracleQuantizer(kind, img, seed=rseed)
+                want_argb, want_idx, want_pal = oq.convert(K, dither)
+                gq = (nq.PnnLABQuantizer if kind else nq.PnnQuantizer)(img, mode=nq.MODE_REFERENCE_SEQUENTIAL, seed=rseed)
+                out = gq.convert(K, dither)
+                if len(out.palette) != len(want_pal) or (out.palette != want_pal).any() or (out.argb != want_argb).any() \
+                        or (out.index.astype(np.int32) != want_idx).any():
+                    n_bad += 1; print("SEQ CONVERT MISMATCH:", tag, flush=True)
         except nq.NqError as e:
-            if e.status in (-3, -4):       # UNSUPPORTED / REFERENCE_THROWS are legitimate outcomes
+            if e.status in (-3, -4) and not TINY:       # UNSUPPORTED / REFERENCE_THROWS are legitimate outcomes (tiny: the oracle did not throw)
                 continue
             n_bad += 1; print("ERROR:", e, tag, flush=True)
         if n_cases % 25 == 0:

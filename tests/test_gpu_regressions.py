@@ -131,3 +131,23 @@ def test_merge_time_limit_has_its_own_status_and_leaves_the_handle_usable(nq):
     q.set_option(3, 0)                                  # automatic again
     pal = q.pnnquan(256)
     assert len(pal) == len(want["palette"]) and (pal == want["palette"]).all()
+
+
+def test_last_band_lower_than_an_explicit_tile_keeps_the_image_tile_numbers(nq, oracle):
+    """csrc/nq_abi.cpp dither_device: a tile set with nq_set_tile was clamped to the BAND's height before the band's first tile number
+    (tile_base = band origin / tile height x tiles per row) was computed.  A last band lower than the tile -- 64x65, bands every 64
+    rows, 8x8 tiles: one row -- then took tile_base 64 / 1 x 8 = 512 instead of 64 / 8 x 8 = 64, so its tiles drew from the random
+    streams of tiles 512.. and 10 of its 64 pixels differed from the whole-image dither.  The automatic tile already followed the whole
+    image.  Found by tests/test_gpu_tiny_geometry.py."""
+    import test_gpu_banded as tb
+    img = synth.gradient_noise(64, 65, 666)
+    seed, K, tile = 77, 256, (8, 8)
+    oq = oracle.OracleQuantizer(1, img, seed=seed)
+    oq.set_bands([0, 64])
+    oq.prescan(K)
+    want_pal = oq.pnnquan(K)
+    want_argb, want_idx = oq.dither(want_pal, True, tile=tile)
+    pal, argb, idx, _ = tb._bands_by_hand(nq, img, 1, K, True, [0, 64], seed, tile)
+    assert (pal == want_pal).all()
+    assert (idx[:64].astype(np.int32) == want_idx[:64]).all() and (argb[:64] == want_argb[:64]).all()
+    assert (idx[64].astype(np.int32) == want_idx[64]).all() and (argb[64] == want_argb[64]).all(), "the one-row band"
