@@ -471,6 +471,47 @@ int nq_hold_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, ui
 int nq_hold_frames(nq_handle* h, int n, const uint32_t* const* argb, uint16_t* const* index, uint32_t* const* out_argb,
                    int width, int height, int threshold, int64_t* out_held);
 
+/* ---- shot detection: where an animation needs a new palette, i.e. the shot_starts the local-colour-table encoders above are fed
+ *      (palette per shot).  The measure is on the COLOUR DISTRIBUTION of a frame, not on pixel positions: a pan over one scene keeps
+ *      its palette.  All frames are width x height, ARGB_8888.
+ *  * Signature of a frame: sig[c][v] = the number of pixels whose channel c has the value v; c = 0..3 for a, r, g, b (shifts 24, 16,
+ *    8, 0), v = 0..255: NQ_SIG_WORDS = 1024 uint32 counts per frame, sig[256 c + v].  Channels are counted as stored (a pixel with
+ *    alpha 0 still contributes its r, g, b); every row sig[c][.] sums to npix = width * height.
+ *  * Score of two signatures A, B (per mille, 0..1000), all arithmetic in int64:
+ *        E_c   = sum over v = 0..254 of | sum over t <= v of (A[c][t] - B[c][t]) |      the 1-D earth mover's distance, <= 255 npix
+ *        score = floor(1000 * max_c E_c / (255 * npix))
+ *    It is graded: a brightness shift of d levels scores d / 255.
+ *  * Rule (an anchor, as in the temporal hold: it moves only when a shot ends):
+ *        A = 0; starts = {0}; scores[0] = 0
+ *        for i = 1 .. n-1:
+ *            scores[i] = score(sig[i], sig[A])
+ *            if scores[i] > threshold_pm and i - A >= min_shot: starts += {i}; A = i
+ *    scores[i] is the value measured against the anchor in force BEFORE the decision.  Comparing with the shot's first frame makes a
+ *    slow drift accumulate until it is taken as a cut; a cut suppressed by min_shot is taken late, when min_shot is reached, not lost.
+ *    threshold_pm is 0..1000 (1000 never cuts), min_shot >= 1.
+ *  * nq_frame_signatures_device: the frames in DEVICE memory, d_argb a host array of n device pointers (4-byte aligned; when every
+ *    one is 16-byte aligned the kernel reads 16 bytes per access, same results); the frames are never written.  out_sig (HOST memory,
+ *    n * NQ_SIG_WORDS words) is filled when the call returns.  nq_frame_signatures: the same with HOST frames (uploaded first).
+ *    h may be a handle of either kind: its stream, scratch and error text are used, its params are neither read nor changed.
+ *  * nq_shots_from_signatures: the rule above over n signatures of frames with npix pixels -- pure host arithmetic, no device and no
+ *    handle.  out_starts (room for n entries) receives the shot starts, *out_n_shots how many there are, out_scores (n entries, or
+ *    NULL: not wanted) the scores.  NQ_ERR_INVALID, outputs untouched: sig, out_starts or out_n_shots NULL, n < 1, npix outside
+ *    1 .. 2^31 - 1, threshold_pm outside 0..1000, min_shot < 1, a row of a signature that does not sum to npix.
+ *  * nq_detect_shots_device / nq_detect_shots: the signatures call followed by nq_shots_from_signatures; n = 1 gives starts = {0}.
+ *  * NQ_ERR_INVALID before any device work, outputs untouched: n < 1, a side outside 1..65535, n * width * height above 2^31 - 1, a
+ *    NULL pointer array or entry, an ARGB pointer that is not 4-byte aligned, threshold_pm outside 0..1000, min_shot < 1, NULL
+ *    out_starts, out_n_shots or out_sig.  The handle stays usable after any of these.
+ *  The kernel: DESIGN.md 5b "Shot detection". ---- */
+#define NQ_SIG_WORDS 1024
+int nq_frame_signatures_device(nq_handle* h, int n, const uint32_t* const* d_argb, int width, int height, uint32_t* out_sig);
+int nq_frame_signatures(nq_handle* h, int n, const uint32_t* const* argb, int width, int height, uint32_t* out_sig);
+int nq_shots_from_signatures(const uint32_t* sig, int n, int64_t npix, int threshold_pm, int min_shot,
+                             int32_t* out_starts, int32_t* out_n_shots, int32_t* out_scores);
+int nq_detect_shots_device(nq_handle* h, int n, const uint32_t* const* d_argb, int width, int height, int threshold_pm, int min_shot,
+                           int32_t* out_starts, int32_t* out_n_shots, int32_t* out_scores);
+int nq_detect_shots(nq_handle* h, int n, const uint32_t* const* argb, int width, int height, int threshold_pm, int min_shot,
+                    int32_t* out_starts, int32_t* out_n_shots, int32_t* out_scores);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

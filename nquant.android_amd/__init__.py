@@ -8,12 +8,13 @@ from .host import (NQ_KIND_RGB, NQ_KIND_LAB, MODE_REFERENCE_SEQUENTIAL, MODE_PAR
                    NqError, Params, PnnQuantizer, PnnLABQuantizer, QuantizedImage, load_library, library_path,
                    abi_symbols, convert_batch_device, convert_batch_host, convert_frames, convert_frames_device,
                    pnnquan_frames_device)
-from .gif import (convert_frames_to_gif, convert_shots_to_gif, encode_gif, encode_gif_delta, encode_gif_delta_device, encode_gif_device,
+from .gif import (convert_clip_to_gif, convert_frames_to_gif, convert_shots_to_gif, encode_gif, encode_gif_delta, encode_gif_delta_device, encode_gif_device,
                   encode_gif_local, encode_gif_local_delta, encode_gif_local_delta_device, encode_gif_local_device, gif_local_max_bytes,
                   gif_max_bytes, write_gif)
 from .png import convert_to_png, encode_png, encode_png_device, png_max_bytes, write_png
 from .apng import apng_max_bytes, convert_frames_to_apng, encode_apng, encode_apng_device, write_apng
 from .hold import hold_frames, hold_frames_device
+from .shots import detect_shots, detect_shots_device, frame_signatures, frame_signatures_device, shots_from_signatures
 from .build import build as build_library
 
 __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARALLEL_TILED", "MODE_LOOKUP_ONLY",
@@ -23,4 +24,5 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "encode_gif_delta", "encode_gif_delta_device", "gif_max_bytes", "gif_local_max_bytes", "encode_gif_local", "encode_gif_local_device",
            "encode_gif_local_delta", "encode_gif_local_delta_device", "convert_shots_to_gif", "encode_png", "encode_png_device", "write_png",
            "convert_to_png", "png_max_bytes", "apng_max_bytes", "encode_apng", "encode_apng_device", "write_apng",
-           "convert_frames_to_apng", "hold_frames", "hold_frames_device"]
+           "convert_frames_to_apng", "hold_frames", "hold_frames_device", "frame_signatures", "frame_signatures_device",
+           "shots_from_signatures", "detect_shots", "detect_shots_device", "convert_clip_to_gif"]

@@ -248,6 +248,12 @@ struct nq_handle {
     std::vector<void*> h_hold_ptrs;
     DevBuf<void*> hold_ptrs;
     DevBuf<unsigned long long> hold_held;
+    // nq_frame_signatures_device: the table of frame pointers (the host copy stays alive for the asynchronous upload) and the n * 1024
+    // counters; nq_frame_signatures stages its frames in d_in; nq_detect_shots*: the signatures on the host
+    std::vector<const uint32_t*> h_sig_ptrs;
+    DevBuf<const uint32_t*> sig_ptrs;
+    DevBuf<uint32_t> d_sig;
+    std::vector<uint32_t> h_sig;
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
@@ -2885,6 +2891,155 @@ int nq_hold_frames(nq_handle* h, int n, const uint32_t* const* argb, uint16_t* c
         NQ_HIP(h, hipStreamSynchronize(h->stream));
         return NQ_OK;
     });
+}
+
+} // extern "C"
+
+// ---- shot detection (nq_shots.hip) ----
+namespace {
+
+// the frames of every form, from the host arrays alone (no device work)
+int sig_check(nq_handle* h, int n, const uint32_t* const* argb, int width, int height) {
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    if (width < 1 || width > 65535 || height < 1 || height > 65535) NQ_FAIL(h, NQ_ERR_INVALID, "%d x %d: sides must be 1..65535", width, height);
+    if ((long long) n * width * height > 2147483647ll)
+        NQ_FAIL(h, NQ_ERR_INVALID, "%d frames of %d x %d: more than 2^31 - 1 pixels", n, width, height);
+    if (!argb) NQ_FAIL(h, NQ_ERR_INVALID, "the array of frame pointers is NULL");
+    for (int i = 0; i < n; ++i)
+        if (!argb[i] || ((uintptr_t) argb[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: pixel pointer NULL or not 4-byte aligned", i);
+    return NQ_OK;
+}
+
+// what the rule takes besides the signatures; false + the reason otherwise
+bool shots_check_rule(int threshold_pm, int min_shot, const int32_t* out_starts, const int32_t* out_n_shots, char* why, size_t len) {
+    if (threshold_pm < 0 || threshold_pm > 1000) { std::snprintf(why, len, "threshold_pm = %d: must be 0..1000", threshold_pm); return false; }
+    if (min_shot < 1) { std::snprintf(why, len, "min_shot = %d: must be at least 1", min_shot); return false; }
+    if (!out_starts || !out_n_shots) { std::snprintf(why, len, "out_starts / out_n_shots is NULL"); return false; }
+    return true;
+}
+
+// floor(1000 max_c E_c / (255 npix)), E_c the 1-D earth mover's distance of channel c's histograms (include/nquant_abi.h)
+int shots_score(const uint32_t* a, const uint32_t* b, int64_t npix) {
+    int64_t worst = 0;
+    for (int c = 0; c < 4; ++c) {
+        int64_t cum = 0, e = 0;
+        for (int v = 0; v < 255; ++v) {
+            cum += (int64_t) a[c * 256 + v] - (int64_t) b[c * 256 + v];
+            e += cum < 0 ? -cum : cum;
+        }
+        worst = std::max(worst, e);
+    }
+    return (int) (1000 * worst / (255 * npix));
+}
+
+// nq_shots_from_signatures: every check first, so that a rejected call has written nothing
+int shots_rule(const uint32_t* sig, int n, int64_t npix, int threshold_pm, int min_shot, int32_t* out_starts, int32_t* out_n_shots,
+               int32_t* out_scores, char* why, size_t len) {
+    if (!shots_check_rule(threshold_pm, min_shot, out_starts, out_n_shots, why, len)) return NQ_ERR_INVALID;
+    if (!sig) { std::snprintf(why, len, "sig is NULL"); return NQ_ERR_INVALID; }
+    if (n < 1) { std::snprintf(why, len, "n = %d: at least one frame", n); return NQ_ERR_INVALID; }
+    if (npix < 1 || npix > 2147483647ll) { std::snprintf(why, len, "npix = %lld: must be 1 .. 2^31 - 1", (long long) npix); return NQ_ERR_INVALID; }
+    for (int i = 0; i < n; ++i)
+        for (int c = 0; c < 4; ++c) {
+            int64_t sum = 0;
+            for (int v = 0; v < 256; ++v) sum += sig[(size_t) i * NQ_SIG_WORDS + c * 256 + v];
+            if (sum != npix) {
+                std::snprintf(why, len, "frame %d: channel %d of the signature sums to %lld, not to npix = %lld", i, c, (long long) sum, (long long) npix);
+                return NQ_ERR_INVALID;
+            }
+        }
+    int anchor = 0, shots = 1;
+    out_starts[0] = 0;
+    if (out_scores) out_scores[0] = 0;
+    for (int i = 1; i < n; ++i) {
+        const int score = shots_score(sig + (size_t) i * NQ_SIG_WORDS, sig + (size_t) anchor * NQ_SIG_WORDS, npix);
+        if (out_scores) out_scores[i] = score;
+        if (score > threshold_pm && i - anchor >= min_shot) { out_starts[shots++] = i; anchor = i; }
+    }
+    *out_n_shots = shots;
+    return NQ_OK;
+}
+
+// nq_frame_signatures_device after the checks: the pointer table goes up, one launch counts the whole sequence, the counters come back
+int signatures_device(nq_handle* h, int n, const uint32_t* const* d_argb, int width, int height, uint32_t* out_sig) {
+    std::vector<const uint32_t*>& t = h->h_sig_ptrs;
+    t.assign(d_argb, d_argb + n);
+    bool vec = true;                                // the 16-byte path needs every frame aligned to it
+    for (int i = 0; i < n; ++i) vec = vec && !((uintptr_t) d_argb[i] & 15);
+    const size_t words = (size_t) n * NQ_SIG_WORDS;
+    NQ_HIP(h, h->sig_ptrs.reserve(n));
+    NQ_HIP(h, h->d_sig.reserve(words));
+    NQ_HIP(h, hipMemcpyAsync(h->sig_ptrs.p, t.data(), n * sizeof(uint32_t*), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemsetAsync(h->d_sig.p, 0, words * sizeof(uint32_t), h->stream));
+    launch_signatures(reinterpret_cast<const unsigned* const*>(h->sig_ptrs.p), n, (long long) width * height, vec, h->n_cus, h->d_sig.p, h->stream);
+    NQ_HIP(h, launch_status());
+    NQ_HIP(h, hipMemcpyAsync(out_sig, h->d_sig.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    return NQ_OK;
+}
+
+// nq_frame_signatures after the checks: the frames lie `pitch` elements apart in d_in, so that every one starts 16-byte aligned
+int signatures_host(nq_handle* h, int n, const uint32_t* const* argb, int width, int height, uint32_t* out_sig) {
+    const size_t px = (size_t) width * height, pitch = (px + 3) & ~(size_t) 3;
+    return host_form(h, [&]() -> int {
+        NQ_HIP(h, h->d_in.reserve(n * pitch));
+        std::vector<const uint32_t*> d_src(n);
+        for (int i = 0; i < n; ++i) {
+            d_src[i] = h->d_in.p + i * pitch;
+            NQ_HIP(h, hipMemcpyAsync(h->d_in.p + i * pitch, argb[i], px * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        }
+        return signatures_device(h, n, d_src.data(), width, height, out_sig);
+    });
+}
+
+// both forms of nq_frame_signatures / nq_detect_shots (out_sig null: detect, the signatures stay in the handle)
+int shots_call(nq_handle* h, bool host, bool detect, int n, const uint32_t* const* argb, int width, int height, uint32_t* out_sig,
+               int threshold_pm, int min_shot, int32_t* out_starts, int32_t* out_n_shots, int32_t* out_scores) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = sig_check(h, n, argb, width, height);
+    if (rc) return rc;
+    char why[256];
+    if (detect && !shots_check_rule(threshold_pm, min_shot, out_starts, out_n_shots, why, sizeof why)) NQ_FAIL(h, NQ_ERR_INVALID, "%s", why);
+    if (!detect && !out_sig) NQ_FAIL(h, NQ_ERR_INVALID, "out_sig is NULL");
+    rc = use_device(h);
+    if (rc) return rc;
+    if (detect) {
+        h->h_sig.resize((size_t) n * NQ_SIG_WORDS);
+        out_sig = h->h_sig.data();
+    }
+    rc = host ? signatures_host(h, n, argb, width, height, out_sig) : signatures_device(h, n, argb, width, height, out_sig);
+    if (rc || !detect) return rc;
+    rc = shots_rule(out_sig, n, (int64_t) width * height, threshold_pm, min_shot, out_starts, out_n_shots, out_scores, why, sizeof why);
+    if (rc) NQ_FAIL(h, rc, "%s", why);
+    return NQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_frame_signatures_device(nq_handle* h, int n, const uint32_t* const* d_argb, int width, int height, uint32_t* out_sig) {
+    return shots_call(h, false, false, n, d_argb, width, height, out_sig, 0, 1, nullptr, nullptr, nullptr);
+}
+
+int nq_frame_signatures(nq_handle* h, int n, const uint32_t* const* argb, int width, int height, uint32_t* out_sig) {
+    return shots_call(h, true, false, n, argb, width, height, out_sig, 0, 1, nullptr, nullptr, nullptr);
+}
+
+int nq_shots_from_signatures(const uint32_t* sig, int n, int64_t npix, int threshold_pm, int min_shot, int32_t* out_starts,
+                             int32_t* out_n_shots, int32_t* out_scores) {
+    char why[256];
+    return shots_rule(sig, n, npix, threshold_pm, min_shot, out_starts, out_n_shots, out_scores, why, sizeof why);
+}
+
+int nq_detect_shots_device(nq_handle* h, int n, const uint32_t* const* d_argb, int width, int height, int threshold_pm, int min_shot,
+                           int32_t* out_starts, int32_t* out_n_shots, int32_t* out_scores) {
+    return shots_call(h, false, true, n, d_argb, width, height, nullptr, threshold_pm, min_shot, out_starts, out_n_shots, out_scores);
+}
+
+int nq_detect_shots(nq_handle* h, int n, const uint32_t* const* argb, int width, int height, int threshold_pm, int min_shot,
+                    int32_t* out_starts, int32_t* out_n_shots, int32_t* out_scores) {
+    return shots_call(h, true, true, n, argb, width, height, nullptr, threshold_pm, min_shot, out_starts, out_n_shots, out_scores);
 }
 
 } // extern "C"

@@ -288,4 +288,10 @@ void launch_png_gather(const PngImage* d_images, int n_images, const unsigned* d
 void launch_hold(const unsigned* const* d_src, unsigned short* const* d_idx, unsigned* const* d_out, int n, long long npix, int threshold,
                  bool vec, unsigned long long* d_held, hipStream_t s);
 
+// ---- shot detection (nq_shots.hip): d_frames is a device array of n frame pointers (npix ARGB pixels per frame, never written), d_sig
+// n * 1024 counters the caller zeroed: d_sig[1024 i + 256 c + v] += pixels of frame i whose channel c (a, r, g, b) is v, in one launch.
+// vec: the 16-byte path -- the caller has checked that EVERY frame pointer is 16-byte aligned; otherwise one pixel per access (4-byte
+// alignment).  cus: compute units of the device (sizes the grid). ----
+void launch_signatures(const unsigned* const* d_frames, int n, long long npix, bool vec, int cus, unsigned* d_sig, hipStream_t s);
+
 } // namespace nq

@@ -10,7 +10,7 @@ LZW chains may write a palette colour within `lossy` per channel of a pixel's ow
 which is what shrinks dithered content; 0 calls the lossless entry points.
 Local colour tables (the nq_encode_gif_local* calls, "GIF encoding, local colour tables"): one palette per frame, so an animation is not
 tied to 256 colours for its whole length.  The practical unit is the shot: convert_shots_to_gif gives every shot its own palette, and
-delta mode there compares the colours shown, not the indices.
+delta mode there compares the colours shown, not the indices; convert_clip_to_gif finds the shots itself (shots.py).
 There is no CPU fallback: without a HIP device every call raises NqError with status -5 (NQ_ERR_NO_DEVICE)."""
 import ctypes as C
 
@@ -305,7 +305,7 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
     (shot_starts=range(n): one palette per frame), then encode_gif_local_delta (delta=False: encode_gif_local) writes all frames, each
     with its shot's palette as its local colour table.  hold (delta=True only) runs per shot and never across a cut: a held index means
     nothing under another table.  seeds, tile, lossy as for convert_frames_to_gif.  Everything runs on one handle.  Cuts are the
-    caller's to find.  Returns (file bytes, list of per-shot palettes)."""
+    caller's to give here; convert_clip_to_gif finds them.  Returns (file bytes, list of per-shot palettes)."""
     lossy = _lossy_keyword(lossy)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
@@ -317,32 +317,69 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
     if seeds is not None and len(list(seeds)) != len(frames):
         raise ValueError("one seed per frame")
     if hold is not None:
-        from .hold import _hold_host, _threshold
+        from .hold import _threshold
         hold = _threshold(hold)
     frames, q = _frames_quantizer(kind, frames, device, mode, tile)
     try:
-        maps, palettes = [], []
-        for a, b in shots:
-            palette, outs = _convert_frames_on(q, frames[a:b], nMaxColors, dither, mode, None if seeds is None else list(seeds)[a:b])
-            shot_maps = [o.index for o in outs]
-            if hold is not None:
-                _hold_host(q._L, q._h, q._check, frames[a:b], shot_maps, None, hold)
-            maps += shot_maps
-            palettes.append(palette)
-        per_frame = [palettes[k] for k, (a, b) in enumerate(shots) for _ in range(a, b)]
-        ptrs = [m.ctypes.data for m in maps]
-        if delta:
-            height, width = _one_size(maps)
-            data, _ = _encode_local(q._L, q._h, "nq_encode_gif_local_delta", ptrs, width, height, per_frame, delays_cs, loop, segment_pixels,
-                                    lossy, q._check, True)
-        else:
-            w = np.array([m.shape[1] for m in maps], np.int32)
-            h = np.array([m.shape[0] for m in maps], np.int32)
-            data, _ = _encode_local(q._L, q._h, "nq_encode_gif_local", ptrs, w, h, per_frame, delays_cs, loop, segment_pixels, lossy,
-                                    q._check, False)
+        return _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta)
     finally:
         q.close()
+
+
+def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta):
+    """convert_shots_to_gif after its checks, on the handle of quantizer `q`, which stays open: `frames` int32 arrays, `shots` the
+    (first frame, one past the last) pairs, hold a checked threshold or None."""
+    if hold is not None:
+        from .hold import _hold_host
+    maps, palettes = [], []
+    for a, b in shots:
+        palette, outs = _convert_frames_on(q, frames[a:b], nMaxColors, dither, mode, None if seeds is None else list(seeds)[a:b])
+        shot_maps = [o.index for o in outs]
+        if hold is not None:
+            _hold_host(q._L, q._h, q._check, frames[a:b], shot_maps, None, hold)
+        maps += shot_maps
+        palettes.append(palette)
+    per_frame = [palettes[k] for k, (a, b) in enumerate(shots) for _ in range(a, b)]
+    ptrs = [m.ctypes.data for m in maps]
+    if delta:
+        height, width = _one_size(maps)
+        data, _ = _encode_local(q._L, q._h, "nq_encode_gif_local_delta", ptrs, width, height, per_frame, delays_cs, loop, segment_pixels,
+                                lossy, q._check, True)
+    else:
+        w = np.array([m.shape[1] for m in maps], np.int32)
+        h = np.array([m.shape[0] for m in maps], np.int32)
+        data, _ = _encode_local(q._L, q._h, "nq_encode_gif_local", ptrs, w, h, per_frame, delays_cs, loop, segment_pixels, lossy,
+                                q._check, False)
     return data, palettes
+
+
+def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, delays_cs=None, loop=0, segment_pixels=0, device=0,
+                        mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, delta=True):
+    """A list of frames in, an animation out: detect_shots (shots.py; cut in per mille, min_shot in frames) finds where the clip needs
+    a new palette, then exactly convert_shots_to_gif with those starts -- both on one handle.  The frames must have one size (delta or
+    not: a signature is compared between frames of one size).  Keywords otherwise as for convert_shots_to_gif.
+    Returns (file bytes, list of per-shot palettes, shot_starts)."""
+    lossy = _lossy_keyword(lossy)
+    if not 1 <= int(nMaxColors) <= 256:
+        raise ValueError("a GIF colour table holds at most 256 entries")
+    if hold is not None and not delta:
+        raise ValueError("hold needs delta=True: full frames store every pixel whether it repeats or not")
+    if len({np.asarray(f).shape for f in frames}) > 1:
+        raise ValueError("shot detection: all frames must have one size")
+    if seeds is not None and len(list(seeds)) != len(frames):
+        raise ValueError("one seed per frame")
+    if hold is not None:
+        from .hold import _threshold
+        hold = _threshold(hold)
+    from .shots import _detect_host
+    frames, q = _frames_quantizer(kind, frames, device, mode, tile)
+    try:
+        starts, _ = _detect_host(q._L, q._h, q._check, frames, cut, min_shot)
+        data, palettes = _shots_to_gif_on(q, frames, _shots(starts, len(frames)), nMaxColors, dither, delays_cs, loop, segment_pixels, mode,
+                                          seeds, hold, lossy, delta)
+    finally:
+        q.close()
+    return data, palettes, starts
 
 
 def _lossy_keyword(lossy):

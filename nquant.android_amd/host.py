@@ -105,6 +105,11 @@ _ABI = {
     "nq_encode_apng": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i64, _pi64, _vp]),
     "nq_hold_frames_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "nq_hold_frames": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "nq_frame_signatures_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp]),
+    "nq_frame_signatures": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp]),
+    "nq_shots_from_signatures": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "nq_detect_shots_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "nq_detect_shots": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
 
