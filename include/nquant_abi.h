@@ -512,6 +512,63 @@ int nq_detect_shots_device(nq_handle* h, int n, const uint32_t* const* d_argb, i
 int nq_detect_shots(nq_handle* h, int n, const uint32_t* const* argb, int width, int height, int threshold_pm, int min_shot,
                     int32_t* out_starts, int32_t* out_n_shots, int32_t* out_scores);
 
+/* ---- palette refinement: k-means (Lloyd) passes over a palette, and the squared error of a palette against the pixels.  The PNN
+ *      merge loop stops at a greedy merge; a few passes of "assign every pixel to its nearest entry, move every entry to the mean of
+ *      its pixels" lower the error further.  Opt-in: no other entry point's results change.  All arithmetic is integer.
+ *  * Inputs: n ARGB_8888 frames, each with its own width and height (as for nq_pnnquan_frames_device); a palette of K entries (1..256)
+ *    in HOST memory, read and written; iterations in 0..64.
+ *  * The channels of a colour are a, r, g, b (shifts 24, 16, 8, 0).  A pixel with a = 0 is NOT COUNTED: it takes part in nothing.  A
+ *    palette entry with a = 0 is PINNED: no pixel is assigned to it and it never changes.  An entry that is not pinned is LIVE.  With
+ *    no live entry, no pixel is counted.
+ *  * d(p, c) = da^2 + dr^2 + dg^2 + db^2.  A counted pixel is assigned to the live entry with the smallest d; on a tie to the lowest
+ *    index.
+ *  * Passes:
+ *        P_0 = the palette as given
+ *        for j = 0 .. iterations:
+ *            assignment pass under P_j:
+ *                cnt[k]   = pixels assigned to k
+ *                sum_c[k] = sum of their channel c, c in {r, g, b}
+ *                sse[j]   = sum over the counted pixels of d(p, its entry)
+ *            if j == iterations: stop
+ *            update: for every live k with cnt[k] > 0 and c in {r, g, b}:
+ *                        P_{j+1}[k].c = floor((2 * sum_c[k] + cnt[k]) / (2 * cnt[k]))          (the mean, half rounds up)
+ *                    the alpha of an entry NEVER changes; empty and pinned entries stay as they are
+ *            if P_{j+1} == P_j: sse[j+1 .. iterations] = sse[j]; stop
+ *  * Outputs: io_palette = the last palette; out_sse: iterations + 1 values; out_counts: K values or NULL, cnt[] of the last
+ *    assignment pass that ran; *out_passes: the number of assignment passes that ran.
+ *  * iterations = 0 is a pure error measurement.  sse is non-increasing, exactly: the rounded mean is the integer minimiser of a
+ *    cluster's squared error per channel, and re-assignment cannot raise the error.  Alpha is part of the distance, so pixels pick
+ *    entries of like alpha; it is not part of the update, so an opaque palette stays opaque.  Integer sums make the result
+ *    independent of the order of the additions: it is deterministic.  The metric is plain ARGB for both kinds of handle.
+ *  * Limits: the sequence holds at most 2^31 - 1 pixels, so every per-entry sum is at most 255 * 2^31 and sse at most 260 100 * 2^31.
+ *  * nq_refine_palette_device: the frames in DEVICE memory, d_argb a host array of n device pointers (4-byte aligned; when every one
+ *    is 16-byte aligned the kernel reads 16 bytes per access, same results); the frames are never written.  nq_refine_palette: the
+ *    same with HOST frames (uploaded first, each on a 16-byte boundary).  h may be a handle of either kind: its stream, scratch and
+ *    error text are used, its params are neither read nor changed.
+ *  * NQ_ERR_INVALID before any device work, every output untouched, the handle still usable: n < 1, a side outside 1..65535, more
+ *    than 2^31 - 1 pixels in total, K outside 1..256, iterations outside 0..64, a NULL pointer array, a NULL entry, NULL io_palette,
+ *    out_sse or out_passes, a frame pointer that is not 4-byte aligned.
+ *  * nq_convert_frames_refined_device / nq_convert_frames_refined: nq_convert_frames[_device] with `refine` update passes between the
+ *    palette and the dither: palette and params are nq_pnnquan_frames_device's, then the palette takes `refine` iterations of the
+ *    passes above over the same frames, then every frame is dithered with the refined palette exactly as nq_convert_frames_device
+ *    does it.  refine = 0 gives nq_convert_frames[_device]'s results in every output, bit for bit.  refine outside 0..64, and
+ *    refine > 0 with nMaxColors > 256 or with a frame pointer that is not 4-byte aligned, are NQ_ERR_INVALID.
+ *  The kernel: DESIGN.md 5d "Palette refinement". ---- */
+int nq_refine_palette_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             uint32_t* io_palette, int K, int iterations,
+                             int64_t* out_sse, int64_t* out_counts, int32_t* out_passes);
+int nq_refine_palette(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                      uint32_t* io_palette, int K, int iterations,
+                      int64_t* out_sse, int64_t* out_counts, int32_t* out_passes);
+int nq_convert_frames_refined_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                                     int nMaxColors, int refine, int dither, const int64_t* rng_seeds, int mode,
+                                     uint32_t* const* d_out_argb, uint16_t* const* d_out_index,
+                                     uint32_t* out_palette, int32_t* out_K);
+int nq_convert_frames_refined(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                              int nMaxColors, int refine, int dither, const int64_t* rng_seeds, int mode,
+                              uint32_t* const* out_argb, uint16_t* const* out_index,
+                              uint32_t* out_palette, int32_t* out_K);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

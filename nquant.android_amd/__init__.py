@@ -15,6 +15,7 @@ from .png import convert_to_png, encode_png, encode_png_device, png_max_bytes, w
 from .apng import apng_max_bytes, convert_frames_to_apng, encode_apng, encode_apng_device, write_apng
 from .hold import hold_frames, hold_frames_device
 from .shots import detect_shots, detect_shots_device, frame_signatures, frame_signatures_device, shots_from_signatures
+from .refine import convert_frames_refined, palette_error, refine_palette, refine_palette_device
 from .build import build as build_library
 
 __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARALLEL_TILED", "MODE_LOOKUP_ONLY",
@@ -25,4 +26,5 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "encode_gif_local_delta", "encode_gif_local_delta_device", "convert_shots_to_gif", "encode_png", "encode_png_device", "write_png",
            "convert_to_png", "png_max_bytes", "apng_max_bytes", "encode_apng", "encode_apng_device", "write_apng",
            "convert_frames_to_apng", "hold_frames", "hold_frames_device", "frame_signatures", "frame_signatures_device",
-           "shots_from_signatures", "detect_shots", "detect_shots_device", "convert_clip_to_gif"]
+           "shots_from_signatures", "detect_shots", "detect_shots_device", "convert_clip_to_gif", "refine_palette",
+           "refine_palette_device", "palette_error", "convert_frames_refined"]

@@ -25,6 +25,7 @@ UNITS = {
     "nq_png.hip": ("device", ["nq_png.hip", "nq_kernels.h"]),
     "nq_hold.hip": ("device", ["nq_hold.hip", "nq_kernels.h"]),
     "nq_shots.hip": ("device", ["nq_shots.hip", "nq_kernels.h"]),
+    "nq_refine.hip": ("device", ["nq_refine.hip", "nq_kernels.h"]),
     "nq_abi.cpp": ("host", ["nq_abi.cpp", "nq_kernels.h", os.path.join(INC, "nquant_abi.h")]),
 }
 

@@ -254,6 +254,12 @@ struct nq_handle {
     DevBuf<const uint32_t*> sig_ptrs;
     DevBuf<uint32_t> d_sig;
     std::vector<uint32_t> h_sig;
+    // nq_refine_palette_device: the frame table and the call's state words (REFINE_* of nq_kernels.h; the host copies stay alive for the
+    // asynchronous copies); nq_refine_palette stages its frames in d_in
+    std::vector<nq::RefineFrame> h_refine_frames;
+    DevBuf<nq::RefineFrame> d_refine_frames;
+    std::vector<unsigned long long> h_refine;
+    DevBuf<unsigned long long> d_refine;
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
@@ -1133,6 +1139,90 @@ int host_images(nq_handle* h, int n, const size_t* px, const uint32_t* const* ar
     });
 }
 
+// ---- palette refinement (nq_refine.hip) ----
+// the arguments of every form, from the host arrays alone (no device work): the sizes first, then the pointers
+int refine_check(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights, const uint32_t* io_palette,
+                 int K, int iterations, const int64_t* out_sse, const int32_t* out_passes, int64_t* out_total) {
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    if (K < 1 || K > 256) NQ_FAIL(h, NQ_ERR_INVALID, "K = %d: must be 1..256", K);
+    if (iterations < 0 || iterations > 64) NQ_FAIL(h, NQ_ERR_INVALID, "iterations = %d: must be 0..64", iterations);
+    if (!argb || !widths || !heights) NQ_FAIL(h, NQ_ERR_INVALID, "the array of frame pointers, widths or heights is NULL");
+    if (!io_palette || !out_sse || !out_passes) NQ_FAIL(h, NQ_ERR_INVALID, "io_palette, out_sse or out_passes is NULL");
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (widths[i] < 1 || widths[i] > 65535 || heights[i] < 1 || heights[i] > 65535)
+            NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: %d x %d: sides must be 1..65535", i, widths[i], heights[i]);
+        total += (int64_t) widths[i] * heights[i];
+        if (total > 2147483647ll) NQ_FAIL(h, NQ_ERR_INVALID, "the sequence holds more than 2^31 - 1 pixels (frame %d)", i);
+    }
+    for (int i = 0; i < n; ++i)
+        if (!argb[i] || ((uintptr_t) argb[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: pixel pointer NULL or not 4-byte aligned", i);
+    *out_total = total;
+    return NQ_OK;
+}
+
+// nq_refine_palette_device after the checks: frame table and state go up, all passes are enqueued, the results come back in one copy
+int refine_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights, int64_t total,
+                  uint32_t* io_palette, int K, int iterations, int64_t* out_sse, int64_t* out_counts, int32_t* out_passes) {
+    std::vector<nq::RefineFrame>& t = h->h_refine_frames;
+    t.resize(n);
+    bool vec = true;                                // the 16-byte path needs every frame aligned to it
+    for (int i = 0; i < n; ++i) {
+        t[i] = {reinterpret_cast<const unsigned*>(d_argb[i]), (long long) widths[i] * heights[i]};
+        vec = vec && !((uintptr_t) d_argb[i] & 15);
+    }
+    std::vector<unsigned long long>& st = h->h_refine;
+    st.assign(nq::REFINE_STATE_WORDS, 0ull);
+    std::memcpy(st.data() + nq::REFINE_PALETTE, io_palette, (size_t) K * sizeof(uint32_t));
+    NQ_HIP(h, h->d_refine_frames.reserve(n));
+    NQ_HIP(h, h->d_refine.reserve(nq::REFINE_STATE_WORDS));
+    NQ_HIP(h, hipMemcpyAsync(h->d_refine_frames.p, t.data(), n * sizeof(nq::RefineFrame), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemcpyAsync(h->d_refine.p, st.data(), st.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
+    launch_refine(h->d_refine_frames.p, n, (long long) total, vec, h->n_cus, K, iterations, h->d_refine.p, h->stream);
+    NQ_HIP(h, launch_status());
+    NQ_HIP(h, hipMemcpyAsync(st.data() + nq::REFINE_DONE, h->d_refine.p + nq::REFINE_DONE,
+                             (nq::REFINE_STATE_WORDS - nq::REFINE_DONE) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(io_palette, st.data() + nq::REFINE_PALETTE, (size_t) K * sizeof(uint32_t));
+    for (int j = 0; j <= iterations; ++j) out_sse[j] = (int64_t) st[nq::REFINE_SSE_OUT + j];
+    if (out_counts) for (int k = 0; k < K; ++k) out_counts[k] = (int64_t) st[nq::REFINE_COUNTS + k];
+    *out_passes = (int32_t) st[nq::REFINE_PASSES];
+    return NQ_OK;
+}
+
+// both forms of nq_refine_palette (host: the frames lie in d_in, every one on a 16-byte boundary)
+int refine_call(nq_handle* h, bool host, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                uint32_t* io_palette, int K, int iterations, int64_t* out_sse, int64_t* out_counts, int32_t* out_passes) {
+    if (!h) return NQ_ERR_INVALID;
+    int64_t total = 0;
+    int rc = refine_check(h, n, argb, widths, heights, io_palette, K, iterations, out_sse, out_passes, &total);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    if (!host) return refine_device(h, n, argb, widths, heights, total, io_palette, K, iterations, out_sse, out_counts, out_passes);
+    return host_form(h, [&]() -> int {
+        std::vector<const uint32_t*> d_src(n);
+        size_t room = 0;
+        for (int i = 0; i < n; ++i) room += ((size_t) widths[i] * heights[i] + 3) & ~(size_t) 3;
+        NQ_HIP(h, h->d_in.reserve(room));
+        size_t at = 0;
+        for (int i = 0; i < n; ++i) {
+            const size_t px = (size_t) widths[i] * heights[i];
+            d_src[i] = h->d_in.p + at;
+            NQ_HIP(h, hipMemcpyAsync(h->d_in.p + at, argb[i], px * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            at += (px + 3) & ~(size_t) 3;
+        }
+        return refine_device(h, n, d_src.data(), widths, heights, total, io_palette, K, iterations, out_sse, out_counts, out_passes);
+    });
+}
+
+// the `refine` argument of the nq_convert_frames_refined forms
+int refine_check_convert(nq_handle* h, int refine, int nMaxColors) {
+    if (refine < 0 || refine > 64) NQ_FAIL(h, NQ_ERR_INVALID, "refine = %d: must be 0..64", refine);
+    if (refine > 0 && nMaxColors > 256) NQ_FAIL(h, NQ_ERR_INVALID, "refine needs nMaxColors <= 256");
+    return NQ_OK;
+}
+
 // ---- setup shared by the batch entry points ----
 // the batch's arguments, from the host arrays alone (hs[0] is not null); `host`: every image's pointers and size as well
 int batch_check(nq_handle* const* hs, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights, int nMaxColors,
@@ -1467,13 +1557,17 @@ int nq_pnnquan_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb,
     return palette_of(h, out_palette, out_K, [&](PaletteJob* job) { return pnnquan_frames_prepare(h, nMaxColors, out_palette, out_K, job); });
 }
 
-int nq_convert_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
-                             int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
-                             uint32_t* const* d_out_argb, uint16_t* const* d_out_index, uint32_t* out_palette, int32_t* out_K) {
+int nq_convert_frames_refined_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                                     int nMaxColors, int refine, int dither, const int64_t* rng_seeds, int mode,
+                                     uint32_t* const* d_out_argb, uint16_t* const* d_out_index, uint32_t* out_palette, int32_t* out_K) {
     if (!h) return NQ_ERR_INVALID;
     int64_t total = 0;
     int rc = frames_check(h, n, d_argb, widths, heights, nMaxColors, true, &total);
     if (rc) return rc;
+    rc = refine_check_convert(h, refine, nMaxColors);
+    if (rc) return rc;
+    for (int i = 0; refine > 0 && i < n; ++i)
+        if ((uintptr_t) d_argb[i] & 3) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: refine needs a 4-byte aligned pixel pointer", i);
     if (!rng_seeds || !d_out_argb || !out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
     for (int i = 0; i < n; ++i) if (!d_out_argb[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: null output pointer", i);
     rc = check_mode(h, mode);
@@ -1486,6 +1580,12 @@ int nq_convert_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb,
     rc = palette_of(h, out_palette, out_K, [&](PaletteJob* job) { return pnnquan_frames_prepare(h, nMaxColors, out_palette, out_K, job); });
     if (rc) return rc;
     const int K = *out_K;
+    if (refine > 0) {                               // `refine` update passes over the same frames; the params stay pnnquan's
+        int64_t sse[65];
+        int32_t passes = 0;
+        rc = refine_device(h, n, d_argb, widths, heights, total, out_palette, K, refine, sse, nullptr, &passes);
+        if (rc) return rc;
+    }
     nq_params& p = h->params;
     // the BlueNoise weight of convert(n, false) counts the SEQUENCE's distinct colours (what dither_device would count for one image)
     if (h->kind == NQ_KIND_LAB && !dither && K > 32 && mode == NQ_MODE_PARALLEL_TILED && p.distinctColors <= 0) {
@@ -1511,11 +1611,20 @@ int nq_convert_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb,
     return NQ_OK;
 }
 
-int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
-                      int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
-                      uint32_t* const* out_argb, uint16_t* const* out_index, uint32_t* out_palette, int32_t* out_K) {
+int nq_convert_frames_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
+                             uint32_t* const* d_out_argb, uint16_t* const* d_out_index, uint32_t* out_palette, int32_t* out_K) {
+    return nq_convert_frames_refined_device(h, n, d_argb, widths, heights, nMaxColors, 0, dither, rng_seeds, mode, d_out_argb, d_out_index,
+                                            out_palette, out_K);
+}
+
+int nq_convert_frames_refined(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                              int nMaxColors, int refine, int dither, const int64_t* rng_seeds, int mode,
+                              uint32_t* const* out_argb, uint16_t* const* out_index, uint32_t* out_palette, int32_t* out_K) {
     if (!h) return NQ_ERR_INVALID;
     int rc = frames_check(h, n, argb, widths, heights, nMaxColors, true, nullptr);
+    if (rc) return rc;
+    rc = refine_check_convert(h, refine, nMaxColors);
     if (rc) return rc;
     if (!out_argb || !rng_seeds || !out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "bad argument");
     for (int i = 0; i < n; ++i) if (!out_argb[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: null output pointer", i);
@@ -1526,8 +1635,15 @@ int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const in
     std::vector<size_t> px(n);
     for (int i = 0; i < n; ++i) px[i] = (size_t) widths[i] * heights[i];
     return host_images(h, n, px.data(), argb, out_argb, out_index, [&](auto in, auto out, auto index) {
-        return nq_convert_frames_device(h, n, in, widths, heights, nMaxColors, dither, rng_seeds, mode, out, index, out_palette, out_K);
+        return nq_convert_frames_refined_device(h, n, in, widths, heights, nMaxColors, refine, dither, rng_seeds, mode, out, index, out_palette,
+                                                out_K);
     });
+}
+
+int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                      int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
+                      uint32_t* const* out_argb, uint16_t* const* out_index, uint32_t* out_palette, int32_t* out_K) {
+    return nq_convert_frames_refined(h, n, argb, widths, heights, nMaxColors, 0, dither, rng_seeds, mode, out_argb, out_index, out_palette, out_K);
 }
 
 int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
@@ -3040,6 +3156,21 @@ int nq_detect_shots_device(nq_handle* h, int n, const uint32_t* const* d_argb, i
 int nq_detect_shots(nq_handle* h, int n, const uint32_t* const* argb, int width, int height, int threshold_pm, int min_shot,
                     int32_t* out_starts, int32_t* out_n_shots, int32_t* out_scores) {
     return shots_call(h, true, true, n, argb, width, height, nullptr, threshold_pm, min_shot, out_starts, out_n_shots, out_scores);
+}
+
+} // extern "C"
+
+// ---- palette refinement (nq_refine.hip) ----
+extern "C" {
+
+int nq_refine_palette_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             uint32_t* io_palette, int K, int iterations, int64_t* out_sse, int64_t* out_counts, int32_t* out_passes) {
+    return refine_call(h, false, n, d_argb, widths, heights, io_palette, K, iterations, out_sse, out_counts, out_passes);
+}
+
+int nq_refine_palette(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                      uint32_t* io_palette, int K, int iterations, int64_t* out_sse, int64_t* out_counts, int32_t* out_passes) {
+    return refine_call(h, true, n, argb, widths, heights, io_palette, K, iterations, out_sse, out_counts, out_passes);
 }
 
 } // extern "C"

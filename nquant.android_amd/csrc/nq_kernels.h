@@ -294,4 +294,23 @@ void launch_hold(const unsigned* const* d_src, unsigned short* const* d_idx, uns
 // alignment).  cus: compute units of the device (sizes the grid). ----
 void launch_signatures(const unsigned* const* d_frames, int n, long long npix, bool vec, int cus, unsigned* d_sig, hipStream_t s);
 
+// ---- palette refinement (nq_refine.hip): d_frames is a device array of n frames (never written), `total` the pixels of the sequence.
+// d_state holds REFINE_STATE_WORDS 64-bit words the caller uploaded: everything 0 but the K palette entries (32 bits each) from
+// REFINE_PALETTE on.  Enqueues the iterations + 1 assignment passes with their update steps; afterwards the words from REFINE_DONE on
+// hold the call's results.  vec: the 16-byte path -- the caller has checked that EVERY frame pointer is 16-byte aligned; otherwise one
+// pixel per access (4-byte alignment).  cus: compute units of the device (sizes the grid).  K is 1..256, iterations 0..64. ----
+struct RefineFrame { const unsigned* pixels; long long npix; };
+enum {
+    REFINE_ACC = 0,                         // [256][4] sums of the running pass: pixels, r, g, b per entry
+    REFINE_SSE_ACC = 1024,                  // ... and its squared error
+    REFINE_DONE = 1025,                     // 1: an update changed nothing, the later passes return at once
+    REFINE_PASSES = 1026,                   // assignment passes that ran
+    REFINE_SSE_OUT = 1027,                  // sse[0 .. 64]
+    REFINE_COUNTS = REFINE_SSE_OUT + 65,    // cnt[] of the last assignment pass that ran
+    REFINE_PALETTE = REFINE_COUNTS + 256,   // 256 entries of 32 bits
+    REFINE_STATE_WORDS = REFINE_PALETTE + 128
+};
+void launch_refine(const RefineFrame* d_frames, int n, long long total, bool vec, int cus, int K, int iterations, unsigned long long* d_state,
+                   hipStream_t s);
+
 } // namespace nq

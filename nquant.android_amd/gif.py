@@ -300,11 +300,12 @@ def _shots(shot_starts, n):
 
 
 def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0,
-                         mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, delta=True):
+                         mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, delta=True):
     """One palette per shot: frames shot_starts[k] .. shot_starts[k + 1] - 1 are shot k and get a convert_frames palette of their own
     (shot_starts=range(n): one palette per frame), then encode_gif_local_delta (delta=False: encode_gif_local) writes all frames, each
     with its shot's palette as its local colour table.  hold (delta=True only) runs per shot and never across a cut: a held index means
-    nothing under another table.  seeds, tile, lossy as for convert_frames_to_gif.  Everything runs on one handle.  Cuts are the
+    nothing under another table.  seeds, tile, lossy as for convert_frames_to_gif; refine (0..64) runs that many k-means passes
+    (refine.py) on every shot's palette over that shot's frames.  Everything runs on one handle.  Cuts are the
     caller's to give here; convert_clip_to_gif finds them.  Returns (file bytes, list of per-shot palettes)."""
     lossy = _lossy_keyword(lossy)
     if not 1 <= int(nMaxColors) <= 256:
@@ -321,19 +322,19 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
         hold = _threshold(hold)
     frames, q = _frames_quantizer(kind, frames, device, mode, tile)
     try:
-        return _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta)
+        return _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine)
     finally:
         q.close()
 
 
-def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta):
+def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine=0):
     """convert_shots_to_gif after its checks, on the handle of quantizer `q`, which stays open: `frames` int32 arrays, `shots` the
-    (first frame, one past the last) pairs, hold a checked threshold or None."""
+    (first frame, one past the last) pairs, hold a checked threshold or None, refine the k-means passes per shot (0: none)."""
     if hold is not None:
         from .hold import _hold_host
     maps, palettes = [], []
     for a, b in shots:
-        palette, outs = _convert_frames_on(q, frames[a:b], nMaxColors, dither, mode, None if seeds is None else list(seeds)[a:b])
+        palette, outs = _convert_frames_on(q, frames[a:b], nMaxColors, dither, mode, None if seeds is None else list(seeds)[a:b], int(refine) or None)
         shot_maps = [o.index for o in outs]
         if hold is not None:
             _hold_host(q._L, q._h, q._check, frames[a:b], shot_maps, None, hold)
@@ -354,7 +355,7 @@ def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segm
 
 
 def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, delays_cs=None, loop=0, segment_pixels=0, device=0,
-                        mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, delta=True):
+                        mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, delta=True):
     """A list of frames in, an animation out: detect_shots (shots.py; cut in per mille, min_shot in frames) finds where the clip needs
     a new palette, then exactly convert_shots_to_gif with those starts -- both on one handle.  The frames must have one size (delta or
     not: a signature is compared between frames of one size).  Keywords otherwise as for convert_shots_to_gif.
@@ -376,7 +377,7 @@ def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, de
     try:
         starts, _ = _detect_host(q._L, q._h, q._check, frames, cut, min_shot)
         data, palettes = _shots_to_gif_on(q, frames, _shots(starts, len(frames)), nMaxColors, dither, delays_cs, loop, segment_pixels, mode,
-                                          seeds, hold, lossy, delta)
+                                          seeds, hold, lossy, delta, refine)
     finally:
         q.close()
     return data, palettes, starts
@@ -400,7 +401,7 @@ def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, 
 
 
 def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
-                          seeds=None, tile=None, hold=None, lossy=0, delta=False):
+                          seeds=None, tile=None, hold=None, lossy=0, refine=0, delta=False):
     """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
     delta=True: encode_gif_delta instead; the frames must have one size.  Seeds are passed on as given: regions that do not move repeat
     in the index maps, and so drop out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.
@@ -408,6 +409,8 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
     two steps, so that pixels whose source moved by no more than it keep their index -- what footage with sensor or codec noise needs
     for its still regions to drop out.  All three steps then run on one handle; the index maps pass through host memory in between.
     lossy: as for encode_gif, applied to whichever encoder runs (with hold: on that same handle).
+    refine (0..64): that many k-means passes on the palette over the frames before the dither (refine.py, convert_frames_refined);
+    0 is the call without it.
     Returns (file bytes, palette)."""
     lossy = _lossy_keyword(lossy)
     if not 1 <= int(nMaxColors) <= 256:
@@ -421,7 +424,7 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
         hold = _threshold(hold)
         frames, q = _frames_quantizer(kind, frames, device, mode, tile)
         try:
-            palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds)
+            palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None)
             maps = [o.index for o in outs]
             height, width = _one_size(maps)
             _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
@@ -430,6 +433,10 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
         finally:
             q.close()
         return data, palette
-    palette, outs = convert_frames(kind, frames, nMaxColors, dither, device=device, mode=mode, seeds=seeds, tile=tile)
+    if int(refine) == 0:
+        palette, outs = convert_frames(kind, frames, nMaxColors, dither, device=device, mode=mode, seeds=seeds, tile=tile)
+    else:
+        from .refine import convert_frames_refined
+        palette, outs = convert_frames_refined(kind, frames, nMaxColors, dither, refine, device=device, mode=mode, seeds=seeds, tile=tile)
     data = (encode_gif_delta if delta else encode_gif)([o.index for o in outs], palette, delays_cs, loop, segment_pixels, device, lossy=lossy)
     return data, palette

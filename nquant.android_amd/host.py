@@ -110,6 +110,10 @@ _ABI = {
     "nq_shots_from_signatures": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "nq_detect_shots_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "nq_detect_shots": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "nq_refine_palette_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _pi32]),
+    "nq_refine_palette": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _pi32]),
+    "nq_convert_frames_refined_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pi32]),
+    "nq_convert_frames_refined": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pi32]),
 }
 
 
@@ -473,8 +477,8 @@ def _frames_quantizer(kind, frames, device, mode, tile):
     return frames, cls(frames[0], device=device, mode=mode, tile=tile)
 
 
-def _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds):
-    """nq_convert_frames of the int32 frames on the handle of quantizer `q`, which stays open."""
+def _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, refine=None):
+    """nq_convert_frames of the int32 frames on the handle of quantizer `q`, which stays open; refine not None: nq_convert_frames_refined."""
     n = len(frames)
     hs = np.array([f.shape[0] for f in frames], np.int32)
     ws = np.array([f.shape[1] for f in frames], np.int32)
@@ -488,8 +492,12 @@ def _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds):
     idx = (C.c_void_p * n)(*[o.ctypes.data for o in idxs])
     pal = np.zeros(max(int(nMaxColors), 2), np.int32)
     K = C.c_int32(0)
-    q._check(q._L.nq_convert_frames(q._h, n, src, ws.ctypes.data, hs.ctypes.data, int(nMaxColors), int(bool(dither)), sd.ctypes.data,
-                                    int(mode), dst, idx, pal.ctypes.data, C.byref(K)))
+    if refine is None:
+        q._check(q._L.nq_convert_frames(q._h, n, src, ws.ctypes.data, hs.ctypes.data, int(nMaxColors), int(bool(dither)), sd.ctypes.data,
+                                        int(mode), dst, idx, pal.ctypes.data, C.byref(K)))
+    else:
+        q._check(q._L.nq_convert_frames_refined(q._h, n, src, ws.ctypes.data, hs.ctypes.data, int(nMaxColors), int(refine), int(bool(dither)),
+                                                sd.ctypes.data, int(mode), dst, idx, pal.ctypes.data, C.byref(K)))
     palette = pal[:K.value].copy()
     return palette, [QuantizedImage(o, i, palette) for o, i in zip(outs, idxs)]
 
