@@ -28,11 +28,12 @@ def rectangles(frames):
     return out
 
 
-def bodies(frames, K):
-    """What each frame's LZW chains encode: frame 0 whole; frame i its rectangle of frame i, unchanged pixels replaced by u."""
+def bodies(frames, K, rects=None):
+    """What each frame's LZW chains encode: frame 0 whole; frame i its rectangle of frame i, unchanged pixels replaced by u.
+    rects: rectangles(frames) where the caller has them already."""
     u = unchanged_index(K)
     out = [np.asarray(frames[0]).astype(np.int64)]
-    for i, (x, y, w, h) in enumerate(rectangles(frames)[1:], 1):
+    for i, (x, y, w, h) in enumerate((rects or rectangles(frames))[1:], 1):
         cur = np.asarray(frames[i]).astype(np.int64)[y:y + h, x:x + w]
         prev = np.asarray(frames[i - 1]).astype(np.int64)[y:y + h, x:x + w]
         out.append(cur if u is None else np.where(cur != prev, cur, u))
@@ -61,7 +62,8 @@ def encode(frames, palette, delays_cs=None, loop=0, segment_pixels=0):
         out += bytes(((c >> 16) & 0xFF, (c >> 8) & 0xFF, c & 0xFF))
     if loop >= 0:
         out += b"\x21\xFF\x0BNETSCAPE2.0\x03\x01" + struct.pack("<H", loop) + b"\x00"
-    for i, ((x, y, w, h), body) in enumerate(zip(rectangles(frames), bodies(frames, K))):
+    rects = rectangles(frames)
+    for i, ((x, y, w, h), body) in enumerate(zip(rects, bodies(frames, K, rects))):
         d = int(delays_cs[i]) if delays_cs is not None else 0
         out += b"\x21\xF9\x04" + struct.pack("<BHB", 1 << 2 | (u is not None), d, u if u is not None else 0) + b"\x00"
         out += b"\x2C" + struct.pack("<HHHHB", x, y, w, h, 0)

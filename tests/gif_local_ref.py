@@ -90,11 +90,12 @@ def rectangles(frames, palettes):
     return out
 
 
-def bodies(frames, palettes):
-    """What each frame's chains encode: frame 0 whole; frame i its rectangle of index_i, pixels outside D replaced by u_i if there is one."""
+def bodies(frames, palettes, rects=None):
+    """What each frame's chains encode: frame 0 whole; frame i its rectangle of index_i, pixels outside D replaced by u_i if there is one.
+    rects: rectangles(frames, palettes) where the caller has them already."""
     frames = _frames(frames)
     out = [frames[0].astype(np.int64)]
-    for i, (x, y, w, h) in enumerate(rectangles(frames, palettes)[1:], 1):
+    for i, (x, y, w, h) in enumerate((rects or rectangles(frames, palettes))[1:], 1):
         u = gif_delta_ref.unchanged_index(len(palettes[i]))
         cur = frames[i].astype(np.int64)[y:y + h, x:x + w]
         out.append(cur if u is None else np.where(changed(frames, palettes, i)[y:y + h, x:x + w], cur, u))
@@ -112,7 +113,8 @@ def encode_delta(frames, palettes, delays_cs=None, loop=0, segment_pixels=0, los
     H, W = frames[0].shape
     out = _head(W, H, n, loop)
     subs = 0
-    for i, ((x, y, w, h), body) in enumerate(zip(rectangles(frames, palettes), bodies(frames, palettes))):
+    rects = rectangles(frames, palettes)
+    for i, ((x, y, w, h), body) in enumerate(zip(rects, bodies(frames, palettes, rects))):
         pal = np.asarray(palettes[i]).astype(np.int64) & 0xFFFFFFFF
         assert all((int(c) >> 24) != 0 for c in pal), "alpha 0 entries are refused for n > 1"
         K = len(pal)
@@ -191,7 +193,11 @@ def parse(gif):
 def compose(gif):
     """The RGB canvas (H, W, 3 uint8) after every frame.  A frame's pixels other than its transparent index are painted at its position
     in its own table's colours; disposal 2 clears the frame's area to black before the next frame, 0 and 1 keep the canvas."""
-    screen, frames = parse(gif)
+    return compose_parsed(*parse(gif))
+
+
+def compose_parsed(screen, frames):
+    """compose() of what parse() returned."""
     canvas = np.zeros((screen["height"], screen["width"], 3), np.uint8)
     out = []
     for f in frames:

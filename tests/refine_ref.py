@@ -50,15 +50,41 @@ def update(palette, cnt, sums):
     return pal.astype(np.uint32)
 
 
+def _flat(f):
+    f = np.asarray(f)
+    return f.reshape(-1).view(np.uint32) if f.dtype == np.int32 else f.reshape(-1)
+
+
 def refine(frames, palette, iterations):
     """(palette as uint32, sse as iterations + 1 int64 values, counts as K int64 values, passes) of the definition."""
-    pixels = np.concatenate([np.asarray(f).reshape(-1).view(np.uint32) if np.asarray(f).dtype == np.int32 else np.asarray(f).reshape(-1)
-                             for f in frames])
+    pixels = np.concatenate([_flat(f) for f in frames])
+    return _passes(lambda pal: assign(pixels, pal), palette, iterations)
+
+
+def refine_weighted(frames, weights, palette, iterations):
+    """refine() of the sequence that holds frames[i] weights[i] times (in any order), at the cost of the distinct frames: cnt, sums and
+    sse of an assignment pass are sums over the pixels, so a frame that occurs m times adds m times what it adds once."""
+    assert len(frames) == len(weights) and all(int(m) >= 0 for m in weights)
+
+    def one_pass(pal):
+        cnt, sums, sse = np.zeros(pal.size, np.int64), np.zeros((pal.size, 3), np.int64), 0
+        for f, m in zip(frames, weights):
+            c, s, e = assign(_flat(f), pal)
+            cnt += int(m) * c
+            sums += int(m) * s
+            sse += int(m) * int(e)
+        return cnt, sums, sse
+
+    return _passes(one_pass, palette, iterations)
+
+
+def _passes(one_pass, palette, iterations):
+    """The passes, the update between them and the early stop over one_pass(palette) -> (cnt, sums, sse)."""
     pal = (np.asarray(palette).reshape(-1).astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
     sse = np.zeros(iterations + 1, np.int64)
     passes = 0
     for j in range(iterations + 1):
-        cnt, sums, sse[j] = assign(pixels, pal)
+        cnt, sums, sse[j] = one_pass(pal)
         passes = j + 1
         if j == iterations:
             break

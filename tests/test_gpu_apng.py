@@ -1,7 +1,7 @@
 """APNG encoding on the GPU (nq_encode_apng / nq_encode_apng_device): the bytes and the rectangles equal the restatement in apng_ref.py
 for every K, segment length, shape, palette kind and kind of change tried; every file composes back to the RGBA frames through
 apng_ref.compose and through Pillow; a sprite over a transparent region un-paints its old place (crop mode); rectangles that start in
-mid-word of the source at depths 1, 2 and 4; frames at odd 2-byte offsets in device memory, never written; convert_frames_to_apng on
+mid-word of the source at depths 1, 2 and 4; frames larger than one grid stride of the difference pass; frames at odd 2-byte offsets in device memory, never written; convert_frames_to_apng on
 a sprite animation, also over a transparent background (which delta GIF refuses); every invalid input, each followed by a valid call
 on the same handle."""
 import ctypes as C
@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 PIL = pytest.importorskip("PIL")
 
-from gif_delta_cases import KS, palette_of, sequence  # noqa: E402
+from gif_delta_cases import BIG_H, BIG_RECTS, BIG_W, KS, device_pool, palette_of, past_one_grid_stride, sequence  # noqa: E402
 from test_apng_cpu import alpha_palette, composes_back  # noqa: E402
 
 SHAPES = ((1, 1), (1, 777), (37, 91), (256, 256))
@@ -97,6 +97,29 @@ def test_noise_that_changes_everywhere_in_long_chains(hd):
             assert rects.tolist() == [[0, 0, 500, 300]] * 3
             assert got == apng_ref.encode(frames, pal, segment_bytes=S), (K, S)
             composes_back(got, frames, pal, (K, S))
+
+
+def test_rectangles_past_one_grid_stride_of_the_difference_pass(nq):
+    """The cap: APNG takes its rectangles from gif_diff_kernel, whose gridDim.x is at most 1024 workgroups of 256 threads of 8 pixels,
+    2 097 152 pixels.  The 1449 x 1450 sequence of test_gpu_gif_delta.py (2 101 050 pixels; gif_delta_cases.past_one_grid_stride) in
+    mark mode, device form at odd 2-byte offsets: the rectangles, and the canvases apng_ref composes from the file."""
+    K = 17
+    rng = np.random.default_rng(K)
+    pal = palette_of(K, rng)
+    frames = past_one_grid_stride(K, rng)
+    buf, host, ptrs = device_pool(frames)
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        got, rects = nq.encode_apng_device(q, ptrs, BIG_W, BIG_H, pal, None, 0, 0, return_rects=True)
+    finally:
+        q.close()
+    assert rects.tolist() == [list(r) for r in BIG_RECTS] == _rects(frames)
+    assert len(got) <= nq.apng_max_bytes(len(frames), BIG_W, BIG_H, 0)
+    own = apng_ref.compose(got)
+    assert len(own) == len(frames)
+    for i, (c, f) in enumerate(zip(own, frames)):
+        assert (c == apng_ref.rgba_of(f, pal)).all(), i
+    assert (buf.cpu().numpy().view(np.uint16) == host).all()
 
 
 @pytest.mark.parametrize("K", [2, 3, 15])

@@ -1,6 +1,7 @@
 """Delta-mode GIF encoding on the GPU (nq_encode_gif_delta / nq_encode_gif_delta_device): the bytes and the rectangles equal the
 restatement in gif_delta_ref.py for every K, segment length, shape and kind of change tried; frames at odd 2-byte offsets in device
-memory, never written; Pillow composes every file back to the frames; a sprite animation through convert_frames_to_gif(delta=True)
+memory, never written; Pillow composes every file back to the frames; frames larger than one grid stride of the difference and body
+kernels and more frame pairs than their grid has rows; a sprite animation through convert_frames_to_gif(delta=True)
 stores only the tiles the sprite touched; every invalid input, each followed by a valid call on the same handle."""
 import ctypes as C
 
@@ -16,7 +17,8 @@ pytestmark = pytest.mark.gpu
 
 PIL = pytest.importorskip("PIL")
 
-from gif_delta_cases import KS, palette_of, pillow_canvases, rgb_of, sequence  # noqa: E402
+from gif_delta_cases import (BIG_H, BIG_RECTS, BIG_W, GRID_Y, KS, MANY_FRAMES, ROWS, device_pool, many_rows, palette_of,  # noqa: E402
+                             past_one_grid_stride, pillow_canvases, rgb_of, sequence)
 
 SHAPES = ((1, 1), (1, 777), (37, 91), (256, 256))
 
@@ -117,6 +119,65 @@ def test_device_form_at_odd_offsets_leaves_the_frames_alone(nq, hd):
         assert nq.encode_gif_delta(frames, pal, delays) == gif_delta_ref.encode(frames, pal, delays_cs=delays)
         assert (buf.cpu().numpy().view(np.uint16) == host).all()
     q.close()
+
+
+# ---- past the launch caps of the difference and body kernels ----
+@pytest.mark.parametrize("S", [0, 65536])
+@pytest.mark.parametrize("K", [17, 256])
+def test_frames_and_bodies_past_one_grid_stride(nq, hd, K, S):
+    """The cap: gridDim.x of gif_diff_kernel and gif_body_kernel is at most 1024 workgroups of 256 threads of 8 pixels, 2 097 152
+    pixels; beyond it a thread takes the step c += gridDim.x * blockDim.x.  1449 x 1450 = 2 101 050 pixels, rows 1448 and 1449 wholly
+    behind the cap (gif_delta_cases.past_one_grid_stride): a change found only there, a whole-frame body longer than one stride, a
+    block in front of the cap and one behind it.  Host form and device form (every frame at an odd 2-byte offset)."""
+    rng = np.random.default_rng(K)
+    pal = palette_of(K, rng)
+    frames = past_one_grid_stride(K, rng)
+    assert gif_delta_ref.rectangles(frames) == BIG_RECTS
+    delays = [3, 0, 7, 1, 65535, 2]
+    want = gif_delta_ref.encode(frames, pal, delays_cs=delays, loop=0, segment_pixels=S)
+    got, rects = _enc(hd, frames, pal, delays, 0, S)
+    assert [tuple(r) for r in rects.tolist()] == BIG_RECTS
+    assert got == want, (K, S, len(got), len(want))
+    buf, host, ptrs = device_pool(frames)
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        got, rects = nq.encode_gif_delta_device(q, ptrs, BIG_W, BIG_H, pal, delays, 0, S, return_rects=True)
+    finally:
+        q.close()
+    assert [tuple(r) for r in rects.tolist()] == BIG_RECTS
+    assert got == want, (K, S, len(got), len(want))
+    assert (buf.cpu().numpy().view(np.uint16) == host).all()
+    canvases = pillow_canvases(got)
+    assert len(canvases) == len(frames)
+    for i, (g, f) in enumerate(zip(canvases, frames)):
+        assert (g == rgb_of(f, pal)).all(), (K, S, i)
+
+
+def test_more_frame_pairs_than_grid_rows(nq):
+    """The cap: gridDim.y of the same two kernels is at most 65 535, one frame pair (one body) each; beyond it a workgroup takes the step
+    f += gridDim.y.  65 540 frames of 3 x 1 are 65 539 pairs: blockIdx.y = 0 .. 3 take a second pair.  The pointer table names eight
+    rows of one small device buffer in a seeded random order (most neighbours differ, some are equal)."""
+    n, K = MANY_FRAMES, 4
+    assert n - 1 > GRID_Y
+    rng = np.random.default_rng(65)
+    pal = palette_of(K, rng)
+    pick = many_rows(n, rng)
+    frames = [ROWS[i].reshape(1, 3) for i in pick]
+    want_rects = gif_delta_ref.rectangles(frames)
+    assert len(set(want_rects[GRID_Y + 1:])) > 1               # frames 65 536 .. 65 539: the second step has work, not all of it equal
+    delays = (np.arange(n) % 7).tolist()
+    want = gif_delta_ref.encode(frames, pal, delays_cs=delays, loop=0)
+    buf, host, ptrs = device_pool(list(ROWS))
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        got, rects = nq.encode_gif_delta_device(q, [ptrs[i] for i in pick], 3, 1, pal, delays, 0, 0, return_rects=True)
+    finally:
+        q.close()
+    assert [tuple(r) for r in rects.tolist()] == want_rects
+    assert got == want, (len(got), len(want))
+    own = gif_delta_ref.compose(got)
+    assert len(own) == n and all((c == f).all() for c, f in zip(own, frames))
+    assert (buf.cpu().numpy().view(np.uint16) == host).all()
 
 
 # ---- the pipeline: a sprite over a static background ----

@@ -1,7 +1,8 @@
 """GIF files with one colour table per frame on the GPU (nq_encode_gif_local* / nq_encode_gif_local_delta*): bytes and rectangles equal
 the restatement in gif_local_ref.py for every K of the definition within one file, every shape, segment length and both thresholds; the
 named edge cases of "changed by colour"; frames at odd 2-byte offsets in device memory, never written; long chains with K alternating
-255 / 256; the lossy bound on Pillow's canvases; every invalid input followed by a valid call; one palette per shot through
+255 / 256; frames larger than one grid stride of the two delta passes and more frame pairs than their grid has rows (the LDS tables
+refilled inside a live workgroup); the lossy bound on Pillow's canvases; every invalid input followed by a valid call; one palette per shot through
 convert_shots_to_gif."""
 import ctypes as C
 
@@ -10,7 +11,8 @@ import pytest
 
 import gif_local_cases as cases
 import gif_local_ref as R
-from gif_delta_cases import palette_of, pillow_canvases
+from gif_delta_cases import (BIG_H, BIG_RECTS, BIG_W, GRID_Y, MANY_FRAMES, ROWS, device_pool, many_rows, palette_of, past_one_grid_stride,
+                             pillow_canvases)
 from nquant.android_amd import gif as G
 from nquant.android_amd import synth
 
@@ -140,6 +142,84 @@ def test_noise_in_long_chains_with_K_alternating_255_and_256(hd):
         assert got == (R.encode_delta if delta else R.encode)(frames, pals, None, 0, 65536)[0], delta
         _within(pillow_canvases(got), want_rgb, 0, delta)
         assert len(got) <= R.max_bytes([f.shape for f in frames], 65536)
+
+
+# ---- past the launch caps of the difference and body kernels ----
+@pytest.mark.parametrize("S", [0, 65536])
+@pytest.mark.parametrize("K", [17, 256])
+def test_frames_and_bodies_past_one_grid_stride(nq, hd, K, S):
+    """The cap: gridDim.x of gif_diff_local_kernel and gif_body_local_kernel is at most 1024 workgroups of 256 threads of 8 pixels,
+    2 097 152 pixels; beyond it a thread takes the step c += gridDim.x * blockDim.x.  The 1449 x 1450 sequence of
+    test_gpu_gif_delta.py (2 101 050 pixels; gif_delta_cases.past_one_grid_stride), here with frames 4 and 5 under a table that is a
+    permutation of the one before, their indices permuted to match: every index of frame 4 in front of the cap differs from frame 3's,
+    and the rectangle is still the block behind the cap, because "differs" is judged on the colour.  Host form and device form (odd 2-byte offsets)."""
+    rng = np.random.default_rng(K)
+    pal = palette_of(K, rng)
+    assert len(set((pal & 0xFFFFFF).tolist())) == K
+    frames = past_one_grid_stride(K, rng)
+    perm = np.roll(np.arange(K), 1).astype(np.uint16)   # entry perm[j] of the new table is entry j of the old: no fixed point
+    pal2 = np.empty_like(pal)
+    pal2[perm] = pal
+    frames[4], frames[5] = perm[frames[4]], perm[frames[5]]
+    assert (frames[4][:BIG_H - 2] != frames[3][:BIG_H - 2]).all()
+    pals = [pal] * 4 + [pal2] * 2
+    assert R.rectangles(frames, pals) == BIG_RECTS
+    delays = [3, 0, 7, 1, 65535, 2]
+    want = R.encode_delta(frames, pals, delays, 0, S)[0]
+    got, rects = _enc(hd, frames, pals, delays, 0, S, 0, True)
+    assert _rects(rects) == BIG_RECTS
+    assert got == want, (K, S, len(got), len(want))
+    buf, host, ptrs = device_pool(frames)
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        got, rects = nq.encode_gif_local_delta_device(q, ptrs, BIG_W, BIG_H, pals, delays, 0, S, return_rects=True)
+    finally:
+        q.close()
+    assert _rects(rects) == BIG_RECTS
+    assert got == want, (K, S, len(got), len(want))
+    assert (buf.cpu().numpy().view(np.uint16) == host).all()
+    _within(pillow_canvases(got), cases.shown(frames, pals), 0, (K, S))
+
+
+def test_more_frame_pairs_than_grid_rows(nq):
+    """The cap: gridDim.y of the same two kernels is at most 65 535, one frame pair (one body) each; beyond it a workgroup takes the step
+    f += gridDim.y and load_tables refills both LDS colour tables between its barriers while the workgroup is still alive.  65 540
+    frames of 3 x 1 are 65 539 pairs: blockIdx.y = 0 .. 3 take a second pair.  The table length alternates between 3 and 4, the table
+    contents come from a pool of four that share some colours and never repeat from one frame to the next, so both LDS tables change
+    at every step; the pointer table names eight rows of one small device buffer in a seeded random order."""
+    n = MANY_FRAMES
+    assert n - 1 > GRID_Y
+    rng = np.random.default_rng(66)
+    pool = [palette_of(4, rng) for _ in range(4)]
+    pool[1][0], pool[2][1], pool[3][2] = pool[0][0], pool[0][1], pool[1][1]     # a colour two tables share, at the same index or another
+    pool[3][0] = pool[2][2]
+    which = np.cumsum(rng.integers(1, 4, n)) % 4               # steps of 1 .. 3 modulo 4: no table twice in a row
+    assert (which[1:] != which[:-1]).all()
+    pals = [pool[c][:3 + i % 2] for i, c in enumerate(which)]
+    pick = many_rows(n, rng, lambda i: 3 + i % 2)
+    frames = [ROWS[i].reshape(1, 3) for i in pick]
+    assert all(int(f.max()) < len(p) for f, p in zip(frames[:64], pals[:64]))
+    delays = (np.arange(n) % 7).tolist()
+    want = R.encode_delta(frames, pals, delays, 0, 0)[0]
+    buf, host, ptrs = device_pool(list(ROWS))
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        got, rects = nq.encode_gif_local_delta_device(q, [ptrs[i] for i in pick], 3, 1, pals, delays, 0, 0, return_rects=True)
+    finally:
+        q.close()
+    assert got == want, (len(got), len(want))
+    # the file is the restatement's, so the rectangles in it are R.rectangles(frames, pals): one parse gives them and the canvases
+    screen, parsed = R.parse(got)
+    want_rects = [(p["x"], p["y"], p["w"], p["h"]) for p in parsed]
+    assert want_rects[:64] == R.rectangles(frames[:64], pals[:64]) and want_rects[GRID_Y - 2:] == R.rectangles(frames[GRID_Y - 3:], pals[GRID_Y - 3:])[1:]
+    assert _rects(rects) == want_rects
+    assert any(r != (0, 0, 1, 1) for r in want_rects[GRID_Y + 1:])      # frames 65 536 .. 65 539: the second step has work
+    own = np.array(R.compose_parsed(screen, parsed))
+    colours = np.array(pool)[which[:, None], ROWS[pick]]       # (n, 3): what every frame shows (cases.shown, for all frames at once)
+    shown = np.stack([(colours >> 16) & 255, (colours >> 8) & 255, colours & 255], -1).reshape(n, 1, 3, 3)
+    assert own.shape == shown.shape and (own == shown).all()
+    assert (shown[:64] == np.array(cases.shown(frames[:64], pals[:64]))).all()
+    assert (buf.cpu().numpy().view(np.uint16) == host).all()
 
 
 @pytest.mark.parametrize("delta", [False, True])

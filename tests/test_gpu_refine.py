@@ -2,7 +2,8 @@
 the restatement in refine_ref.py exactly -- at the smallest shapes that reach each path of the kernel (one pixel, less than one
 vector group, a tail, whole groups only, several workgroups), with 16-byte aligned frames (vector path) and frames offset by one
 element (scalar path), frames of different sizes in one call, K = 1 .. 256; alpha (pinned entries, uncounted pixels, no live entry);
-ties and empty entries; sums above 2^32; the early stop; frames untouched; every rejected argument leaves the outputs alone and the
+ties and empty entries; sums above 2^32; tens of thousands of small frames, which carry every workgroup through the flush inside
+the round loop; the early stop; frames untouched; every rejected argument leaves the outputs alone and the
 handle usable; convert_frames_refined is the composition of pnnquan_frames_device, the restatement and dither_device; and the GIF /
 APNG wrappers pass `refine` on."""
 import ctypes as C
@@ -178,6 +179,79 @@ def test_sums_wider_than_32_bits(nq, q):
         if ww == w:
             assert n == 17203200 and 255 * n > 2**32
     assert bool((frame == -1).all())
+
+
+# ---- the flush inside the round loop, in the kernel as it ships ----
+FLUSH_PIXELS, REF_THREADS = 1 << 24, 256            # nq_refine.hip's values; test_refine_cpu.py holds the source to them
+MANY = {"vector": (0, 40000, 4), "scalar": (1, 140000, 1)}      # path: elements behind a 16-byte boundary, frames, pixels per lane and round
+DRAW = (0.25, 0.25, 0.10, 0.20, 0.20)               # how often the table names each of the first five frames of the pool
+MARK, MARK_ENTRY = 0x01285AC8, 0x013C46B4           # the marker frame's one colour (alpha 1; b = 200) and the palette entry only it reaches
+
+
+def _pool():
+    """Five small frames: 64 x 32 is 512 vector groups (two workgroups with all four waves counting); 33 x 31 is 255 groups and a tail
+    of 3; 1 x 1 is a tail alone; 16 x 16 of one colour takes the wave-match add; 9 x 7 holds pixels with alpha 0 (its other pixels are
+    opaque: the marker's entry must stay the marker's).  The sixth is the marker, 64 x 32 of MARK."""
+    pool = [synth.gradient_noise(64, 32, 41), synth.gradient_noise(33, 31, 42), synth.gradient_noise(1, 1, 43),
+            np.full((16, 16), 0xFF2060A0, np.uint32), synth.with_alpha(synth.gradient_noise(9, 7, 44), 44, p_transparent=0.1, p_semi=0.0),
+            np.full((32, 64), MARK, np.uint32)]
+    al = pool[4].view(np.uint32) >> 24
+    assert (al == 0).any() and (al == 255).any() and ((al == 0) | (al == 255)).all()
+    return pool
+
+
+@pytest.mark.parametrize("K,iterations", [(16, 0), (16, 3), (256, 1)])
+@pytest.mark.parametrize("path", sorted(MANY))
+def test_many_small_frames_pass_the_flush_inside_the_round_loop(nq, q, path, K, iterations):
+    """The cap: a workgroup flushes its 32-bit LDS counters inside the round loop once `seen` would pass REF_FLUSH_PIXELS = 2^24, and
+    `seen` grows by REF_THREADS * G = 1024 (vector path) or 256 (scalar path) per round whether or not the round's lanes hold pixels.
+    A frame of G pixels or more costs every workgroup at least one round, so the number of frames alone carries a workgroup past the
+    flush: it comes at the top of round 16 384 and 32 768 (counted from 0) on the vector path, 65 536 and 131 072 on the scalar path.
+    40 000 frames x 1024 = 40 960 000 and 140 000 x 256 = 35 840 000 both exceed 2 x 2^24 = 33 554 432; the 1 x 1 frames, which cost the
+    vector path no round (0 groups; workgroup 0 a tail round), are drawn less often than the others so that the frames that do cost
+    one, counted below, still exceed 32 768.  Workgroup 0 adds a round per frame with a tail and so flushes at other rounds than the rest.
+    The table names five frames of one small buffer in a seeded random order, so the round in front of a flush is not always the same
+    frame's.  Exact against refine_weighted (test_refine_cpu.py holds that equal to refine() of the expanded sequence).
+
+    What makes a lost add visible.  Every frame of the pool occurs thousands of times, and the outputs are counts, errors and ROUNDED
+    means: one LDS add lost in front of a flush (the failure DESIGN.md 5d records: the b sums of the round before) moves no mean of
+    such an entry.  So the round in front of each flush of the workgroups other than 0 (on the scalar path: of all of them) is the
+    marker: a flat frame that occurs only there, whose pixels are the only ones its palette entry gets.  One wave's b sum less and
+    that entry's blue drops by 200 * 256 / 4096 = 12 (vector path; the marker's groups 256 .. 511 are workgroup 1's) or by 200 * 64 /
+    4096 = 3 (scalar path; 256 pixels each for workgroups 0 .. 7), which the palette and sse[1..] show for iterations >= 1."""
+    shift, n, G = MANY[path]
+    assert n * REF_THREADS * G > 2 * FLUSH_PIXELS
+    pool = _pool()
+    sizes = np.array([f.size for f in pool])
+    order = np.random.default_rng(n).choice(5, n, p=DRAW)
+    # the marker in front of both flushes: the frame that is round 16 384 k - 1 (65 536 k - 1) of the workgroups other than 0 costs them
+    # a round, and so does the marker that takes its place
+    between = FLUSH_PIXELS // (REF_THREADS * G)
+    cost = np.cumsum(sizes[order] >= G)
+    slots = [int(np.flatnonzero(cost == between * k)[0]) for k in (1, 2)]
+    order[slots] = 5
+    assert (np.cumsum(sizes[order] >= G) == cost).all() and slots[1] < n - 1
+    weights = np.bincount(order, minlength=len(pool))
+    assert (weights > 0).all() and weights[5] == 2
+    # rounds of a workgroup other than 0 (one per frame with a whole group: 512 groups are one round of two workgroups or more), and
+    # of workgroup 0, which also takes the tails
+    rounds = int(weights[sizes >= G].sum())
+    rounds0 = rounds + int(weights[sizes % G != 0].sum())
+    assert rounds * REF_THREADS * G > 2 * FLUSH_PIXELS
+    assert rounds0 > rounds if G > 1 else rounds0 == rounds == n
+    assert int((weights * sizes).sum()) // 16384 >= 8          # (launch_refine: eight workgroups at the least)
+    palette = _opaque_palette(K, 50 + K)
+    palette[K - 1] = MARK_ENTRY
+    want = refine_ref.refine_weighted(pool, weights, palette, iterations)
+    assert iterations == 0 or want[3] > 1                      # an update after a flushed pass is part of the result
+    assert want[2][K - 1] == 2 * 2048 and (iterations == 0 or want[0][K - 1] == MARK)      # the marker's pixels and no others
+    s = _Stream(pool, shift)
+    ptrs = [s.ptrs[i] for i in order]
+    keep = palette.copy()
+    got = nq.refine_palette_device(q, ptrs, [s.widths[i] for i in order], [s.heights[i] for i in order], palette, iterations)
+    _same(got, want, (path, K, iterations))
+    assert int(got[2].sum()) == int((weights * [int(((f.view(np.uint32) >> 24) != 0).sum()) for f in pool]).sum())
+    assert (palette == keep).all() and s.unchanged()
 
 
 def test_a_fixed_point_stops_after_one_pass(nq, q):

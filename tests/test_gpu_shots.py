@@ -2,7 +2,7 @@
 the smallest shapes that reach each path of the kernel (one pixel, less than one vector group, whole groups only, a tail, several
 workgroups per frame), on content that reaches each way a count is added (every lane its own value, runs of equal neighbours inside
 a lane, a channel or a whole frame that is one value across a wave), with 16-byte aligned frames (vector path) and frames offset by
-one element (scalar path); more frames than any per-block batching; 81 920 pixels of ONE colour in four counters; a frame with
+one element (scalar path); more frames than any per-block batching, and 20 000 frames; 81 920 pixels of ONE colour in four counters; a frame with
 transparency; frames and guard elements untouched; the host form equals the device form; starts and scores of the two clips of the CPU
 tests; every rejected argument leaves the outputs alone and the handle usable; and convert_clip_to_gif equals convert_shots_to_gif
 with the starts it found."""
@@ -123,6 +123,32 @@ def test_more_frames_than_any_batching(nq):
     q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
     try:
         _device_case(nq, q, _frames(7, 3, 40, 2), "40 frames")
+    finally:
+        q.close()
+
+
+@pytest.mark.parametrize("shape", [(7, 3), (64, 64)], ids=lambda s: "%dx%d" % s)
+def test_many_frames_are_many_workgroups(nq, shape):
+    """launch_signatures works bpf and the grid n * bpf out from n: with n = 20 000 the cap of workgroups per frame,
+    ceil(8 * CUs / n), is 1 on any device of fewer than 2500 CUs, so bpf = 1 and the grid is 20 000 workgroups -- five hundred times
+    the 40 frames of the test above, and at 64 x 64 (4096 pixels < SIG_MIN_PIXELS, bpf = 1 from the size as well) four rounds per
+    workgroup on the vector path and sixteen on the scalar path.  The table names four frames, one of each kind of content, in a seeded random order; the expected signatures are
+    shots_ref.signatures of the frames the table names (21 pixels: all 20 000; 64 x 64: the four, indexed by the same order)."""
+    w, h = shape
+    n = 20000
+    pool = [_frame(w, h, kind, 60 + kind) for kind in range(4)]
+    order = np.random.default_rng(w).integers(0, 4, n)
+    assert len(set(order[:8].tolist())) > 1
+    want = shots_ref.signatures([pool[i] for i in order]) if w * h < 100 else shots_ref.signatures(pool)[order]
+    assert want.shape == (n, 4, 256) and (want.sum(axis=2) == w * h).all()
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        for shift in (0, 1):
+            s = _Stream(pool, shift)
+            got = nq.frame_signatures_device(q, [s.ptrs[i] for i in order], w, h)
+            assert got.shape == want.shape and got.dtype == np.uint32
+            assert (got == want).all(), (shape, shift, np.argwhere(got != want)[:4].tolist())
+            assert s.unchanged(), (shape, shift)
     finally:
         q.close()
 

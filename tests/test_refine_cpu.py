@@ -85,6 +85,33 @@ def test_no_live_entry_and_no_counted_pixel():
     assert pal.tolist() == [0xFF123456] and (sse == 0).all() and (cnt == 0).all() and passes == 1
 
 
+@pytest.mark.parametrize("iterations", [0, 1, 4])
+def test_weighted_frames_equal_the_expanded_sequence(iterations):
+    """refine_weighted(pool, weights) is refine() of the sequence that repeats every frame of the pool that often, in all four outputs:
+    what lets test_gpu_refine.py state the result of a call with 140 000 frames from five assignment passes."""
+    pool = [synth.gradient_noise(33, 31, 21), synth.with_alpha(synth.gradient_noise(9, 7, 22), 22), np.full((4, 4), 0xFF3060C0, np.uint32)]
+    weights = (5, 3, 1)
+    rng = np.random.default_rng(23)
+    order = rng.permutation(np.repeat(np.arange(3), weights))
+    for K in (2, 16):
+        palette = rng.integers(0, 1 << 24, K).astype(np.uint32) | np.uint32(0xFF000000)
+        want = refine_ref.refine([pool[i] for i in order], palette, iterations)
+        got = refine_ref.refine_weighted(pool, weights, palette, iterations)
+        assert got[0].tolist() == want[0].tolist() and got[1].tolist() == want[1].tolist() and got[2].tolist() == want[2].tolist()
+        assert got[3] == want[3]
+        assert iterations == 0 or got[3] > 1
+
+
+def test_the_constants_the_flush_test_counts_with():
+    """tests/test_gpu_refine.py reaches the flush inside the round loop of the shipped kernel by the number of frames alone, and works
+    that number out from these two values.  Changing either must fail here, not silently move the flush out of the test's reach."""
+    import re
+    src = open(os.path.join(HERE, "..", "nquant.android_amd", "csrc", "nq_refine.hip")).read()
+    assert re.search(r"^#define NQ_REFINE_FLUSH_PIXELS \(1 << 24\)$", src, re.M)
+    assert re.search(r"^constexpr unsigned REF_FLUSH_PIXELS = NQ_REFINE_FLUSH_PIXELS;", src, re.M)
+    assert re.search(r"^constexpr int REF_THREADS = 256;$", src, re.M)
+
+
 # sse[0] and the ratios sse[j] / sse[0], j = 1, 4, 8, of the stored palettes on the sample picture, computed with this restatement.
 # The 256-entry palettes hold alpha-254 entries (23 and 89 of them) and the picture is opaque: their pixels keep a distance of 1 in
 # alpha through every pass, because the alpha of an entry never changes.  (Moving alpha to the mean as well would give 0.923 / 0.889 /
