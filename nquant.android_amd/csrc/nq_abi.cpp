@@ -192,6 +192,12 @@ struct nq_handle {
     std::vector<uint32_t> dev_palette;  // what d_palette holds, as far as the host knows (empty: unknown): an upload of the same entries is skipped
     uint32_t* fetched_palette = nullptr; int fetched_len = 0;      // palette_fetch -> palette_check
     long long merge_readback[37] = {0}; // d_scalars[4..41) as the merge kernel left it: one copy per image ([36] = status word)
+    // nq_convert_batch_device (first handle of the batch): the palettes and the 37 read-back words of all merge jobs of the call come
+    // back as ONE block -- gathered on the device (launch_merge_readback), then one copy into page-locked memory
+    DevBuf<long long> d_readback;
+    long long* h_readback = nullptr; size_t h_readback_words = 0;
+    // page-locked landing slots of this handle's two scalar read-backs per image: [0..2] the pre-scan's scan3, [4] the bin count
+    long long* pin = nullptr;
     int merge_variant[2] = {0, 0};     // nq_get_merge_variant: {workgroup-size code, helpers} launch_merge picked for this handle's last merge job
     long long team_stats[16] = {0};    // merge teams: {work records published, results used, timed-out waits, ticks waited, helpers, still speculating}
     DevBuf<unsigned long long> team;  // 256 u64 of hand-off words of this handle's merge team
@@ -273,6 +279,8 @@ struct nq_handle {
         if (copy_stream) (void) hipStreamDestroy(copy_stream);
         if (lane_stream) (void) hipStreamDestroy(lane_stream);
         for (auto& ls : more_lanes) if (ls) (void) hipStreamDestroy(ls);
+        if (h_readback) (void) hipHostFree(h_readback);
+        if (pin) (void) hipHostFree(pin);
     }
 };
 
@@ -308,6 +316,7 @@ int use_device(nq_handle* h) {
         NQ_HIP(h, h->d_scalars.reserve(64));
         NQ_HIP(h, h->d_ints.reserve(8 + 64));
         NQ_HIP(h, h->d_bincache.reserve(65536));
+        if (!h->pin) NQ_HIP(h, hipHostMalloc((void**) &h->pin, 8 * sizeof(long long), hipHostMallocDefault));
         for (auto& e : h->ev) NQ_HIP(h, hipEventCreate(&e));
         for (auto& e : h->bev) NQ_HIP(h, hipEventCreate(&e));
         h->tables_ready = true;
@@ -348,9 +357,12 @@ void* packed_lists(nq_handle* h) { return h->sc->cell_lists.p + 2 * (size_t) 655
 // candidate lists per colour cell for this palette (nq_lists.inc); empty view = full scans
 // sal_pixels != null: the saliency map of these n pixels is wanted in h->sc->saliency as well; *sal_done says whether it was built here
 // (beside the LAB list builders, one launch) or is left to the caller
+// d_failed != null: the hand-back count of the dither kernel this call is about to launch; *failed_cleared says whether the builders'
+// launch zeroed it (LAB with nearest lists), else launch_gilbert_fast does
 int prepare_lists(nq_handle* h, const DevParams& P, nq::ListsView* out, const int* sal_pixels = nullptr, int64_t sal_n = 0, int sal_subst = 0,
-                  bool* sal_done = nullptr) {
+                  bool* sal_done = nullptr, int* d_failed = nullptr, bool* failed_cleared = nullptr) {
     if (sal_done) *sal_done = false;
+    if (failed_cleared) *failed_cleared = false;
     out->closest = out->closestCount = out->nearest = out->nearestCount = nullptr;
     if (!h->use_lists || P.K > 256 || P.K < 8) return NQ_OK;
     const size_t LB = (size_t) 65536 * 32;
@@ -377,26 +389,35 @@ int prepare_lists(nq_handle* h, const DevParams& P, nq::ListsView* out, const in
         h->sc->cell_box_ready = true;
     }
     if (sal_pixels) NQ_HIP(h, h->sc->saliency.reserve((size_t) sal_n));
-    const bool sal_built = launch_build_lists(P, h->d_palette.p, wA, wR, wG, wB, nearest, h->sc->cell_box.p, base, base + 2 * LB, base + LB,
-                                              base + 2 * LB + 65536, h->stream, sal_pixels, sal_n, sal_pixels ? h->sc->saliency.p : nullptr, sal_subst);
-    if (sal_done) *sal_done = sal_built;
     // (a negative ratio makes the closest error non-monotone in its terms: the list argument does not hold, full scans)
     if (!(h->kind == NQ_KIND_LAB && P.ratio < 0)) { out->closest = base; out->closestCount = base + 2 * LB; }
     if (nearest) { out->nearest = base + LB; out->nearestCount = base + 2 * LB + 65536; }
-    if (h->use_fast_dither && fast_pack_wanted(P, *out)) launch_pack_lists(*out, packed_lists(h), h->stream);
+    // the packed records of the specialised kernels: written by the LAB builders themselves (NQ_PACK_IN_BUILDERS=0: by the separate
+    // launch, as for the RGB kind -- the two must agree byte for byte, tests/test_gpu_batch_plumbing.py)
+    const bool pack = h->use_fast_dither && fast_pack_wanted(P, *out);
+    bool pack_in_builders = true;
+    if (const char* e = std::getenv("NQ_PACK_IN_BUILDERS")) pack_in_builders = std::atoi(e) != 0;
+    bool folded = false;
+    const bool sal_built = launch_build_lists(P, h->d_palette.p, wA, wR, wG, wB, nearest, h->sc->cell_box.p, base, base + 2 * LB, base + LB,
+                                              base + 2 * LB + 65536, h->stream, sal_pixels, sal_n, sal_pixels ? h->sc->saliency.p : nullptr, sal_subst,
+                                              pack && pack_in_builders ? packed_lists(h) : nullptr, d_failed, &folded);
+    if (sal_done) *sal_done = sal_built;
+    if (failed_cleared) *failed_cleared = folded && d_failed;
+    if (pack && !(folded && pack_in_builders)) launch_pack_lists(*out, packed_lists(h), h->stream);
     return NQ_OK;
 }
 
 // prepare_lists of one dither pass; in a frames call (reuse_lists) the lists of the first frame serve every later frame -- same palette,
 // same params, so the same lists -- and a saliency map wanted there is left to the caller (launch_saliency)
 int lists_for_call(nq_handle* h, const DevParams& P, nq::ListsView* out, const int* sal_pixels = nullptr, int64_t sal_n = 0, int sal_subst = 0,
-                   bool* sal_done = nullptr) {
+                   bool* sal_done = nullptr, int* d_failed = nullptr, bool* failed_cleared = nullptr) {
     if (h->reuse_lists && h->lists_built) {
         if (sal_done) *sal_done = false;
+        if (failed_cleared) *failed_cleared = false;
         *out = h->saved_lv;
         return NQ_OK;
     }
-    const int rc = prepare_lists(h, P, out, sal_pixels, sal_n, sal_subst, sal_done);
+    const int rc = prepare_lists(h, P, out, sal_pixels, sal_n, sal_subst, sal_done, d_failed, failed_cleared);
     if (!rc && h->reuse_lists) { h->saved_lv = *out; h->lists_built = true; }
     return rc;
 }
@@ -527,9 +548,10 @@ int palette_prepare(nq_handle* h, const double* d_hists, int n_bands, int nMaxCo
     nq::Bins B = bins_of(h);
     int* d_maxbins = h->d_ints.p;
     launch_compact(kind, d_hists, n_bands, B, d_maxbins, h->d_ints.p + 8, h->stream);
-    int maxbins = 0;
-    NQ_HIP(h, hipMemcpyAsync(&maxbins, d_maxbins, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    int* const pin_maxbins = reinterpret_cast<int*>(h->pin + 4);
+    NQ_HIP(h, hipMemcpyAsync(pin_maxbins, d_maxbins, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
+    const int maxbins = *pin_maxbins;
     if (maxbins <= 0) NQ_FAIL(h, NQ_ERR_INVALID, "empty image");
     p.maxbins = maxbins;
     short quan_rt = 1;
@@ -645,13 +667,18 @@ int palette_prepare(nq_handle* h, const double* d_hists, int n_bands, int nMaxCo
 }
 
 // the merge loops (P9) of n prepared images in one launch per kind, on the stream of `owner`
-int merge_launch(nq_handle* owner, const PaletteJob* const* jobs, int n) {
+// order (nullable): order[j] = the index in jobs[] of the j-th job of owner->d_jobs
+int merge_launch(nq_handle* owner, const PaletteJob* const* jobs, int n, std::vector<int>* order = nullptr) {
     std::vector<nq::MergeJob> host;
     std::vector<nq_handle*> of;                             // host[i] is the job of handle of[i]
     int n_lab = 0;
+    if (order) order->clear();
     for (int pass = 1; pass >= 0; --pass) {                 // LAB jobs first, then RGB
         for (int i = 0; i < n; ++i)
-            if (jobs[i]->merge && jobs[i]->mj.np.kind == pass) { host.push_back(jobs[i]->mj); of.push_back(jobs[i]->h); }
+            if (jobs[i]->merge && jobs[i]->mj.np.kind == pass) {
+                host.push_back(jobs[i]->mj); of.push_back(jobs[i]->h);
+                if (order) order->push_back(i);
+            }
         if (pass == 1) n_lab = (int) host.size();
     }
     if (host.empty()) return NQ_OK;
@@ -778,16 +805,16 @@ int pnnquan_prepare(nq_handle* h, const uint32_t* d_argb, int width, int height,
     if (nMaxColors >= 64) {
         int rcw = reserve_palette_ws(h, n);
         if (rcw) return rcw;
-        words = launch_front((const int*) d_argb, n, d_scan3, h->sc->vals_a.p, (int) 0x00FFFFFFu, h->stream);
+        words = launch_front((const int*) d_argb, n, d_scan3, h->sc->vals_a.p, (int) 0x00FFFFFFu, h->sc->seg.p + 2 * 65536, h->stream);
     }
     if (!words) launch_prescan((const int*) d_argb, n, 0, d_scan3, h->stream);
-    long long scan3[3];
-    NQ_HIP(h, hipMemcpyAsync(scan3, d_scan3, sizeof scan3, hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipMemcpyAsync(h->pin, d_scan3, 3 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     NQ_HIP(h, hipStreamSynchronize(h->stream));
+    const long long scan3[3] = {h->pin[0], h->pin[1], h->pin[2]};
     return palette_after_scan(h, scan3, d_argb, n, nMaxColors, out_palette, out_K, job, [&](const nq::HistParams& hp, const nq::SortWorkspace& ws) {
         // (the speculative words hold 5-6-5 keys and the default transparent colour: right exactly for an image without transparency)
         const bool words_ready = words && !hp.hasSemi && !hp.hasTransp;
-        launch_histogram(h->kind, (const int*) d_argb, n, hp, ws, h->sc->hist.p, h->stream, words_ready);
+        launch_histogram(h->kind, (const int*) d_argb, n, hp, ws, h->sc->hist.p, h->stream, words_ready, /* occ_cleared by launch_front */ words_ready);
     });
 }
 
@@ -988,7 +1015,12 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
     nq::ListsView lv;
     bool sal_done = false;
     const bool want_sal = !staged && hasSal;            // (the map of THIS call's pixels; the builders and the map share one launch where they can)
-    { int rcl = lists_for_call(h, P, &lv, want_sal ? (const int*) d_argb : nullptr, n, salSubst ? 1 : 0, &sal_done); if (rcl) return rcl; }
+    // (the specialised dither kernel's hand-back list is sized here, so that the builders' launch can clear its count)
+    const bool maybe_fast = !ov.blue_only && !sequential && h->use_fast_dither && K > 32 && K <= 256;
+    bool failed_cleared = false;
+    if (maybe_fast) NQ_HIP(h, h->d_failed.reserve((size_t) T.tiles_x * T.tiles_y + 1));
+    { int rcl = lists_for_call(h, P, &lv, want_sal ? (const int*) d_argb : nullptr, n, salSubst ? 1 : 0, &sal_done, maybe_fast ? h->d_failed.p : nullptr,
+                               &failed_cleared); if (rcl) return rcl; }
     const float* d_sal = nullptr;
     if (staged) d_sal = hasSal ? ov.d_sal : nullptr;
     else if (hasSal) {
@@ -1015,7 +1047,7 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
         // production path (nq_dither_fast.hip); the tiles it cannot finish come back as a list for the generic kernel below
         NQ_HIP(h, h->d_failed.reserve((size_t) T.tiles_x * T.tiles_y + 1));
         NQ_HIP(h, launch_gilbert_fast(P, G, T, lv, (const int*) d_argb, d_sal, h->d_palette.p, (long long) seed, d_out_index,
-                                      post ? nullptr : (int*) d_out_argb, h->d_failed.p, packed_lists(h), h->stream));
+                                      post ? nullptr : (int*) d_out_argb, h->d_failed.p, packed_lists(h), h->stream, failed_cleared));
         d_tile_list = h->d_failed.p;
         h->last_dither_fast = 1;
     }
@@ -1720,21 +1752,42 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
     }
     for (int k = 1; k < L; ++k) NQ_HIP(h0, hipStreamSynchronize(lane_s[k]));          // every prepare has been issued: join before the merge launch
     (void) hipEventRecord(h0->bev[1], lane_s[0]);
-    rc = merge_launch(h0, jp.data(), n);
+    std::vector<int> order;
+    rc = merge_launch(h0, jp.data(), n, &order);
     if (rc) return rc;
     (void) hipEventRecord(h0->bev[2], lane_s[0]);
     // behind the merge launch everything runs on lane 0 again: two dither kernels side by side would only slow each other down
     for (int i = 0; i < n; ++i) { hs[i]->stream = lane_s[0]; hs[i]->sc = lane_sc[0]; }
     for (int i = 0; i < n; ++i) if (jobs[i].merge) rec(hs[i], 4);
     // every palette of the batch comes back behind ONE wait; the per-image passes then follow each other on the stream with no
-    // host round trip in between (a wait per image left the GPU idle for ~0.1 ms of every image's ~1 ms)
-    for (int i = 0; i < n; ++i)
-        if (jobs[i].merge) {
-            rc = palette_fetch(hs[i], jobs[i], out_palettes + (size_t) i * palette_stride);
-            if (rc) return batch_fail(h0, hs[i], rc);
+    // host round trip in between (a wait per image left the GPU idle for ~0.1 ms of every image's ~1 ms).  And in ONE copy: a kernel
+    // gathers every job's palette and read-back words (palette_fetch's two copies per image) into one block, which lands in page-locked
+    // memory; slot j of it belongs to image order[j].  (Stage event 5 is recorded by the image's dither pass.)
+    const size_t n_jobs = order.size();
+    size_t slot_words = 0;
+    if (n_jobs) {
+        int max_plen = 0;
+        for (int i : order) max_plen = std::max(max_plen, jobs[i].plen);
+        slot_words = 37 + ((size_t) max_plen + 1) / 2;
+        NQ_HIP(h0, h0->d_readback.reserve(n_jobs * slot_words));
+        if (h0->h_readback_words < n_jobs * slot_words) {
+            if (h0->h_readback) { (void) hipHostFree(h0->h_readback); h0->h_readback = nullptr; h0->h_readback_words = 0; }
+            NQ_HIP(h0, hipHostMalloc((void**) &h0->h_readback, n_jobs * slot_words * sizeof(long long), hipHostMallocDefault));
+            h0->h_readback_words = n_jobs * slot_words;
         }
+        nq::launch_merge_readback(h0->d_jobs.p, (int) n_jobs, h0->d_readback.p, (long long) slot_words, lane_s[0]);
+        NQ_HIP(h0, hipMemcpyAsync(h0->h_readback, h0->d_readback.p, n_jobs * slot_words * sizeof(long long), hipMemcpyDeviceToHost, lane_s[0]));
+    }
     NQ_HIP(h0, hipStreamSynchronize(lane_s[0]));
     NQ_HIP(h0, launch_status());
+    for (size_t j = 0; j < n_jobs; ++j) {
+        const int i = order[j];
+        const long long* slot = h0->h_readback + j * slot_words;
+        uint32_t* pal = out_palettes + (size_t) i * palette_stride;
+        std::memcpy(hs[i]->merge_readback, slot, sizeof hs[i]->merge_readback);
+        std::memcpy(pal, slot + 37, (size_t) jobs[i].plen * sizeof(uint32_t));
+        hs[i]->fetched_palette = pal; hs[i]->fetched_len = jobs[i].plen;       // (what palette_fetch leaves for palette_check)
+    }
     for (int i = 0; i < n; ++i)
         if (jobs[i].merge) {
             rc = palette_check(hs[i], jobs[i], out_K + i);

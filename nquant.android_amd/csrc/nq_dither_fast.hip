@@ -58,6 +58,33 @@ struct FastArgs {
 #define NQ_KO(bit) false
 #endif
 
+// how often a wavefront of the dither kernel takes its whole-wavefront fallbacks (tools/fast_counts.py builds this file with
+// -DNQ_FAST_COUNT, never the shipped library): NQ_COUNT(slot, cond) adds 1 for the wavefront when cond holds in any of its active lanes,
+// NQ_COUNT_SUM(slot, cond, v) adds v over the lanes where it holds, NQ_COUNT_MAX(slot, cond, v) the largest v among them (the trip count
+// of a loop that all lanes walk together) -- one atomic per wavefront each
+#ifdef NQ_FAST_COUNT
+enum { FC_NEAREST = 0, FC_NEAREST_EXACT, FC_NEAREST_EXACT_LANES, FC_NEAREST_EXACT_N2_SUM, FC_NEAREST_EXACT_N2_MAX, FC_NEAREST_TAIL, FC_CLOSEST,
+       FC_CLOSEST_TAIL, FC_CLOSEST_EXACT, FC_YDIFF, FC_YDIFF_F64, FC_TANH, FC_TANH_LIBRARY, FC_SLOTS = 16 };
+__device__ unsigned long long g_fast_count[FC_SLOTS];
+__device__ __forceinline__ void fast_count_add(int slot, bool cond, unsigned long long v, bool use_max) {
+    const unsigned long long active = __ballot(1), m = __ballot(cond);
+    if (!m) return;
+    unsigned long long r = 0ULL;
+    for (unsigned long long mm = m; mm; mm &= mm - 1) {          // (uniform: the lanes of m are active, their v is read lane by lane)
+        const unsigned long long o = (unsigned) __builtin_amdgcn_readlane((int) v, __ffsll((long long) mm) - 1);
+        r = use_max ? (o > r ? o : r) : r + o;
+    }
+    if ((int) (threadIdx.x & 63) == __ffsll((long long) active) - 1) atomicAdd(&g_fast_count[slot], r);
+}
+#define NQ_COUNT(slot, cond) do { if (__ballot(cond) && (int) (threadIdx.x & 63) == __ffsll((long long) __ballot(1)) - 1) atomicAdd(&g_fast_count[slot], 1ULL); } while (0)
+#define NQ_COUNT_SUM(slot, cond, v) fast_count_add(slot, cond, (unsigned long long) (v), false)
+#define NQ_COUNT_MAX(slot, cond, v) fast_count_add(slot, cond, (unsigned long long) (v), true)
+#else
+#define NQ_COUNT(slot, cond)
+#define NQ_COUNT_SUM(slot, cond, v)
+#define NQ_COUNT_MAX(slot, cond, v)
+#endif
+
 // initWeights(25) (NQ/GilbertCurve.java:336-354) as bit patterns; the host compares them with its own table
 #define NQ_FAST_W(t) __uint_as_float(k_fast_w25[t])
 static constexpr unsigned k_fast_w25[25] = {
@@ -123,6 +150,8 @@ __device__ __forceinline__ float tanh_to_float(float xf) {
     const double x = (double) xf;
     const double ax = fabs(x);
     float r;
+    NQ_COUNT(FC_TANH, true);
+    NQ_COUNT(FC_TANH_LIBRARY, ax < 0.5);
     if (ax >= 9.2) r = 1.0f;                     // 1 - tanh < 2 exp(-18.4) = 2.1e-8 < 2^-25: rounds to 1.0f
     else if (ax < 0.5) r = tanh_library(ax);     // not reached by the limiter (|e| >= ditherMax); kept for completeness
     else {
@@ -151,6 +180,7 @@ __device__ __forceinline__ float tanh_to_float(float xf) {
         const double v = 1.0 - 2.0 * t * rc;
         const float lo = (float) (v - 1e-14), hi = (float) (v + 1e-14);
         r = lo;
+        NQ_COUNT(FC_TANH_LIBRARY, lo != hi);
         if (lo != hi) r = tanh_library(ax);
     }
     return x < 0 ? -r : r;
@@ -188,6 +218,7 @@ __device__ __forceinline__ void fast_closest_step(FastClosest& t, int k, int c2,
     int F = (int) e;                                             // e >= 0, < 2^20
     const float frac = e - (float) F;
     const float delta = __builtin_fmaf(e, 9.5367431640625e-07f, 1e-6f);
+    NQ_COUNT(FC_CLOSEST_EXACT, (frac < delta || frac > 1.0f - delta) && F <= t.e1);
     if ((frac < delta || frac > 1.0f - delta) && F <= t.e1) F = (int) closest_err_exact(c2, cr, cg, cb, wr, wg, wb, ratio);
     // `if (err < closest[2]) ... else if (err < closest[3])` with int thresholds == the same tests on floor(err)
     const bool lt0 = F < t.e0, lt1 = F < t.e1;
@@ -256,6 +287,8 @@ __device__ __forceinline__ FastClosest fast_closest_tuple(const FastLds& S, cons
     const int cr = c_red(c), cg = c_green(c), cb = c_blue(c);
     const float crf = (float) cr, cgf = (float) cg, cbf = (float) cb;
     FastClosest t; t.c0 = t.c1 = 0; t.e0 = t.e1 = 2147483647;
+    NQ_COUNT(FC_CLOSEST, true);
+    NQ_COUNT(FC_CLOSEST_TAIL, n1 > 8);
     // the first eight entries straight-line (the longest list of a wavefront is ~7): their palette words are requested together,
     // no shift register, no loop control; the rare longer lists continue in the rolled loop
     {
@@ -294,6 +327,8 @@ __device__ __forceinline__ int fast_nearest32(const FastLds& S, const FastLookup
     lab32_of(c, S.gamma32, L1, A1, B1);
     float d1 = 3.0e38f, d2 = 3.0e38f;
     int k1 = X.kfirst;
+    NQ_COUNT(FC_NEAREST, true);
+    NQ_COUNT(FC_NEAREST_TAIL, n2 > 8);
     {
         int kk[8]; float4 ll[8];
 #pragma unroll
@@ -336,6 +371,10 @@ __device__ __forceinline__ int fast_nearest32(const FastLds& S, const FastLookup
 __device__ __forceinline__ int fast_nearest(const FastLds& S, const FastLookup& X, int c, uint4 na, int n2, int cell) {
     bool safe;
     int k1 = fast_nearest32(S, X, c, na, n2, cell, safe);
+    NQ_COUNT(FC_NEAREST_EXACT, !safe);
+    NQ_COUNT_SUM(FC_NEAREST_EXACT_LANES, !safe, 1);
+    NQ_COUNT_SUM(FC_NEAREST_EXACT_N2_SUM, !safe, n2);
+    NQ_COUNT_MAX(FC_NEAREST_EXACT_N2_MAX, !safe, n2);
     if (!safe) k1 = fast_nearest_exact(S, c, na, X.cont + 65536 + cell, n2, X.kfirst);
     return k1;
 }
@@ -398,6 +437,8 @@ __device__ __forceinline__ bool fast_ydiff_cmp(const FastLds& S, int c1, int c2,
     const float y2 = __builtin_fmaf(g[c_blue(c2)], 0.0722f, __builtin_fmaf(g[c_green(c2)], 0.7152f, g[c_red(c2)] * 0.2126f));
     const float yd = fabsf(y2 - y1) * 100.0f;
     const float thr32 = (float) thr;
+    NQ_COUNT(FC_YDIFF, true);
+    NQ_COUNT(FC_YDIFF_F64, !(fabsf(yd - thr32) > 1e-3f));
     if (fabsf(yd - thr32) > 1e-3f) return gt ? yd > thr32 : yd < thr32;
     const double d = Y_Diff_y(color2Y_t(c1, S.gamma), color2Y_t(c2, S.gamma));
     return gt ? d > thr : d < thr;
@@ -944,7 +985,7 @@ static FastArgs fast_args(const DevParams& P, const ListsView& lv, void* d_packe
 }
 hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv, const int* d_pixels,
                                const float* d_saliency, const int* d_palette, long long seed, unsigned short* d_index, int* d_argb,
-                               int* d_failed, void* d_packed, hipStream_t s) {
+                               int* d_failed, void* d_packed, hipStream_t s, bool failed_cleared) {
     const int ntiles = T.tiles_x * T.tiles_y;
     const int tilepx = T.tile_w * T.tile_h;
     FastArgs F = fast_args(P, lv, d_packed, s);
@@ -956,7 +997,7 @@ hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const
     if (const char* e = std::getenv("NQ_FAST_DEBUG")) F.debug = std::atoi(e);
 #endif
     F.vecOut = (T.tile_w % 4 == 0) && (T.width % 4 == 0) && ((uintptr_t) d_index % 8 == 0) && (!d_argb || (uintptr_t) d_argb % 16 == 0);
-    hipError_t e = hipMemsetAsync(d_failed, 0, sizeof(int), s);
+    hipError_t e = failed_cleared ? hipSuccess : hipMemsetAsync(d_failed, 0, sizeof(int), s);
     if (e != hipSuccess) return e;
     const size_t lds = fast_lds_bytes(tilepx, F.strideBytes);
     const int grid = (ntiles + 255) / 256;
@@ -1014,3 +1055,15 @@ void launch_fast_bluenoise(const DevParams& P, const ListsView& lv, const int* d
 }
 
 } // namespace nq
+
+#ifdef NQ_FAST_COUNT
+// counting build only: the counters since the last reset (FC_* order), read after the caller has waited for its kernels
+extern "C" int nq_fast_counts(unsigned long long* out16, int reset) {
+    hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(nq::g_fast_count), sizeof nq::g_fast_count);
+    if (e == hipSuccess && reset) {
+        const unsigned long long z[nq::FC_SLOTS] = {0};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(nq::g_fast_count), z, sizeof z);
+    }
+    return e == hipSuccess ? 0 : -1;
+}
+#endif

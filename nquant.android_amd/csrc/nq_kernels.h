@@ -59,11 +59,14 @@ void launch_cell_lab_box(float* d_box /* [65536][6] */, hipStream_t s);
 // a saliency map to build beside the LAB candidate lists (the three passes are independent; one launch, nq_dither.inc build_lab_lists_kernel)
 struct SalJob { const int* pixels; long long N; float* out; long long vec4; int salSubst; int blocks; };
 // d_sal_pixels != null: the saliency map of these N pixels is wanted too -- returns true when it went into the same launch (LAB with
-// nearest lists), false when the caller has to launch_saliency itself
+// nearest lists), false when the caller has to launch_saliency itself.
+// d_packed / d_failed (nullable): the LAB launch also writes the packed records of launch_pack_lists (both lists must be in use) and
+// zeroes d_failed[0], the hand-back count of launch_gilbert_fast; *folded says whether it did -- false: the caller launches
+// launch_pack_lists itself and launch_gilbert_fast clears the count
 bool launch_build_lists(const DevParams& P, const int* d_palette, double wA, double wR, double wG, double wB, bool nearest,
                         const float* d_box, unsigned char* d_closest, unsigned char* d_closestCount, unsigned char* d_nearest,
                         unsigned char* d_nearestCount, hipStream_t s, const int* d_sal_pixels = nullptr, int64_t N = 0, float* d_sal_out = nullptr,
-                        int salSubst = 0);
+                        int salSubst = 0, void* d_packed = nullptr, int* d_failed = nullptr, bool* folded = nullptr);
 void launch_saliency(const DevParams& P, int salSubst, const int* d_pixels, int64_t N, float* d_out, hipStream_t s);
 
 void launch_nearest_index(const DevParams& P, const int* d_palette, const ListsView& lv, const int* d_colors, int64_t M, short* d_out, hipStream_t s);
@@ -85,7 +88,8 @@ void launch_gilbert(const DevParams& P, const GilbertConsts& G, const TileGeom& 
 bool gilbert_fast_eligible(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv);
 hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv, const int* d_pixels,
                                const float* d_saliency, const int* d_palette, long long seed, unsigned short* d_index, int* d_argb,
-                               int* d_failed /* int[1 + tiles] */, void* d_packed /* 65536 x 64 bytes */, hipStream_t s);
+                               int* d_failed /* int[1 + tiles] */, void* d_packed /* 65536 x 64 bytes */, hipStream_t s,
+                               bool failed_cleared = false /* d_failed[0] was zeroed by the launch_build_lists in front of this call */);
 bool fast_lookup_eligible(const DevParams& P, const ListsView& lv);
 bool fast_pack_wanted(const DevParams& P, const ListsView& lv);     // the packed records are needed (LAB lookups, or the RGB dither kernel)
 // packs the two lists of every colour cell into the 32-byte records (+ continuations) the specialised kernels read; must follow
@@ -143,8 +147,10 @@ void launch_prescan(const int* d_pixels, int64_t n, int64_t index_offset, long l
 // pre-scan + the histogram's packed sort words (5-6-5 keys, default transparent colour) in one read of the image; false: not
 // applicable (n not a multiple of 4 / unaligned buffers) and nothing was launched.  The words are valid only if the scan then
 // reports no alpha == 0 pixel and no semi-transparency and nMaxColors >= 64 (launch_histogram(..., words_ready = true)).
+// d_occ_count (nullable): the occupied-bin counters of the SortWorkspace this image's launch_histogram will use (seg_end + 65536), cleared
+// by the same kernel -- launch_histogram(..., words_ready = true, occ_cleared = true) then issues no fill for them
 bool launch_front(const int* d_pixels, int64_t n, long long* d_scan3, int* d_words /* SortWorkspace::vals_a */, int defaultTransparent,
-                  hipStream_t s);
+                  unsigned* d_occ_count, hipStream_t s);
 // ---- the same passes over a sequence of frames read in place (nq_palette.inc frames_kernel): frame f's pixel i has the global index
 // offset + i; the work list holds (frame, chunk) items of at most NQ_FRAME_CHUNK pixels, none crossing a frame boundary ----
 struct FrameDesc { const int* pixels; long long n; long long offset; };
@@ -157,7 +163,7 @@ enum { FRAMES_SCAN = 0, FRAMES_FRONT = 1, FRAMES_KEYS = 2, FRAMES_SUBST = 3 };
 void launch_frames_pass(int op, const FrameDesc* d_frames, int n_frames, const FrameChunk* d_items, int n_items, long long* d_scan3,
                         unsigned* d_words, unsigned* d_idx, int color, int keyfmt, hipStream_t s);
 void launch_histogram(int kind, const int* d_pixels, int64_t n, const HistParams& hp, const SortWorkspace& ws,
-                      double* d_hist, hipStream_t s, bool words_ready = false);
+                      double* d_hist, hipStream_t s, bool words_ready = false, bool occ_cleared = false);
 // d_blockcnt: int[64] scratch (occupied bins per 1024-bin slice)
 void launch_compact(int kind, const double* d_hists, int n_bands, const Bins& B, int* d_maxbins, int* d_blockcnt, hipStream_t s);
 void launch_quanfn(float* d_cnt, int maxbins, int fn, hipStream_t s);
@@ -186,6 +192,9 @@ struct MergeJob {
 // attribute call / launch.  out_variant (nullable; untouched when n <= 0): {the workgroup-size code as NQ_MERGE_THREADS spells it -- 512, 256,
 // 128, or 127 for the dense variant --, helper workgroups per job} of the kernel that was launched.
 hipError_t launch_merge(int kind, const MergeJob* d_jobs, int n, int n_in_flight, int n_cus, int helpers, hipStream_t s, int* out_variant = nullptr);
+// after launch_merge on the same stream, one workgroup per job: slot j of d_out (slot_words 64-bit words each, >= 37 + (plen + 1) / 2)
+// receives the 37 words behind job j's `stats` ([36] = its status word) and, from word 37 on, its palette[plen]
+void launch_merge_readback(const MergeJob* d_jobs, int n, long long* d_out, long long slot_words, hipStream_t s);
 // helpers launch_merge would use for n jobs of one kind when n_in_flight loops share a device of n_cus compute units (0..7;
 // NQ_MERGE_HELPERS overrides).  Sized on THIS call's jobs: merge launches of other handles / threads on the same device are not
 // counted -- correctness does not depend on it (every wait of a team is bounded, nq_merge.inc), only the speed-up does.

@@ -55,7 +55,9 @@ void launch_cell_lab_box(float* d_box, hipStream_t s) {
 
 bool launch_build_lists(const DevParams& P, const int* d_palette, double wA, double wR, double wG, double wB, bool nearest,
                         const float* d_box, unsigned char* d_closest, unsigned char* d_closestCount, unsigned char* d_nearest,
-                        unsigned char* d_nearestCount, hipStream_t s, const int* d_sal_pixels, int64_t N, float* d_sal_out, int salSubst) {
+                        unsigned char* d_nearestCount, hipStream_t s, const int* d_sal_pixels, int64_t N, float* d_sal_out, int salSubst,
+                        void* d_packed, int* d_failed, bool* folded) {
+    if (folded) *folded = false;
     if (nearest && P.kind == 1) {          // LAB: both builders (and the saliency map, if one is wanted) side by side in one launch
         SalJob sal;
         std::memset(&sal, 0, sizeof sal);
@@ -67,7 +69,8 @@ bool launch_build_lists(const DevParams& P, const int* d_palette, double wA, dou
         const size_t smem = std::max(palette_smem_bytes(P.kind, P.K), (size_t) 256 * sizeof(double));
         allow_big_lds(build_lab_lists_kernel, smem);
         hipLaunchKernelGGL(build_lab_lists_kernel, dim3(2 * 65536 / 256 + sal.blocks), dim3(256), smem, s, P, d_palette,
-                           wA, wR, wG, wB, P.hasAlpha ? 1 : 0, d_box, d_closest, d_closestCount, d_nearest, d_nearestCount, sal);
+                           wA, wR, wG, wB, P.hasAlpha ? 1 : 0, d_box, d_closest, d_closestCount, d_nearest, d_nearestCount, sal, d_packed, d_failed);
+        if (folded) *folded = true;
         return sal.blocks > 0;
     }
     hipLaunchKernelGGL(build_closest_lists_kernel, dim3(65536 / 256), dim3(256), 0, s, P, d_palette,
@@ -220,11 +223,11 @@ void launch_prescan(const int* d_pixels, int64_t n, int64_t index_offset, long l
                        (long long) index_offset, d_scan3);
     hipLaunchKernelGGL(prescan_color_kernel, dim3(1), dim3(1), 0, s, d_pixels, (long long) n, (long long) index_offset, d_scan3);
 }
-bool launch_front(const int* d_pixels, int64_t n, long long* d_scan3, int* d_words, int defaultTransparent, hipStream_t s) {
+bool launch_front(const int* d_pixels, int64_t n, long long* d_scan3, int* d_words, int defaultTransparent, unsigned* d_occ_count, hipStream_t s) {
     if (n < 4 || (n & 3) || ((uintptr_t) d_pixels & 15) || ((uintptr_t) d_words & 15)) return false;
     (void) hipMemsetAsync(d_scan3, 0xFF, 3 * sizeof(long long), s);      // {-1, -1, -1}: prescan_color_kernel adds the 1 to the count
     hipLaunchKernelGGL(front_kernel, dim3(grid_for(n / 4, 256, 256 * 8)), dim3(256), 0, s, (const int4*) d_pixels, (long long) (n / 4), 0LL,
-                       d_scan3, (uint4*) d_words, defaultTransparent);
+                       d_scan3, (uint4*) d_words, defaultTransparent, d_occ_count);
     hipLaunchKernelGGL(prescan_color_kernel, dim3(1), dim3(1), 0, s, d_pixels, (long long) n, 0LL, d_scan3);
     return true;
 }
@@ -242,14 +245,17 @@ void launch_frames_pass(int op, const FrameDesc* d_frames, int n_frames, const F
     if (scan) hipLaunchKernelGGL(frames_prescan_color_kernel, dim3(1), dim3(1), 0, s, d_frames, n_frames, d_scan3);
 }
 void launch_histogram(int kind, const int* d_pixels, int64_t n, const HistParams& hp, const SortWorkspace& ws,
-                      double* d_hist, hipStream_t s, bool words_ready) {
+                      double* d_hist, hipStream_t s, bool words_ready, bool occ_cleared) {
     unsigned* const pk_a = reinterpret_cast<unsigned*>(ws.vals_a);
     unsigned* const pk_b = reinterpret_cast<unsigned*>(ws.vals_b);
-    if (!words_ready)
-        hipLaunchKernelGGL(bin_keys_kernel, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, d_pixels, (long long) n, hp, pk_a);
+    unsigned* const occ_count = ws.seg_end + 65536;             // [0] occupied bins, [1] fat bins
+    // the two counters start at zero: cleared by bin_keys_kernel, or by the launch_front whose words are used (occ_cleared), else by a fill
+    if (!words_ready) {
+        hipLaunchKernelGGL(bin_keys_kernel, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, d_pixels, (long long) n, hp, pk_a, occ_count);
+        occ_cleared = true;
+    }
     size_t tmp = ws.tmp_bytes;
     (void) rocprim::radix_sort_keys<HistSortConfig>(ws.tmp, tmp, (const unsigned*) pk_a, pk_b, (size_t) n, 16, 32, s);
-    unsigned* const occ_count = ws.seg_end + 65536;             // [0] occupied bins, [1] fat bins
     unsigned* const occ_list = occ_count + 64;
     unsigned* const fat_list = occ_list + 65536;                // [NQ_FAT_CAP]
     // RGB kind: a bin is "fat" (a workgroup of its own, hist_fat_rgb_kernel) from 16 384 pixels up; never more than NQ_FAT_CAP - 1 of them
@@ -259,7 +265,7 @@ void launch_histogram(int kind, const int* d_pixels, int64_t n, const HistParams
         if (const char* f = std::getenv("NQ_HIST_FAT_MIN")) { const long t = std::atol(f); if (t >= 1) fat_min = (unsigned) std::min<long>(t, 0x7FFFFFFFL); }
         fat_min = std::max(fat_min, (unsigned) (n / NQ_FAT_CAP) + 1u);
     }
-    (void) hipMemsetAsync(occ_count, 0, 2 * sizeof(unsigned), s);
+    if (!occ_cleared) (void) hipMemsetAsync(occ_count, 0, 2 * sizeof(unsigned), s);
     hipLaunchKernelGGL(occupied_bins_kernel, dim3(64), dim3(1024), 0, s, (const unsigned*) pk_b, (unsigned) n, ws.seg_start, ws.seg_end, occ_count, occ_list, d_hist,
                        fat_min, fat_list);
     const int keyfmt = hp.hasSemi ? 2 : hp.hasTransp ? 1 : 0;          // getColorIndex: 4-4-4-4 / 1-5-5-5 / 5-6-5
@@ -367,5 +373,21 @@ hipError_t launch_merge(int kind, const MergeJob* d_jobs, int n, int n_in_flight
         return launch_merge_variant(m128::merge_kernel<1, false, false>, sizeof(m128::MergeLds), 128, d_jobs, n, s);
     }
     return launch_merge_variant(m128::merge_kernel<0, false, false>, sizeof(m128::MergeLds), 128, d_jobs, n, s);
+}
+// what a batch reads back of its merge jobs, gathered into one block (one copy to the host instead of two per image)
+__global__ void __launch_bounds__(64) merge_readback_kernel(const MergeJob* __restrict__ jobs, int n, long long* __restrict__ out, long long slot_words) {
+    const int j = blockIdx.x;
+    if (j >= n) return;
+    const long long* __restrict__ stats = jobs[j].stats;
+    const int* __restrict__ palette = jobs[j].palette;
+    const int plen = jobs[j].plen;
+    long long* o = out + (size_t) j * slot_words;
+    if (threadIdx.x < 37) o[threadIdx.x] = stats[threadIdx.x];
+    int* op = reinterpret_cast<int*>(o + 37);
+    for (int t = threadIdx.x; t < plen; t += blockDim.x) op[t] = palette[t];
+}
+void launch_merge_readback(const MergeJob* d_jobs, int n, long long* d_out, long long slot_words, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(merge_readback_kernel, dim3(n), dim3(64), 0, s, d_jobs, n, d_out, slot_words);
 }
 } // namespace nq

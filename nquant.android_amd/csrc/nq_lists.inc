@@ -34,6 +34,17 @@ __device__ __forceinline__ void list_store(unsigned char* out, const unsigned lo
     ulonglong2* o = reinterpret_cast<ulonglong2*>(out);
     o[0] = make_ulonglong2(acc[0], acc[1]); o[1] = make_ulonglong2(acc[2], acc[3]);
 }
+// The cell's half of the 32-byte record the specialised kernels read (half 0: closest, 1: nearest) and its continuation entry, in the layout of
+// pack_lists_kernel (nq_dither_fast.hip): bytes 0..14 the first candidates, byte 15 their number, candidates 15..30 in cont[half][cell]; a
+// cell whose count is above 31 (32 entries, or NQ_LIST_FULLSCAN) gets 255 and zeros.  acc holds zeros behind the list's last entry, so the
+// zero padding is the accumulator's own.  packed: [65536][2] records followed by the [2][65536] continuation entries (16 bytes each).
+__device__ __forceinline__ void list_store_packed(void* packed, int half, int cell, const unsigned long long (&acc)[4], int count) {
+    ulonglong2* rec = reinterpret_cast<ulonglong2*>(packed);
+    const bool ok = count <= 31;
+    const unsigned long long top = (unsigned long long) (ok ? count : 255) << 56;
+    rec[2 * cell + half] = ok ? make_ulonglong2(acc[0], (acc[1] & 0x00FFFFFFFFFFFFFFULL) | top) : make_ulonglong2(0ULL, top);
+    rec[2 * 65536 + half * 65536 + cell] = ok ? make_ulonglong2((acc[1] >> 56) | (acc[2] << 8), (acc[2] >> 56) | (acc[3] << 8)) : make_ulonglong2(0ULL, 0ULL);
+}
 __device__ __forceinline__ float rl_f(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
 // the two smallest values of the wavefront's (m1 <= m2) pairs, in every lane
 __device__ __forceinline__ void wave_two_smallest(float& m1, float& m2) {
@@ -48,7 +59,7 @@ __device__ __forceinline__ void wave_two_smallest(float& m1, float& m2) {
 // closest-error lists.  weights W[4] = total weight of da^2, dr^2, dg^2, db^2 in err
 __device__ __forceinline__ void closest_lists_body(const DevParams& P, const int* __restrict__ g_palette, double wA, double wR,
                                                    double wG, double wB, unsigned char* __restrict__ lists,
-                                                   unsigned char* __restrict__ counts, int block) {
+                                                   unsigned char* __restrict__ counts, int block, void* packed = nullptr) {
     // in the per-cell scans the palette index k is uniform over the wavefront: g_palette[k] is a scalar load and its channels are
     // unpacked on the scalar unit -- the vector ALUs only see the per-cell arithmetic
     const int* __restrict__ pal = g_palette;
@@ -128,7 +139,9 @@ __device__ __forceinline__ void closest_lists_body(const DevParams& P, const int
         }
     }
     list_store(out, acc);
-    counts[cell] = (K > 256 || n > NQ_LIST_CAP) ? NQ_LIST_FULLSCAN : (unsigned char) n;
+    const int count = (K > 256 || n > NQ_LIST_CAP) ? NQ_LIST_FULLSCAN : n;
+    counts[cell] = (unsigned char) count;
+    if (packed) list_store_packed(packed, 0, cell, acc, count);
 }
 __global__ void __launch_bounds__(256) build_closest_lists_kernel(DevParams P, const int* __restrict__ g_palette, double wA, double wR,
                                                                   double wG, double wB, unsigned char* __restrict__ lists,
@@ -201,7 +214,8 @@ __global__ void __launch_bounds__(256) cell_lab_box_kernel(float* __restrict__ b
 // start index use the full scan.
 __device__ __forceinline__ void nearest_lists_body(const DevParams& P, const int* __restrict__ g_palette, int kstart,
                                                    const float* __restrict__ box,
-                                                   unsigned char* __restrict__ lists, unsigned char* __restrict__ counts, int block, unsigned char* smem) {
+                                                   unsigned char* __restrict__ lists, unsigned char* __restrict__ counts, int block, unsigned char* smem,
+                                                   void* packed = nullptr) {
     PalView pal = stage_palette(P, g_palette, smem);
     const int lane = threadIdx.x & 63;
     const int wave_global = (block * (int) blockDim.x + (int) threadIdx.x) >> 6;
@@ -277,7 +291,9 @@ __device__ __forceinline__ void nearest_lists_body(const DevParams& P, const int
         }
     }
     list_store(out, acc);
-    counts[cell] = (K > 256 || n > NQ_LIST_CAP) ? NQ_LIST_FULLSCAN : (unsigned char) n;
+    const int count = (K > 256 || n > NQ_LIST_CAP) ? NQ_LIST_FULLSCAN : n;
+    counts[cell] = (unsigned char) count;
+    if (packed) list_store_packed(packed, 1, cell, acc, count);
 }
 __global__ void __launch_bounds__(256) build_nearest_lists_kernel(DevParams P, const int* __restrict__ g_palette, int kstart,
                                                                   const float* __restrict__ box,

@@ -41,8 +41,11 @@ __device__ __forceinline__ unsigned pack_bin_pixel(int c, int keyfmt);         /
 // semi-transparent, nMaxColors >= 64: 5-6-5 keys, pixels with alpha <= 15 read as the default m_transparentColor).  Which configuration
 // the image has is only known once the scan is complete, so the words are written speculatively: the caller uses them when scan3 says
 // the image is of that kind and runs bin_keys_kernel otherwise.  Four pixels per lane (16-byte accesses).
+// occ_zero (nullable): the two counters occupied_bins_kernel adds to later on this stream are cleared here (one fill per image less).
 __global__ void __launch_bounds__(256) front_kernel(const int4* __restrict__ pixels4, long long n4, long long index_offset,
-                                                    long long* __restrict__ scan3, uint4* __restrict__ packed4, int defaultTransparent) {
+                                                    long long* __restrict__ scan3, uint4* __restrict__ packed4, int defaultTransparent,
+                                                    unsigned* __restrict__ occ_zero) {
+    if (occ_zero && blockIdx.x == 0 && threadIdx.x == 0) { occ_zero[0] = 0u; occ_zero[1] = 0u; }
     long long maxIdx = -1, semi = 0;
     for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long) gridDim.x * blockDim.x) {
         const int4 v = pixels4[i];
@@ -108,7 +111,9 @@ __device__ __forceinline__ int unpack_bin_pixel(unsigned w, int keyfmt) {
     }
     return c_argb((int) a, (int) r, (int) g, (int) b);
 }
-__global__ void __launch_bounds__(256) bin_keys_kernel(const int* __restrict__ pixels, long long n, HistParams hp, unsigned* __restrict__ packed) {
+__global__ void __launch_bounds__(256) bin_keys_kernel(const int* __restrict__ pixels, long long n, HistParams hp, unsigned* __restrict__ packed,
+                                                       unsigned* __restrict__ occ_zero /* occupied_bins_kernel's two counters: cleared here */) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { occ_zero[0] = 0u; occ_zero[1] = 0u; }
     const int keyfmt = hp.hasSemi ? 2 : hp.hasTransp ? 1 : 0;
     for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x) {
         int pixel = pixels[i];
