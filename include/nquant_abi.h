@@ -569,6 +569,48 @@ int nq_convert_frames_refined(nq_handle* h, int n, const uint32_t* const* argb, 
                               uint32_t* const* out_argb, uint16_t* const* out_index,
                               uint32_t* out_palette, int32_t* out_K);
 
+/* ---- frame reduction: crop a sequence of ARGB_8888 frames and area-average it down to the size of the file, in front of everything
+ *      above (gifski --width, ffmpeg scale= before palettegen).  Averaging is in linear light (or, on request, in stored values), alpha
+ *      is premultiplied while averaging, and all arithmetic is integer: the result is deterministic and can be restated bit for bit.
+ *  * Inputs: n frames of src_width x src_height words, rows contiguous; a crop rectangle (crop_x, crop_y, crop_w, crop_h) inside each
+ *    frame; a target size dst_width x dst_height with 1 <= dst_width <= crop_w and 1 <= dst_height <= crop_h (this is a reducer:
+ *    enlarging is refused); flags: bit 0 is NQ_RESAMPLE_LINEAR.  Write cw, ch, dw, dh for the crop's and the target's sides.  All of
+ *    the following are exact integers, unsigned 64-bit where sums are formed.
+ *  * Table T[v], v = 0..255.  With NQ_RESAMPLE_LINEAR, T is the 256-entry table of include/nq_srgb_linear_16.inc:
+ *    L[v] = floor(65535 f(v / 255) + 0.5), f the sRGB decoding function (c / 12.92 for c <= 0.04045, else ((c + 0.055) / 1.055)^2.4);
+ *    strictly increasing, L[0..3] = 0, 20, 40, 60, L[254] = 64952, L[255] = 65535; the committed file is the normative one.  Without
+ *    the flag T[v] = 257 v.
+ *  * Weights.  Output column x covers [x cw, (x + 1) cw) on an axis where source column j of the crop covers [j dw, (j + 1) dw);
+ *    wx(x, j) is the length of the overlap, nonzero for j = floor(x cw / dw) .. floor(((x + 1) cw - 1) / dw); the weights of one x sum
+ *    to cw.  Every product is at most 65535^2 < 2^32 (an unsigned 32-bit word, not a signed one).  wy(y, i) likewise with ch, dh.
+ *    W = cw ch.
+ *  * Sums of output pixel (x, y) over its footprint, with a, r, g, b the channels of source pixel (crop_x + j, crop_y + i):
+ *        S_a = sum of wx wy a            S_c = sum of wx wy T[c] a    for c = r, g, b        (S_c <= W 65535 255 < 2^56)
+ *  * Output: S_a = 0 gives 0x00000000.  Otherwise A = floor((2 S_a + W) / (2 W)); per channel t = floor((2 S_c + S_a) / (2 S_a)) and
+ *    the stored value is the smallest v with 2 t <= T[v] + T[v + 1], or 255 if there is none (the nearest table entry, ties to the
+ *    smaller); the word is A << 24 | r << 16 | g << 8 | b.  A transparent source pixel contributes nothing to the colour.
+ *    Consequences: with dw = cw and dh = ch the call copies the crop exactly for every pixel with a > 0 (a = 0 becomes 0), in both
+ *    modes; opaque input gives A = 255 everywhere.
+ *  * nq_resample_frames_device: d_src and d_dst are host arrays of n DEVICE pointers; the call is asynchronous on the handle's
+ *    stream.  Sources are never written; nothing outside the n dw dh output words is written.  Pointers need 4-byte alignment; when
+ *    every source pointer is 16-byte aligned and src_width is a multiple of 4 the kernel reads 16 bytes per access (any crop_x),
+ *    otherwise one pixel per access, with the same results.  h may be a handle of either kind: its stream, scratch and error text are
+ *    used, its params are neither read nor changed.
+ *    nq_resample_frames: the same with HOST buffers (the frames are uploaded, the device form runs, the n outputs are copied back; the
+ *    call returns when they are there).
+ *  * NQ_ERR_INVALID before any device work, every buffer untouched, the handle still usable: n < 1, a source side outside 1..65535, a
+ *    crop that is empty or leaves the frame, a target side < 1 or larger than the crop's, unknown flag bits, a NULL pointer array or
+ *    entry, a pointer that is not 4-byte aligned, n src_width src_height above 2^31 - 1, an output that overlaps any source frame or
+ *    another output.
+ *  The kernel: DESIGN.md 5e "Frame reduction". ---- */
+#define NQ_RESAMPLE_LINEAR 1
+int nq_resample_frames_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_width, int src_height,
+                              int crop_x, int crop_y, int crop_w, int crop_h,
+                              uint32_t* const* d_dst, int dst_width, int dst_height, int flags);
+int nq_resample_frames(nq_handle* h, int n, const uint32_t* const* src, int src_width, int src_height,
+                       int crop_x, int crop_y, int crop_w, int crop_h,
+                       uint32_t* const* dst, int dst_width, int dst_height, int flags);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

@@ -266,6 +266,10 @@ struct nq_handle {
     DevBuf<nq::RefineFrame> d_refine_frames;
     std::vector<unsigned long long> h_refine;
     DevBuf<unsigned long long> d_refine;
+    // nq_resample_frames_device: the tables of frame pointers (source, output: n each; the host copy stays alive for the asynchronous
+    // upload); nq_resample_frames stages its frames in d_in and their reductions in d_out_argb
+    std::vector<void*> h_resample_ptrs;
+    DevBuf<void*> resample_ptrs;
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
@@ -3224,6 +3228,111 @@ int nq_refine_palette_device(nq_handle* h, int n, const uint32_t* const* d_argb,
 int nq_refine_palette(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
                       uint32_t* io_palette, int K, int iterations, int64_t* out_sse, int64_t* out_counts, int32_t* out_passes) {
     return refine_call(h, true, n, argb, widths, heights, io_palette, K, iterations, out_sse, out_counts, out_passes);
+}
+
+} // extern "C"
+
+// ---- frame reduction (nq_resample.hip) ----
+namespace {
+
+// every argument of both forms, from the host arrays alone (no device work)
+int resample_check(nq_handle* h, int n, const uint32_t* const* src, int src_width, int src_height, int crop_x, int crop_y, int crop_w,
+                   int crop_h, uint32_t* const* dst, int dst_width, int dst_height, int flags) {
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    if (src_width < 1 || src_width > 65535 || src_height < 1 || src_height > 65535)
+        NQ_FAIL(h, NQ_ERR_INVALID, "%d x %d: source sides must be 1..65535", src_width, src_height);
+    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > src_width - crop_w || crop_y > src_height - crop_h)
+        NQ_FAIL(h, NQ_ERR_INVALID, "crop %d x %d at (%d, %d): empty or outside the %d x %d frame", crop_w, crop_h, crop_x, crop_y, src_width,
+                src_height);
+    if (dst_width < 1 || dst_width > crop_w || dst_height < 1 || dst_height > crop_h)
+        NQ_FAIL(h, NQ_ERR_INVALID, "target %d x %d: sides must be 1 .. the crop's (%d x %d); this call only reduces", dst_width, dst_height,
+                crop_w, crop_h);
+    if (flags & ~NQ_RESAMPLE_LINEAR) NQ_FAIL(h, NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) flags);
+    if ((long long) n * src_width * src_height > 2147483647ll)
+        NQ_FAIL(h, NQ_ERR_INVALID, "%d frames of %d x %d: more than 2^31 - 1 pixels", n, src_width, src_height);
+    if (!src || !dst) NQ_FAIL(h, NQ_ERR_INVALID, "the array of source / output pointers is NULL");
+    for (int i = 0; i < n; ++i) {
+        if (!src[i] || ((uintptr_t) src[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: source pointer NULL or not 4-byte aligned", i);
+        if (!dst[i] || ((uintptr_t) dst[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: output pointer NULL or not 4-byte aligned", i);
+    }
+    // no output may overlap a source frame or another output: in the order of their first bytes, a buffer overlaps an earlier one
+    // exactly when it begins before the furthest end seen so far
+    struct Span { uintptr_t begin, end; bool out; };
+    std::vector<Span> spans;
+    spans.reserve(2 * (size_t) n);
+    const uintptr_t src_bytes = (uintptr_t) src_width * src_height * sizeof(uint32_t), dst_bytes = (uintptr_t) dst_width * dst_height * sizeof(uint32_t);
+    for (int i = 0; i < n; ++i) {
+        spans.push_back({(uintptr_t) src[i], (uintptr_t) src[i] + src_bytes, false});
+        spans.push_back({(uintptr_t) dst[i], (uintptr_t) dst[i] + dst_bytes, true});
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.begin < b.begin; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const Span& sp : spans) {
+        if (sp.begin < (sp.out ? end_any : end_out)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source frame or another output");
+        end_any = std::max(end_any, sp.end);
+        if (sp.out) end_out = std::max(end_out, sp.end);
+    }
+    return NQ_OK;
+}
+
+// nq_resample_frames_device after the checks: the pointer tables go up, one launch reduces the sequence
+int resample_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_width, int crop_x, int crop_y, int crop_w, int crop_h,
+                    uint32_t* const* d_dst, int dst_width, int dst_height, int flags) {
+    std::vector<void*>& t = h->h_resample_ptrs;
+    t.assign(2 * (size_t) n, nullptr);
+    bool vec = src_width % 4 == 0;                  // the 16-byte path needs every row of every source aligned to it
+    for (int i = 0; i < n; ++i) {
+        t[i] = const_cast<uint32_t*>(d_src[i]); t[n + (size_t) i] = d_dst[i];     // (the kernel reads the sources only)
+        vec = vec && !((uintptr_t) d_src[i] & 15);
+    }
+    NQ_HIP(h, h->resample_ptrs.reserve(t.size()));
+    // (the call returns with this upload only enqueued: safe for the reason given in hold_device)
+    NQ_HIP(h, hipMemcpyAsync(h->resample_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+    launch_resample(reinterpret_cast<const unsigned* const*>(h->resample_ptrs.p), reinterpret_cast<unsigned* const*>(h->resample_ptrs.p + n), n,
+                    src_width, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, (flags & NQ_RESAMPLE_LINEAR) != 0, vec, h->stream);
+    NQ_HIP(h, launch_status());
+    return NQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_resample_frames_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_width, int src_height, int crop_x, int crop_y,
+                              int crop_w, int crop_h, uint32_t* const* d_dst, int dst_width, int dst_height, int flags) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = resample_check(h, n, d_src, src_width, src_height, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return resample_device(h, n, d_src, src_width, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+}
+
+int nq_resample_frames(nq_handle* h, int n, const uint32_t* const* src, int src_width, int src_height, int crop_x, int crop_y, int crop_w,
+                       int crop_h, uint32_t* const* dst, int dst_width, int dst_height, int flags) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = resample_check(h, n, src, src_width, src_height, crop_x, crop_y, crop_w, crop_h, dst, dst_width, dst_height, flags);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    // frames and outputs lie a multiple of 4 elements apart in the staging buffers, so that every frame starts 16-byte aligned
+    const size_t spx = (size_t) src_width * src_height, spitch = (spx + 3) & ~(size_t) 3;
+    const size_t dpx = (size_t) dst_width * dst_height, dpitch = (dpx + 3) & ~(size_t) 3;
+    return host_form(h, [&]() -> int {
+        NQ_HIP(h, h->d_in.reserve(n * spitch));
+        NQ_HIP(h, h->d_out_argb.reserve(n * dpitch));
+        std::vector<const uint32_t*> d_src(n);
+        std::vector<uint32_t*> d_dst(n);
+        for (int i = 0; i < n; ++i) {
+            d_src[i] = h->d_in.p + i * spitch; d_dst[i] = h->d_out_argb.p + i * dpitch;
+            NQ_HIP(h, hipMemcpyAsync(h->d_in.p + i * spitch, src[i], spx * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        }
+        const int rc2 = resample_device(h, n, d_src.data(), src_width, crop_x, crop_y, crop_w, crop_h, d_dst.data(), dst_width, dst_height, flags);
+        if (rc2) return rc2;
+        for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dst[i], d_dst[i], dpx * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        NQ_HIP(h, hipStreamSynchronize(h->stream));
+        return NQ_OK;
+    });
 }
 
 } // extern "C"

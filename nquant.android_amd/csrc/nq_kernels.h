@@ -322,4 +322,12 @@ enum {
 void launch_refine(const RefineFrame* d_frames, int n, long long total, bool vec, int cus, int K, int iterations, unsigned long long* d_state,
                    hipStream_t s);
 
+// ---- frame reduction (nq_resample.hip): d_src / d_dst are device arrays of n frame pointers (src_width pixels per source row, never
+// written; dst_width * dst_height pixels per output).  The crop (crop_x, crop_y, crop_w, crop_h) of every source is area-averaged to
+// dst_width x dst_height (1 <= dst <= crop on both sides) in one launch, by the integer rule of include/nquant_abi.h "frame reduction";
+// linear: through the sRGB table, else in stored values.  vec: the 16-byte path -- the caller has checked that EVERY source pointer is
+// 16-byte aligned and src_width is a multiple of 4; otherwise one pixel per access (4-byte alignment).  Outputs need 4-byte alignment. ----
+void launch_resample(const unsigned* const* d_src, unsigned* const* d_dst, int n, int src_width, int crop_x, int crop_y, int crop_w,
+                     int crop_h, int dst_width, int dst_height, bool linear, bool vec, hipStream_t s);
+
 } // namespace nq

@@ -300,13 +300,15 @@ def _shots(shot_starts, n):
 
 
 def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0,
-                         mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, delta=True):
+                         mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None,
+                         linear_resample=True, delta=True):
     """One palette per shot: frames shot_starts[k] .. shot_starts[k + 1] - 1 are shot k and get a convert_frames palette of their own
     (shot_starts=range(n): one palette per frame), then encode_gif_local_delta (delta=False: encode_gif_local) writes all frames, each
     with its shot's palette as its local colour table.  hold (delta=True only) runs per shot and never across a cut: a held index means
     nothing under another table.  seeds, tile, lossy as for convert_frames_to_gif; refine (0..64) runs that many k-means passes
-    (refine.py) on every shot's palette over that shot's frames.  Everything runs on one handle.  Cuts are the
-    caller's to give here; convert_clip_to_gif finds them.  Returns (file bytes, list of per-shot palettes)."""
+    (refine.py) on every shot's palette over that shot's frames.  size / crop / linear_resample as for convert_frames_to_gif.
+    Everything runs on one handle.  Cuts are the caller's to give here; convert_clip_to_gif finds them.
+    Returns (file bytes, list of per-shot palettes)."""
     lossy = _lossy_keyword(lossy)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
@@ -322,6 +324,9 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
         hold = _threshold(hold)
     frames, q = _frames_quantizer(kind, frames, device, mode, tile)
     try:
+        if size is not None or crop is not None:
+            from .resample import _resample_host
+            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
         return _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine)
     finally:
         q.close()
@@ -355,10 +360,12 @@ def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segm
 
 
 def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, delays_cs=None, loop=0, segment_pixels=0, device=0,
-                        mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, delta=True):
+                        mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None,
+                        linear_resample=True, delta=True):
     """A list of frames in, an animation out: detect_shots (shots.py; cut in per mille, min_shot in frames) finds where the clip needs
     a new palette, then exactly convert_shots_to_gif with those starts -- both on one handle.  The frames must have one size (delta or
-    not: a signature is compared between frames of one size).  Keywords otherwise as for convert_shots_to_gif.
+    not: a signature is compared between frames of one size).  With size or crop the frames are reduced first (resample.py) and the
+    shots are detected on the result.  Keywords otherwise as for convert_shots_to_gif.
     Returns (file bytes, list of per-shot palettes, shot_starts)."""
     lossy = _lossy_keyword(lossy)
     if not 1 <= int(nMaxColors) <= 256:
@@ -375,6 +382,9 @@ def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, de
     from .shots import _detect_host
     frames, q = _frames_quantizer(kind, frames, device, mode, tile)
     try:
+        if size is not None or crop is not None:
+            from .resample import _resample_host
+            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
         starts, _ = _detect_host(q._L, q._h, q._check, frames, cut, min_shot)
         data, palettes = _shots_to_gif_on(q, frames, _shots(starts, len(frames)), nMaxColors, dither, delays_cs, loop, segment_pixels, mode,
                                           seeds, hold, lossy, delta, refine)
@@ -401,7 +411,7 @@ def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, 
 
 
 def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
-                          seeds=None, tile=None, hold=None, lossy=0, refine=0, delta=False):
+                          seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None, linear_resample=True, delta=False):
     """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
     delta=True: encode_gif_delta instead; the frames must have one size.  Seeds are passed on as given: regions that do not move repeat
     in the index maps, and so drop out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.
@@ -411,6 +421,9 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
     lossy: as for encode_gif, applied to whichever encoder runs (with hold: on that same handle).
     refine (0..64): that many k-means passes on the palette over the frames before the dither (refine.py, convert_frames_refined);
     0 is the call without it.
+    size / crop / linear_resample: with size=(width, height) or crop=(x, y, width, height) given, the frames (then all of one size)
+    are first cropped and area-averaged down to `size` (None: the crop's size) as resample_frames does it (resample.py; in linear
+    light unless linear_resample=False), and everything else runs on the result, all on one handle.
     Returns (file bytes, palette)."""
     lossy = _lossy_keyword(lossy)
     if not 1 <= int(nMaxColors) <= 256:
@@ -419,6 +432,29 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
         raise ValueError("hold needs delta=True: full frames store every pixel whether it repeats or not")
     if delta and len({np.asarray(f).shape for f in frames}) > 1:
         raise ValueError("delta mode: all frames must have one size")
+    if size is not None or crop is not None:
+        from .resample import _resample_host
+        if hold is not None:
+            from .hold import _hold_host, _threshold
+            hold = _threshold(hold)
+        frames, q = _frames_quantizer(kind, frames, device, mode, tile)
+        try:
+            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
+            palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None)
+            maps = _index_maps([o.index for o in outs])
+            height, width = _one_size(maps)
+            if hold is not None:
+                _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
+            ptrs = [a.ctypes.data for a in maps]
+            if delta:
+                data, _ = _encode_delta(q._L, q._h, "nq_encode_gif_delta", ptrs, width, height, palette, delays_cs, loop, segment_pixels,
+                                        q._check, lossy)
+            else:
+                data = _encode(q._L, q._h, "nq_encode_gif", ptrs, np.array([width] * len(maps), np.int32),
+                               np.array([height] * len(maps), np.int32), palette, delays_cs, loop, segment_pixels, q._check, lossy)
+        finally:
+            q.close()
+        return data, palette
     if hold is not None:
         from .hold import _hold_host, _threshold
         hold = _threshold(hold)

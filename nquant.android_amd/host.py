@@ -114,6 +114,8 @@ _ABI = {
     "nq_refine_palette": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _pi32]),
     "nq_convert_frames_refined_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pi32]),
     "nq_convert_frames_refined": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pi32]),
+    "nq_resample_frames_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32]),
+    "nq_resample_frames": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32]),
 }
 
 
