@@ -611,6 +611,75 @@ int nq_resample_frames(nq_handle* h, int n, const uint32_t* const* src, int src_
                        int crop_x, int crop_y, int crop_w, int crop_h,
                        uint32_t* const* dst, int dst_width, int dst_height, int flags);
 
+/* ---- ordered dither: a positional dither for frame sequences (ffmpeg paletteuse=dither=bayer, ImageMagick -ordered-dither).  The
+ *      index of a pixel depends on its colour, its coordinates and the palette only -- not on any other pixel, as in the Gilbert-curve
+ *      error diffusion of the convert calls.  An unchanged pixel gives an unchanged index in every frame, at any tile size, with no
+ *      seeds, and the pattern is stationary in time.  It is the positional form of what the reference's closestColorIndex does with
+ *      Random: choose between the two closest entries in proportion to where the pixel lies between them.  Opt-in: no other entry
+ *      point's results change.  All arithmetic is integer.
+ *  * Inputs: n ARGB_8888 frames, each with its own width and height (as for nq_convert_frames); a palette of K entries (1..256) in
+ *    HOST memory, only read; limit in 0..255.
+ *  * Terms as in "palette refinement": the channels of a colour are a, r, g, b (shifts 24, 16, 8, 0);
+ *    d(p, c) = da^2 + dr^2 + dg^2 + db^2; a palette entry with a != 0 is LIVE; T = the first entry with a = 0, or -1 when there is none.
+ *  * A pixel with a = 0 while T >= 0 gets index T and is NOT COUNTED in the statistics.  Every other pixel is COUNTED:
+ *        with no live entry it gets index T (T = 0 then);
+ *        otherwise, over the live entries j, key(j) = (d(p, P[j]) << 8) | j
+ *            i1 = the j of the smallest key
+ *            i2 = the j of the smallest key among the live j != i1 (there is none when one entry is live)
+ *            d1, d2 = their distances, D = d2 - d1 >= 0
+ *  * Mask: m = mask[(y & 63) * 64 + (x & 63)] + 128, in 0..255, with mask the 4096 signed bytes of include/nq_blue_noise_64x64.inc
+ *    (every value -128..127 occurs exactly 16 times) and x, y the pixel's column and row in its own frame.  The same mask is used in
+ *    every frame.
+ *  * Choice: the pixel takes i2 iff ALL of
+ *        limit > 0;  i2 exists;
+ *        the largest |difference| of the four channels of P[i1] and P[i2] is <= limit;
+ *        (255 - 2 m) * den > 256 * D,   den = d(P[i1], P[i2]);
+ *    otherwise it takes i1.
+ *  * Why that inequality: with num = (p - P[i1]).(P[i2] - P[i1]) and t = num / den, the position of p's projection on the segment
+ *    from P[i1] to P[i2] (t <= 1/2, since i1 is the nearer), D = den - 2 num.  The inequality is therefore t > (2 m + 1) / 512: i2 is
+ *    chosen at a share t of the positions.  A pixel beyond i1 (t <= 0) never takes i2; duplicate entries (den = 0) are never mixed;
+ *    every product stays below 2^31 (|255 - 2 m| <= 255, den and D <= 260 100).
+ *  * Outputs: out_index[i][p] = the entry taken; out_argb[i][p] (optional) = the palette word of that entry.
+ *    out_stats (optional, HOST memory, 2 n int64 values): stats[2 i] = the counted pixels of frame i that took i2,
+ *    stats[2 i + 1] = the sum over frame i's counted pixels of d(p, the entry taken).  Integer sums: deterministic.
+ *  * Consequences: limit = 0 is the plain nearest entry (the assignment of "palette refinement").  Every pixel shows i1, or an entry
+ *    within `limit` per channel of i1: the metric of the temporal hold's threshold and the GIF encoders' lossy mode, on purpose.
+ *    Equal pixels at equal coordinates give equal indices, whatever else is in the frames.
+ *  * What it does not do: a source pixel that moves by one level can still flip an index near a threshold, so noisy footage still wants
+ *    the temporal hold.
+ *  * nq_dither_ordered_device: the frames and outputs in DEVICE memory; d_argb, d_out_argb, d_out_index are host arrays of n device
+ *    pointers.  d_out_argb may be NULL as a whole (no ARGB output), d_out_index may not.  ARGB pointers need 4-byte, index pointers
+ *    2-byte alignment; when every source and ARGB output is 16-byte and every index map 8-byte aligned the kernel handles four pixels
+ *    per access, otherwise one (same results).  The sources are never written and nothing outside the n * width * height elements of
+ *    any output is written.  With out_stats == NULL the call is asynchronous on the handle's stream; otherwise it returns when the
+ *    statistics are there.  h may be a handle of either kind: its stream, scratch and error text are used, its params are neither
+ *    read nor changed.  nq_dither_ordered: the same with HOST buffers (the frames are uploaded, the device form runs, index maps and
+ *    outputs are copied back).
+ *  * nq_convert_frames_ordered_device / nq_convert_frames_ordered: (1) palette and params of nq_pnnquan_frames_device (out_palette
+ *    has room for max(nMaxColors, 2) entries), (2) `refine` passes of nq_refine_palette_device over the same frames (0: none), (3) the
+ *    call above with that palette and no statistics.  The results equal those three calls made one after another.  The call returns
+ *    when the outputs are written.
+ *  * NQ_ERR_INVALID before any device work, every buffer untouched, the handle still usable: n < 1, a side outside 1..65535, more
+ *    than 2^31 - 1 pixels in total, K outside 1..256, limit outside 0..255, in the convert forms nMaxColors outside 1..256 or refine
+ *    outside 0..64, a NULL pointer array, entry, palette (out_palette, out_K) or index array, an ARGB pointer that is not 4-byte
+ *    aligned, an index pointer that is not 2-byte aligned, an output that overlaps a source frame or another output.  A NULL handle
+ *    is refused the same way.
+ *  The kernel: DESIGN.md 5f "Ordered dither". ---- */
+int nq_dither_ordered_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             const uint32_t* palette, int K, int limit,
+                             uint32_t* const* d_out_argb, uint16_t* const* d_out_index, int64_t* out_stats);
+int nq_dither_ordered(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                      const uint32_t* palette, int K, int limit,
+                      uint32_t* const* out_argb, uint16_t* const* out_index, int64_t* out_stats);
+int nq_convert_frames_ordered_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                                     int nMaxColors, int refine, int limit,
+                                     uint32_t* const* d_out_argb, uint16_t* const* d_out_index,
+                                     uint32_t* out_palette, int32_t* out_K);
+int nq_convert_frames_ordered(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                              int nMaxColors, int refine, int limit,
+                              uint32_t* const* out_argb, uint16_t* const* out_index,
+                              uint32_t* out_palette, int32_t* out_K);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

@@ -12,7 +12,7 @@ import numpy as np
 
 from .gif import _Handle, _delays, _index_maps, _palette
 from .hold import _hold_host, _threshold
-from .host import MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frames_quantizer, load_library
+from .host import MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frames_quantizer, _ordered_keyword, load_library
 
 
 def _one_size(maps):
@@ -84,7 +84,8 @@ def write_apng(path, frames, palette, delays_cs=None, loop=0, segment_bytes=0, d
 
 
 def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, seeds=None, tile=None, segment_bytes=0, device=0,
-                           mode=MODE_PARALLEL_TILED, return_rects=False, hold=None, refine=0, size=None, crop=None, linear_resample=True):
+                           mode=MODE_PARALLEL_TILED, return_rects=False, hold=None, refine=0, size=None, crop=None, linear_resample=True,
+                           ordered=None):
     """convert_frames (one shared palette for the ARGB frames, which must have one size) followed by encode_apng of the index maps on
     the same handle.  nMaxColors <= 256.  Seeds are passed on as given: regions that do not move repeat in the index maps, and so drop
     out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.  hold (None: no such pass): an integer
@@ -93,11 +94,14 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
     refine (0..64): that many k-means passes on the palette over the frames before the dither (refine.py); 0 is the call without it.
     size / crop / linear_resample: with size=(width, height) or crop=(x, y, width, height) given, the frames are first cropped and
     area-averaged down to `size` (None: the crop's size) as resample_frames does it (resample.py), on the same handle.
+    ordered (None: the error-diffusion dither): an integer 0..255 dithers the frames with the ordered dither (ordered.py) with that
+    limit instead; dither, mode and tile then take no part, and seeds may not be given.
     Returns (file bytes, palette); with return_rects=True (file bytes, palette, rectangles)."""
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a PNG palette holds at most 256 entries")
     if len({np.asarray(f).shape for f in frames}) > 1:
         raise ValueError("APNG: all frames must have one size")
+    ordered = _ordered_keyword(ordered, seeds)
     if hold is not None:
         hold = _threshold(hold)
     frames, q = _frames_quantizer(kind, frames, device, mode, tile)
@@ -105,7 +109,7 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
         if size is not None or crop is not None:
             from .resample import _resample_host
             frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
-        palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None)
+        palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
         maps = _index_maps([o.index for o in outs])
         height, width = _one_size(maps)
         if hold is not None:

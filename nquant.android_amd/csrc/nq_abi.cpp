@@ -270,6 +270,13 @@ struct nq_handle {
     // upload); nq_resample_frames stages its frames in d_in and their reductions in d_out_argb
     std::vector<void*> h_resample_ptrs;
     DevBuf<void*> resample_ptrs;
+    // nq_dither_ordered_device: the frame table, the palette (256 words) and the 2 n statistics (the host copies stay alive for the
+    // asynchronous uploads); nq_dither_ordered stages its frames in d_in / d_out_index / d_out_argb
+    std::vector<nq::OrderedFrame> h_ordered_frames;
+    DevBuf<nq::OrderedFrame> d_ordered_frames;
+    std::vector<unsigned> h_ordered_pal;
+    DevBuf<unsigned> d_ordered_pal;
+    DevBuf<unsigned long long> d_ordered_stats;
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
@@ -3332,6 +3339,212 @@ int nq_resample_frames(nq_handle* h, int n, const uint32_t* const* src, int src_
         for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dst[i], d_dst[i], dpx * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
         NQ_HIP(h, hipStreamSynchronize(h->stream));
         return NQ_OK;
+    });
+}
+
+} // extern "C"
+
+// ---- ordered dither (nq_ordered.hip) ----
+namespace {
+
+// the frames and outputs of every form, from the host arrays alone (no device work): the sizes first, then the pointers
+int ordered_check_frames(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                         uint32_t* const* out_argb, uint16_t* const* out_index, int64_t* out_total) {
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    if (!argb || !widths || !heights) NQ_FAIL(h, NQ_ERR_INVALID, "the array of frame pointers, widths or heights is NULL");
+    if (!out_index) NQ_FAIL(h, NQ_ERR_INVALID, "the array of index pointers is NULL");
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (widths[i] < 1 || widths[i] > 65535 || heights[i] < 1 || heights[i] > 65535)
+            NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: %d x %d: sides must be 1..65535", i, widths[i], heights[i]);
+        total += (int64_t) widths[i] * heights[i];
+        if (total > 2147483647ll) NQ_FAIL(h, NQ_ERR_INVALID, "the sequence holds more than 2^31 - 1 pixels (frame %d)", i);
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!argb[i] || ((uintptr_t) argb[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: pixel pointer NULL or not 4-byte aligned", i);
+        if (!out_index[i] || ((uintptr_t) out_index[i] & 1)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: index pointer NULL or not 2-byte aligned", i);
+        if (out_argb && (!out_argb[i] || ((uintptr_t) out_argb[i] & 3)))
+            NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: output pointer NULL or not 4-byte aligned", i);
+    }
+    // no output may overlap a source frame or another output (the sources may overlap each other: they are only read); as in
+    // resample_check, a buffer overlaps an earlier one exactly when it begins before the furthest end seen so far
+    struct Span { uintptr_t begin, end; bool out; };
+    std::vector<Span> spans;
+    spans.reserve(3 * (size_t) n);
+    for (int i = 0; i < n; ++i) {
+        const uintptr_t px = (uintptr_t) widths[i] * heights[i];
+        spans.push_back({(uintptr_t) argb[i], (uintptr_t) argb[i] + px * sizeof(uint32_t), false});
+        spans.push_back({(uintptr_t) out_index[i], (uintptr_t) out_index[i] + px * sizeof(uint16_t), true});
+        if (out_argb) spans.push_back({(uintptr_t) out_argb[i], (uintptr_t) out_argb[i] + px * sizeof(uint32_t), true});
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.begin < b.begin; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const Span& sp : spans) {
+        if (sp.begin < (sp.out ? end_any : end_out)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source frame or another output");
+        end_any = std::max(end_any, sp.end);
+        if (sp.out) end_out = std::max(end_out, sp.end);
+    }
+    *out_total = total;
+    return NQ_OK;
+}
+
+// every argument of both forms of nq_dither_ordered
+int ordered_check(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights, const uint32_t* palette,
+                  int K, int limit, uint32_t* const* out_argb, uint16_t* const* out_index, int64_t* out_total) {
+    if (K < 1 || K > 256) NQ_FAIL(h, NQ_ERR_INVALID, "K = %d: must be 1..256", K);
+    if (limit < 0 || limit > 255) NQ_FAIL(h, NQ_ERR_INVALID, "limit = %d: must be 0..255", limit);
+    if (!palette) NQ_FAIL(h, NQ_ERR_INVALID, "palette is NULL");
+    return ordered_check_frames(h, n, argb, widths, heights, out_argb, out_index, out_total);
+}
+
+// ... and of both forms of nq_convert_frames_ordered
+int ordered_check_convert(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights, int nMaxColors,
+                          int refine, int limit, uint32_t* const* out_argb, uint16_t* const* out_index, const uint32_t* out_palette,
+                          const int32_t* out_K, int64_t* out_total) {
+    if (nMaxColors < 1 || nMaxColors > 256) NQ_FAIL(h, NQ_ERR_INVALID, "nMaxColors = %d: must be 1..256", nMaxColors);
+    if (refine < 0 || refine > 64) NQ_FAIL(h, NQ_ERR_INVALID, "refine = %d: must be 0..64", refine);
+    if (limit < 0 || limit > 255) NQ_FAIL(h, NQ_ERR_INVALID, "limit = %d: must be 0..255", limit);
+    if (!out_palette || !out_K) NQ_FAIL(h, NQ_ERR_INVALID, "out_palette or out_K is NULL");
+    return ordered_check_frames(h, n, argb, widths, heights, out_argb, out_index, out_total);
+}
+
+// nq_dither_ordered_device after the checks: frame table and palette go up, one launch dithers the sequence, the statistics come back
+// when wanted
+int ordered_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights, int64_t total,
+                   const uint32_t* palette, int K, int limit, uint32_t* const* d_out_argb, uint16_t* const* d_out_index, int64_t* out_stats) {
+    std::vector<nq::OrderedFrame>& t = h->h_ordered_frames;
+    t.resize(n);
+    bool vec = true;                                // the four-pixel path: 16-byte sources and ARGB outputs, 8-byte index maps, every frame
+    for (int i = 0; i < n; ++i) {
+        t[i] = {reinterpret_cast<const unsigned*>(d_argb[i]), d_out_index[i], d_out_argb ? reinterpret_cast<unsigned*>(d_out_argb[i]) : nullptr,
+                (long long) widths[i] * heights[i], widths[i], 0};
+        vec = vec && !(((uintptr_t) d_argb[i] | (uintptr_t) (d_out_argb ? d_out_argb[i] : nullptr)) & 15) && !((uintptr_t) d_out_index[i] & 7);
+    }
+    std::vector<unsigned>& pal = h->h_ordered_pal;
+    pal.assign(256, 0u);
+    std::memcpy(pal.data(), palette, (size_t) K * sizeof(uint32_t));
+    int T = -1;                                     // the first entry with alpha 0
+    for (int k = K - 1; k >= 0; --k) if ((pal[k] >> 24) == 0) T = k;
+    NQ_HIP(h, h->d_ordered_frames.reserve(n));
+    NQ_HIP(h, h->d_ordered_pal.reserve(256));
+    if (out_stats) NQ_HIP(h, h->d_ordered_stats.reserve(2 * (size_t) n));
+    // (with out_stats == NULL the call returns with these uploads only enqueued: safe for the reason given in hold_device)
+    NQ_HIP(h, hipMemcpyAsync(h->d_ordered_frames.p, t.data(), n * sizeof(nq::OrderedFrame), hipMemcpyHostToDevice, h->stream));
+    NQ_HIP(h, hipMemcpyAsync(h->d_ordered_pal.p, pal.data(), 256 * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    if (out_stats) NQ_HIP(h, hipMemsetAsync(h->d_ordered_stats.p, 0, 2 * (size_t) n * sizeof(unsigned long long), h->stream));
+    launch_ordered(h->d_ordered_frames.p, n, (long long) total, vec, d_out_argb != nullptr, h->d_ordered_pal.p, K, T, limit,
+                   out_stats ? h->d_ordered_stats.p : nullptr, h->stream);
+    NQ_HIP(h, launch_status());
+    if (!out_stats) return NQ_OK;
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "statistics");
+    NQ_HIP(h, hipMemcpyAsync(out_stats, h->d_ordered_stats.p, 2 * (size_t) n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    return NQ_OK;
+}
+
+// The host form of both calls: the frames go up into d_in, step(sources, ARGB outputs or null, index maps) runs on the device copies,
+// index maps and outputs come back.  Frames lie a multiple of 4 elements apart in the staging buffers, so that every source and
+// ARGB output starts 16-byte and every index map 8-byte aligned (the four-pixel path).
+template <typename Step>
+int ordered_host(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights, uint32_t* const* out_argb,
+                 uint16_t* const* out_index, Step step) {
+    return host_form(h, [&]() -> int {
+        std::vector<size_t> at(n + 1, 0);
+        for (int i = 0; i < n; ++i) at[i + 1] = at[i] + (((size_t) widths[i] * heights[i] + 3) & ~(size_t) 3);
+        NQ_HIP(h, h->d_in.reserve(at[n]));
+        NQ_HIP(h, h->d_out_index.reserve(at[n]));
+        if (out_argb) NQ_HIP(h, h->d_out_argb.reserve(at[n]));
+        std::vector<const uint32_t*> d_src(n);
+        std::vector<uint16_t*> d_idx(n);
+        std::vector<uint32_t*> d_out(n);
+        for (int i = 0; i < n; ++i) {
+            d_src[i] = h->d_in.p + at[i]; d_idx[i] = h->d_out_index.p + at[i]; d_out[i] = out_argb ? h->d_out_argb.p + at[i] : nullptr;
+            NQ_HIP(h, hipMemcpyAsync(h->d_in.p + at[i], argb[i], (size_t) widths[i] * heights[i] * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        }
+        const int rc = step(d_src.data(), out_argb ? d_out.data() : nullptr, d_idx.data());
+        if (rc) return rc;
+        for (int i = 0; i < n; ++i) {
+            const size_t px = (size_t) widths[i] * heights[i];
+            NQ_HIP(h, hipMemcpyAsync(out_index[i], d_idx[i], px * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+            if (out_argb) NQ_HIP(h, hipMemcpyAsync(out_argb[i], d_out[i], px * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        }
+        NQ_HIP(h, hipStreamSynchronize(h->stream));
+        return NQ_OK;
+    });
+}
+
+// nq_convert_frames_ordered_device after the checks: the three calls it stands for, one after another
+int ordered_convert_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights, int64_t total,
+                           int nMaxColors, int refine, int limit, uint32_t* const* d_out_argb, uint16_t* const* d_out_index,
+                           uint32_t* out_palette, int32_t* out_K) {
+    int rc = nq_pnnquan_frames_device(h, n, d_argb, widths, heights, nMaxColors, out_palette, out_K);
+    if (rc) return rc;
+    const int K = *out_K;
+    if (K < 1 || K > 256) NQ_FAIL(h, NQ_ERR_UNSUPPORTED, "the palette has %d entries: the ordered dither takes 1..256", K);
+    if (refine > 0) {
+        int64_t sse[65];
+        int32_t passes = 0;
+        rc = refine_device(h, n, d_argb, widths, heights, total, out_palette, K, refine, sse, nullptr, &passes);
+        if (rc) return rc;
+    }
+    rc = ordered_device(h, n, d_argb, widths, heights, total, out_palette, K, limit, d_out_argb, d_out_index, nullptr);
+    if (rc) return rc;
+    NQ_HIP(h, hipStreamSynchronize(h->stream));
+    return NQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_dither_ordered_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                             const uint32_t* palette, int K, int limit, uint32_t* const* d_out_argb, uint16_t* const* d_out_index,
+                             int64_t* out_stats) {
+    if (!h) return NQ_ERR_INVALID;
+    int64_t total = 0;
+    int rc = ordered_check(h, n, d_argb, widths, heights, palette, K, limit, d_out_argb, d_out_index, &total);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return ordered_device(h, n, d_argb, widths, heights, total, palette, K, limit, d_out_argb, d_out_index, out_stats);
+}
+
+int nq_dither_ordered(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                      const uint32_t* palette, int K, int limit, uint32_t* const* out_argb, uint16_t* const* out_index, int64_t* out_stats) {
+    if (!h) return NQ_ERR_INVALID;
+    int64_t total = 0;
+    int rc = ordered_check(h, n, argb, widths, heights, palette, K, limit, out_argb, out_index, &total);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return ordered_host(h, n, argb, widths, heights, out_argb, out_index, [&](auto in, auto out, auto index) {
+        return ordered_device(h, n, in, widths, heights, total, palette, K, limit, out, index, out_stats);
+    });
+}
+
+int nq_convert_frames_ordered_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
+                                     int nMaxColors, int refine, int limit, uint32_t* const* d_out_argb, uint16_t* const* d_out_index,
+                                     uint32_t* out_palette, int32_t* out_K) {
+    if (!h) return NQ_ERR_INVALID;
+    int64_t total = 0;
+    int rc = ordered_check_convert(h, n, d_argb, widths, heights, nMaxColors, refine, limit, d_out_argb, d_out_index, out_palette, out_K, &total);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return ordered_convert_device(h, n, d_argb, widths, heights, total, nMaxColors, refine, limit, d_out_argb, d_out_index, out_palette, out_K);
+}
+
+int nq_convert_frames_ordered(nq_handle* h, int n, const uint32_t* const* argb, const int32_t* widths, const int32_t* heights,
+                              int nMaxColors, int refine, int limit, uint32_t* const* out_argb, uint16_t* const* out_index,
+                              uint32_t* out_palette, int32_t* out_K) {
+    if (!h) return NQ_ERR_INVALID;
+    int64_t total = 0;
+    int rc = ordered_check_convert(h, n, argb, widths, heights, nMaxColors, refine, limit, out_argb, out_index, out_palette, out_K, &total);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return ordered_host(h, n, argb, widths, heights, out_argb, out_index, [&](auto in, auto out, auto index) {
+        return ordered_convert_device(h, n, in, widths, heights, total, nMaxColors, refine, limit, out, index, out_palette, out_K);
     });
 }
 

@@ -330,4 +330,14 @@ void launch_refine(const RefineFrame* d_frames, int n, long long total, bool vec
 void launch_resample(const unsigned* const* d_src, unsigned* const* d_dst, int n, int src_width, int crop_x, int crop_y, int crop_w,
                      int crop_h, int dst_width, int dst_height, bool linear, bool vec, hipStream_t s);
 
+// ---- ordered dither (nq_ordered.hip): d_frames is a device array of n frames, `total` the pixels of the sequence (sizes the grid),
+// d_palette the K entries (1..256) in device memory, T the first entry with alpha 0 or -1, limit 0..255.  One launch writes every
+// frame's index map and, with out, its ARGB output (then every frame's `argb` is set); d_stats: 2 n sums the caller zeroed, {pixels
+// that took the second entry, squared error} per frame, or null.  vec: the four-pixel path -- the caller has checked that EVERY source
+// and ARGB output is 16-byte and every index map 8-byte aligned; otherwise one pixel per access (4-byte / 2-byte alignment).  The
+// sources are never written; no output may overlap a source or another output. ----
+struct OrderedFrame { const unsigned* pixels; unsigned short* index; unsigned* argb; long long npix; int width; int pad; };
+void launch_ordered(const OrderedFrame* d_frames, int n, long long total, bool vec, bool out, const unsigned* d_palette, int K, int T, int limit,
+                    unsigned long long* d_stats, hipStream_t s);
+
 } // namespace nq

@@ -16,7 +16,8 @@ import ctypes as C
 
 import numpy as np
 
-from .host import MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frame_sizes, _frames_quantizer, convert_frames, load_library
+from .host import (MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frame_sizes, _frames_quantizer, _ordered_keyword, convert_frames,
+                   load_library)
 
 
 def _palette(palette):
@@ -301,15 +302,17 @@ def _shots(shot_starts, n):
 
 def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0,
                          mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None,
-                         linear_resample=True, delta=True):
+                         linear_resample=True, ordered=None, delta=True):
     """One palette per shot: frames shot_starts[k] .. shot_starts[k + 1] - 1 are shot k and get a convert_frames palette of their own
     (shot_starts=range(n): one palette per frame), then encode_gif_local_delta (delta=False: encode_gif_local) writes all frames, each
     with its shot's palette as its local colour table.  hold (delta=True only) runs per shot and never across a cut: a held index means
     nothing under another table.  seeds, tile, lossy as for convert_frames_to_gif; refine (0..64) runs that many k-means passes
-    (refine.py) on every shot's palette over that shot's frames.  size / crop / linear_resample as for convert_frames_to_gif.
+    (refine.py) on every shot's palette over that shot's frames.  size / crop / linear_resample and ordered as for
+    convert_frames_to_gif.
     Everything runs on one handle.  Cuts are the caller's to give here; convert_clip_to_gif finds them.
     Returns (file bytes, list of per-shot palettes)."""
     lossy = _lossy_keyword(lossy)
+    ordered = _ordered_keyword(ordered, seeds)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
     if hold is not None and not delta:
@@ -327,19 +330,22 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
         if size is not None or crop is not None:
             from .resample import _resample_host
             frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
-        return _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine)
+        return _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine, ordered)
     finally:
         q.close()
 
 
-def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine=0):
+def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine=0,
+                     ordered=None):
     """convert_shots_to_gif after its checks, on the handle of quantizer `q`, which stays open: `frames` int32 arrays, `shots` the
-    (first frame, one past the last) pairs, hold a checked threshold or None, refine the k-means passes per shot (0: none)."""
+    (first frame, one past the last) pairs, hold a checked threshold or None, refine the k-means passes per shot (0: none), ordered a
+    checked limit of the ordered dither or None."""
     if hold is not None:
         from .hold import _hold_host
     maps, palettes = [], []
     for a, b in shots:
-        palette, outs = _convert_frames_on(q, frames[a:b], nMaxColors, dither, mode, None if seeds is None else list(seeds)[a:b], int(refine) or None)
+        palette, outs = _convert_frames_on(q, frames[a:b], nMaxColors, dither, mode, None if seeds is None else list(seeds)[a:b], int(refine) or None,
+                                           ordered)
         shot_maps = [o.index for o in outs]
         if hold is not None:
             _hold_host(q._L, q._h, q._check, frames[a:b], shot_maps, None, hold)
@@ -361,13 +367,14 @@ def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segm
 
 def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, delays_cs=None, loop=0, segment_pixels=0, device=0,
                         mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None,
-                        linear_resample=True, delta=True):
+                        linear_resample=True, ordered=None, delta=True):
     """A list of frames in, an animation out: detect_shots (shots.py; cut in per mille, min_shot in frames) finds where the clip needs
     a new palette, then exactly convert_shots_to_gif with those starts -- both on one handle.  The frames must have one size (delta or
     not: a signature is compared between frames of one size).  With size or crop the frames are reduced first (resample.py) and the
     shots are detected on the result.  Keywords otherwise as for convert_shots_to_gif.
     Returns (file bytes, list of per-shot palettes, shot_starts)."""
     lossy = _lossy_keyword(lossy)
+    ordered = _ordered_keyword(ordered, seeds)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
     if hold is not None and not delta:
@@ -387,7 +394,7 @@ def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, de
             frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
         starts, _ = _detect_host(q._L, q._h, q._check, frames, cut, min_shot)
         data, palettes = _shots_to_gif_on(q, frames, _shots(starts, len(frames)), nMaxColors, dither, delays_cs, loop, segment_pixels, mode,
-                                          seeds, hold, lossy, delta, refine)
+                                          seeds, hold, lossy, delta, refine, ordered)
     finally:
         q.close()
     return data, palettes, starts
@@ -411,7 +418,8 @@ def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, 
 
 
 def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
-                          seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None, linear_resample=True, delta=False):
+                          seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None, linear_resample=True, ordered=None,
+                          delta=False):
     """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
     delta=True: encode_gif_delta instead; the frames must have one size.  Seeds are passed on as given: regions that do not move repeat
     in the index maps, and so drop out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.
@@ -424,8 +432,12 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
     size / crop / linear_resample: with size=(width, height) or crop=(x, y, width, height) given, the frames (then all of one size)
     are first cropped and area-averaged down to `size` (None: the crop's size) as resample_frames does it (resample.py; in linear
     light unless linear_resample=False), and everything else runs on the result, all on one handle.
+    ordered (None: the error-diffusion dither): an integer 0..255 dithers the frames with the ordered dither (ordered.py,
+    convert_frames_ordered) with that limit instead: a pixel's index then depends on its colour, its position and the palette only, so
+    unchanged pixels repeat without seeds.  dither, mode and tile then take no part, and seeds may not be given.
     Returns (file bytes, palette)."""
     lossy = _lossy_keyword(lossy)
+    ordered = _ordered_keyword(ordered, seeds)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
     if hold is not None and not delta:
@@ -440,7 +452,7 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
         frames, q = _frames_quantizer(kind, frames, device, mode, tile)
         try:
             frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
-            palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None)
+            palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
             maps = _index_maps([o.index for o in outs])
             height, width = _one_size(maps)
             if hold is not None:
@@ -460,7 +472,7 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
         hold = _threshold(hold)
         frames, q = _frames_quantizer(kind, frames, device, mode, tile)
         try:
-            palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None)
+            palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
             maps = [o.index for o in outs]
             height, width = _one_size(maps)
             _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
@@ -469,7 +481,10 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
         finally:
             q.close()
         return data, palette
-    if int(refine) == 0:
+    if ordered is not None:
+        from .ordered import convert_frames_ordered
+        palette, outs = convert_frames_ordered(kind, frames, nMaxColors, ordered, refine, device=device)
+    elif int(refine) == 0:
         palette, outs = convert_frames(kind, frames, nMaxColors, dither, device=device, mode=mode, seeds=seeds, tile=tile)
     else:
         from .refine import convert_frames_refined

@@ -116,6 +116,10 @@ _ABI = {
     "nq_convert_frames_refined": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pi32]),
     "nq_resample_frames_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32]),
     "nq_resample_frames": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32]),
+    "nq_dither_ordered_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "nq_dither_ordered": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "nq_convert_frames_ordered_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _pi32]),
+    "nq_convert_frames_ordered": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _pi32]),
 }
 
 
@@ -479,9 +483,25 @@ def _frames_quantizer(kind, frames, device, mode, tile):
     return frames, cls(frames[0], device=device, mode=mode, tile=tile)
 
 
-def _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, refine=None):
-    """nq_convert_frames of the int32 frames on the handle of quantizer `q`, which stays open; refine not None: nq_convert_frames_refined."""
+def _ordered_keyword(ordered, seeds):
+    """The `ordered` keyword of the converters: None, or the limit 0..255 of the ordered dither (ordered.py) that replaces the error
+    diffusion.  It takes no seeds; a bool is not a limit."""
+    if ordered is None:
+        return None
+    if isinstance(ordered, (bool, np.bool_)):
+        raise TypeError("ordered is an integer 0..255 or None")
+    if seeds is not None:
+        raise ValueError("the ordered dither takes no seeds")
+    if not 0 <= int(ordered) <= 255:
+        raise ValueError("ordered must be 0..255, got %r" % (ordered,))
+    return int(ordered)
+
+
+def _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, refine=None, ordered=None):
+    """nq_convert_frames of the int32 frames on the handle of quantizer `q`, which stays open; refine not None: nq_convert_frames_refined;
+    ordered not None: nq_convert_frames_ordered with that limit (dither, mode and seeds then take no part)."""
     n = len(frames)
+    ordered = _ordered_keyword(ordered, seeds)
     hs = np.array([f.shape[0] for f in frames], np.int32)
     ws = np.array([f.shape[1] for f in frames], np.int32)
     sd = np.array([0] * n if seeds is None else list(seeds), np.int64)
@@ -494,7 +514,10 @@ def _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, refine=None):
     idx = (C.c_void_p * n)(*[o.ctypes.data for o in idxs])
     pal = np.zeros(max(int(nMaxColors), 2), np.int32)
     K = C.c_int32(0)
-    if refine is None:
+    if ordered is not None:
+        q._check(q._L.nq_convert_frames_ordered(q._h, n, src, ws.ctypes.data, hs.ctypes.data, int(nMaxColors), int(refine or 0), ordered,
+                                                dst, idx, pal.ctypes.data, C.byref(K)))
+    elif refine is None:
         q._check(q._L.nq_convert_frames(q._h, n, src, ws.ctypes.data, hs.ctypes.data, int(nMaxColors), int(bool(dither)), sd.ctypes.data,
                                         int(mode), dst, idx, pal.ctypes.data, C.byref(K)))
     else:
