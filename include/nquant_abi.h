@@ -611,6 +611,70 @@ int nq_resample_frames(nq_handle* h, int n, const uint32_t* const* src, int src_
                        int crop_x, int crop_y, int crop_w, int crop_h,
                        uint32_t* const* dst, int dst_width, int dst_height, int flags);
 
+/* ---- YUV input: 8-bit YUV 4:2:0 frames (NV12, NV21, I420, YV12: what a hardware video decoder, Android's camera and MediaCodec
+ *      write) in front of the frame path.  nq_frames_from_yuv* converts a sequence 1:1 to ARGB_8888 words; nq_resample_frames_yuv*
+ *      converts and reduces it in one step, without the full-size ARGB frames ever existing.  All arithmetic is integer: the result
+ *      is deterministic and can be restated bit for bit.
+ *  * The frame: width x height, both 1..65535, and three byte pointers y, u, v.  Luma of pixel (x, y) is y[y * y_stride + x].  The
+ *    chroma planes are cw2 = (width + 1) >> 1 by ch2 = (height + 1) >> 1 samples; the chroma of pixel (x, y) is
+ *    u[(y >> 1) * c_stride + (x >> 1) * c_step], likewise v (sample replication).  c_step is 1 or 2.  This is Android's Image.Plane
+ *    (buffer, rowStride, pixelStride).  The named layouts:
+ *        NV12           u = uv, v = uv + 1     c_step 2
+ *        NV21           v = vu, u = vu + 1     c_step 2
+ *        I420 / YV12    two planes             c_step 1
+ *    All n frames of a call share width, height, y_stride, c_stride, c_step and the flag word.
+ *  * yuv_flags: NQ_YUV_BT709 = 1 (otherwise BT.601); NQ_YUV_FULL_RANGE = 2 (otherwise limited range: luma offset yo = 16; in full
+ *    range yo = 0).
+ *  * Coefficients: floor(65536 e + 1/2) of the exact rationals e below, with Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722
+ *    (BT.709), Kg = 1 - Kr - Kb, and sy = 255/219, sc = 255/224 in limited range, both 1 in full range:
+ *        cy = sy    crv = sc 2 (1 - Kr)    cgu = sc 2 (1 - Kb) Kb / Kg    cgv = sc 2 (1 - Kr) Kr / Kg    cbu = sc 2 (1 - Kb)
+ *                          cy      crv     cgu     cgv     cbu
+ *        601 limited    76309   104597   25675   53279  132201
+ *        601 full       65536    91881   22553   46802  116130
+ *        709 limited    76309   117489   13975   34925  138438
+ *        709 full       65536   103206   12276   30679  121609
+ *  * Output, per pixel with its Y and its chroma sample U, V:
+ *        R = clamp((cy (Y - yo) + crv (V - 128) + 32768) >> 16)
+ *        G = clamp((cy (Y - yo) - cgu (U - 128) - cgv (V - 128) + 32768) >> 16)
+ *        B = clamp((cy (Y - yo) + cbu (U - 128) + 32768) >> 16)
+ *    >> is the arithmetic shift of a signed 32-bit value (a floor), clamp is to 0..255, the word is 0xFF << 24 | R << 16 | G << 8 | B.
+ *    Every intermediate is below 3.6e7 in magnitude.  Each channel is within one level of round-half-up of the exact real formula
+ *    (and differs from it at all in at most 5.2e-4 of the 2^24 triples); full-range grey (U = V = 128) is the identity; in limited
+ *    range Y = 16 gives 0 and Y = 235 gives 255.
+ *  * nq_frames_from_yuv_device: d_y, d_u, d_v, d_dst are host arrays of n DEVICE pointers; output i is width x height words, rows
+ *    contiguous.  nq_resample_frames_yuv_device is DEFINED as that call followed by nq_resample_frames_device with the same crop,
+ *    target and flags ("frame reduction"), bit for bit; output i is dst_width x dst_height words.  The chroma of crop pixel (j, i) is
+ *    the frame's sample ((crop_x + j) >> 1, (crop_y + i) >> 1): an odd crop_x or crop_y shifts the pairing.  The alpha is 255
+ *    everywhere.  Both calls are asynchronous on the handle's stream, never write the sources and write nothing outside the n
+ *    outputs.  h may be a handle of either kind: its stream, scratch and error text are used, its params are neither read nor changed.
+ *    Any plane pointers are accepted; outputs need 4-byte alignment.  When width, every y pointer and y_stride are multiples of 4 and
+ *    the chroma is either interleaved (c_step 2, u and v one byte apart in the same order in every frame, the lower one and c_stride
+ *    multiples of 4) or planar with u, v and c_stride even (and, 1:1, every output is 16-byte aligned), the kernels load 4 luma bytes
+ *    per access and store 16; otherwise one pixel per access, with the same results.
+ *    nq_frames_from_yuv / nq_resample_frames_yuv: the same with HOST buffers.  Per frame the luma span ((height - 1) y_stride + width
+ *    bytes) and the chroma spans ((ch2 - 1) c_stride + (cw2 - 1) c_step + 1 bytes each) are uploaded -- one span where u's and v's
+ *    overlap or touch, as in the interleaved layouts --, the device form runs, the n outputs are copied back; the call returns when
+ *    they are there.
+ *  * NQ_ERR_INVALID before any device work, every buffer untouched, the handle still usable: n < 1, a side outside 1..65535,
+ *    y_stride < width, c_step not 1 or 2, c_stride < c_step (cw2 - 1) + 1, unknown bits in either flag word, a NULL pointer array or
+ *    entry, an output pointer that is not 4-byte aligned, n width height above 2^31 - 1, the crop and target errors of
+ *    nq_resample_frames, an output that overlaps a source span or another output.
+ *  The kernels: DESIGN.md 5g "YUV input". ---- */
+#define NQ_YUV_BT709 1
+#define NQ_YUV_FULL_RANGE 2
+int nq_frames_from_yuv_device(nq_handle* h, int n, const uint8_t* const* d_y, const uint8_t* const* d_u, const uint8_t* const* d_v,
+                              int width, int height, int y_stride, int c_stride, int c_step, int yuv_flags, uint32_t* const* d_dst);
+int nq_frames_from_yuv(nq_handle* h, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
+                       int width, int height, int y_stride, int c_stride, int c_step, int yuv_flags, uint32_t* const* dst);
+int nq_resample_frames_yuv_device(nq_handle* h, int n, const uint8_t* const* d_y, const uint8_t* const* d_u, const uint8_t* const* d_v,
+                                  int src_width, int src_height, int y_stride, int c_stride, int c_step, int yuv_flags,
+                                  int crop_x, int crop_y, int crop_w, int crop_h,
+                                  uint32_t* const* d_dst, int dst_width, int dst_height, int flags);
+int nq_resample_frames_yuv(nq_handle* h, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
+                           int src_width, int src_height, int y_stride, int c_stride, int c_step, int yuv_flags,
+                           int crop_x, int crop_y, int crop_w, int crop_h,
+                           uint32_t* const* dst, int dst_width, int dst_height, int flags);
+
 /* ---- ordered dither: a positional dither for frame sequences (ffmpeg paletteuse=dither=bayer, ImageMagick -ordered-dither).  The
  *      index of a pixel depends on its colour, its coordinates and the palette only -- not on any other pixel, as in the Gilbert-curve
  *      error diffusion of the convert calls.  An unchanged pixel gives an unchanged index in every frame, at any tile size, with no

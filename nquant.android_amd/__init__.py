@@ -18,6 +18,7 @@ from .shots import detect_shots, detect_shots_device, frame_signatures, frame_si
 from .refine import convert_frames_refined, palette_error, refine_palette, refine_palette_device
 from .resample import fit_size, resample_frames, resample_frames_device
 from .ordered import convert_frames_ordered, dither_ordered, dither_ordered_device
+from .yuv import frames_from_yuv, frames_from_yuv_device, resample_frames_yuv, resample_frames_yuv_device, yuv_planes
 from .build import build as build_library
 
 __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARALLEL_TILED", "MODE_LOOKUP_ONLY",
@@ -30,4 +31,5 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "convert_frames_to_apng", "hold_frames", "hold_frames_device", "frame_signatures", "frame_signatures_device",
            "shots_from_signatures", "detect_shots", "detect_shots_device", "convert_clip_to_gif", "refine_palette",
            "refine_palette_device", "palette_error", "convert_frames_refined", "fit_size", "resample_frames", "resample_frames_device",
-           "dither_ordered", "dither_ordered_device", "convert_frames_ordered"]
+           "dither_ordered", "dither_ordered_device", "convert_frames_ordered", "frames_from_yuv", "frames_from_yuv_device",
+           "resample_frames_yuv", "resample_frames_yuv_device", "yuv_planes"]

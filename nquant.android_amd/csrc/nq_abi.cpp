@@ -270,6 +270,11 @@ struct nq_handle {
     // upload); nq_resample_frames stages its frames in d_in and their reductions in d_out_argb
     std::vector<void*> h_resample_ptrs;
     DevBuf<void*> resample_ptrs;
+    // nq_frames_from_yuv_device / nq_resample_frames_yuv_device: the table of plane and output pointers (y, u, v, output: n each; the host
+    // copy stays alive for the asynchronous upload); the host forms stage the planes' byte spans in yuv_in and the outputs in d_out_argb
+    std::vector<const void*> h_yuv_ptrs;
+    DevBuf<const void*> yuv_ptrs;
+    DevBuf<unsigned char> yuv_in;
     // nq_dither_ordered_device: the frame table, the palette (256 words) and the 2 n statistics (the host copies stay alive for the
     // asynchronous uploads); nq_dither_ordered stages its frames in d_in / d_out_index / d_out_argb
     std::vector<nq::OrderedFrame> h_ordered_frames;
@@ -3339,6 +3344,240 @@ int nq_resample_frames(nq_handle* h, int n, const uint32_t* const* src, int src_
         for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dst[i], d_dst[i], dpx * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
         NQ_HIP(h, hipStreamSynchronize(h->stream));
         return NQ_OK;
+    });
+}
+
+} // extern "C"
+
+// ---- YUV input (nq_yuv.hip) ----
+namespace {
+
+// the n frames of a call: plane pointers (host arrays), one geometry and one flag word
+struct YuvFrames {
+    int n;
+    const uint8_t* const* y; const uint8_t* const* u; const uint8_t* const* v;
+    int width, height, y_stride, c_stride, c_step, yuv_flags;
+    // bytes from a plane's first sample to one past its last
+    uintptr_t y_span() const { return (uintptr_t) (height - 1) * (uintptr_t) y_stride + (uintptr_t) width; }
+    uintptr_t c_span() const {
+        return (uintptr_t) ((height + 1) / 2 - 1) * (uintptr_t) c_stride + (uintptr_t) ((width + 1) / 2 - 1) * (uintptr_t) c_step + 1;
+    }
+};
+
+// floor(65536 e + 1/2) of the rationals of include/nquant_abi.h "YUV input", by flag word: {cy, crv, cgu, cgv, cbu, yo}
+const YuvCoef YUV_COEF[4] = {
+    {76309, 104597, 25675, 53279, 132201, 16},      // BT.601, limited range
+    {76309, 117489, 13975, 34925, 138438, 16},      // NQ_YUV_BT709
+    {65536, 91881, 22553, 46802, 116130, 0},        // NQ_YUV_FULL_RANGE
+    {65536, 103206, 12276, 30679, 121609, 0},       // both
+};
+
+// every argument of the four entry points, from the host arrays alone (no device work).  nq_frames_from_yuv* pass the whole frame as
+// crop and target, and flags 0.
+int yuv_check(nq_handle* h, const YuvFrames& a, int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* dst, int dst_width,
+              int dst_height, int flags) {
+    const int n = a.n;
+    if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    if (a.width < 1 || a.width > 65535 || a.height < 1 || a.height > 65535)
+        NQ_FAIL(h, NQ_ERR_INVALID, "%d x %d: source sides must be 1..65535", a.width, a.height);
+    if (a.y_stride < a.width) NQ_FAIL(h, NQ_ERR_INVALID, "y_stride = %d: shorter than a row of %d pixels", a.y_stride, a.width);
+    if (a.c_step != 1 && a.c_step != 2) NQ_FAIL(h, NQ_ERR_INVALID, "c_step = %d: must be 1 or 2", a.c_step);
+    if (a.c_stride < a.c_step * ((a.width + 1) / 2 - 1) + 1)
+        NQ_FAIL(h, NQ_ERR_INVALID, "c_stride = %d: shorter than a chroma row of %d samples %d apart", a.c_stride, (a.width + 1) / 2, a.c_step);
+    if (a.yuv_flags & ~(NQ_YUV_BT709 | NQ_YUV_FULL_RANGE)) NQ_FAIL(h, NQ_ERR_INVALID, "yuv_flags = 0x%x: unknown bits", (unsigned) a.yuv_flags);
+    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > a.width - crop_w || crop_y > a.height - crop_h)
+        NQ_FAIL(h, NQ_ERR_INVALID, "crop %d x %d at (%d, %d): empty or outside the %d x %d frame", crop_w, crop_h, crop_x, crop_y, a.width,
+                a.height);
+    if (dst_width < 1 || dst_width > crop_w || dst_height < 1 || dst_height > crop_h)
+        NQ_FAIL(h, NQ_ERR_INVALID, "target %d x %d: sides must be 1 .. the crop's (%d x %d); this call only reduces", dst_width, dst_height,
+                crop_w, crop_h);
+    if (flags & ~NQ_RESAMPLE_LINEAR) NQ_FAIL(h, NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) flags);
+    if ((long long) n * a.width * a.height > 2147483647ll)
+        NQ_FAIL(h, NQ_ERR_INVALID, "%d frames of %d x %d: more than 2^31 - 1 pixels", n, a.width, a.height);
+    if (!a.y || !a.u || !a.v || !dst) NQ_FAIL(h, NQ_ERR_INVALID, "an array of plane / output pointers is NULL");
+    for (int i = 0; i < n; ++i) {
+        if (!a.y[i] || !a.u[i] || !a.v[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: a plane pointer is NULL", i);
+        if (!dst[i] || ((uintptr_t) dst[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: output pointer NULL or not 4-byte aligned", i);
+    }
+    // no output may overlap a plane's span or another output (resample_check's sweep, on byte spans): in the order of their first
+    // bytes, a buffer overlaps an earlier one exactly when it begins before the furthest end seen so far
+    struct Span { uintptr_t begin, end; bool out; };
+    std::vector<Span> spans;
+    spans.reserve(4 * (size_t) n);
+    const uintptr_t dst_bytes = (uintptr_t) dst_width * dst_height * sizeof(uint32_t);
+    for (int i = 0; i < n; ++i) {
+        spans.push_back({(uintptr_t) a.y[i], (uintptr_t) a.y[i] + a.y_span(), false});
+        spans.push_back({(uintptr_t) a.u[i], (uintptr_t) a.u[i] + a.c_span(), false});
+        spans.push_back({(uintptr_t) a.v[i], (uintptr_t) a.v[i] + a.c_span(), false});
+        spans.push_back({(uintptr_t) dst[i], (uintptr_t) dst[i] + dst_bytes, true});
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span& p, const Span& q) { return p.begin < q.begin; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const Span& sp : spans) {
+        if (sp.begin < (sp.out ? end_any : end_out)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source plane or another output");
+        end_any = std::max(end_any, sp.end);
+        if (sp.out) end_out = std::max(end_out, sp.end);
+    }
+    return NQ_OK;
+}
+
+// The kernels' path for DEVICE frames `a` and outputs d_dst, and the pointer table on its way to the device.  The wide paths need,
+// for EVERY frame: width, y and y_stride multiples of 4 (out16: and the output 16-byte aligned), and either c_step 2 with u and v
+// one byte apart in the same order, the lower one and c_stride multiples of 4 (interleaved: NV12, NV21), or c_step 1 with u, v and
+// c_stride even (planar: I420, YV12).  Everything else takes the byte path.
+int yuv_table(nq_handle* h, const YuvFrames& a, uint32_t* const* d_dst, bool out16, int* path, bool* swap) {
+    const int n = a.n;
+    bool wide = a.width % 4 == 0 && a.y_stride % 4 == 0;
+    bool inter = a.c_step == 2 && a.c_stride % 4 == 0, planar = a.c_step == 1 && a.c_stride % 2 == 0;
+    int order = 0;                                  // +1: u is the lower pointer of every frame so far, -1: v is
+    for (int i = 0; i < n; ++i) {
+        const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i];
+        wide = wide && !((uintptr_t) a.y[i] & 3) && !(out16 && ((uintptr_t) d_dst[i] & 15));
+        const int o = v == u + 1 ? 1 : u == v + 1 ? -1 : 0;
+        inter = inter && o != 0 && (order == 0 || order == o) && !(std::min(u, v) & 3);
+        if (o) order = o;
+        planar = planar && !((u | v) & 1);
+    }
+    *path = wide && inter ? YUV_WIDE_INTERLEAVED : wide && planar ? YUV_WIDE_PLANAR : YUV_BYTE;
+    *swap = order < 0;
+    std::vector<const void*>& t = h->h_yuv_ptrs;
+    t.assign(4 * (size_t) n, nullptr);
+    for (int i = 0; i < n; ++i) {
+        t[i] = a.y[i];
+        t[n + (size_t) i] = *path == YUV_WIDE_INTERLEAVED ? std::min(a.u[i], a.v[i]) : a.u[i];
+        t[2 * (size_t) n + i] = a.v[i];
+        t[3 * (size_t) n + i] = d_dst[i];             // (the only pointers the kernels write through)
+    }
+    NQ_HIP(h, h->yuv_ptrs.reserve(t.size()));
+    // (the call returns with this upload only enqueued: safe for the reason given in hold_device)
+    NQ_HIP(h, hipMemcpyAsync(h->yuv_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+    return NQ_OK;
+}
+
+// nq_frames_from_yuv_device after the checks: the pointer table goes up, one launch converts the sequence
+int yuv_device(nq_handle* h, const YuvFrames& a, uint32_t* const* d_dst) {
+    int path; bool swap;
+    const int rc = yuv_table(h, a, d_dst, true, &path, &swap);
+    if (rc) return rc;
+    launch_yuv_argb(h->yuv_ptrs.p, a.n, a.width, a.height, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.yuv_flags], h->stream);
+    NQ_HIP(h, launch_status());
+    return NQ_OK;
+}
+
+// nq_resample_frames_yuv_device after the checks: the pointer table goes up, one launch converts and reduces the sequence
+int resample_yuv_device(nq_handle* h, const YuvFrames& a, int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* d_dst,
+                        int dst_width, int dst_height, int flags) {
+    int path; bool swap;
+    const int rc = yuv_table(h, a, d_dst, false, &path, &swap);
+    if (rc) return rc;
+    launch_resample_yuv(h->yuv_ptrs.p, a.n, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.yuv_flags], crop_x, crop_y, crop_w,
+                        crop_h, dst_width, dst_height, (flags & NQ_RESAMPLE_LINEAR) != 0, h->stream);
+    NQ_HIP(h, launch_status());
+    return NQ_OK;
+}
+
+// The host forms: per frame the luma span and the chroma spans go up into yuv_in -- ONE span where u's and v's overlap or touch (the
+// interleaved layouts, and planes that follow each other) -- each at a 16-byte boundary, which keeps what the wide paths need of a
+// layout that has it; the outputs (out_px words each) are staged in d_out_argb 16-byte aligned.  device(frames, outputs) runs the
+// device form on the staged copies.
+template <typename Device>
+int yuv_host(nq_handle* h, const YuvFrames& a, uint32_t* const* dst, size_t out_px, Device device) {
+    const int n = a.n;
+    const size_t up16 = 15;
+    const uintptr_t yb = a.y_span(), cb = a.c_span();
+    struct Place { size_t y, lo, hi; bool joined; };          // offsets in yuv_in: luma, the lower chroma span, the other one
+    std::vector<Place> at(n);
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i], lo = std::min(u, v), hi = std::max(u, v);
+        at[i].y = total; total += (yb + up16) & ~up16;
+        at[i].joined = hi <= lo + cb;
+        at[i].lo = total;
+        if (at[i].joined) { at[i].hi = total + (hi - lo); total += (hi - lo + cb + up16) & ~up16; }
+        else { total += (cb + up16) & ~up16; at[i].hi = total; total += (cb + up16) & ~up16; }
+    }
+    const size_t dpitch = (out_px + 3) & ~(size_t) 3;
+    return host_form(h, [&]() -> int {
+        NQ_HIP(h, h->yuv_in.reserve(total));
+        NQ_HIP(h, h->d_out_argb.reserve(n * dpitch));
+        std::vector<const uint8_t*> dy(n), du(n), dv(n);
+        std::vector<uint32_t*> d_dst(n);
+        unsigned char* base = h->yuv_in.p;
+        for (int i = 0; i < n; ++i) {
+            const bool u_low = a.u[i] <= a.v[i];
+            const uint8_t* lo = u_low ? a.u[i] : a.v[i];
+            const uint8_t* hi = u_low ? a.v[i] : a.u[i];
+            dy[i] = base + at[i].y; d_dst[i] = h->d_out_argb.p + i * dpitch;
+            (u_low ? du : dv)[i] = base + at[i].lo; (u_low ? dv : du)[i] = base + at[i].hi;
+            NQ_HIP(h, hipMemcpyAsync(base + at[i].y, a.y[i], yb, hipMemcpyHostToDevice, h->stream));
+            if (at[i].joined) {
+                NQ_HIP(h, hipMemcpyAsync(base + at[i].lo, lo, (size_t) (hi - lo) + cb, hipMemcpyHostToDevice, h->stream));
+            } else {
+                NQ_HIP(h, hipMemcpyAsync(base + at[i].lo, lo, cb, hipMemcpyHostToDevice, h->stream));
+                NQ_HIP(h, hipMemcpyAsync(base + at[i].hi, hi, cb, hipMemcpyHostToDevice, h->stream));
+            }
+        }
+        YuvFrames d = a;
+        d.y = dy.data(); d.u = du.data(); d.v = dv.data();
+        const int rc = device(d, d_dst.data());
+        if (rc) return rc;
+        for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dst[i], d_dst[i], out_px * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        NQ_HIP(h, hipStreamSynchronize(h->stream));
+        return NQ_OK;
+    });
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_frames_from_yuv_device(nq_handle* h, int n, const uint8_t* const* d_y, const uint8_t* const* d_u, const uint8_t* const* d_v,
+                              int width, int height, int y_stride, int c_stride, int c_step, int yuv_flags, uint32_t* const* d_dst) {
+    if (!h) return NQ_ERR_INVALID;
+    const YuvFrames a = {n, d_y, d_u, d_v, width, height, y_stride, c_stride, c_step, yuv_flags};
+    int rc = yuv_check(h, a, 0, 0, width, height, d_dst, width, height, 0);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return yuv_device(h, a, d_dst);
+}
+
+int nq_frames_from_yuv(nq_handle* h, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
+                       int width, int height, int y_stride, int c_stride, int c_step, int yuv_flags, uint32_t* const* dst) {
+    if (!h) return NQ_ERR_INVALID;
+    const YuvFrames a = {n, y, u, v, width, height, y_stride, c_stride, c_step, yuv_flags};
+    int rc = yuv_check(h, a, 0, 0, width, height, dst, width, height, 0);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return yuv_host(h, a, dst, (size_t) width * height, [&](const YuvFrames& d, uint32_t* const* d_dst) { return yuv_device(h, d, d_dst); });
+}
+
+int nq_resample_frames_yuv_device(nq_handle* h, int n, const uint8_t* const* d_y, const uint8_t* const* d_u, const uint8_t* const* d_v,
+                                  int src_width, int src_height, int y_stride, int c_stride, int c_step, int yuv_flags,
+                                  int crop_x, int crop_y, int crop_w, int crop_h,
+                                  uint32_t* const* d_dst, int dst_width, int dst_height, int flags) {
+    if (!h) return NQ_ERR_INVALID;
+    const YuvFrames a = {n, d_y, d_u, d_v, src_width, src_height, y_stride, c_stride, c_step, yuv_flags};
+    int rc = yuv_check(h, a, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return resample_yuv_device(h, a, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+}
+
+int nq_resample_frames_yuv(nq_handle* h, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
+                           int src_width, int src_height, int y_stride, int c_stride, int c_step, int yuv_flags,
+                           int crop_x, int crop_y, int crop_w, int crop_h,
+                           uint32_t* const* dst, int dst_width, int dst_height, int flags) {
+    if (!h) return NQ_ERR_INVALID;
+    const YuvFrames a = {n, y, u, v, src_width, src_height, y_stride, c_stride, c_step, yuv_flags};
+    int rc = yuv_check(h, a, crop_x, crop_y, crop_w, crop_h, dst, dst_width, dst_height, flags);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return yuv_host(h, a, dst, (size_t) dst_width * dst_height, [&](const YuvFrames& d, uint32_t* const* d_dst) {
+        return resample_yuv_device(h, d, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
     });
 }
 

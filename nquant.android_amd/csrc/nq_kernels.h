@@ -330,6 +330,21 @@ void launch_refine(const RefineFrame* d_frames, int n, long long total, bool vec
 void launch_resample(const unsigned* const* d_src, unsigned* const* d_dst, int n, int src_width, int crop_x, int crop_y, int crop_w,
                      int crop_h, int dst_width, int dst_height, bool linear, bool vec, hipStream_t s);
 
+// ---- YUV 4:2:0 input (nq_yuv.hip; include/nquant_abi.h "YUV input"): d_tab is a device array of 4 n pointers -- the frames' y, u, v
+// planes (bytes, never written) and their outputs (ARGB words), n each.  Luma of pixel (x, y) is y[y * y_stride + x], its chroma
+// u / v[(y >> 1) * c_stride + (x >> 1) * c_step]; k: the coefficients of the call's flag word.  path: YUV_BYTE takes any pointers and
+// strides.  The wide paths -- the caller has checked for EVERY frame: width a multiple of 4, y and y_stride multiples of 4, and
+// YUV_WIDE_INTERLEAVED: c_step 2, the two chroma pointers one byte apart, the lower one (it goes into the u slot of the table; swap:
+// it is v's, the same for every frame) and c_stride multiples of 4; YUV_WIDE_PLANAR: c_step 1, u, v and c_stride even.
+// launch_yuv_argb converts 1:1 into tight width x height outputs; its wide paths also need every output 16-byte aligned.
+// launch_resample_yuv is launch_resample on the converted frames, bit for bit, without forming them (outputs: 4-byte alignment). ----
+enum { YUV_BYTE = 0, YUV_WIDE_INTERLEAVED = 1, YUV_WIDE_PLANAR = 2 };
+struct YuvCoef { int cy, crv, cgu, cgv, cbu, yo; };
+void launch_yuv_argb(const void* const* d_tab, int n, int width, int height, int y_stride, int c_stride, int c_step, int path, bool swap,
+                     const YuvCoef& k, hipStream_t s);
+void launch_resample_yuv(const void* const* d_tab, int n, int y_stride, int c_stride, int c_step, int path, bool swap, const YuvCoef& k,
+                         int crop_x, int crop_y, int crop_w, int crop_h, int dst_width, int dst_height, bool linear, hipStream_t s);
+
 // ---- ordered dither (nq_ordered.hip): d_frames is a device array of n frames, `total` the pixels of the sequence (sizes the grid),
 // d_palette the K entries (1..256) in device memory, T the first entry with alpha 0 or -1, limit 0..255.  One launch writes every
 // frame's index map and, with out, its ARGB output (then every frame's `argb` is set); d_stats: 2 n sums the caller zeroed, {pixels

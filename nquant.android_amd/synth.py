@@ -1,4 +1,4 @@
-"""Deterministic synthetic ARGB_8888 inputs: splitmix64(seed + i) per pixel.  Used by bench.py and the
+"""Deterministic synthetic ARGB_8888 (and YUV 4:2:0) inputs: splitmix64(seed + i) per pixel.  Used by bench.py and the
 tests; pure numpy (inputs only -- no quantizer arithmetic lives here)."""
 import numpy as np
 
@@ -100,6 +100,33 @@ def tile_photo(rgb, width, height, slot=0):
     r = np.minimum(rgb[..., 0] + np.uint32(slot % 7), np.uint32(255))
     a = ((np.uint32(255) << np.uint32(24)) | (r << np.uint32(16)) | (rgb[..., 1] << np.uint32(8)) | rgb[..., 2]).view(np.int32)
     return np.ascontiguousarray(np.tile(a, (height // a.shape[0] + 1, width // a.shape[1] + 1))[:height, :width])
+
+
+def yuv420(width, height, seed, layout="nv12", noise=24):
+    """One 8-bit YUV 4:2:0 frame as a contiguous uint8 buffer of width * height + 2 * cw2 * ch2 bytes in `layout` ("nv12", "nv21",
+    "i420", "yv12"; yuv.yuv_planes gives its planes): luma follows a diagonal ramp over the whole 0..255 range, u and v follow waves
+    across and down the frame, each with uniform noise of `noise` levels peak to peak -- values outside the limited range occur, so
+    the conversion's clamps are reached."""
+    cw2, ch2 = (width + 1) // 2, (height + 1) // 2
+    z = splitmix64(seed, width * height)
+    y, x = np.divmod(np.arange(width * height, dtype=np.int64), width)
+    fx, fy = x / max(width - 1, 1), y / max(height - 1, 1)
+    ny = (z & np.uint64(0xFF)).astype(np.float64) / 255.0 - 0.5
+    luma = np.clip(np.rint(255.0 * (0.5 * fx + 0.5 * fy) + noise * ny), 0, 255).astype(np.uint8)
+    zc = splitmix64(seed ^ 0xC420, cw2 * ch2)
+    cy, cx = np.divmod(np.arange(cw2 * ch2, dtype=np.int64), cw2)
+    gx, gy = cx / max(cw2 - 1, 1), cy / max(ch2 - 1, 1)
+    nu = (zc & np.uint64(0xFF)).astype(np.float64) / 255.0 - 0.5
+    nv = ((zc >> np.uint64(8)) & np.uint64(0xFF)).astype(np.float64) / 255.0 - 0.5
+    u = np.clip(np.rint(128.0 + 110.0 * np.sin(2.0 * np.pi * gx) + noise * nu), 0, 255).astype(np.uint8)
+    v = np.clip(np.rint(128.0 + 110.0 * np.cos(2.0 * np.pi * gy) + noise * nv), 0, 255).astype(np.uint8)
+    if layout in ("nv12", "nv21"):
+        chroma = np.stack([u, v] if layout == "nv12" else [v, u], 1).reshape(-1)
+    elif layout in ("i420", "yv12"):
+        chroma = np.concatenate([u, v] if layout == "i420" else [v, u])
+    else:
+        raise ValueError("layout must be nv12, nv21, i420 or yv12, got %r" % (layout,))
+    return np.concatenate([luma, chroma])
 
 
 def gradient_noise_torch(width, height, seed, device="cuda", noise=24, row0=0, rows=None):
