@@ -675,6 +675,69 @@ int nq_resample_frames_yuv(nq_handle* h, int n, const uint8_t* const* y, const u
                            int crop_x, int crop_y, int crop_w, int crop_h,
                            uint32_t* const* dst, int dst_width, int dst_height, int flags);
 
+/* ---- orientation: turn and mirror a frame sequence (ffmpeg transpose / autorotate; Android's sensorOrientation and MediaCodec's
+ *      KEY_ROTATION).  A camera or a decoder writes frames in sensor orientation; these calls bring them upright on the device, as
+ *      ARGB words or straight from the YUV planes, alone or together with the reducer.  Words are moved, never changed.
+ *  * orientation is 1..8 with EXIF's meaning.  Source frame: W x H, pixel src(x, y).
+ *        code   output   out(x, y) =             name
+ *         1     W x H    src(x, y)               identity
+ *         2     W x H    src(W-1-x, y)           mirror left-right
+ *         3     W x H    src(W-1-x, H-1-y)       180 degrees
+ *         4     W x H    src(x, H-1-y)           mirror top-bottom
+ *         5     H x W    src(y, x)               transpose
+ *         6     H x W    src(y, H-1-x)           90 degrees clockwise
+ *         7     H x W    src(W-1-y, H-1-x)       transverse
+ *         8     H x W    src(W-1-y, x)           270 degrees clockwise
+ *    A clip with rotation r (clockwise, to be applied for display) takes 1, 6, 3, 8 for r = 0, 90, 180, 270; mirrored left-right
+ *    afterwards 2, 5, 4, 7.
+ *  * nq_orient_frames_device: n frames of src_width x src_height words, rows contiguous; output i holds the oriented frame, rows
+ *    contiguous (src_height words per row for codes 5..8).
+ *    nq_frames_from_yuv_oriented_device  IS  nq_frames_from_yuv_device, then nq_orient_frames_device, without the unturned ARGB frames
+ *    ever existing.  The chroma sample of a pixel is that of its SOURCE coordinates.
+ *    nq_resample_frames_oriented_device  IS  nq_orient_frames_device, then nq_resample_frames_device: the crop and the target are
+ *    given in oriented (as displayed) coordinates.
+ *    nq_resample_frames_yuv_oriented_device  IS  convert, then orient, then reduce.
+ *    All three bit for bit.  The reducing calls map the crop back into the source, reduce there into handle scratch and orient the
+ *    small result: the overlap weights of "frame reduction" are symmetric under the reflection of an axis, swapping the axes swaps wx
+ *    and wy in a product, and the sums are integers, so orienting commutes with the reducer exactly.
+ *  * The _device forms take host arrays of n DEVICE pointers and are asynchronous on the handle's stream; sources are never written
+ *    and nothing outside the n outputs is written.  h may be a handle of either kind: its stream, scratch and error text are used,
+ *    its params are neither read nor changed.  Pointers to words need 4-byte alignment.  nq_orient_frames_device moves 16 bytes per
+ *    access when every source and output is 16-byte aligned, src_width is a multiple of 4 and, for codes 5..8, so is src_height;
+ *    nq_frames_from_yuv_oriented_device when nq_frames_from_yuv_device would and, for codes 5..8, height is a multiple of 4;
+ *    otherwise one word (one pixel) per access, with the same results.
+ *    The forms without _device: the same with HOST buffers (upload, the device form, the n outputs copied back; the call returns
+ *    when they are there).
+ *  * NQ_ERR_INVALID before any device work, every buffer untouched, the handle still usable: orientation outside 1..8; every error
+ *    of the calls the definition names, the crop being checked against the ORIENTED frame; an output that overlaps a source or
+ *    another output (in-place use included).
+ *  The kernels: DESIGN.md 5h "Orientation". ---- */
+int nq_orient_frames_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_width, int src_height, int orientation,
+                            uint32_t* const* d_dst);
+int nq_orient_frames(nq_handle* h, int n, const uint32_t* const* src, int src_width, int src_height, int orientation,
+                     uint32_t* const* dst);
+int nq_frames_from_yuv_oriented_device(nq_handle* h, int n, const uint8_t* const* d_y, const uint8_t* const* d_u,
+                                       const uint8_t* const* d_v, int width, int height, int y_stride, int c_stride, int c_step,
+                                       int yuv_flags, int orientation, uint32_t* const* d_dst);
+int nq_frames_from_yuv_oriented(nq_handle* h, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
+                                int width, int height, int y_stride, int c_stride, int c_step, int yuv_flags, int orientation,
+                                uint32_t* const* dst);
+int nq_resample_frames_oriented_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_width, int src_height,
+                                       int orientation, int crop_x, int crop_y, int crop_w, int crop_h,
+                                       uint32_t* const* d_dst, int dst_width, int dst_height, int flags);
+int nq_resample_frames_oriented(nq_handle* h, int n, const uint32_t* const* src, int src_width, int src_height,
+                                int orientation, int crop_x, int crop_y, int crop_w, int crop_h,
+                                uint32_t* const* dst, int dst_width, int dst_height, int flags);
+int nq_resample_frames_yuv_oriented_device(nq_handle* h, int n, const uint8_t* const* d_y, const uint8_t* const* d_u,
+                                           const uint8_t* const* d_v, int src_width, int src_height, int y_stride, int c_stride,
+                                           int c_step, int yuv_flags, int orientation,
+                                           int crop_x, int crop_y, int crop_w, int crop_h,
+                                           uint32_t* const* d_dst, int dst_width, int dst_height, int flags);
+int nq_resample_frames_yuv_oriented(nq_handle* h, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
+                                    int src_width, int src_height, int y_stride, int c_stride, int c_step, int yuv_flags,
+                                    int orientation, int crop_x, int crop_y, int crop_w, int crop_h,
+                                    uint32_t* const* dst, int dst_width, int dst_height, int flags);
+
 /* ---- ordered dither: a positional dither for frame sequences (ffmpeg paletteuse=dither=bayer, ImageMagick -ordered-dither).  The
  *      index of a pixel depends on its colour, its coordinates and the palette only -- not on any other pixel, as in the Gilbert-curve
  *      error diffusion of the convert calls.  An unchanged pixel gives an unchanged index in every frame, at any tile size, with no

@@ -19,6 +19,7 @@ from .refine import convert_frames_refined, palette_error, refine_palette, refin
 from .resample import fit_size, resample_frames, resample_frames_device
 from .ordered import convert_frames_ordered, dither_ordered, dither_ordered_device
 from .yuv import frames_from_yuv, frames_from_yuv_device, resample_frames_yuv, resample_frames_yuv_device, yuv_planes
+from .orient import orient_frames, orient_frames_device, orientation, oriented_size, source_rect
 from .build import build as build_library
 
 __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARALLEL_TILED", "MODE_LOOKUP_ONLY",
@@ -32,4 +33,5 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "shots_from_signatures", "detect_shots", "detect_shots_device", "convert_clip_to_gif", "refine_palette",
            "refine_palette_device", "palette_error", "convert_frames_refined", "fit_size", "resample_frames", "resample_frames_device",
            "dither_ordered", "dither_ordered_device", "convert_frames_ordered", "frames_from_yuv", "frames_from_yuv_device",
-           "resample_frames_yuv", "resample_frames_yuv_device", "yuv_planes"]
+           "resample_frames_yuv", "resample_frames_yuv_device", "yuv_planes", "orient_frames", "orient_frames_device", "orientation",
+           "oriented_size", "source_rect"]

@@ -85,7 +85,7 @@ def write_apng(path, frames, palette, delays_cs=None, loop=0, segment_bytes=0, d
 
 def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, seeds=None, tile=None, segment_bytes=0, device=0,
                            mode=MODE_PARALLEL_TILED, return_rects=False, hold=None, refine=0, size=None, crop=None, linear_resample=True,
-                           ordered=None, yuv=None):
+                           ordered=None, yuv=None, orient=1):
     """convert_frames (one shared palette for the ARGB frames, which must have one size) followed by encode_apng of the index maps on
     the same handle.  nMaxColors <= 256.  Seeds are passed on as given: regions that do not move repeat in the index maps, and so drop
     out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.  hold (None: no such pass): an integer
@@ -98,6 +98,8 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
     limit instead; dither, mode and tile then take no part, and seeds may not be given.
     yuv (None: the frames are ARGB words): a dict with the keys bt709 / full_range says that `frames` are (y, u, v) tuples of 8-bit
     YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
+    orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
+    converting kernel --; size and crop are then those of the oriented frames.
     Returns (file bytes, palette); with return_rects=True (file bytes, palette, rectangles)."""
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a PNG palette holds at most 256 entries")
@@ -106,6 +108,8 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
     ordered = _ordered_keyword(ordered, seeds)
     if hold is not None:
         hold = _threshold(hold)
+    from .orient import _code as _orient_code
+    orient = _orient_code(orient)
     if yuv is None:
         frames, q = _frames_quantizer(kind, frames, device, mode, tile)
     else:
@@ -113,10 +117,10 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
         frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
     try:
         if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv)
-        elif size is not None or crop is not None:
+            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
+        elif size is not None or crop is not None or orient != 1:
             from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
+            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
         palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
         maps = _index_maps([o.index for o in outs])
         height, width = _one_size(maps)

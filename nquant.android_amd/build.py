@@ -28,7 +28,8 @@ UNITS = {
     "nq_refine.hip": ("device", ["nq_refine.hip", "nq_kernels.h"]),
     "nq_ordered.hip": ("device", ["nq_ordered.hip", "nq_kernels.h", os.path.join(INC, "nq_blue_noise_64x64.inc")]),
     "nq_resample.hip": ("device", ["nq_resample.hip", "nq_resample.inc", "nq_kernels.h", os.path.join(INC, "nq_srgb_linear_16.inc")]),
-    "nq_yuv.hip": ("device", ["nq_yuv.hip", "nq_resample.inc", "nq_kernels.h", os.path.join(INC, "nq_srgb_linear_16.inc")]),
+    "nq_yuv.hip": ("device", ["nq_yuv.hip", "nq_yuv.inc", "nq_resample.inc", "nq_kernels.h", os.path.join(INC, "nq_srgb_linear_16.inc")]),
+    "nq_orient.hip": ("device", ["nq_orient.hip", "nq_yuv.inc", "nq_kernels.h"]),
     "nq_abi.cpp": ("host", ["nq_abi.cpp", "nq_kernels.h", os.path.join(INC, "nquant_abi.h")]),
 }
 

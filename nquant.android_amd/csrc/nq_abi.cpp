@@ -275,6 +275,11 @@ struct nq_handle {
     std::vector<const void*> h_yuv_ptrs;
     DevBuf<const void*> yuv_ptrs;
     DevBuf<unsigned char> yuv_in;
+    // nq_orient_frames_device: the tables of frame pointers (source, output: n each; the host copy stays alive for the asynchronous
+    // upload).  The reducing *_oriented calls reduce into orient_tmp (the frames 16-byte aligned) and orient from there.
+    std::vector<void*> h_orient_ptrs;
+    DevBuf<void*> orient_ptrs;
+    DevBuf<uint32_t> orient_tmp;
     // nq_dither_ordered_device: the frame table, the palette (256 words) and the 2 n statistics (the host copies stay alive for the
     // asynchronous uploads); nq_dither_ordered stages its frames in d_in / d_out_index / d_out_argb
     std::vector<nq::OrderedFrame> h_ordered_frames;
@@ -3424,10 +3429,11 @@ int yuv_check(nq_handle* h, const YuvFrames& a, int crop_x, int crop_y, int crop
 // The kernels' path for DEVICE frames `a` and outputs d_dst, and the pointer table on its way to the device.  The wide paths need,
 // for EVERY frame: width, y and y_stride multiples of 4 (out16: and the output 16-byte aligned), and either c_step 2 with u and v
 // one byte apart in the same order, the lower one and c_stride multiples of 4 (interleaved: NV12, NV21), or c_step 1 with u, v and
-// c_stride even (planar: I420, YV12).  Everything else takes the byte path.
-int yuv_table(nq_handle* h, const YuvFrames& a, uint32_t* const* d_dst, bool out16, int* path, bool* swap) {
+// c_stride even (planar: I420, YV12).  Everything else takes the byte path.  rows4 (the turning codes of nq_orient.hip): the wide paths
+// also need height a multiple of 4.
+int yuv_table(nq_handle* h, const YuvFrames& a, uint32_t* const* d_dst, bool out16, int* path, bool* swap, bool rows4 = false) {
     const int n = a.n;
-    bool wide = a.width % 4 == 0 && a.y_stride % 4 == 0;
+    bool wide = a.width % 4 == 0 && a.y_stride % 4 == 0 && !(rows4 && a.height % 4);
     bool inter = a.c_step == 2 && a.c_stride % 4 == 0, planar = a.c_step == 1 && a.c_stride % 2 == 0;
     int order = 0;                                  // +1: u is the lower pointer of every frame so far, -1: v is
     for (int i = 0; i < n; ++i) {
@@ -3578,6 +3584,246 @@ int nq_resample_frames_yuv(nq_handle* h, int n, const uint8_t* const* y, const u
     if (rc) return rc;
     return yuv_host(h, a, dst, (size_t) dst_width * dst_height, [&](const YuvFrames& d, uint32_t* const* d_dst) {
         return resample_yuv_device(h, d, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+    });
+}
+
+} // extern "C"
+
+// ---- orientation (nq_orient.hip) ----
+namespace {
+
+// The geometry of an oriented call, from its numbers alone: the code, the source sides, and -- reduce: for the reducing calls -- the
+// crop against the ORIENTED frame.  On success the crop is mapped back into source coordinates and, for the turning codes, the
+// target's sides are swapped: the reducer runs on the source with these, and orienting its result gives the call's (orienting
+// commutes with the reducer: DESIGN.md 5h).  out(x, y) = src(sx, sy) with sx running with or against (fx) one oriented axis and sy
+// with or against (fy) the other; codes 5..8 swap the axes.
+int orient_geometry(nq_handle* h, int width, int height, int orientation, bool reduce, int* crop_x, int* crop_y, int* crop_w, int* crop_h,
+                    int* dst_width, int* dst_height) {
+    if (orientation < 1 || orientation > 8) NQ_FAIL(h, NQ_ERR_INVALID, "orientation = %d: must be 1..8 (EXIF)", orientation);
+    if (width < 1 || width > 65535 || height < 1 || height > 65535)
+        NQ_FAIL(h, NQ_ERR_INVALID, "%d x %d: source sides must be 1..65535", width, height);
+    if (!reduce) return NQ_OK;
+    const bool turn = orientation >= 5;
+    const bool fx = orientation == 2 || orientation == 3 || orientation == 7 || orientation == 8;
+    const bool fy = orientation == 3 || orientation == 4 || orientation == 6 || orientation == 7;
+    const int ow = turn ? height : width, oh = turn ? width : height;
+    const int cx = *crop_x, cy = *crop_y, cw = *crop_w, ch = *crop_h;
+    if (cw < 1 || ch < 1 || cx < 0 || cy < 0 || cx > ow - cw || cy > oh - ch)
+        NQ_FAIL(h, NQ_ERR_INVALID, "crop %d x %d at (%d, %d): empty or outside the oriented %d x %d frame", cw, ch, cx, cy, ow, oh);
+    // along the source's columns lies the oriented y axis when the code turns, else the x axis
+    const int a = turn ? cy : cx, al = turn ? ch : cw, b = turn ? cx : cy, bl = turn ? cw : ch;
+    *crop_x = fx ? width - a - al : a; *crop_w = al;
+    *crop_y = fy ? height - b - bl : b; *crop_h = bl;
+    if (turn) std::swap(*dst_width, *dst_height);
+    return NQ_OK;
+}
+
+// nq_orient_frames_device after the checks: the pointer tables go up, one launch orients the sequence
+int orient_device(nq_handle* h, int n, const uint32_t* const* d_src, int width, int height, int orientation, uint32_t* const* d_dst) {
+    std::vector<void*>& t = h->h_orient_ptrs;
+    t.assign(2 * (size_t) n, nullptr);
+    bool wide = width % 4 == 0 && !(orientation >= 5 && height % 4);     // the 16-byte path: loads along width, turned stores along height
+    for (int i = 0; i < n; ++i) {
+        t[i] = const_cast<uint32_t*>(d_src[i]); t[n + (size_t) i] = d_dst[i];     // (the kernel reads the sources only)
+        wide = wide && !(((uintptr_t) d_src[i] | (uintptr_t) d_dst[i]) & 15);
+    }
+    NQ_HIP(h, h->orient_ptrs.reserve(t.size()));
+    // (the call returns with this upload only enqueued: safe for the reason given in hold_device)
+    NQ_HIP(h, hipMemcpyAsync(h->orient_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+    launch_orient(reinterpret_cast<const unsigned* const*>(h->orient_ptrs.p), reinterpret_cast<unsigned* const*>(h->orient_ptrs.p + n), n, width,
+                  height, orientation, wide, h->stream);
+    NQ_HIP(h, launch_status());
+    return NQ_OK;
+}
+
+// room for n reduced frames of px words in orient_tmp, each at a 16-byte boundary (growing the buffer frees the old one, which waits
+// for the device)
+int orient_room(nq_handle* h, int n, size_t px, std::vector<uint32_t*>& d_tmp) {
+    const size_t pitch = (px + 3) & ~(size_t) 3;
+    NQ_HIP(h, h->orient_tmp.reserve(n * pitch));
+    d_tmp.resize(n);
+    for (int i = 0; i < n; ++i) d_tmp[i] = h->orient_tmp.p + i * pitch;
+    return NQ_OK;
+}
+
+// nq_resample_frames_oriented_device after the checks; crop and target are the SOURCE's (orient_geometry).  Code 1 is the reducer alone.
+int resample_oriented_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_width, int orientation, int crop_x, int crop_y,
+                             int crop_w, int crop_h, uint32_t* const* d_dst, int dst_width, int dst_height, int flags) {
+    if (orientation == 1) return resample_device(h, n, d_src, src_width, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+    std::vector<uint32_t*> d_tmp;
+    int rc = orient_room(h, n, (size_t) dst_width * dst_height, d_tmp);
+    if (rc) return rc;
+    rc = resample_device(h, n, d_src, src_width, crop_x, crop_y, crop_w, crop_h, d_tmp.data(), dst_width, dst_height, flags);
+    if (rc) return rc;
+    return orient_device(h, n, d_tmp.data(), dst_width, dst_height, orientation, d_dst);
+}
+
+// nq_frames_from_yuv_oriented_device after the checks: the pointer table goes up, one launch converts and orients the sequence
+int yuv_orient_device(nq_handle* h, const YuvFrames& a, int orientation, uint32_t* const* d_dst) {
+    int path; bool swap;
+    const int rc = yuv_table(h, a, d_dst, true, &path, &swap, orientation >= 5);
+    if (rc) return rc;
+    launch_yuv_orient(h->yuv_ptrs.p, a.n, a.width, a.height, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.yuv_flags], orientation,
+                      h->stream);
+    NQ_HIP(h, launch_status());
+    return NQ_OK;
+}
+
+// nq_resample_frames_yuv_oriented_device after the checks; crop and target are the SOURCE's.  Code 1 is the fused reducer alone.
+int resample_yuv_oriented_device(nq_handle* h, const YuvFrames& a, int orientation, int crop_x, int crop_y, int crop_w, int crop_h,
+                                 uint32_t* const* d_dst, int dst_width, int dst_height, int flags) {
+    if (orientation == 1) return resample_yuv_device(h, a, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+    std::vector<uint32_t*> d_tmp;
+    int rc = orient_room(h, a.n, (size_t) dst_width * dst_height, d_tmp);
+    if (rc) return rc;
+    rc = resample_yuv_device(h, a, crop_x, crop_y, crop_w, crop_h, d_tmp.data(), dst_width, dst_height, flags);
+    if (rc) return rc;
+    return orient_device(h, a.n, d_tmp.data(), dst_width, dst_height, orientation, d_dst);
+}
+
+// The host forms of the two ARGB calls: the frames go up into d_in, device(sources, outputs) runs on the staged copies (16-byte
+// aligned), the n outputs of out_px words come back from d_out_argb.
+template <typename Device>
+int orient_host(nq_handle* h, int n, const uint32_t* const* src, size_t src_px, uint32_t* const* dst, size_t out_px, Device device) {
+    const size_t spitch = (src_px + 3) & ~(size_t) 3, dpitch = (out_px + 3) & ~(size_t) 3;
+    return host_form(h, [&]() -> int {
+        NQ_HIP(h, h->d_in.reserve(n * spitch));
+        NQ_HIP(h, h->d_out_argb.reserve(n * dpitch));
+        std::vector<const uint32_t*> d_src(n);
+        std::vector<uint32_t*> d_dst(n);
+        for (int i = 0; i < n; ++i) {
+            d_src[i] = h->d_in.p + i * spitch; d_dst[i] = h->d_out_argb.p + i * dpitch;
+            NQ_HIP(h, hipMemcpyAsync(h->d_in.p + i * spitch, src[i], src_px * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        }
+        const int rc = device(d_src.data(), d_dst.data());
+        if (rc) return rc;
+        for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dst[i], d_dst[i], out_px * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        NQ_HIP(h, hipStreamSynchronize(h->stream));
+        return NQ_OK;
+    });
+}
+
+// every argument of both forms of nq_orient_frames: resample_check's, with the whole frame as crop and target (a turned output
+// holds as many words)
+int orient_check(nq_handle* h, int n, const uint32_t* const* src, int width, int height, int orientation, uint32_t* const* dst) {
+    const int rc = orient_geometry(h, width, height, orientation, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return rc ? rc : resample_check(h, n, src, width, height, 0, 0, width, height, dst, width, height, 0);
+}
+
+// ... of nq_resample_frames_oriented: on success crop and target are the source's
+int resample_oriented_check(nq_handle* h, int n, const uint32_t* const* src, int width, int height, int orientation, int* crop_x, int* crop_y,
+                            int* crop_w, int* crop_h, uint32_t* const* dst, int* dst_width, int* dst_height, int flags) {
+    const int rc = orient_geometry(h, width, height, orientation, true, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height);
+    return rc ? rc : resample_check(h, n, src, width, height, *crop_x, *crop_y, *crop_w, *crop_h, dst, *dst_width, *dst_height, flags);
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_orient_frames_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_width, int src_height, int orientation,
+                            uint32_t* const* d_dst) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = orient_check(h, n, d_src, src_width, src_height, orientation, d_dst);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return orient_device(h, n, d_src, src_width, src_height, orientation, d_dst);
+}
+
+int nq_orient_frames(nq_handle* h, int n, const uint32_t* const* src, int src_width, int src_height, int orientation, uint32_t* const* dst) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = orient_check(h, n, src, src_width, src_height, orientation, dst);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    const size_t px = (size_t) src_width * src_height;
+    return orient_host(h, n, src, px, dst, px, [&](const uint32_t* const* d_src, uint32_t* const* d_dst) {
+        return orient_device(h, n, d_src, src_width, src_height, orientation, d_dst);
+    });
+}
+
+int nq_resample_frames_oriented_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_width, int src_height, int orientation,
+                                       int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* d_dst, int dst_width,
+                                       int dst_height, int flags) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = resample_oriented_check(h, n, d_src, src_width, src_height, orientation, &crop_x, &crop_y, &crop_w, &crop_h, d_dst, &dst_width,
+                                     &dst_height, flags);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return resample_oriented_device(h, n, d_src, src_width, orientation, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+}
+
+int nq_resample_frames_oriented(nq_handle* h, int n, const uint32_t* const* src, int src_width, int src_height, int orientation,
+                                int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* dst, int dst_width, int dst_height,
+                                int flags) {
+    if (!h) return NQ_ERR_INVALID;
+    int rc = resample_oriented_check(h, n, src, src_width, src_height, orientation, &crop_x, &crop_y, &crop_w, &crop_h, dst, &dst_width,
+                                     &dst_height, flags);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return orient_host(h, n, src, (size_t) src_width * src_height, dst, (size_t) dst_width * dst_height,
+                       [&](const uint32_t* const* d_src, uint32_t* const* d_dst) {
+        return resample_oriented_device(h, n, d_src, src_width, orientation, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+    });
+}
+
+int nq_frames_from_yuv_oriented_device(nq_handle* h, int n, const uint8_t* const* d_y, const uint8_t* const* d_u, const uint8_t* const* d_v,
+                                       int width, int height, int y_stride, int c_stride, int c_step, int yuv_flags, int orientation,
+                                       uint32_t* const* d_dst) {
+    if (!h) return NQ_ERR_INVALID;
+    const YuvFrames a = {n, d_y, d_u, d_v, width, height, y_stride, c_stride, c_step, yuv_flags};
+    int rc = orient_geometry(h, width, height, orientation, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (!rc) rc = yuv_check(h, a, 0, 0, width, height, d_dst, width, height, 0);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return yuv_orient_device(h, a, orientation, d_dst);
+}
+
+int nq_frames_from_yuv_oriented(nq_handle* h, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
+                                int width, int height, int y_stride, int c_stride, int c_step, int yuv_flags, int orientation,
+                                uint32_t* const* dst) {
+    if (!h) return NQ_ERR_INVALID;
+    const YuvFrames a = {n, y, u, v, width, height, y_stride, c_stride, c_step, yuv_flags};
+    int rc = orient_geometry(h, width, height, orientation, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (!rc) rc = yuv_check(h, a, 0, 0, width, height, dst, width, height, 0);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return yuv_host(h, a, dst, (size_t) width * height,
+                    [&](const YuvFrames& d, uint32_t* const* d_dst) { return yuv_orient_device(h, d, orientation, d_dst); });
+}
+
+int nq_resample_frames_yuv_oriented_device(nq_handle* h, int n, const uint8_t* const* d_y, const uint8_t* const* d_u,
+                                           const uint8_t* const* d_v, int src_width, int src_height, int y_stride, int c_stride, int c_step,
+                                           int yuv_flags, int orientation, int crop_x, int crop_y, int crop_w, int crop_h,
+                                           uint32_t* const* d_dst, int dst_width, int dst_height, int flags) {
+    if (!h) return NQ_ERR_INVALID;
+    const YuvFrames a = {n, d_y, d_u, d_v, src_width, src_height, y_stride, c_stride, c_step, yuv_flags};
+    int rc = orient_geometry(h, src_width, src_height, orientation, true, &crop_x, &crop_y, &crop_w, &crop_h, &dst_width, &dst_height);
+    if (!rc) rc = yuv_check(h, a, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return resample_yuv_oriented_device(h, a, orientation, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
+}
+
+int nq_resample_frames_yuv_oriented(nq_handle* h, int n, const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v,
+                                    int src_width, int src_height, int y_stride, int c_stride, int c_step, int yuv_flags, int orientation,
+                                    int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* dst, int dst_width, int dst_height,
+                                    int flags) {
+    if (!h) return NQ_ERR_INVALID;
+    const YuvFrames a = {n, y, u, v, src_width, src_height, y_stride, c_stride, c_step, yuv_flags};
+    int rc = orient_geometry(h, src_width, src_height, orientation, true, &crop_x, &crop_y, &crop_w, &crop_h, &dst_width, &dst_height);
+    if (!rc) rc = yuv_check(h, a, crop_x, crop_y, crop_w, crop_h, dst, dst_width, dst_height, flags);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (rc) return rc;
+    return yuv_host(h, a, dst, (size_t) dst_width * dst_height, [&](const YuvFrames& d, uint32_t* const* d_dst) {
+        return resample_yuv_oriented_device(h, d, orientation, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
     });
 }
 

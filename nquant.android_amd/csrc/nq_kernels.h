@@ -345,6 +345,18 @@ void launch_yuv_argb(const void* const* d_tab, int n, int width, int height, int
 void launch_resample_yuv(const void* const* d_tab, int n, int y_stride, int c_stride, int c_step, int path, bool swap, const YuvCoef& k,
                          int crop_x, int crop_y, int crop_w, int crop_h, int dst_width, int dst_height, bool linear, hipStream_t s);
 
+// ---- orientation (nq_orient.hip; include/nquant_abi.h "orientation"): every frame of width x height is turned / mirrored by the
+// EXIF code `orientation` (1..8, checked by the caller) into a tight output of width x height (codes 1..4) or height x width
+// (codes 5..8) words, in one launch.  launch_orient: d_src / d_dst are device arrays of n frame pointers (sources never written).
+// wide: the 16-byte path -- the caller has checked that EVERY pointer is 16-byte aligned, width is a multiple of 4 and, for codes
+// 5..8, so is height; otherwise one word per access (4-byte alignment).  launch_yuv_orient is launch_yuv_argb followed by
+// launch_orient, bit for bit, without forming the unturned frames: d_tab and the other arguments as for launch_yuv_argb; its wide
+// paths need what launch_yuv_argb's need and, for codes 5..8, height a multiple of 4. ----
+void launch_orient(const unsigned* const* d_src, unsigned* const* d_dst, int n, int width, int height, int orientation, bool wide,
+                   hipStream_t s);
+void launch_yuv_orient(const void* const* d_tab, int n, int width, int height, int y_stride, int c_stride, int c_step, int path, bool swap,
+                       const YuvCoef& k, int orientation, hipStream_t s);
+
 // ---- ordered dither (nq_ordered.hip): d_frames is a device array of n frames, `total` the pixels of the sequence (sizes the grid),
 // d_palette the K entries (1..256) in device memory, T the first entry with alpha 0 or -1, limit 0..255.  One launch writes every
 // frame's index map and, with out, its ARGB output (then every frame's `argb` is set); d_stats: 2 n sums the caller zeroed, {pixels

@@ -302,7 +302,7 @@ def _shots(shot_starts, n):
 
 def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0,
                          mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None,
-                         linear_resample=True, ordered=None, yuv=None, delta=True):
+                         linear_resample=True, ordered=None, yuv=None, orient=1, delta=True):
     """One palette per shot: frames shot_starts[k] .. shot_starts[k + 1] - 1 are shot k and get a convert_frames palette of their own
     (shot_starts=range(n): one palette per frame), then encode_gif_local_delta (delta=False: encode_gif_local) writes all frames, each
     with its shot's palette as its local colour table.  hold (delta=True only) runs per shot and never across a cut: a held index means
@@ -311,10 +311,14 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
     convert_frames_to_gif.
     yuv (None: the frames are ARGB words): a dict with the keys bt709 / full_range says that `frames` are (y, u, v) tuples of 8-bit
     YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
+    orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
+    converting kernel --; size and crop are then those of the oriented frames.
     Everything runs on one handle.  Cuts are the caller's to give here; convert_clip_to_gif finds them.
     Returns (file bytes, list of per-shot palettes)."""
     lossy = _lossy_keyword(lossy)
     ordered = _ordered_keyword(ordered, seeds)
+    from .orient import _code as _orient_code
+    orient = _orient_code(orient)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
     if hold is not None and not delta:
@@ -334,10 +338,10 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
         frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
     try:
         if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv)
-        elif size is not None or crop is not None:
+            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
+        elif size is not None or crop is not None or orient != 1:
             from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
+            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
         return _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine, ordered)
     finally:
         q.close()
@@ -375,7 +379,7 @@ def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segm
 
 def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, delays_cs=None, loop=0, segment_pixels=0, device=0,
                         mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None,
-                        linear_resample=True, ordered=None, yuv=None, delta=True):
+                        linear_resample=True, ordered=None, yuv=None, orient=1, delta=True):
     """A list of frames in, an animation out: detect_shots (shots.py; cut in per mille, min_shot in frames) finds where the clip needs
     a new palette, then exactly convert_shots_to_gif with those starts -- both on one handle.  The frames must have one size (delta or
     not: a signature is compared between frames of one size).  With size or crop the frames are reduced first (resample.py) and the
@@ -383,6 +387,8 @@ def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, de
     Returns (file bytes, list of per-shot palettes, shot_starts)."""
     lossy = _lossy_keyword(lossy)
     ordered = _ordered_keyword(ordered, seeds)
+    from .orient import _code as _orient_code
+    orient = _orient_code(orient)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
     if hold is not None and not delta:
@@ -402,10 +408,10 @@ def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, de
         frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
     try:
         if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv)
-        elif size is not None or crop is not None:
+            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
+        elif size is not None or crop is not None or orient != 1:
             from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
+            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
         starts, _ = _detect_host(q._L, q._h, q._check, frames, cut, min_shot)
         data, palettes = _shots_to_gif_on(q, frames, _shots(starts, len(frames)), nMaxColors, dither, delays_cs, loop, segment_pixels, mode,
                                           seeds, hold, lossy, delta, refine, ordered)
@@ -433,7 +439,7 @@ def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, 
 
 def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
                           seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None, linear_resample=True, ordered=None,
-                          yuv=None, delta=False):
+                          yuv=None, orient=1, delta=False):
     """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
     delta=True: encode_gif_delta instead; the frames must have one size.  Seeds are passed on as given: regions that do not move repeat
     in the index maps, and so drop out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.
@@ -451,16 +457,20 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
     unchanged pixels repeat without seeds.  dither, mode and tile then take no part, and seeds may not be given.
     yuv (None: the frames are ARGB words): a dict with the keys bt709 / full_range says that `frames` are (y, u, v) tuples of 8-bit
     YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
+    orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
+    converting kernel --; size and crop are then those of the oriented frames.
     Returns (file bytes, palette)."""
     lossy = _lossy_keyword(lossy)
     ordered = _ordered_keyword(ordered, seeds)
+    from .orient import _code as _orient_code
+    orient = _orient_code(orient)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a GIF colour table holds at most 256 entries")
     if hold is not None and not delta:
         raise ValueError("hold needs delta=True: full frames store every pixel whether it repeats or not")
     if yuv is None and delta and len({np.asarray(f).shape for f in frames}) > 1:
         raise ValueError("delta mode: all frames must have one size")
-    if size is not None or crop is not None or yuv is not None:
+    if size is not None or crop is not None or yuv is not None or orient != 1:
         from .resample import _resample_host
         if hold is not None:
             from .hold import _hold_host, _threshold
@@ -472,9 +482,9 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
             frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
         try:
             if yuv is None:
-                frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
+                frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
             else:
-                frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv)
+                frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
             palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
             maps = _index_maps([o.index for o in outs])
             height, width = _one_size(maps)

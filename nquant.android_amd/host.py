@@ -120,6 +120,14 @@ _ABI = {
     "nq_frames_from_yuv": (_i32, [_vp, _i32, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     "nq_resample_frames_yuv_device": (_i32, [_vp, _i32, _vp, _vp, _vp] + [_i32] * 10 + [_vp, _i32, _i32, _i32]),
     "nq_resample_frames_yuv": (_i32, [_vp, _i32, _vp, _vp, _vp] + [_i32] * 10 + [_vp, _i32, _i32, _i32]),
+    "nq_orient_frames_device": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "nq_orient_frames": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "nq_frames_from_yuv_oriented_device": (_i32, [_vp, _i32, _vp, _vp, _vp] + [_i32] * 7 + [_vp]),
+    "nq_frames_from_yuv_oriented": (_i32, [_vp, _i32, _vp, _vp, _vp] + [_i32] * 7 + [_vp]),
+    "nq_resample_frames_oriented_device": (_i32, [_vp, _i32, _vp] + [_i32] * 7 + [_vp, _i32, _i32, _i32]),
+    "nq_resample_frames_oriented": (_i32, [_vp, _i32, _vp] + [_i32] * 7 + [_vp, _i32, _i32, _i32]),
+    "nq_resample_frames_yuv_oriented_device": (_i32, [_vp, _i32, _vp, _vp, _vp] + [_i32] * 11 + [_vp, _i32, _i32, _i32]),
+    "nq_resample_frames_yuv_oriented": (_i32, [_vp, _i32, _vp, _vp, _vp] + [_i32] * 11 + [_vp, _i32, _i32, _i32]),
     "nq_dither_ordered_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "nq_dither_ordered": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "nq_convert_frames_ordered_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _pi32]),

@@ -63,12 +63,14 @@ def dither_ordered_device(q, d_pixels, widths, heights, palette, limit, d_out_in
                    None if d_out_argb is None else list(d_out_argb), return_stats)
 
 
-def convert_frames_ordered(kind, frames, nMaxColors, limit, refine=0, device=0, size=None, crop=None, linear_resample=True, yuv=None):
+def convert_frames_ordered(kind, frames, nMaxColors, limit, refine=0, device=0, size=None, crop=None, linear_resample=True, yuv=None, orient=1):
     """nq_convert_frames_ordered on host arrays: one shared palette for the frames (convert_frames' palette), `refine` (0..64) k-means
     passes on it over the same frames (refine.py), then the ordered dither with `limit` (0..255).  nMaxColors <= 256.
-    size / crop / linear_resample / yuv as for convert_frames_refined.  Returns what convert_frames returns: (palette, [QuantizedImage per frame])."""
+    size / crop / linear_resample / yuv / orient as for convert_frames_refined.  Returns what convert_frames returns: (palette, [QuantizedImage per frame])."""
     if not 0 <= int(refine) <= 64:
         raise ValueError("refine must be 0..64, got %r" % (refine,))
+    from .orient import _code as _orient_code
+    orient = _orient_code(orient)
     if yuv is None:
         frames, q = _frames_quantizer(kind, frames, device, MODE_PARALLEL_TILED, None)
     else:
@@ -76,10 +78,10 @@ def convert_frames_ordered(kind, frames, nMaxColors, limit, refine=0, device=0, 
         frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, MODE_PARALLEL_TILED, None)
     try:
         if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv)
-        elif size is not None or crop is not None:
+            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
+        elif size is not None or crop is not None or orient != 1:
             from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
+            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
         return _convert_frames_on(q, frames, nMaxColors, False, MODE_PARALLEL_TILED, None, int(refine), _limit(limit))
     finally:
         q.close()

@@ -70,16 +70,20 @@ def palette_error(frames, palette, device=0):
 
 
 def convert_frames_refined(kind, frames, nMaxColors, dither, refine, device=0, mode=MODE_PARALLEL_TILED, seeds=None, tile=None, size=None,
-                           crop=None, linear_resample=True, yuv=None):
+                           crop=None, linear_resample=True, yuv=None, orient=1):
     """nq_convert_frames_refined on host arrays: convert_frames with `refine` (0..64) k-means passes on the shared palette, over the
     same frames, between the palette and the dither.  nMaxColors <= 256 unless refine is 0, which gives convert_frames' results.
     size / crop / linear_resample: with size=(width, height) or crop=(x, y, width, height) given, the frames (then all of one size) are
     first cropped and area-averaged down to `size` (None: the crop's size) as resample_frames does it (resample.py), on the same handle.
     yuv (None: the frames are ARGB words): a dict with the keys bt709 / full_range says that `frames` are (y, u, v) tuples of 8-bit
     YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
+    orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
+    converting kernel --; size and crop are then those of the oriented frames.
     Returns (palette, [QuantizedImage per frame])."""
     if not 0 <= int(refine) <= 64:
         raise ValueError("refine must be 0..64, got %r" % (refine,))
+    from .orient import _code as _orient_code
+    orient = _orient_code(orient)
     if yuv is None:
         frames, q = _frames_quantizer(kind, frames, device, mode, tile)
     else:
@@ -87,10 +91,10 @@ def convert_frames_refined(kind, frames, nMaxColors, dither, refine, device=0, m
         frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
     try:
         if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv)
-        elif size is not None or crop is not None:
+            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
+        elif size is not None or crop is not None or orient != 1:
             from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample)
+            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
         return _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, refine)
     finally:
         q.close()

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from .gif import _Handle
+from .orient import _code, oriented_size
 from .resample import RESAMPLE_LINEAR, _geometry
 
 YUV_BT709 = 1
@@ -111,12 +112,16 @@ def _arr(ptrs):
     return (C.c_void_p * max(len(ptrs), 1))(*[int(p) for p in ptrs])
 
 
-def _call(L, handle, check, entry, y, u, v, width, height, y_stride, c_stride, c_step, flags, dst, geometry, linear):
-    """One of the four entry points: geometry None is the 1:1 conversion, else (crop_x, crop_y, crop_w, crop_h, dst_w, dst_h)."""
+def _call(L, handle, check, entry, y, u, v, width, height, y_stride, c_stride, c_step, flags, dst, geometry, linear, orient=1):
+    """One of the four entry points: geometry None is the 1:1 conversion, else (crop_x, crop_y, crop_w, crop_h, dst_w, dst_h).  With
+    orient != 1 (a checked code of orient.py) the _oriented form of `entry` is called."""
     n = len(y)
     if not (len(u) == len(v) == len(dst) == n):
         raise ValueError("one u, v and output per frame")
     head = (handle, n, _arr(y), _arr(u), _arr(v), int(width), int(height), int(y_stride), int(c_stride), int(c_step), int(flags))
+    if orient != 1:
+        entry = entry[:-len("_device")] + "_oriented_device" if entry.endswith("_device") else entry + "_oriented"
+        head += (int(orient),)
     if geometry is None:
         check(getattr(L, entry)(*head, _arr(dst)))
     else:
@@ -124,21 +129,21 @@ def _call(L, handle, check, entry, y, u, v, width, height, y_stride, c_stride, c
         check(getattr(L, entry)(*head, cx, cy, cw, ch, _arr(dst), dw, dh, RESAMPLE_LINEAR if linear else 0))
 
 
-def _yuv_host(L, handle, check, frames, size, crop, linear, flags):
-    """nq_frames_from_yuv (size and crop None) or nq_resample_frames_yuv of host frames on an open handle.  Returns the ARGB frames as
-    a list of int32 arrays."""
+def _yuv_host(L, handle, check, frames, size, crop, linear, flags, orient=1):
+    """nq_frames_from_yuv (size and crop None) or nq_resample_frames_yuv of host frames on an open handle; with orient != 1 (a checked
+    code of orient.py) their _oriented forms.  Returns the ARGB frames as a list of int32 arrays."""
     planes, width, height, y_stride, c_stride, c_step = _host_frames(frames)
     geometry = None
-    out_w, out_h = width, height
+    out_w, out_h = (height, width) if orient >= 5 else (width, height)
     if size is not None or crop is not None:
-        geometry = _geometry(width, height, size, crop)
+        geometry = _geometry(width, height, size, crop, orient)
         out_w, out_h = geometry[4:]
         if out_w < 1 or out_h < 1:
             raise ValueError("resample: the target must be at least 1 x 1, got %d x %d" % (out_w, out_h))
     outs = [np.zeros((out_h, out_w), np.int32) for _ in planes]
     _call(L, handle, check, "nq_frames_from_yuv" if geometry is None else "nq_resample_frames_yuv", [p[0].ctypes.data for p in planes],
           [p[1].ctypes.data for p in planes], [p[2].ctypes.data for p in planes], width, height, y_stride, c_stride, c_step, flags,
-          [o.ctypes.data for o in outs], geometry, linear)
+          [o.ctypes.data for o in outs], geometry, linear, orient)
     return outs
 
 
@@ -154,46 +159,53 @@ def _yuv_quantizer(kind, frames, yuv, device, mode, tile):
     return frames, cls(np.zeros((2, 2), np.int32), device=device, mode=mode, tile=tile), flags
 
 
-def frames_from_yuv(frames, bt709=False, full_range=False, device=0):
+def frames_from_yuv(frames, bt709=False, full_range=False, device=0, orient=1):
     """nq_frames_from_yuv on host arrays: `frames` are (y, u, v) tuples of one size (see the module text).  bt709: the BT.709 matrix
-    instead of BT.601; full_range: Y, U, V use 0..255 instead of 16..235 / 16..240.  Returns a list of int32 ARGB_8888 arrays of
-    shape (height, width), alpha 255."""
+    instead of BT.601; full_range: Y, U, V use 0..255 instead of 16..235 / 16..240.  orient (1..8, orient.py): the frames come out
+    oriented (nq_frames_from_yuv_oriented: one kernel).  Returns a list of int32 ARGB_8888 arrays of shape (height, width) -- the
+    oriented frame's --, alpha 255."""
+    orient = _code(orient)
     hd = _Handle(device)
     try:
-        return _yuv_host(hd._L, hd._h, hd._check, frames, None, None, True, _flags(bt709, full_range))
+        return _yuv_host(hd._L, hd._h, hd._check, frames, None, None, True, _flags(bt709, full_range), orient)
     finally:
         hd.close()
 
 
-def resample_frames_yuv(frames, size, crop=None, linear=True, bt709=False, full_range=False, device=0):
+def resample_frames_yuv(frames, size, crop=None, linear=True, bt709=False, full_range=False, device=0, orient=1):
     """nq_resample_frames_yuv on host arrays: frames_from_yuv followed by resample_frames(size, crop, linear), bit for bit, in one
     kernel.  size = (width, height) of the result (None: the crop's), crop = (x, y, width, height) inside the frames (None: the whole
-    frame).  Returns a list of int32 arrays of shape (height, width)."""
+    frame).  orient (1..8, orient.py): the frames are oriented before they are reduced, and size and crop are those of the oriented
+    frames (nq_resample_frames_yuv_oriented).  Returns a list of int32 arrays of shape (height, width)."""
+    orient = _code(orient)
     frames = list(frames)
     hd = _Handle(device)
     try:
         if size is None and crop is None:
-            crop = (0, 0) + _host_frames(frames)[1:3]
-        return _yuv_host(hd._L, hd._h, hd._check, frames, size, crop, linear, _flags(bt709, full_range))
+            crop = (0, 0) + oriented_size(*_host_frames(frames)[1:3], orient)
+        return _yuv_host(hd._L, hd._h, hd._check, frames, size, crop, linear, _flags(bt709, full_range), orient)
     finally:
         hd.close()
 
 
-def frames_from_yuv_device(q, d_y, d_u, d_v, width, height, y_stride, c_stride, c_step, d_dst, bt709=False, full_range=False):
+def frames_from_yuv_device(q, d_y, d_u, d_v, width, height, y_stride, c_stride, c_step, d_dst, bt709=False, full_range=False, orient=1):
     """nq_frames_from_yuv_device on the handle of quantizer `q`: d_y[i], d_u[i], d_v[i] are the HIP device addresses of frame i's planes
     (never written), d_dst[i] that of its width x height ARGB words (4-byte aligned).  NV12: d_v[i] = d_u[i] + 1 and c_step 2; NV21:
-    d_u[i] = d_v[i] + 1.  The work is left running on the handle's stream."""
+    d_u[i] = d_v[i] + 1.  orient as for frames_from_yuv.  The work is left running on the handle's stream."""
+    orient = _code(orient)
     if len(d_y) == 0:
         raise ValueError("no frames")
     _call(q._L, q._h, q._check, "nq_frames_from_yuv_device", list(d_y), list(d_u), list(d_v), width, height, y_stride, c_stride, c_step,
-          _flags(bt709, full_range), list(d_dst), None, True)
+          _flags(bt709, full_range), list(d_dst), None, True, orient)
 
 
 def resample_frames_yuv_device(q, d_y, d_u, d_v, src_width, src_height, y_stride, c_stride, c_step, d_dst, size, crop=None, linear=True,
-                               bt709=False, full_range=False):
+                               bt709=False, full_range=False, orient=1):
     """nq_resample_frames_yuv_device on the handle of quantizer `q`: planes as for frames_from_yuv_device, d_dst[i] the address of frame
-    i's size[0] x size[1] result; size, crop, linear as for resample_frames.  The work is left running on the handle's stream."""
+    i's size[0] x size[1] result; size, crop, linear, orient as for resample_frames_yuv.  The work is left running on the handle's
+    stream."""
+    orient = _code(orient)
     if len(d_y) == 0:
         raise ValueError("no frames")
     _call(q._L, q._h, q._check, "nq_resample_frames_yuv_device", list(d_y), list(d_u), list(d_v), src_width, src_height, y_stride, c_stride,
-          c_step, _flags(bt709, full_range), list(d_dst), _geometry(src_width, src_height, size, crop), linear)
+          c_step, _flags(bt709, full_range), list(d_dst), _geometry(src_width, src_height, size, crop, orient), linear, orient)
