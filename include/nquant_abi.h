@@ -84,7 +84,14 @@ int nq_create(int kind, int device, nq_handle** out);
 void nq_destroy(nq_handle* h);
 const char* nq_last_error(const nq_handle* h);   /* h may be NULL: last error of nq_create on this thread */
 int nq_abi_version(void);
-/* All work of the handle is enqueued on this hipStream_t (NULL = the default stream). */
+/* All work of the handle is enqueued on this hipStream_t (NULL = the default stream): a call's reads of its device inputs are ordered
+ * after the work the caller has queued on that stream before the call, its writes before the work queued there afterwards; the
+ * calls marked "asynchronous" return without waiting for either.  Host arrays a call takes (pointer tables, palettes) belong to the
+ * caller again when the call returns.
+ * Precondition: the handle's earlier work has completed (the caller has waited for the previous stream, or the last call was one
+ * that returns when its results are there).  State the handle keeps on the device -- the uploaded palette, the candidate lists, the
+ * cell boxes, the curve tables -- is ordered only against the stream it was written on; a switch while that work is still running
+ * is undefined.  (tests/test_gpu_streams.py: parts A, C and D.) */
 int nq_set_stream(nq_handle* h, void* hip_stream);
 /* Tile of the PARALLEL_TILED decomposition; <= 0 (default) = automatic: 8x8 when that gives the GPU at least 131072
  * independent chains (images from about 2900^2 pixels), 4x4 below that -- for every form of the error queue (a tile chain of the
@@ -156,6 +163,8 @@ int nq_convert_device(nq_handle* h, const uint32_t* d_argb, int width, int heigh
  *      together).  Results are identical to n separate nq_convert_device calls.  The merge loop of one image is a
  *      sequential chain that occupies one CU; here the n merge loops run side by side in ONE launch (one workgroup
  *      each), the other stages run image after image on the first handle's stream and share its per-pixel scratch.
+ *      The stages in front of the merge loops run on up to eight internal streams; every one of them starts behind the work queued on
+ *      the first handle's stream when the call is made, so inputs written asynchronously on that stream are read after their producer.
  *      hs[i] are distinct handles on one device (mixing kinds is allowed); all pointer arrays are host arrays of n
  *      device pointers; out_palettes[i * palette_stride ...] / out_K[i] receive palette i
  *      (palette_stride >= max(nMaxColors, 2)); d_out_index may be NULL. ---- */

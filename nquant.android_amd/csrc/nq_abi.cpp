@@ -203,6 +203,7 @@ struct nq_handle {
     DevBuf<unsigned long long> team;  // 256 u64 of hand-off words of this handle's merge team
     bool light_events = false;        // batch entry points: this image records only the stage events 0, 5, 6 (see rec)
     hipEvent_t bev[4] = {nullptr};    // batch entry points: phase boundaries on the launch stream (first handle of the batch)
+    hipEvent_t lane_gate = nullptr;   // nq_convert_batch_device: what the first handle's stream holds at entry; the other lanes wait for it
     float batch_phase_ms[4] = {0};
     bool ext_distinct_valid = false, ext_distinct_many = false;  // nq_set_distinct: image-wide distinct colours (first-occurrence order) of the split pipeline
     std::vector<int32_t> ext_distinct;
@@ -297,6 +298,7 @@ struct nq_handle {
         for (auto& kv : paths) (void) hipFree(kv.second);
         for (auto& e : ev) if (e) (void) hipEventDestroy(e);
         for (auto& e : bev) if (e) (void) hipEventDestroy(e);
+        if (lane_gate) (void) hipEventDestroy(lane_gate);
         if (copy_stream) (void) hipStreamDestroy(copy_stream);
         if (lane_stream) (void) hipStreamDestroy(lane_stream);
         for (auto& ls : more_lanes) if (ls) (void) hipStreamDestroy(ls);
@@ -340,6 +342,7 @@ int use_device(nq_handle* h) {
         if (!h->pin) NQ_HIP(h, hipHostMalloc((void**) &h->pin, 8 * sizeof(long long), hipHostMallocDefault));
         for (auto& e : h->ev) NQ_HIP(h, hipEventCreate(&e));
         for (auto& e : h->bev) NQ_HIP(h, hipEventCreate(&e));
+        NQ_HIP(h, hipEventCreateWithFlags(&h->lane_gate, hipEventDisableTiming));
         h->tables_ready = true;
     }
     return NQ_OK;
@@ -1728,6 +1731,14 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
     std::vector<PaletteJob> jobs(n);
     std::vector<const PaletteJob*> jp(n);
     (void) hipEventRecord(h0->bev[0], lane_s[0]);
+    // The lanes are streams of their own (non-blocking: they do not follow the NULL stream either), and the caller may have queued the
+    // producer of d_argb[] on the first handle's stream: every other lane starts behind what that stream holds now.  No host wait; the
+    // join in front of the merge launch orders the other direction.  (tests/test_gpu_streams.py, part B)
+    for (int k = 1; k < L; ++k)
+        if (lane_s[k] != lane_s[0]) {
+            if (k == 1) NQ_HIP(h0, hipEventRecord(h0->lane_gate, lane_s[0]));
+            NQ_HIP(h0, hipStreamWaitEvent(lane_s[k], h0->lane_gate, 0));
+        }
     {
         // One host thread per lane (round 4): pnnquan_prepare waits twice for the device per image (the pre-scan's scalars, the bin count),
         // and a single issuing thread that blocks there leaves the other lanes without new work -- only two images ever overlapped.  Lane k's
@@ -3022,6 +3033,8 @@ int hold_device(nq_handle* h, int n, const uint32_t* const* d_argb, uint16_t* co
     // With out_held == NULL the call returns with this upload only enqueued, and the next call on the handle rewrites `t` and may
     // regrow hold_ptrs.  Both are safe for the reason the encoders' table uploads are: the runtime copies a small pageable source
     // into its own staging memory before hipMemcpyAsync returns, and DevBuf::reserve frees through hipFree, which waits for the device.
+    // Held by tests/test_gpu_streams.py (two asynchronous calls back to back behind a gated stream, the second with more frames): a
+    // runtime that read the source later would fail there, and the tables would then need page-locked slots guarded by events.
     NQ_HIP(h, hipMemcpyAsync(h->hold_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
     if (out_held) NQ_HIP(h, hipMemsetAsync(h->hold_held.p, 0, n * sizeof(unsigned long long), h->stream));
     launch_hold(reinterpret_cast<const unsigned* const*>(h->hold_ptrs.p), reinterpret_cast<unsigned short* const*>(h->hold_ptrs.p + n),
