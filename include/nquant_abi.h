@@ -110,6 +110,10 @@ int nq_set_band(nq_handle* h, int y0, int image_height);
 /* NQ_OPT_FAST_DITHER (default 1): run the specialised dither kernel (csrc/nq_dither_fast.inc) where the configuration allows
  * it (LAB, 32 < K <= 256, no semi-transparency, DITHER_MAX 25, PARALLEL_TILED); 0 = the generic kernel everywhere.  Same results. */
 #define NQ_OPT_FAST_DITHER 2
+/* NQ_OPT_DITHER_CHAIN (default 0 = automatic): the specialised kernel first walks a wavefront's tiles without the error-diffusion chain
+ * wherever ditherPixel replaces the accumulated colour by a colour of the source pixel (LAB, dither, saliencies, 2 * acceptedDiff > 100),
+ * and starts over with the chain only when a step needs it (direct branch, second stage); 1 = every step runs the chain.  Same results. */
+#define NQ_OPT_DITHER_CHAIN 4
 /* NQ_OPT_MERGE_WALL_SECONDS (default 0 = automatic: 60 s + 1 ms per histogram bin and per merge loop sharing a compute unit with it):
  * seconds of residency after which a merge loop of this handle's calls gives up with NQ_ERR_TIME_LIMIT.  Every loop of the persistent
  * merge kernel is bounded; this bound only exists so that a corrupt heap cannot keep the GPU for hours. */

@@ -175,6 +175,7 @@ struct nq_handle {
     DevBuf<float> d_user_sal;
     int band_y0 = 0, band_image_h = 0; // nq_set_band: this handle dithers a row band of a larger image (0, 0 = a whole image)
     int use_fast_dither = 1;          // NQ_OPT_FAST_DITHER: the specialised dither kernel where the configuration allows it
+    int dither_chain_always = 0;      // NQ_OPT_DITHER_CHAIN: 1 = the specialised kernel runs the error chain in every step (no light walk)
     bool dither_events_fresh = false; // the last call on the handle was a stand-alone dither (events 5..7 are newer than stage_ms)
     int last_dither_fast = 0;         // diagnostics: 1 if the last dither pass ran gilbert_fast_kernel
     int last_dither_failed_tiles = 0; // ... and how many tiles it handed back to the generic kernel (read lazily)
@@ -1071,7 +1072,8 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
         // production path (nq_dither_fast.hip); the tiles it cannot finish come back as a list for the generic kernel below
         NQ_HIP(h, h->d_failed.reserve((size_t) T.tiles_x * T.tiles_y + 1));
         NQ_HIP(h, launch_gilbert_fast(P, G, T, lv, (const int*) d_argb, d_sal, h->d_palette.p, (long long) seed, d_out_index,
-                                      post ? nullptr : (int*) d_out_argb, h->d_failed.p, packed_lists(h), h->stream, failed_cleared));
+                                      post ? nullptr : (int*) d_out_argb, h->d_failed.p, packed_lists(h), h->stream, failed_cleared,
+                                      h->dither_chain_always != 0));
         d_tile_list = h->d_failed.p;
         h->last_dither_fast = 1;
     }
@@ -1420,6 +1422,7 @@ int nq_set_option(nq_handle* h, int option, int value) {
     if (!h) return NQ_ERR_INVALID;
     if (option == NQ_OPT_CELL_LISTS) { h->use_lists = value != 0; return NQ_OK; }
     if (option == NQ_OPT_FAST_DITHER) { h->use_fast_dither = value != 0; return NQ_OK; }
+    if (option == NQ_OPT_DITHER_CHAIN) { h->dither_chain_always = value != 0; return NQ_OK; }
     if (option == NQ_OPT_MERGE_WALL_SECONDS) { h->merge_wall_s = value > 0 ? value : 0; return NQ_OK; }
     NQ_FAIL(h, NQ_ERR_INVALID, "unknown option %d", option);
 }

@@ -45,6 +45,7 @@ struct FastArgs {
     const uint4* packed;     // [65536][2]: per colour cell {closest list, nearest list} in one 32-byte record (pack_lists_kernel)
     const uint4* cont;       // [2][65536]: candidates 15..30 of the closest / nearest lists
     int debug;               // timing experiments only (builds with -DNQ_FAST_KNOCKOUT): bit mask of stages to leave out
+    int chainAlways;         // NQ_OPT_DITHER_CHAIN = 1: every wavefront runs the error chain (no light walk)
 };
 // instruction budget by block (tools/fast_budget.py compiles this file with -DNQ_FAST_MARKS and counts between the markers)
 #ifdef NQ_FAST_MARKS
@@ -64,7 +65,8 @@ struct FastArgs {
 // of a loop that all lanes walk together) -- one atomic per wavefront each
 #ifdef NQ_FAST_COUNT
 enum { FC_NEAREST = 0, FC_NEAREST_EXACT, FC_NEAREST_EXACT_LANES, FC_NEAREST_EXACT_N2_SUM, FC_NEAREST_EXACT_N2_MAX, FC_NEAREST_TAIL, FC_CLOSEST,
-       FC_CLOSEST_TAIL, FC_CLOSEST_EXACT, FC_YDIFF, FC_YDIFF_F64, FC_TANH, FC_TANH_LIBRARY, FC_SLOTS = 16 };
+       FC_CLOSEST_TAIL, FC_CLOSEST_EXACT, FC_YDIFF, FC_YDIFF_F64, FC_TANH, FC_TANH_LIBRARY, FC_CHAIN_LIGHT, FC_CHAIN_REWALK,
+       FC_SLOTS = 16 };
 __device__ unsigned long long g_fast_count[FC_SLOTS];
 __device__ __forceinline__ void fast_count_add(int slot, bool cond, unsigned long long v, bool use_max) {
     const unsigned long long active = __ballot(1), m = __ballot(cond);
@@ -446,14 +448,18 @@ __device__ __forceinline__ bool fast_ydiff_cmp(const FastLds& S, int c1, int c2,
 
 // ditherPixel (NQ/GilbertCurve.java:125-185) for K > 32, up to its final lookup: returns the colour handed to it.
 // qcur = palette[qPixels[bidx]] = palette[0] at this point (the array is fresh).
-__device__ __forceinline__ int fast_dither_color(const FastLds& S, const GilbertConsts& G, int K, int x, int y, int c2, int pixel, float sal) {
+// LIGHT: the caller has no accumulated colour (c2 is not read).  It guarantees 2 * acceptedDiff > 100, so the first stage replaces c2
+// by a colour of the source pixel alone; the accumulated colour could only come back through the second stage, and every entry into
+// that stage sets `need` and returns (the caller then runs the step with the chain).
+template <bool LIGHT>
+__device__ __forceinline__ int fast_dither_color(const FastLds& S, const GilbertConsts& G, int K, int x, int y, int c2, int pixel, float sal, bool& need) {
     const float beta = G.beta;
     const int qcur = S.argb[0];
     const double weight = G.weightAbs;
     const float strength = 1 / 3.0f;
     const int acceptedDiff = max(2, K - G.margin);
     const int c_in = c2;
-    if (2 * acceptedDiff > 100 || fast_ydiff_cmp(S, pixel, c2, (double) (2 * acceptedDiff), false)) {       // Y_Diff <= 100 always
+    if (LIGHT || 2 * acceptedDiff > 100 || fast_ydiff_cmp(S, pixel, c2, (double) (2 * acceptedDiff), false)) {       // Y_Diff <= 100 always
         float kappa;
         if (K > 64) kappa = sal < .6f ? beta * .15f / sal : beta * .4f / sal;
         else if (weight < .005) kappa = beta * normal_distribution_cold(sal, .5f) + beta;
@@ -462,6 +468,7 @@ __device__ __forceinline__ int fast_dither_color(const FastLds& S, const Gilbert
     }
     const double gamma = beta;                  // K > 32
     if (gamma * acceptedDiff < 100.5 && fast_ydiff_cmp(S, pixel, c2, gamma * acceptedDiff, true)) {
+        if (LIGHT) { need = true; return c2; }
         if (G.margin > 6) {
             // :150-168 for K > 32: kappa = beta * normalDistribution(sal, peak) or one of two closed forms
             float kappa = sal < .4f ? beta * .4f * sal : beta * .4f / sal;
@@ -502,6 +509,34 @@ __device__ __forceinline__ void fast_accumulate(const float (&q)[NQ_FQ][4], floa
     }
     // keeps the five instantiations apart: without it the optimiser sinks them into ONE body fed by 100 register copies per case
     asm volatile("; window offset %0" :: "n"(U));
+}
+
+// Ditherable.nearestColorIndex(palette, c, bidx) = closestColorIndex (K > 4), NQ/PnnLABQuantizer.java:407-474: the step's lookup, shared by
+// the light walk and the full walk of the kernel below (LIGHT only names the markers of tools/fast_budget.py)
+#define NQ_MARK_L(name) do { if (LIGHT) NQ_MARK("light_" name); else NQ_MARK(name); } while (0)
+template <bool LIGHT>
+__device__ __forceinline__ int fast_lab_index(const FastLds& S, const FastLookup& X, const FastArgs& F, int K, int c, long long& rng, bool& failed) {
+    int qidx = 0;
+    if (c_alpha(c) <= 0xF) failed = true;           // transparent colour: the generic kernel redoes this tile
+    else {
+        const int cell = NQ_KO(1) ? 0 : cell_of(c);
+        const uint4 la = X.packed[2 * cell], na = X.packed[2 * cell + 1];
+        const int ncl = (int) (la.w >> 24), nnr = (int) (na.w >> 24);
+        if (ncl == 255 || nnr == 255) failed = true;
+        const int n1 = (ncl == 255 || NQ_KO(16)) ? 0 : ncl, n2 = nnr == 255 ? 0 : nnr;
+        NQ_MARK_L("lists_fetched");
+        const FastClosest t = fast_closest_tuple(S, X, c, la, n1, cell);
+        NQ_MARK_L("closest_done");
+        const int idx = fast_closest_pick(t, rng);              // :465-468
+        const int ci = idx ? t.c1 : t.c0, ei = idx ? t.e1 : t.e0;
+        qidx = ci;
+        NQ_MARK_L("picked");
+        if ((ei >= K || ci == 0 || c_alpha(S.argb[ci]) < c_alpha(c)) && !NQ_KO(2)) {
+            qidx = fast_nearest(S, X, c, na, n2, cell);
+        }
+        NQ_MARK_L("nearest_done");
+    }
+    return qidx;
 }
 
 // KIND 1: PnnLABQuantizer (the family described at the top).  KIND 0: PnnQuantizer with dither = true, 32 < K <= 256, an image without
@@ -571,21 +606,71 @@ __global__ void __launch_bounds__(256, MINWAVES) gilbert_fast_kernel(DevParams P
     const bool illusionAll = S.blue[0] > G.thresold;                      // yDiff == 1: TELL_BLUE_NOISE[(int) 4096.0 & 4095]
     bool failed = false;
 
-    float q[NQ_FQ][4];
-#pragma unroll
-    for (int t = 0; t < NQ_FQ; ++t) { q[t][0] = q[t][1] = q[t][2] = q[t][3] = 0.f; }     // run(): initWeights(25) zero boxes
-
     // software pipeline: the pixel (and saliency) of step s + 1 is requested during step s
     unsigned d_next = 0;
     int bidx_next = 0, pixel_next = 0;
     float sal_next = 0.f;
-    if (steps > 0) {
+    const int maxsteps = T.path_len[0];
+
+    // ---- light walk.  With branchA and 2 * acceptedDiff > 100, ditherPixel replaces the accumulated colour by a colour of the source
+    // pixel before anything reads it (fast_dither_color<true>), and what follows the lookup (error, maxErr, limiter, queue) only feeds
+    // later accumulations: the index of a step depends on the error chain only when the step takes the direct branch (:213) or enters
+    // the second stage of ditherPixel.  So the wavefront first walks its tiles WITHOUT the chain -- same colour, same lookup, same
+    // draws from `rng` in the same order -- until a lane meets such a step (one ballot per step, wavefront-uniform exit); only then it
+    // starts over with the full walk below, which overwrites `stage`.  Launches where no step can do without the chain skip this.
+    bool rewalk = true;
+    if (KIND == 1 && branchA && 2 * max(2, K - G.margin) > 100 && !F.chainAlways) {
+        rewalk = false;
+        if (steps > 0) {
+            d_next = path[0];
+            bidx_next = (x0 + (int) (d_next & 0xFFFFu)) + (y0 + (int) (d_next >> 16)) * width;
+            pixel_next = pixels[bidx_next];
+            sal_next = saliency[bidx_next];
+        }
+        for (int s = 0; s < maxsteps; ++s) {
+            bool need = false;
+            int c = 0, pos = 0;
+            if (s < steps) {
+                const int pixel = pixel_next;
+                const float sal = sal_next;
+                const int dxx = (int) (d_next & 0xFFFFu), dyy = (int) (d_next >> 16);
+                const int xx = x0 + dxx, yy = y0 + dyy + T.y_origin;
+                pos = dyy * T.tile_w + dxx;
+                if (s + 1 < steps) {
+                    d_next = path[s + 1];
+                    bidx_next = (x0 + (int) (d_next & 0xFFFFu)) + (y0 + (int) (d_next >> 16)) * width;
+                    pixel_next = pixels[bidx_next];
+                    sal_next = saliency[bidx_next];
+                }
+                NQ_MARK("light_begin");
+                need = K >= 256 && sal > .99f;
+                if (!need) c = fast_dither_color<true>(S, G, K, xx, yy, 0, pixel, sal, need);
+                NQ_MARK("light_color");
+            }
+            if (__ballot(need)) { rewalk = true; break; }
+            if (s < steps) {
+                const int qidx = fast_lab_index<true>(S, X, F, K, c, rng, failed);
+                stage[pos] = (unsigned char) qidx;
+                NQ_MARK("light_end");
+            }
+        }
+        NQ_COUNT(FC_CHAIN_LIGHT, live && !rewalk);
+        NQ_COUNT(FC_CHAIN_REWALK, live && rewalk);
+        if (rewalk) rng = jr_seed((long long) mix64((unsigned long long) seed + (unsigned long long) (T.tile_base + tile)));
+    }
+
+    // ---- full walk
+    float q[NQ_FQ][4];
+#pragma unroll
+    for (int t = 0; t < NQ_FQ; ++t) { q[t][0] = q[t][1] = q[t][2] = q[t][3] = 0.f; }     // run(): initWeights(25) zero boxes
+
+    if (rewalk && steps > 0) {
         d_next = path[0];
         bidx_next = (x0 + (int) (d_next & 0xFFFFu)) + (y0 + (int) (d_next >> 16)) * width;
         pixel_next = pixels[bidx_next];
         if (hasSal) sal_next = saliency[bidx_next];
     }
-    const int maxsteps = T.path_len[0];
+    if (rewalk)
     for (int s = 0; s < maxsteps; ++s) {
         const int u = s % 5;                    // uniform: position of this step inside the window
         if (s < steps) {
@@ -621,10 +706,10 @@ __global__ void __launch_bounds__(256, MINWAVES) gilbert_fast_kernel(DevParams P
 
             // :212-229 (K > 32: never branch B)
             int c = c2;
-            if (branchA && !(K >= 256 && sal > .99f) && !NQ_KO(8)) c = fast_dither_color(S, G, K, xx, yy, c2, pixel, sal);
+            bool unused = false;
+            if (branchA && !(K >= 256 && sal > .99f) && !NQ_KO(8)) c = fast_dither_color<false>(S, G, K, xx, yy, c2, pixel, sal, unused);
             NQ_MARK("dither_color");
 
-            // ---- Ditherable.nearestColorIndex(palette, c, bidx) = closestColorIndex (K > 4), NQ/PnnLABQuantizer.java:407-474
             int qidx = 0;
             if (KIND == 0) {
                 // the candidate lists hold for opaque colours only (the alpha term of an entry is then the same for the whole cell)
@@ -637,25 +722,7 @@ __global__ void __launch_bounds__(256, MINWAVES) gilbert_fast_kernel(DevParams P
                     else qidx = fast_nearest_rgb(S, rpa, rpr, rpg, rpb, c, na, nnr, X.cont + 65536 + cell);
                 }
             }
-            else if (c_alpha(c) <= 0xF) failed = true;      // transparent colour: the generic kernel redoes this tile
-            else {
-                const int cell = NQ_KO(1) ? 0 : cell_of(c);
-                const uint4 la = X.packed[2 * cell], na = X.packed[2 * cell + 1];
-                const int ncl = (int) (la.w >> 24), nnr = (int) (na.w >> 24);
-                if (ncl == 255 || nnr == 255) failed = true;
-                const int n1 = (ncl == 255 || NQ_KO(16)) ? 0 : ncl, n2 = nnr == 255 ? 0 : nnr;
-                NQ_MARK("lists_fetched");
-                const FastClosest t = fast_closest_tuple(S, X, c, la, n1, cell);
-                NQ_MARK("closest_done");
-                const int idx = fast_closest_pick(t, rng);              // :465-468
-                const int ci = idx ? t.c1 : t.c0, ei = idx ? t.e1 : t.e0;
-                qidx = ci;
-                NQ_MARK("picked");
-                if ((ei >= K || ci == 0 || c_alpha(S.argb[ci]) < c_alpha(c)) && !NQ_KO(2)) {
-                    qidx = fast_nearest(S, X, c, na, n2, cell);
-                }
-                NQ_MARK("nearest_done");
-            }
+            else qidx = fast_lab_index<false>(S, X, F, K, c, rng, failed);
 
             // :236-264
             const int cq = S.argb[qidx];
@@ -985,7 +1052,7 @@ static FastArgs fast_args(const DevParams& P, const ListsView& lv, void* d_packe
 }
 hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv, const int* d_pixels,
                                const float* d_saliency, const int* d_palette, long long seed, unsigned short* d_index, int* d_argb,
-                               int* d_failed, void* d_packed, hipStream_t s, bool failed_cleared) {
+                               int* d_failed, void* d_packed, hipStream_t s, bool failed_cleared, bool chain_always) {
     const int ntiles = T.tiles_x * T.tiles_y;
     const int tilepx = T.tile_w * T.tile_h;
     FastArgs F = fast_args(P, lv, d_packed, s);
@@ -993,6 +1060,7 @@ hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const
     F.strideBytes = fast_stride_bytes(tilepx);
     F.failedCap = ntiles;
     F.failed = d_failed;
+    F.chainAlways = chain_always ? 1 : 0;
 #ifdef NQ_FAST_KNOCKOUT
     if (const char* e = std::getenv("NQ_FAST_DEBUG")) F.debug = std::atoi(e);
 #endif

@@ -89,7 +89,8 @@ bool gilbert_fast_eligible(const DevParams& P, const GilbertConsts& G, const Til
 hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv, const int* d_pixels,
                                const float* d_saliency, const int* d_palette, long long seed, unsigned short* d_index, int* d_argb,
                                int* d_failed /* int[1 + tiles] */, void* d_packed /* 65536 x 64 bytes */, hipStream_t s,
-                               bool failed_cleared = false /* d_failed[0] was zeroed by the launch_build_lists in front of this call */);
+                               bool failed_cleared = false /* d_failed[0] was zeroed by the launch_build_lists in front of this call */,
+                               bool chain_always = false /* NQ_OPT_DITHER_CHAIN = 1: no light walk, every step runs the error chain */);
 bool fast_lookup_eligible(const DevParams& P, const ListsView& lv);
 bool fast_pack_wanted(const DevParams& P, const ListsView& lv);     // the packed records are needed (LAB lookups, or the RGB dither kernel)
 // packs the two lists of every colour cell into the 32-byte records (+ continuations) the specialised kernels read; must follow

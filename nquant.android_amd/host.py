@@ -18,7 +18,7 @@ MODE_REFERENCE_SEQUENTIAL, MODE_PARALLEL_TILED, MODE_LOOKUP_ONLY = 0, 1, 2
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-OPT_CELL_LISTS, OPT_FAST_DITHER, OPT_MERGE_WALL_SECONDS = 1, 2, 3
+OPT_CELL_LISTS, OPT_FAST_DITHER, OPT_MERGE_WALL_SECONDS, OPT_DITHER_CHAIN = 1, 2, 3, 4
 
 
 class NqError(RuntimeError):

@@ -1,5 +1,6 @@
 """Runs the dither pass of the bench image `reps` times (for rocprofv3 --kernel-trace --stats / --pmc).
-Usage: python tools/dither_only.py [size] [reps] [tile] [fast 0|1] [dither 0|1] [mode 1 = PARALLEL_TILED | 2 = LOOKUP_ONLY]"""
+Usage: python tools/dither_only.py [size] [reps] [tile] [fast 0|1] [dither 0|1] [mode 1 = PARALLEL_TILED | 2 = LOOKUP_ONLY]
+       [chain 0 = automatic | 1 = NQ_OPT_DITHER_CHAIN on: the error chain in every step]"""
 import os
 import sys
 
@@ -15,6 +16,7 @@ tile = int(sys.argv[3]) if len(sys.argv) > 3 else 8
 fast = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 dither = int(sys.argv[5]) if len(sys.argv) > 5 else 1
 mode = int(sys.argv[6]) if len(sys.argv) > 6 else 1
+chain = int(sys.argv[7]) if len(sys.argv) > 7 else 0
 img = synth.gradient_noise(W, H, 3)
 d_in = torch.from_numpy(img.reshape(-1)).cuda()
 q = nq.PnnLABQuantizer(np.zeros((1, 1), np.int32), mode=1, seed=3)
@@ -22,6 +24,7 @@ q.width, q.height = W, H
 pal = q.pnnquan_device(d_in.data_ptr(), 256)
 q.set_tile(tile, tile)
 q.set_option(host.OPT_FAST_DITHER, fast)
+q.set_option(host.OPT_DITHER_CHAIN, chain)
 d_out = torch.zeros(W * H, dtype=torch.int32, device="cuda")
 d_idx = torch.zeros(W * H, dtype=torch.int16, device="cuda")
 acc = []

@@ -2,6 +2,7 @@
 Compiles csrc/nq_dither_fast.hip with -DNQ_FAST_MARKS (asm comments between the blocks of one pixel step; the markers carry no
 instruction and the marked build is never shipped) into build/isa_marks and counts the instructions of the LAB kernel between consecutive
 markers in layout order.  The step's blocks are laid out in program order, so the counts are the STATIC instructions on the path of a step;
+the light walk (markers light_*, see DESIGN.md section 4) comes first, the full walk after it;
 what a wavefront executes differs where a block holds a loop (the rolled candidate loops beyond eight entries, the limiter's three turns)
 or exec-masked branches that no lane takes (the f64 fallbacks).  Of the five accumulation bodies and the five queue pushes one runs per step.
 Usage: python tools/fast_budget.py [--nobuild]"""
@@ -57,11 +58,17 @@ def main():
              "dither_color": "cell index + gather of the 32-byte list record", "lists_fetched": "closestColorIndex: 8 straight-line candidates + rolled tail + f64 arbiter",
              "closest_done": "java.util.Random draw + modulo + pick", "picked": "nearestColorIndex: float32 Lab + 8 straight-line candidates + tail + exact fallback call",
              "nearest_done": "error = adjusted - palette colour, blue-noise gate", "error_formed": "limiter loop body (runs three times per step): tanh / illusion / division",
+             "light_begin": "LIGHT WALK: direct-branch test + ditherPixel colour of the source pixel (fast_dither_color<true>)",
+             "light_color": "light: ballot + exit test, cell index + gather of the 32-byte list record",
+             "light_lists_fetched": "light: closestColorIndex", "light_closest_done": "light: java.util.Random draw + modulo + pick",
+             "light_picked": "light: nearestColorIndex", "light_nearest_done": "light: index staging",
+             "light_end": "light: loop control, next-pixel prefetch; then the window reset and the full walk's prologue",
              "limited": "queue push (case 3 incl. nothing else)", "push 3": "queue push", "push 2": "queue push", "push 1": "queue push",
              "push 0": "queue push case 0 + the window move (once per five steps) + index staging", "step_end": "loop control, next-pixel prefetch (laid out ahead of step_begin)"}
     order = ["valu", "valu_pk_f32", "valu_f64", "salu", "branch", "lds", "vmem", "wait/nop"]
     print("%-26s %s   what" % ("segment (opening marker)", " ".join("%9s" % o for o in order)))
     first = True
+    seen_begin = False
     for name, c in segs:
         if name == "prologue" and first:
             first = False
@@ -69,7 +76,8 @@ def main():
         if name in ("prologue",):
             continue
         print("%-26s %s   %s" % (name, " ".join("%9d" % c.get(o, 0) for o in order), label.get(name, "")))
-        if name == "step_end" and not first and segs.index((name, c)) > 3:
+        seen_begin = seen_begin or name == "step_begin"
+        if name == "step_end" and seen_begin:
             break
 
 

@@ -15,7 +15,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 NAMES = ["fast_nearest", "fast_nearest_exact", "  lanes that needed it", "  sum of n2 over those lanes", "  sum of the largest n2 (trips of its loop)",
          "fast_nearest32 rolled tail (n2 > 8)", "fast_closest_tuple", "fast_closest_tuple rolled tail (n1 > 8)",
-         "closest_err_exact (per candidate step)", "fast_ydiff_cmp", "f64 Y_Diff", "tanh_to_float", "tanh_library"]
+         "closest_err_exact (per candidate step)", "fast_ydiff_cmp", "f64 Y_Diff", "tanh_to_float", "tanh_library",
+         "wavefronts that finished in the light walk", "wavefronts that walked again with the chain"]
 
 
 def main():
@@ -49,6 +50,8 @@ def main():
         lines += ["", "per fast_nearest_exact call: %.2f lanes need it, mean n2 of those lanes %.2f, loop trips (largest n2) %.2f"
                   % (v[2] / v[1], v[3] / max(v[2], 1), v[4] / v[1]),
                   "share of fast_nearest wavefront-steps that call it: %.4f; share of lanes: %.5f" % (v[1] / max(v[0], 1), v[2] / (64.0 * max(v[0], 1)))]
+    lines += ["", "light walk (NQ_OPT_DITHER_CHAIN = 0): %d wavefronts finished without the error chain, %d walked again with it (of %d)"
+              % (v[13], v[14], W * H // 4096)]
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if len(sys.argv) > 1:
