@@ -171,7 +171,10 @@ int nq_convert_device(nq_handle* h, const uint32_t* d_argb, int width, int heigh
  *      the first handle's stream when the call is made, so inputs written asynchronously on that stream are read after their producer.
  *      hs[i] are distinct handles on one device (mixing kinds is allowed); all pointer arrays are host arrays of n
  *      device pointers; out_palettes[i * palette_stride ...] / out_K[i] receive palette i
- *      (palette_stride >= max(nMaxColors, 2)); d_out_index may be NULL. ---- */
+ *      (palette_stride >= max(nMaxColors, 2)); d_out_index may be NULL.
+ *      The dither passes of ALL n images run on the first handle's stream and read state of hs[i] (palette, candidate lists, curve
+ *      tables): before the next call on any hs[i] that is set to ANOTHER stream, wait for the first handle's stream -- the
+ *      precondition of nq_set_stream, with the batch's stream as hs[i]'s "previous stream". ---- */
 int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* d_argb, const int32_t* widths,
                             const int32_t* heights, int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
                             uint32_t* const* d_out_argb, uint16_t* const* d_out_index,
@@ -875,6 +878,8 @@ int nq_palette_from_histograms_device(nq_handle* h, const double* d_hists, int n
  * same early return as a single GPU would. */
 int nq_band_distinct_device(nq_handle* h, const uint32_t* d_argb, int64_t n_pixels, int cap, int64_t* out_count,
                             uint32_t* out_colors);
+/* The list belongs to the image of the last nq_set_scan: nq_set_scan forgets it, so every image's round hands over its own (or, with
+ * <= nMaxColors occupied bins and none handed over, ends with NQ_ERR_UNSUPPORTED). */
 int nq_set_distinct(nq_handle* h, int64_t count, const uint32_t* colors);
 
 /* Image-wide distinct-colour count of a banded LAB run (it sets the BlueNoise weight of convert(n, false),
@@ -919,6 +924,14 @@ int nq_get_merge_variant(const nq_handle* h, int32_t* out_threads, int32_t* out_
  * amortised per-image times (the per-handle stage times of nq_get_stage_ms are event spans that include queueing behind the
  * other images of the batch). */
 int nq_get_batch_phase_ms(const nq_handle* h0, float* out4);
+/* Bytes of device memory the library holds in THIS PROCESS, over all handles: every grow-only workspace buffer, the curve tables
+ * and the batch rings, counted where they are allocated and freed (a host-side counter, no device traffic; hipMalloc's own rounding
+ * is not included).  A handle's buffers only grow, so the count is constant once every call of a workload has run once; nq_destroy
+ * gives back everything nq_create and the handle's calls took.  Curve tables: shapes up to 32 x 32 are kept for the handle's life,
+ * of the larger ones (the whole image of REFERENCE_SEQUENTIAL) at most four, the most recent one per shape slot of a dither pass
+ * (tile, right column, bottom row, corner; csrc/nq_abi.cpp: get_path).
+ * (tests/test_gpu_handle_lifecycle.py, part D.)  Diagnostics. */
+int nq_get_device_bytes(int64_t* out);
 
 #ifdef __cplusplus
 }

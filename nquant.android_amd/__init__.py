@@ -6,7 +6,7 @@ Python host-side mirror used by the tests and bench.py.  It never imports the CP
 constructing a quantizer without a usable HIP device raises."""
 from .host import (NQ_KIND_RGB, NQ_KIND_LAB, MODE_REFERENCE_SEQUENTIAL, MODE_PARALLEL_TILED, MODE_LOOKUP_ONLY,
                    NqError, Params, PnnQuantizer, PnnLABQuantizer, QuantizedImage, load_library, library_path,
-                   abi_symbols, convert_batch_device, convert_batch_host, convert_frames, convert_frames_device,
+                   abi_symbols, device_bytes, convert_batch_device, convert_batch_host, convert_frames, convert_frames_device,
                    pnnquan_frames_device)
 from .gif import (convert_clip_to_gif, convert_frames_to_gif, convert_shots_to_gif, encode_gif, encode_gif_delta, encode_gif_delta_device, encode_gif_device,
                   encode_gif_local, encode_gif_local_delta, encode_gif_local_delta_device, encode_gif_local_device, gif_local_max_bytes,
@@ -24,7 +24,7 @@ from .build import build as build_library
 
 __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARALLEL_TILED", "MODE_LOOKUP_ONLY",
            "NqError", "Params", "PnnQuantizer", "PnnLABQuantizer", "QuantizedImage", "load_library", "library_path",
-           "abi_symbols", "build_library", "convert_batch_device", "convert_batch_host", "convert_frames",
+           "abi_symbols", "device_bytes", "build_library", "convert_batch_device", "convert_batch_host", "convert_frames",
            "convert_frames_device", "pnnquan_frames_device", "encode_gif", "encode_gif_device", "write_gif", "convert_frames_to_gif",
            "encode_gif_delta", "encode_gif_delta_device", "gif_max_bytes", "gif_local_max_bytes", "encode_gif_local", "encode_gif_local_device",
            "encode_gif_local_delta", "encode_gif_local_delta_device", "convert_shots_to_gif", "encode_png", "encode_png_device", "write_png",

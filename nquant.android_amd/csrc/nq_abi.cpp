@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <string>
 #include <utility>
@@ -27,14 +28,25 @@ namespace {
 
 const float kCoeffs[3][3] = {{0.299f, 0.587f, 0.114f}, {-0.14713f, -0.28886f, 0.436f}, {0.615f, -0.51499f, -0.10001f}};
 
+// nq_get_device_bytes: bytes of device memory the library holds in this process (every DevBuf -- the workspaces, the per-call tables, the
+// batch rings -- and the curve tables of get_path)
+std::atomic<int64_t> g_device_bytes{0};
+
 template <typename T> struct DevBuf {
     T* p = nullptr; size_t n = 0;
-    ~DevBuf() { if (p) (void) hipFree(p); }
+    ~DevBuf() { release(); }
+    void release() {
+        if (!p) return;
+        (void) hipFree(p);
+        g_device_bytes -= (int64_t) (n * sizeof(T));
+        p = nullptr; n = 0;
+    }
     hipError_t reserve(size_t count) {
         if (count <= n) return hipSuccess;
-        if (p) { (void) hipFree(p); p = nullptr; n = 0; }
-        hipError_t e = hipMalloc((void**) &p, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
+        release();
+        hipError_t e = hipMalloc((void**) &p, count * sizeof(T));
+        if (e == hipSuccess) { n = count; g_device_bytes += (int64_t) (n * sizeof(T)); }
+        else p = nullptr;
         return e;
     }
 };
@@ -148,6 +160,8 @@ struct Scratch {
     DevBuf<float> cell_box;           // Lab bounding box of every 5-6-5 cell (palette independent, built once)
     bool cell_box_ready = false;
 };
+
+inline size_t path_bytes(int w, int hgt) { const size_t n = (size_t) w * hgt; return (n ? n : 1) * sizeof(uint32_t); }
 
 struct nq_handle {
     int kind = 0, device = 0;
@@ -292,11 +306,15 @@ struct nq_handle {
     DevBuf<float> binf;               // f[4], cnt, err : 6 x 65536
     DevBuf<double> bind;              // d[4] : 4 x 65536
     DevBuf<int> bini;                 // nn, tm, mtm : 3 x 65536
-    std::map<std::pair<int, int>, uint32_t*> paths;   // curve tables on the device, by shape
+    std::map<std::pair<int, int>, uint32_t*> paths;   // curve tables on the device, by shape: the shapes get_path keeps (both sides <= NQ_PATH_KEEP_SIDE)
+    // ... and the larger shapes (a whole image in REFERENCE_SEQUENTIAL, a tile set beyond NQ_PATH_KEEP_SIDE): one grow-only table per shape
+    // slot of a dither pass, holding the most recent shape asked for there
+    DevBuf<uint32_t> big_path[4];
+    int big_w[4] = {0, 0, 0, 0}, big_h[4] = {0, 0, 0, 0};
     hipEvent_t ev[NQ_N_STAGES + 1] = {nullptr};
     bool tables_ready = false;
     ~nq_handle() {
-        for (auto& kv : paths) (void) hipFree(kv.second);
+        for (auto& kv : paths) { (void) hipFree(kv.second); g_device_bytes -= (int64_t) path_bytes(kv.first.first, kv.first.second); }
         for (auto& e : ev) if (e) (void) hipEventDestroy(e);
         for (auto& e : bev) if (e) (void) hipEventDestroy(e);
         if (lane_gate) (void) hipEventDestroy(lane_gate);
@@ -447,16 +465,44 @@ int lists_for_call(nq_handle* h, const DevParams& P, nq::ListsView* out, const i
     return rc;
 }
 
-int get_path(nq_handle* h, int w, int hgt, const uint32_t** out) {
+// The curve table of shape w x hgt for shape slot `slot` (0..3: full tile, right column, bottom row, corner) of a dither pass.
+// What a handle keeps: shapes with both sides <= NQ_PATH_KEEP_SIDE stay for the handle's life (the tiles of PARALLEL_TILED and their
+// remainders: at most NQ_PATH_KEEP_SIDE^2 shapes of at most 4 * NQ_PATH_KEEP_SIDE^2 bytes, 4 MB); of the larger shapes -- the whole
+// image in REFERENCE_SEQUENTIAL, a tile set beyond that side -- only the most recent one per slot, in a grow-only buffer, and slots
+// of one pass that want the same shape share it.  So a handle holds at most four tables of the largest shapes it has seen, not one
+// per image size.  (Rewriting a slot is ordered on the handle's stream behind the pass that read it; a regrowing hipFree waits.  In a
+// batch call the passes of every handle run on the FIRST handle's stream: like the handle's other buffers, a slot is safe to rewrite
+// once the batch call's work has completed, which include/nquant_abi.h states as the precondition of the next call on any of its handles.)
+constexpr int NQ_PATH_KEEP_SIDE = 32;
+
+hipError_t upload_path(nq_handle* h, uint32_t* d, const std::vector<uint32_t>& p) {
+    hipError_t e = hipMemcpyAsync(d, p.data(), p.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // p goes out of scope
+    return e;
+}
+
+int get_path(nq_handle* h, int w, int hgt, int slot, const uint32_t** out) {
+    if (w > NQ_PATH_KEEP_SIDE || hgt > NQ_PATH_KEEP_SIDE) {
+        for (int t = 0; t <= slot; ++t)       // (earlier slots are settled for this pass; later ones may still be rewritten by it)
+            if (h->big_w[t] == w && h->big_h[t] == hgt) { *out = h->big_path[t].p; return NQ_OK; }
+        std::vector<uint32_t> p = gilbert_path(w, hgt);
+        h->big_w[slot] = h->big_h[slot] = 0;
+        NQ_HIP(h, h->big_path[slot].reserve(p.size() ? p.size() : 1));
+        hipError_t e = upload_path(h, h->big_path[slot].p, p);
+        if (e != hipSuccess) NQ_FAIL(h, NQ_ERR_HIP, "curve table upload failed: %s", hipGetErrorString(e));
+        h->big_w[slot] = w; h->big_h[slot] = hgt;
+        *out = h->big_path[slot].p;
+        return NQ_OK;
+    }
     auto key = std::make_pair(w, hgt);
     auto it = h->paths.find(key);
     if (it == h->paths.end()) {
         std::vector<uint32_t> p = gilbert_path(w, hgt);
         uint32_t* d = nullptr;
-        NQ_HIP(h, hipMalloc((void**) &d, (p.size() ? p.size() : 1) * sizeof(uint32_t)));
-        hipError_t e = hipMemcpyAsync(d, p.data(), p.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // p goes out of scope
+        NQ_HIP(h, hipMalloc((void**) &d, path_bytes(w, hgt)));
+        hipError_t e = upload_path(h, d, p);
         if (e != hipSuccess) { (void) hipFree(d); NQ_FAIL(h, NQ_ERR_HIP, "curve table upload failed: %s", hipGetErrorString(e)); }
+        g_device_bytes += (int64_t) path_bytes(w, hgt);
         it = h->paths.emplace(key, d).first;
     }
     *out = it->second;
@@ -1032,7 +1078,7 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
     const int rw = width - (T.tiles_x - 1) * T.tile_w, rh = height - (T.tiles_y - 1) * T.tile_h;
     const int sw[4] = {T.tile_w, rw, T.tile_w, rw}, shh[4] = {T.tile_h, T.tile_h, rh, rh};
     for (int s = 0; s < 4; ++s) {
-        int rc = get_path(h, sw[s], shh[s], &T.path[s]);
+        int rc = get_path(h, sw[s], shh[s], s, &T.path[s]);
         if (rc) return rc;
         T.path_len[s] = sw[s] * shh[s]; T.shape_w[s] = sw[s]; T.shape_h[s] = shh[s];
     }
@@ -1473,6 +1519,11 @@ int nq_get_merge_stats(const nq_handle* h, int64_t* out8) {
 int nq_get_team_stats(const nq_handle* h, int64_t* out16) {
     if (!h || !out16) return NQ_ERR_INVALID;
     std::memcpy(out16, h->team_stats, sizeof h->team_stats);
+    return NQ_OK;
+}
+int nq_get_device_bytes(int64_t* out) {
+    if (!out) return NQ_ERR_INVALID;
+    *out = g_device_bytes.load();
     return NQ_OK;
 }
 int nq_get_merge_variant(const nq_handle* h, int32_t* out_threads, int32_t* out_helpers) {
@@ -1957,6 +2008,9 @@ int nq_band_scan_device(nq_handle* h, const uint32_t* d_argb, int64_t n_pixels, 
 int nq_set_scan(nq_handle* h, int nMaxColors, int64_t transparent_index, uint32_t transparent_color, int64_t semi_count) {
     if (!h) return NQ_ERR_INVALID;
     apply_scan(h, nMaxColors, transparent_index, transparent_color, semi_count);
+    // a new image's split round: the distinct colours handed over for the image before say nothing about this one (they used to stay valid
+    // for the handle's life, and a later few-colours image without nq_set_distinct took its palette from them instead of NQ_ERR_UNSUPPORTED)
+    h->ext_distinct_valid = false; h->ext_distinct_many = false; h->ext_distinct.clear();
     return NQ_OK;
 }
 

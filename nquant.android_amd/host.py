@@ -75,6 +75,7 @@ _ABI = {
     "nq_get_team_stats": (_i32, [_vp, _pi64]),
     "nq_get_merge_variant": (_i32, [_vp, _pi32, _pi32]),
     "nq_get_dither_path": (_i32, [_vp, _pi32, _pi32]),
+    "nq_get_device_bytes": (_i32, [_pi64]),
     "nq_set_band": (_i32, [_vp, _i32, _i32]),
     "nq_selftest_ciede": (_i32, [_vp, _vp, _i64, _vp]),
     "nq_gilbert_dither": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, C.c_double, _i32, _i64, _i32, _vp, _vp]),
@@ -137,6 +138,15 @@ _ABI = {
 
 def abi_symbols():
     return list(_ABI)
+
+
+def device_bytes():
+    """Bytes of device memory the library holds in this process, over all handles (nq_get_device_bytes)."""
+    out = C.c_int64(0)
+    rc = load_library().nq_get_device_bytes(C.byref(out))
+    if rc != 0:
+        raise NqError(rc, "nq_get_device_bytes")
+    return out.value
 
 
 def library_path():

@@ -41,6 +41,11 @@ SENT_INDEX = 0xA5A5
 TILE = (16, 16)
 WIDE, NARROW = (48, 40, 0), (45, 37, 1)         # (width, height, shift): the 16-byte paths; the one-element paths (odd sides, one element off)
 SHAPES = (WIDE, NARROW)
+# (width, height, shift, K of the encoders' maps), 5 frames: the smallest shape whose encoder scratch has more than one entry per frame --
+# 33 847 pixels are three LZW chains of 16 384, 182 * 187 = 34 034 raw bytes two deflate chains of 32 768 --, with 3 x 3 partly filled
+# 64 x 64 orient tiles and an odd-sided 4:2:0 frame (tests/lifecycle_ops.py)
+LARGE = (181, 187, 1, 256)
+LARGE_FRAMES = 5
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -210,7 +215,9 @@ def want(case):
     return _REF[case.name]
 
 
-def _frame_cases():
+def _frame_cases(shapes=SHAPES, n=3):
+    """The frame and encoder cases at every shape of `shapes`: (width, height, shift) or (width, height, shift, K of the encoders' maps;
+    default 256 at shift 0, else 16), n frames each."""
     import apng_ref
     import gif_delta_ref
     import gif_ref
@@ -223,16 +230,17 @@ def _frame_cases():
     import shots_ref
     import yuv_ref
     cases = []
-    n = 3
-    for w, h, shift in SHAPES:
+    for shape in shapes:
+        w, h, shift = shape[:3]
         tag = "%dx%d" % (w, h)
         frames = argb_frames(w, h, n, 7000 + w)
         planes = yuv_frames(w, h, n, 7100 + w)
         footage = still_frames(w, h, n, 7200 + w)
         maps = index_maps(w, h, n, 256, 7300 + w)
         outs = argb_frames(w, h, n, 7400 + w)
-        size, crop = ((20, 16), None) if shift == 0 else ((13, 11), (3, 2, 40, 33))
-        osize, ocrop = ((16, 20), None) if shift == 0 else ((11, 13), (2, 3, 33, 40))      # of the turned frame (codes 5..8)
+        small = (13, 11) if w < 64 else (w // 3 + 1, h // 4 + 1)                           # (45 x 37: 13 x 11 of the crop 40 x 33 at (3, 2))
+        size, crop = ((20, 16), None) if shift == 0 else (small, (3, 2, w - 5, h - 4))
+        osize, ocrop = ((16, 20), None) if shift == 0 else (small[::-1], (2, 3, h - 4, w - 5))     # of the turned frame (codes 5..8)
         pal256, pal16 = palette(256, 7500 + w), palette(16, 7600 + w)
         turn = 6 if shift == 0 else 5
 
@@ -286,10 +294,10 @@ def _frame_cases():
             return {"starts": list(starts), "scores": np.asarray(scores, np.int32)}
         cases.append(Case("detect_shots-" + tag, {"argb": frames}, detect, False, shift=shift, w=w, h=h))
 
-        K = 256 if shift == 0 else 16
+        K = shape[3] if len(shape) > 3 else 256 if shift == 0 else 16
         epal = pal256 if K == 256 else pal16
         emaps = index_maps(w, h, n, K, 7700 + w, still=True)
-        delays = [3, 0, 65535]
+        delays = ([3, 0, 65535] * n)[:n]
         cases.append(Case("gif-" + tag, {"index": emaps}, lambda i, p=epal: {"file": gif_ref.encode(i["index"], p, delays_cs=delays, loop=0)},
                           False, K=K, shift=shift, palette=epal, delays=delays, w=w, h=h))
         cases.append(Case("gif_delta-" + tag, {"index": emaps},

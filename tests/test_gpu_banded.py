@@ -24,14 +24,18 @@ TILED = 1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bands_by_hand(nq, img, kind, K, dither, row_starts, seed, tile=None):
-    """The band pipeline with the reductions done here (what parallel.convert_banded does across ranks).  Returns palette, argb, index."""
+def _bands_by_hand(nq, img, kind, K, dither, row_starts, seed, tile=None, qs=None):
+    """The band pipeline with the reductions done here (what parallel.convert_banded does across ranks).  Returns palette, argb, index.
+    qs: one open handle of `kind` per band to run it on, their tile set by the caller (tests/lifecycle_ops.py); they keep their band."""
     import torch
     H, W = img.shape
     Q = nq.PnnLABQuantizer if kind else nq.PnnQuantizer
     bounds = list(row_starts) + [H]
     nb = len(row_starts)
-    qs = [Q(np.zeros((1, 1), np.int32), mode=TILED, seed=seed, tile=tile) for _ in range(nb)]
+    if qs is None:
+        qs = [Q(np.zeros((1, 1), np.int32), mode=TILED, seed=seed, tile=tile) for _ in range(nb)]
+    for q in qs:
+        q.mode, q.seed = TILED, seed
     L = qs[0]._L
     d_img = torch.from_numpy(img.reshape(-1).copy()).cuda()
     bands = [d_img[bounds[b] * W: bounds[b + 1] * W] for b in range(nb)]

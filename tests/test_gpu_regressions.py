@@ -151,3 +151,63 @@ def test_last_band_lower_than_an_explicit_tile_keeps_the_image_tile_numbers(nq, 
     assert (pal == want_pal).all()
     assert (idx[:64].astype(np.int32) == want_idx[:64]).all() and (argb[:64] == want_argb[:64]).all()
     assert (idx[64].astype(np.int32) == want_idx[64]).all() and (argb[64] == want_argb[64]).all(), "the one-row band"
+
+
+def test_sequential_converts_of_many_sizes_keep_one_curve_table(nq, oracle):
+    """csrc/nq_abi.cpp get_path: the curve tables stayed on the device by shape until nq_destroy, and in REFERENCE_SEQUENTIAL the shape is the
+    whole image -- a long-lived handle kept 4 * w * h bytes for every image size it had converted (found by reading; nothing reported what
+    a handle holds before nq_get_device_bytes).  Three sizes, none larger than the first: the handle holds what it held after the first,
+    and every result is the oracle's (the one table is rewritten in place, also when a size comes back)."""
+    q = nq.PnnLABQuantizer(np.zeros((1, 1), np.int32), mode=nq.MODE_REFERENCE_SEQUENTIAL, seed=3)
+    try:
+        held = None
+        for w, h in ((64, 48), (40, 48), (64, 33), (40, 48)):
+            img = synth.gradient_noise(w, h, 900 + w + h)
+            want_argb, want_idx, want_pal = oracle.OracleQuantizer(1, img, seed=3).convert(16, True)
+            q.pixels, q.width, q.height = img.reshape(-1), w, h
+            out = q.convert(16, True)
+            assert (out.palette == want_pal).all() and (out.index.astype(np.int32) == want_idx).all() and (out.argb == want_argb).all(), (w, h)
+            held = nq.device_bytes() if held is None else held
+            assert nq.device_bytes() == held, "%d x %d left %d more bytes on the device" % (w, h, nq.device_bytes() - held)
+    finally:
+        q.close()
+
+
+def test_distinct_colours_of_one_image_do_not_serve_the_next(nq):
+    """csrc/nq_abi.cpp nq_set_distinct: the image-wide list of distinct colours of the split pipeline stayed valid for the handle's life.
+    A later image with <= nMaxColors occupied bins whose round handed none over took its early-return palette from the list of the
+    image BEFORE, with NQ_OK, instead of ending with NQ_ERR_UNSUPPORTED.  nq_set_scan, which starts an image's round, now forgets it."""
+    import ctypes as C
+    import torch
+    q = nq.PnnLABQuantizer(np.zeros((1, 1), np.int32), mode=nq.MODE_PARALLEL_TILED)
+    L = q._L
+
+    def front(img):
+        d_img = torch.from_numpy(img.reshape(-1).copy()).cuda()
+        s3 = torch.empty(3, dtype=torch.int64, device="cuda")
+        q._check(L.nq_band_scan_device(q._h, C.c_void_p(d_img.data_ptr()), d_img.numel(), 0, 64, C.c_void_p(s3.data_ptr())))
+        torch.cuda.synchronize()
+        q._check(L.nq_set_scan(q._h, 64, -1, C.c_uint32(0xFFFFFFFF), 0))
+        hist = torch.zeros(65536 * 5, dtype=torch.float64, device="cuda")
+        q._check(L.nq_band_histogram_device(q._h, C.c_void_p(d_img.data_ptr()), d_img.numel(), C.c_void_p(hist.data_ptr())))
+        return d_img, hist
+
+    def palette(hist):
+        pal, k = np.zeros(64, np.int32), C.c_int32(0)
+        rc = L.nq_palette_from_histograms_device(q._h, C.c_void_p(hist.data_ptr()), 1, 64, pal.ctypes.data, C.byref(k))
+        torch.cuda.synchronize()
+        return rc, pal[:k.value].copy()
+    try:
+        first, second = synth.few_colors(48, 40, 21, 12), synth.few_colors(48, 40, 22, 9)
+        d_img, hist = front(first)
+        cnt, cols = C.c_int64(0), np.zeros(64, np.int32)
+        q._check(L.nq_band_distinct_device(q._h, C.c_void_p(d_img.data_ptr()), d_img.numel(), 64, C.byref(cnt), cols.ctypes.data))
+        assert cnt.value == len(set(first.reshape(-1).tolist()))
+        q._check(L.nq_set_distinct(q._h, cnt.value, cols.ctypes.data))
+        rc, pal = palette(hist)
+        assert rc == 0 and sorted(pal.tolist()) == sorted(set(first.reshape(-1).tolist()))
+        d_img, hist = front(second)
+        rc, pal = palette(hist)
+        assert rc == -3, "status %d, palette of %d entries: the colours of the image before" % (rc, len(pal))
+    finally:
+        q.close()
