@@ -82,7 +82,8 @@ typedef struct nq_params {
  * kernel attributes) is set up per handle on the handle's device, nothing is cached per process. */
 int nq_create(int kind, int device, nq_handle** out);
 void nq_destroy(nq_handle* h);
-const char* nq_last_error(const nq_handle* h);   /* h may be NULL: last error of nq_create on this thread */
+const char* nq_last_error(const nq_handle* h);   /* h may be NULL: the thread's handle-free text -- the last error of nq_create or of a
+                                                  * call that takes no handle (nq_compare_*) on this thread */
 int nq_abi_version(void);
 /* All work of the handle is enqueued on this hipStream_t (NULL = the default stream): a call's reads of its device inputs are ordered
  * after the work the caller has queued on that stream before the call, its writes before the work queued there afterwards; the
@@ -822,6 +823,73 @@ int nq_convert_frames_ordered(nq_handle* h, int n, const uint32_t* const* argb, 
                               int nMaxColors, int refine, int limit,
                               uint32_t* const* out_argb, uint16_t* const* out_index,
                               uint32_t* out_palette, int32_t* out_K);
+
+/* ---- quality measurement: what a conversion did to the picture.  n pairs of frames -- the source and the output of any of the calls
+ *      above -- are compared in one streaming pass on the device: the per-pixel squared error (dither raises it), the error of the
+ *      8 x 8 block means in linear light (dither is there to lower it) and SSIM on luma over the same blocks (pngquant and gifski
+ *      --quality; the reference has no such step).  All arithmetic is integer: the result is deterministic and can be restated bit for bit.
+ *      These calls take NO handle: they are pure functions of their arguments and keep no state, so they take the device ordinal (and
+ *      the device forms a hipStream_t) directly.
+ *  * Inputs: n pairs of frames; pair i is widths[i] x heights[i].  src and out are ARGB_8888 words, channels a, r, g, b at shifts 24,
+ *    16, 8, 0.  flags: bit 0 is NQ_COMPARE_LINEAR; unknown bits are refused.
+ *  * Per frame 16 signed 64-bit slots.  All of the following are exact integers, signed 64-bit where sums are formed.
+ *  * Seen colour: a pixel with a = 0 has r = g = b = 0 for everything below.  Alpha is a channel of its own.
+ *  * Per pixel: sse_c += (s_c - o_c)^2 for c = a, r, g, b; maxdiff = the largest |s_c - o_c| over pixels and channels.
+ *  * Blocks: the frame is tiled with 8 x 8 blocks anchored at (0, 0); edge blocks are partial; N = the pixels of a block, 1..64.
+ *  * Table T[v]: with NQ_COMPARE_LINEAR the table of include/nq_srgb_linear_16.inc (the normative copy the reducer uses); without the
+ *    flag T[v] = 257 v.
+ *  * Block means.  Premultiplied 16-bit values P_a = 257 a and P_c = floor((T[c] a + 127) / 255) for c = r, g, b; block sums S_c over
+ *    src and S'_c over out; means m = floor((2 S + N) / (2 N)) and m' likewise; lf_c += (m - m')^2.
+ *  * Luma: y = (77 r + 150 g + 29 b + 128) >> 8, y* = floor((y a + 127) / 255).  Per block over y* of src (x) and out (y): Sx, Sy, Sxx,
+ *    Syy, Sxy.
+ *  * SSIM per block:
+ *        C1 = floor((65025 N^2 + 5000) / 10000)          C2 = floor((585225 N^2 + 5000) / 10000)
+ *        A1 = 2 Sx Sy + C1                               B1 = Sx^2 + Sy^2 + C1
+ *        A2 = 2 (N Sxy - Sx Sy) + C2                     B2 = N (Sxx + Syy) - Sx^2 - Sy^2 + C2
+ *        l = floor(32768 A1 / B1)     cs = floor(32768 A2 / B2)     q = floor(l cs / 32768)
+ *    floor rounds toward minus infinity; A2, and so cs and q, can be negative.  ssim += q; deficit = the largest 32768 - q over the
+ *    blocks.
+ *  * Bounds: every term A1, B1, |A2|, B2 is below 2^30 (Sx <= 64 * 255, Sxx <= 64 * 255^2), so 32768 A is below 2^45; B1, B2 >= C1 > 0;
+ *    0 <= l <= 32768, |cs| <= 32768 (Cauchy-Schwarz), -32768 <= q <= 32768, 0 <= deficit <= 65536.
+ *  * Slots:   0 pixels   1 blocks   2..5 sse a, r, g, b   6 maxdiff   7..10 lf a, r, g, b   11 ssim   12 deficit   13..15 0
+ *    Identical frames give zeros everywhere except slots 0, 1 and 11; slot 11 is then 32768 x blocks.
+ *  * Limits: a side is 1..65535, a frame holds at most 2^31 - 1 pixels, n is 1..65535.  So pixels < 2^31, blocks <= 2^26,
+ *    sse <= 255^2 (2^31 - 1) < 2^47, maxdiff <= 255, lf <= 65535^2 2^26 < 2^58, |ssim| <= 2^15 2^26 = 2^41.
+ *  * What the slots mean (formed by the caller, in floating point; nquant.android_amd.compare.Quality):
+ *        psnr        = 10 log10(65025 * 3 * pixels / (sse_r + sse_g + sse_b)), infinite at 0
+ *        lf_psnr     = 10 log10(65535^2 * 3 * blocks / (lf_r + lf_g + lf_b)), infinite at 0
+ *        ssim        = slot 11 / (32768 * blocks)
+ *        worst_block = 1 - deficit / 32768
+ *        max_diff    = slot 6
+ *    Over a sequence the slots add, slots 6 and 12 take the maximum.
+ *  * Indexed form: out is a uint16_t index map plus a palette of K entries, K in 1..256, in HOST memory; the output word is
+ *    palette[index].  An index >= K reads as the word 0; nq_compare_indexed then returns NQ_ERR_INVALID after the run, with every slot
+ *    written (as the encoders report it).  nq_compare_indexed_device waits for nothing and so cannot report it: there such an index
+ *    only reads as the word 0.
+ *  * Device forms: d_src, d_out / d_index are host arrays of n DEVICE pointers, d_result 16 n slots in DEVICE memory.  The call is
+ *    asynchronous on hip_stream (NULL = the default stream) of device `device`, ordered against it like a handle's calls are against
+ *    the handle's stream; it allocates no device memory and waits for nothing; the pointer tables, the sides and the palette belong
+ *    to the caller again on return.  Frames need 4-byte alignment, index maps 2-byte; groups of 16 consecutive pairs share a
+ *    launch, and where every pointer of a group is 16-byte aligned (index maps: 8-byte) and every width a multiple of 4 the kernel reads
+ *    16 bytes per access, otherwise one pixel per access, with the same results.  Frames are never written; nothing but the 16 n
+ *    slots is.
+ *  * Host forms: the same with HOST frames and a host result (uploaded to temporary buffers, the device form, the 16 n slots copied
+ *    back); they return when the results are there, with everything freed: nq_get_device_bytes is the same before and after.
+ *  * Errors: status as elsewhere; the text is the thread's handle-free one, nq_last_error(NULL).  NQ_ERR_INVALID comes first, before
+ *    any device is touched, with every output untouched: n outside 1..65535, a side outside 1..65535, a frame above 2^31 - 1 pixels,
+ *    unknown flag bits, K outside 1..256, a negative device, a NULL table, entry, palette or result, a frame pointer that is not
+ *    4-byte aligned (2-byte for an index map), a result that is not 8-byte aligned, a result that overlaps a frame.  Then
+ *    NQ_ERR_NO_DEVICE (no usable device; a device ordinal past the last one is NQ_ERR_INVALID), or NQ_ERR_HIP.
+ *  The kernel: DESIGN.md 5k "Quality measurement". ---- */
+#define NQ_COMPARE_LINEAR 1
+int nq_compare_frames_device(int device, void* hip_stream, int n, const uint32_t* const* d_src, const uint32_t* const* d_out,
+                             const int32_t* widths, const int32_t* heights, int flags, int64_t* d_result);
+int nq_compare_indexed_device(int device, void* hip_stream, int n, const uint32_t* const* d_src, const uint16_t* const* d_index,
+                              const uint32_t* palette, int K, const int32_t* widths, const int32_t* heights, int flags, int64_t* d_result);
+int nq_compare_frames(int device, int n, const uint32_t* const* src, const uint32_t* const* out,
+                      const int32_t* widths, const int32_t* heights, int flags, int64_t* result);
+int nq_compare_indexed(int device, int n, const uint32_t* const* src, const uint16_t* const* index, const uint32_t* palette, int K,
+                       const int32_t* widths, const int32_t* heights, int flags, int64_t* result);
 
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */

@@ -20,6 +20,7 @@ from .resample import fit_size, resample_frames, resample_frames_device
 from .ordered import convert_frames_ordered, dither_ordered, dither_ordered_device
 from .yuv import frames_from_yuv, frames_from_yuv_device, resample_frames_yuv, resample_frames_yuv_device, yuv_planes
 from .orient import orient_frames, orient_frames_device, orientation, oriented_size, source_rect
+from .compare import Quality, choose_colors, compare_frames, compare_frames_device, compare_indexed, compare_indexed_device
 from .build import build as build_library
 
 __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARALLEL_TILED", "MODE_LOOKUP_ONLY",
@@ -34,4 +35,5 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "refine_palette_device", "palette_error", "convert_frames_refined", "fit_size", "resample_frames", "resample_frames_device",
            "dither_ordered", "dither_ordered_device", "convert_frames_ordered", "frames_from_yuv", "frames_from_yuv_device",
            "resample_frames_yuv", "resample_frames_yuv_device", "yuv_planes", "orient_frames", "orient_frames_device", "orientation",
-           "oriented_size", "source_rect"]
+           "oriented_size", "source_rect", "Quality", "choose_colors", "compare_frames", "compare_frames_device", "compare_indexed",
+           "compare_indexed_device"]

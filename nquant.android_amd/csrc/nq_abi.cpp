@@ -4104,3 +4104,160 @@ int nq_convert_frames_ordered(nq_handle* h, int n, const uint32_t* const* argb, 
 }
 
 } // extern "C"
+
+// ---- quality measurement (nq_compare.hip): stateless calls -- no handle, the error text goes to the thread's handle-free string ----
+namespace {
+
+#define NQ_CMP_FAIL(code, ...) do { char _b[512]; std::snprintf(_b, sizeof _b, __VA_ARGS__); g_create_error = _b; return (code); } while (0)
+#define NQ_CMP_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { \
+    NQ_CMP_FAIL(NQ_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); } } while (0)
+
+// one call: n pairs; out[i] is an ARGB frame or, with `indexed`, a uint16 index map into palette[0 .. K)
+struct CompareCall {
+    int device, n;
+    const uint32_t* const* src; const void* const* out;
+    bool indexed; const uint32_t* palette; int K;
+    const int32_t* widths; const int32_t* heights;
+    int flags; int64_t* result;
+};
+
+// NQ_ERR_INVALID of the four entry points, before any device is touched (the pointers may be host or device addresses alike)
+int compare_check(const CompareCall& c) {
+    if (c.device < 0) NQ_CMP_FAIL(NQ_ERR_INVALID, "device = %d: a device ordinal is not negative", c.device);
+    if (c.n < 1 || c.n > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "n = %d: 1..65535 pairs of frames", c.n);
+    if (c.flags & ~NQ_COMPARE_LINEAR) NQ_CMP_FAIL(NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) c.flags);
+    if (c.indexed && (c.K < 1 || c.K > 256)) NQ_CMP_FAIL(NQ_ERR_INVALID, "K = %d: a palette has 1..256 entries", c.K);
+    if (!c.src || !c.out || !c.widths || !c.heights) NQ_CMP_FAIL(NQ_ERR_INVALID, "an array of frame pointers or of sides is NULL");
+    if (c.indexed && !c.palette) NQ_CMP_FAIL(NQ_ERR_INVALID, "palette is NULL");
+    if (!c.result || ((uintptr_t) c.result & 7)) NQ_CMP_FAIL(NQ_ERR_INVALID, "result is NULL or not 8-byte aligned");
+    const uintptr_t r0 = (uintptr_t) c.result, r1 = r0 + (uintptr_t) c.n * 16 * sizeof(int64_t);
+    for (int i = 0; i < c.n; ++i) {
+        const int w = c.widths[i], h = c.heights[i];
+        if (w < 1 || w > 65535 || h < 1 || h > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: %d x %d: sides must be 1..65535", i, w, h);
+        const uintptr_t px = (uintptr_t) w * (uintptr_t) h;
+        if (px > 2147483647u) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: %d x %d: more than 2^31 - 1 pixels", i, w, h);
+        const uintptr_t s0 = (uintptr_t) c.src[i], o0 = (uintptr_t) c.out[i], obytes = px * (c.indexed ? sizeof(uint16_t) : sizeof(uint32_t));
+        if (!s0 || (s0 & 3)) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: source pointer NULL or not 4-byte aligned", i);
+        if (!o0 || (o0 & (c.indexed ? 1 : 3)))
+            NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: %s pointer NULL or not %d-byte aligned", i, c.indexed ? "index map" : "output", c.indexed ? 2 : 4);
+        if ((s0 < r1 && r0 < s0 + px * sizeof(uint32_t)) || (o0 < r1 && r0 < o0 + obytes))
+            NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: result overlaps the frame", i);
+    }
+    return NQ_OK;
+}
+
+int compare_use_device(int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        NQ_CMP_FAIL(NQ_ERR_NO_DEVICE, "no HIP device available (libnquant_hip has no CPU fallback)");
+    if (device >= count) NQ_CMP_FAIL(NQ_ERR_INVALID, "device ordinal out of range");
+    NQ_CMP_HIP(hipSetDevice(device));
+    return NQ_OK;
+}
+
+// after the checks: the result zeroed, then one launch per COMPARE_FRAMES_PER_LAUNCH pairs, all on s; nothing is allocated or awaited.
+// c.result and the frames are device memory, *d_bad as launch_compare wants it.
+int compare_device(const CompareCall& c, int* d_bad, hipStream_t s) {
+    NQ_CMP_HIP(hipMemsetAsync(c.result, 0, (size_t) c.n * 16 * sizeof(int64_t), s));
+    for (int first = 0; first < c.n; first += COMPARE_FRAMES_PER_LAUNCH) {
+        const int count = std::min(c.n - first, (int) COMPARE_FRAMES_PER_LAUNCH);
+        CompareLaunch a;
+        std::memset(&a, 0, sizeof a);
+        bool vec = true;                             // the 16-byte path needs every frame of the launch to allow it
+        for (int i = 0; i < count; ++i) {
+            a.frame[i] = {c.src[first + i], c.out[first + i], c.widths[first + i], c.heights[first + i], 0u, 0};
+            vec = vec && c.widths[first + i] % 4 == 0 && !((uintptr_t) c.src[first + i] & 15) &&
+                  !((uintptr_t) c.out[first + i] & (c.indexed ? 7 : 15));
+        }
+        a.result = reinterpret_cast<long long*>(c.result + 16 * (size_t) first);
+        a.first = first;
+        a.linear = (c.flags & NQ_COMPARE_LINEAR) != 0;
+        launch_compare(a, count, vec, c.indexed, c.palette, c.K, d_bad, s);
+    }
+    NQ_CMP_HIP(launch_status());
+    return NQ_OK;
+}
+
+// the host forms: frames and index maps uploaded to temporary buffers (every one on a 16-byte boundary), the device form, the
+// results read back; everything is freed when the call returns
+int compare_host(const CompareCall& c) {
+    int rc = compare_check(c);
+    if (rc) return rc;
+    rc = compare_use_device(c.device);
+    if (rc) return rc;
+    DevBuf<uint32_t> d_px;
+    DevBuf<int64_t> d_res;
+    DevBuf<int> d_bad;
+    std::vector<size_t> at(2 * (size_t) c.n);        // first word of src i, of out i
+    size_t words = 0;
+    for (int i = 0; i < c.n; ++i) {
+        const size_t px = (size_t) c.widths[i] * c.heights[i];
+        at[2 * (size_t) i] = words; words += (px + 3) & ~(size_t) 3;
+        at[2 * (size_t) i + 1] = words; words += ((c.indexed ? (px + 1) / 2 : px) + 3) & ~(size_t) 3;
+    }
+    hipStream_t s = nullptr;
+    int bad = INT_MAX;
+    auto body = [&]() -> int {
+        NQ_CMP_HIP(d_px.reserve(words));
+        NQ_CMP_HIP(d_res.reserve(16 * (size_t) c.n));
+        NQ_CMP_HIP(d_bad.reserve(1));
+        std::vector<const uint32_t*> d_src(c.n);
+        std::vector<const void*> d_out(c.n);
+        for (int i = 0; i < c.n; ++i) {
+            const size_t px = (size_t) c.widths[i] * c.heights[i];
+            d_src[i] = d_px.p + at[2 * (size_t) i]; d_out[i] = d_px.p + at[2 * (size_t) i + 1];
+            NQ_CMP_HIP(hipMemcpyAsync(d_px.p + at[2 * (size_t) i], c.src[i], px * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            NQ_CMP_HIP(hipMemcpyAsync(d_px.p + at[2 * (size_t) i + 1], c.out[i], px * (c.indexed ? sizeof(uint16_t) : sizeof(uint32_t)),
+                                      hipMemcpyHostToDevice, s));
+        }
+        NQ_CMP_HIP(hipMemcpyAsync(d_bad.p, &bad, sizeof bad, hipMemcpyHostToDevice, s));
+        CompareCall d = c;
+        d.src = d_src.data(); d.out = d_out.data(); d.result = d_res.p;
+        const int rc2 = compare_device(d, d_bad.p, s);
+        if (rc2) return rc2;
+        NQ_CMP_HIP(hipMemcpyAsync(c.result, d_res.p, 16 * (size_t) c.n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        NQ_CMP_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, s));
+        NQ_CMP_HIP(hipStreamSynchronize(s));
+        return NQ_OK;
+    };
+    rc = body();
+    if (rc) { (void) hipStreamSynchronize(s); return rc; }
+    if (bad != INT_MAX) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: an index >= K = %d (it was read as the word 0)", bad, c.K);
+    return NQ_OK;
+}
+
+int compare_device_form(const CompareCall& c, void* hip_stream) {
+    int rc = compare_check(c);
+    if (rc) return rc;
+    rc = compare_use_device(c.device);
+    if (rc) return rc;
+    return compare_device(c, nullptr, (hipStream_t) hip_stream);
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_compare_frames_device(int device, void* hip_stream, int n, const uint32_t* const* d_src, const uint32_t* const* d_out,
+                             const int32_t* widths, const int32_t* heights, int flags, int64_t* d_result) {
+    return compare_device_form({device, n, d_src, reinterpret_cast<const void* const*>(d_out), false, nullptr, 0, widths, heights, flags, d_result},
+                               hip_stream);
+}
+
+int nq_compare_indexed_device(int device, void* hip_stream, int n, const uint32_t* const* d_src, const uint16_t* const* d_index,
+                              const uint32_t* palette, int K, const int32_t* widths, const int32_t* heights, int flags, int64_t* d_result) {
+    return compare_device_form({device, n, d_src, reinterpret_cast<const void* const*>(d_index), true, palette, K, widths, heights, flags, d_result},
+                               hip_stream);
+}
+
+int nq_compare_frames(int device, int n, const uint32_t* const* src, const uint32_t* const* out, const int32_t* widths,
+                      const int32_t* heights, int flags, int64_t* result) {
+    return compare_host({device, n, src, reinterpret_cast<const void* const*>(out), false, nullptr, 0, widths, heights, flags, result});
+}
+
+int nq_compare_indexed(int device, int n, const uint32_t* const* src, const uint16_t* const* index, const uint32_t* palette, int K,
+                       const int32_t* widths, const int32_t* heights, int flags, int64_t* result) {
+    return compare_host({device, n, src, reinterpret_cast<const void* const*>(index), true, palette, K, widths, heights, flags, result});
+}
+
+} // extern "C"

@@ -368,4 +368,18 @@ struct OrderedFrame { const unsigned* pixels; unsigned short* index; unsigned* a
 void launch_ordered(const OrderedFrame* d_frames, int n, long long total, bool vec, bool out, const unsigned* d_palette, int K, int T, int limit,
                     unsigned long long* d_stats, hipStream_t s);
 
+// ---- quality measurement (nq_compare.hip; include/nquant_abi.h "quality measurement"): `count` pairs of frames (1 ..
+// COMPARE_FRAMES_PER_LAUNCH) go to the kernel BY VALUE, so a launch needs no table in device memory.  frame[i].out is an ARGB frame or,
+// with `indexed`, a uint16 index map into `palette` (K entries in HOST memory, 1..256; copied into the launch).  result: 16 64-bit
+// slots per frame of the launch, in device memory, zeroed by the caller on the same stream; `first`: the number of frame[0] in the
+// call, for *d_bad (device, may be null): the caller puts INT_MAX there, it is lowered to the number of a frame that holds an index
+// >= K.  vec: the 16-byte path -- the caller has checked for EVERY frame of the launch: src (and an ARGB out) 16-byte aligned, an index
+// map 8-byte aligned, width a multiple of 4; otherwise one pixel per access (4-byte / 2-byte alignment).  Sides are 1..65535.  Nothing
+// but the result slots (and *d_bad) is written.  compare_grid: workgroups a frame of this size gets (tests count with it). ----
+constexpr int COMPARE_FRAMES_PER_LAUNCH = 16;
+struct CompareFrame { const void* src; const void* out; int width, height; unsigned strips_x_rcp; int pad; };   // strips_x_rcp: launch_compare's
+struct CompareLaunch { CompareFrame frame[COMPARE_FRAMES_PER_LAUNCH]; long long* result; int first; int linear; };
+int compare_grid(int width, int height);
+void launch_compare(const CompareLaunch& a, int count, bool vec, bool indexed, const unsigned* palette, int K, int* d_bad, hipStream_t s);
+
 } // namespace nq

@@ -133,6 +133,10 @@ _ABI = {
     "nq_dither_ordered": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "nq_convert_frames_ordered_device": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _pi32]),
     "nq_convert_frames_ordered": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _pi32]),
+    "nq_compare_frames_device": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "nq_compare_indexed_device": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "nq_compare_frames": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "nq_compare_indexed": (_i32, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
 }
 
 
