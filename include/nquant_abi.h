@@ -130,6 +130,56 @@ int nq_get_list_counts(nq_handle* h, uint8_t* closest_counts, uint8_t* nearest_c
  * out9[9 i + 4..7] = the same from the literal functions, out9[9 i + 8] = 1 when the fast pass decided (else find_nn uses the
  * literal values).  Wherever it decided the two quadruples must be identical. */
 int nq_selftest_ciede(nq_handle* h, const float* lab_pairs, int64_t n, uint32_t* out9);
+/* Self-test hook of the specialised dither kernel's scalar shortcuts (csrc/nq_dither_fast.hip): one launch that calls the SAME device
+ * functions as the dither kernel, with qa / qb / qc derived as in every dither launch, the constant tables of the dither launch and
+ * PR, PG, PB, ratio of the handle's params (nq_set_params).  `which` selects the filter; n = number of elements evaluated (at most
+ * 2^26 per call except for the counting forms).
+ * Range modes take in = int64_t {first, count, a0, a1} (count must equal n) and enumerate first .. first + n - 1 on the device:
+ *   TANH           element = float bit pattern x.  out[2 i] = bits of tanh_to_float(x), out[2 i + 1] = 1 when tanh_library decided.
+ *   CLOSEST_ERR    element = |dr| << 16 | |dg| << 8 | |db|, a0 = sign mask (bit 2 / 1 / 0: dr / dg / db negative; d = entry - colour).
+ *                  out[3 i] = the F fast_closest_step leaves in an empty tuple (closest[2] = closest[3] = INT_MAX, so a value near an
+ *                  integer always takes the exact evaluation), out[3 i + 1] = bits of the float32 form e32, out[3 i + 2] = 1 when
+ *                  closest_err_exact ran.
+ *   NEXTINT        element = uu in [0, 2^31), the draw next(31) of nextInt(32767).  out[i] = folded r | accepted << 16.
+ *   NEXTINT_COUNT  the same range against plain 64-bit C on the device (uu % 32767; rejected iff uu - r + 32766 >= 2^31).
+ *                  out = four words: uint64 number of disagreements, uint64 first disagreeing uu (all ones: none).
+ *   REM_COUNT      element = r << 15 | dsum in [0, 2^30); the pairs 0 <= r < 32767, 1 <= dsum <= r are compared with plain r % dsum.
+ *                  out as NEXTINT_COUNT (first disagreeing element).
+ *   YDIFF_RANGE    element = opaque colour 0xFF000000 | rgb as c1; a0 = c2; a1 = thresholds << 1 | gt, the thresholds (at most 32
+ *                  doubles) follow the header.  out[3 i] = bits of the float32 yd, out[3 i + 1] = decision bit per threshold,
+ *                  out[3 i + 2] = bit per threshold where the f64 path decided.
+ *   LAB32, LAB64   element = rgb of an opaque colour.  out[3 i + 0..2] = bits of L, A, B of lab32_of / of RGB2LAB_fast.
+ *   NEAR_D32       element = rgb of an opaque colour, a0 = palette index.  out[i] = bits of the float32 distance fast_nearest32 forms
+ *                  against that entry of the palette the handle's last lookup or dither call put on the device (at most 256 entries).
+ * Explicit modes take n records at `in`:
+ *   CLOSEST_ERR_PAIRS  int32 {colour, palette entry}; out as CLOSEST_ERR.
+ *   REM                int32 {r, dsum}; out[i] = the remainder fast_closest_pick uses.
+ *   YDIFF              {int32 c1, c2, gt, 0; double thr}; out[3 i] = decision, out[3 i + 1] = bits of yd, out[3 i + 2] = f64 path decided.
+ *   NEAR_D32_PAIRS     int32 {colour, palette index}; out as NEAR_D32.  An index past the palette is the caller's error (here and in
+ *                      NEAR_SAFE only its low 8 bits are used, and an entry past the palette reads as the colour 0).
+ *   TANH_BITS          uint32 float bit patterns; out as TANH.
+ *   NEXTINT_LIST       int32 uu in [0, 2^31); out as NEXTINT.
+ *   NEAR_SAFE          int32 {colour, ka | kb << 8}; out[i] = the index fast_nearest32 picks from the two-entry list {ka, kb} | safe << 16
+ *                      (safe: the runner-up is more than 2 NQ_FAST_NEAR_EPS behind, so the exact scan is skipped).
+ * tests/test_gpu_fast_filters.py holds each against the oracle over its whole domain. */
+#define NQ_FAST_ST_TANH 0
+#define NQ_FAST_ST_CLOSEST_ERR 1
+#define NQ_FAST_ST_CLOSEST_ERR_PAIRS 2
+#define NQ_FAST_ST_NEXTINT 3
+#define NQ_FAST_ST_NEXTINT_COUNT 4
+#define NQ_FAST_ST_REM 5
+#define NQ_FAST_ST_REM_COUNT 6
+#define NQ_FAST_ST_YDIFF 7
+#define NQ_FAST_ST_YDIFF_RANGE 8
+#define NQ_FAST_ST_LAB32 9
+#define NQ_FAST_ST_LAB64 10
+#define NQ_FAST_ST_NEAR_D32 11
+#define NQ_FAST_ST_NEAR_D32_PAIRS 12
+#define NQ_FAST_ST_TANH_BITS 13
+#define NQ_FAST_ST_NEXTINT_LIST 14
+#define NQ_FAST_ST_NEAR_SAFE 15
+#define NQ_FAST_ST_MODES 16
+int nq_selftest_fast(nq_handle* h, int which, const void* in, int64_t n, uint32_t* out);
 int nq_get_params(const nq_handle* h, nq_params* out);
 int nq_set_params(nq_handle* h, const nq_params* in);
 

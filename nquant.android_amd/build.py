@@ -20,7 +20,8 @@ INC = os.path.join("..", "..", "include")
 UNITS = {
     "nq_kernels.hip": ("device", ["nq_kernels.hip", "nq_device.h", "nq_kernels.h", "nq_dither.inc", "nq_palette.inc", "nq_merge.inc", "nq_lists.inc",
                                   os.path.join(INC, "nq_blue_noise_64x64.inc")]),
-    "nq_dither_fast.hip": ("device", ["nq_dither_fast.hip", "nq_device.h", "nq_kernels.h", os.path.join(INC, "nq_blue_noise_64x64.inc")]),
+    "nq_dither_fast.hip": ("device", ["nq_dither_fast.hip", "nq_device.h", "nq_kernels.h", os.path.join(INC, "nq_blue_noise_64x64.inc"),
+                                      os.path.join(INC, "nquant_abi.h")]),
     "nq_gif.hip": ("device", ["nq_gif.hip", "nq_kernels.h"]),
     "nq_png.hip": ("device", ["nq_png.hip", "nq_kernels.h"]),
     "nq_hold.hip": ("device", ["nq_hold.hip", "nq_kernels.h"]),

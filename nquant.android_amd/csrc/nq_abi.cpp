@@ -1487,6 +1487,53 @@ int nq_selftest_ciede(nq_handle* h, const float* lab_pairs, int64_t n, uint32_t*
     if (e != hipSuccess) NQ_FAIL(h, NQ_ERR_HIP, "nq_selftest_ciede: %s", hipGetErrorString(e));
     return NQ_OK;
 }
+int nq_selftest_fast(nq_handle* h, int which, const void* in, int64_t n, uint32_t* out) {
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (which < 0 || which >= NQ_FAST_ST_MODES || !in || n <= 0 || !out) NQ_FAIL(h, NQ_ERR_INVALID, "nq_selftest_fast: bad argument");
+    // per mode: bytes of an explicit input record (0 = a range header {first, count, a0, a1}), output words per element (0 = the four
+    // words of a counting form), end of the range's domain
+    static const struct { int rec_bytes, out_words; int64_t domain; } k_mode[] = {
+        {0, 2, (int64_t) 1 << 32}, {0, 3, 1 << 24}, {8, 3, 0}, {0, 1, (int64_t) 1 << 31}, {0, 0, (int64_t) 1 << 31}, {8, 1, 0}, {0, 0, 1 << 30},
+        {24, 3, 0}, {0, 3, 1 << 24}, {0, 3, 1 << 24}, {0, 3, 1 << 24}, {0, 1, 1 << 24}, {8, 1, 0}, {4, 2, 0}, {4, 1, 0}, {8, 1, 0}};
+    static_assert(sizeof k_mode / sizeof k_mode[0] == NQ_FAST_ST_MODES && NQ_FAST_ST_MODES == NQ_FAST_ST_NEAR_SAFE + 1, "one row per NQ_FAST_ST_* mode, in their order");
+    const auto& m = k_mode[which];
+    const bool counting = m.out_words == 0;
+    if (!counting && n > ((int64_t) 1 << 26)) NQ_FAIL(h, NQ_ERR_INVALID, "nq_selftest_fast: more than 2^26 elements in one call");
+    int64_t first = 0, a0 = 0, a1 = 0;
+    const void* up = in;              // what goes to the device
+    size_t up_bytes = (size_t) n * (size_t) m.rec_bytes;
+    if (m.rec_bytes == 0) {
+        const int64_t* hdr = (const int64_t*) in;
+        first = hdr[0]; a0 = hdr[2]; a1 = hdr[3];
+        if (hdr[1] != n || first < 0 || first > m.domain || n > m.domain - first) NQ_FAIL(h, NQ_ERR_INVALID, "nq_selftest_fast: range outside the domain");
+        up = nullptr;
+        if (which == NQ_FAST_ST_CLOSEST_ERR && (a0 < 0 || a0 > 7)) NQ_FAIL(h, NQ_ERR_INVALID, "nq_selftest_fast: sign mask");
+        if (which == NQ_FAST_ST_YDIFF_RANGE) {
+            if (a1 < 0 || (a1 >> 1) > 32) NQ_FAIL(h, NQ_ERR_INVALID, "nq_selftest_fast: more than 32 thresholds");
+            up = hdr + 4; up_bytes = (size_t) (a1 >> 1) * sizeof(double);
+        }
+    }
+    const bool wants_palette = which == NQ_FAST_ST_NEAR_D32 || which == NQ_FAST_ST_NEAR_D32_PAIRS || which == NQ_FAST_ST_NEAR_SAFE;
+    const int K = (int) h->dev_palette.size();
+    if (wants_palette && (K < 1 || K > 256 || !h->d_palette.p)) NQ_FAIL(h, NQ_ERR_INVALID, "nq_selftest_fast: no palette of at most 256 entries on the device (run a lookup first)");
+    if (which == NQ_FAST_ST_NEAR_D32 && (a0 < 0 || a0 >= K)) NQ_FAIL(h, NQ_ERR_INVALID, "nq_selftest_fast: palette index");
+    const DevParams P = dev_params(h, wants_palette ? K : 0);
+    const size_t out_bytes = counting ? 16 : (size_t) n * (size_t) m.out_words * sizeof(uint32_t);
+    const uint64_t count_init[2] = {0, ~(uint64_t) 0};
+    void* d_in = nullptr; unsigned* d_out = nullptr;
+    hipError_t e = hipMalloc((void**) &d_out, out_bytes);
+    if (e == hipSuccess && up_bytes) e = hipMalloc(&d_in, up_bytes);
+    if (e == hipSuccess && up_bytes) e = hipMemcpyAsync(d_in, up, up_bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && counting) e = hipMemcpyAsync(d_out, count_init, 16, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) { launch_fast_selftest(P, wants_palette ? h->d_palette.p : nullptr, which, d_in, first, n, a0, a1, d_out, h->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (d_in) (void) hipFree(d_in);
+    if (d_out) (void) hipFree(d_out);
+    if (e != hipSuccess) NQ_FAIL(h, NQ_ERR_HIP, "nq_selftest_fast: %s", hipGetErrorString(e));
+    return NQ_OK;
+}
 int nq_get_dither_path(nq_handle* h, int32_t* out_fast, int32_t* out_failed_tiles) {
     if (!h) return NQ_ERR_INVALID;
     if (out_fast) *out_fast = h->last_dither_fast;

@@ -2,6 +2,7 @@
 // Build flags as nq_kernels.hip (-ffp-contract=off -fno-fast-math).  Own copy of the constant tables (upload_tables_fast).
 #include "nq_device.h"
 #include "nq_kernels.h"
+#include "../../include/nquant_abi.h"      // NQ_FAST_ST_*: the modes of nq_selftest_fast
 #include <cstring>
 #include <cmath>
 #include <cstdlib>
@@ -25,13 +26,14 @@
 //  * nearestColorIndex (NQ/PnnLABQuantizer.java:369-375, K > 32): the argmin is first sought with a float32 Lab of the colour;
 //    if the runner-up is not clearly (2 eps) behind, the exact f64 path (RGB2LAB_fast + reference arithmetic) decides;
 //  * (float) Math.tanh((double) x) (NQ/GilbertCurve.java:246): 1 - 2t/(1 + t), t = exp(-2|x|) in f64 with a 4e-16 error, accepted
-//    when v +- 1e-14 round to the same float, else the library tanh decides;
-//  * Y_Diff threshold tests: float32 first, f64 when within 1e-3 of the threshold;
+//    when v +- 1.5e-14 round to the same float, else the library tanh decides;
+//  * Y_Diff threshold tests: float32 first, f64 when within 2.2e-3 of the threshold;
 //  * pixel + saliency of the next step are fetched while the current step computes; indices are staged per lane in LDS
 //    (conflict-free stride) and leave as whole rows (16-byte stores).
 //
 // Exactness of the float32 filters is argued next to each of them; tests/test_gpu_parity.py checks the kernel against the
-// oracle (tiled cases, the 2^24 colour cube for the lookups) and against the generic kernel (NQ_OPT_FAST_DITHER off).
+// oracle (tiled cases, the 2^24 colour cube for the lookups) and against the generic kernel (NQ_OPT_FAST_DITHER off);
+// tests/test_gpu_fast_filters.py runs every filter on its own over its whole input domain (nq_selftest_fast, fast_selftest_kernel below).
 
 namespace nq {
 
@@ -145,17 +147,21 @@ __host__ __device__ __forceinline__ int fast_stride_bytes(int tilepx) {
 // ---- (float) Math.tanh((double) x) --------------------------------------------------------------------------------------------
 // v = 1 - 2t/(1 + t), t = exp(-2|x|): Cody-Waite reduction, degree-12 Taylor polynomial on |f| <= ln2/2 (truncation 1.7e-16),
 // two Newton steps on v_rcp_f64; |v - tanh| < 1e-15.  The float nearest to v is the float nearest to tanh unless a rounding
-// boundary lies within that error: then (v - 1e-14) and (v + 1e-14) round differently and the library decides (3e-7 of all calls).
+// boundary lies within that error: then (v - 1.5e-14) and (v + 1.5e-14) round differently and the library decides (5e-7 of all calls).
+// The window is wider than the error needs: every input whose f64 tanh (any libm, last place) lies within 1.2e-14 of a boundary takes
+// the library, which tests/test_gpu_fast_filters.py demands over all 3.5e7 floats of 0.5 <= |x| < 9.2.
 __device__ __attribute__((noinline)) float tanh_library(double ax) { return (float) tanh(ax); }      // cold: 3e-7 of the calls
 __device__ __attribute__((noinline)) float normal_distribution_cold(float x, float peak) { return normalDistribution(x, peak); }
-__device__ __forceinline__ float tanh_to_float(float xf) {
+// library: whether tanh_library decided (self-test only)
+__device__ __forceinline__ float tanh_to_float_x(float xf, bool& library) {
     const double x = (double) xf;
     const double ax = fabs(x);
     float r;
+    library = false;
     NQ_COUNT(FC_TANH, true);
     NQ_COUNT(FC_TANH_LIBRARY, ax < 0.5);
     if (ax >= 9.2) r = 1.0f;                     // 1 - tanh < 2 exp(-18.4) = 2.1e-8 < 2^-25: rounds to 1.0f
-    else if (ax < 0.5) r = tanh_library(ax);     // not reached by the limiter (|e| >= ditherMax); kept for completeness
+    else if (ax < 0.5) { r = tanh_library(ax); library = true; }     // not reached by the limiter (|e| >= ditherMax); kept for completeness
     else {
         const double z = -2.0 * ax;
         const double n = rint(z * 1.4426950408889634);
@@ -180,13 +186,14 @@ __device__ __forceinline__ float tanh_to_float(float xf) {
         rc = fma(fma(-d, rc, 1.0), rc, rc);
         rc = fma(fma(-d, rc, 1.0), rc, rc);
         const double v = 1.0 - 2.0 * t * rc;
-        const float lo = (float) (v - 1e-14), hi = (float) (v + 1e-14);
+        const float lo = (float) (v - 1.5e-14), hi = (float) (v + 1.5e-14);
         r = lo;
         NQ_COUNT(FC_TANH_LIBRARY, lo != hi);
-        if (lo != hi) r = tanh_library(ax);
+        if (lo != hi) { r = tanh_library(ax); library = true; }
     }
     return x < 0 ? -r : r;
 }
+__device__ __forceinline__ float tanh_to_float(float xf) { bool library; return tanh_to_float_x(xf, library); }
 
 // ---- closestColorIndex, one candidate, the reference's statement sequence (NQ/PnnLABQuantizer.java:421-445, no semi-transparency,
 // ratio >= 0: every term is >= 0 and the gates only leave early a candidate that neither branch takes) -> err as f64
@@ -211,8 +218,10 @@ struct FastClosest { int c0, c1, e0, e1; };      // closest[0..3]
 // real-number form, which the reference's f64 sum follows to 2^-22 relative (it rounds coeff * d to FLOAT before squaring:
 // NQ/PnnLABQuantizer.java:434-440, 2 * 2^-24 per YUV term).  |e32 - err| <= e32 * 2^-20 + 1e-6 =: delta is a safe bound; the
 // integer part is taken from e32 unless e32 lies within delta of an integer AND the candidate could enter the tuple.
-__device__ __forceinline__ void fast_closest_step(FastClosest& t, int k, int c2, float crf, float cgf, float cbf, int cr, int cg, int cb,
-                                                  float qa, float qb, float qc, double wr, double wg, double wb, double ratio) {
+// floor(err) of the candidate as the step below uses it; e1 = closest[3] of the tuple so far.  e32 / exact (self-test only): the float32
+// value and whether closest_err_exact ran
+__device__ __forceinline__ int fast_closest_floor(int e1, int c2, float crf, float cgf, float cbf, int cr, int cg, int cb,
+                                                  float qa, float qb, float qc, double wr, double wg, double wb, double ratio, float& e32, bool& exact) {
     const float dr = (float) ((c2 >> 16) & 0xFF) - crf, dg = (float) ((c2 >> 8) & 0xFF) - cgf, db = (float) (c2 & 0xFF) - cbf;
     float e = qa * (dr * dr);
     e = __builtin_fmaf(qb, dg * dg, e);
@@ -220,8 +229,16 @@ __device__ __forceinline__ void fast_closest_step(FastClosest& t, int k, int c2,
     int F = (int) e;                                             // e >= 0, < 2^20
     const float frac = e - (float) F;
     const float delta = __builtin_fmaf(e, 9.5367431640625e-07f, 1e-6f);
-    NQ_COUNT(FC_CLOSEST_EXACT, (frac < delta || frac > 1.0f - delta) && F <= t.e1);
-    if ((frac < delta || frac > 1.0f - delta) && F <= t.e1) F = (int) closest_err_exact(c2, cr, cg, cb, wr, wg, wb, ratio);
+    NQ_COUNT(FC_CLOSEST_EXACT, (frac < delta || frac > 1.0f - delta) && F <= e1);
+    e32 = e;
+    exact = (frac < delta || frac > 1.0f - delta) && F <= e1;
+    if (exact) F = (int) closest_err_exact(c2, cr, cg, cb, wr, wg, wb, ratio);
+    return F;
+}
+__device__ __forceinline__ void fast_closest_step(FastClosest& t, int k, int c2, float crf, float cgf, float cbf, int cr, int cg, int cb,
+                                                  float qa, float qb, float qc, double wr, double wg, double wb, double ratio) {
+    float e32; bool exact;
+    const int F = fast_closest_floor(t.e1, c2, crf, cgf, cbf, cr, cg, cb, qa, qb, qc, wr, wg, wb, ratio, e32, exact);
     // `if (err < closest[2]) ... else if (err < closest[3])` with int thresholds == the same tests on floor(err)
     const bool lt0 = F < t.e0, lt1 = F < t.e1;
     t.c1 = lt0 ? t.c0 : (lt1 ? k : t.c1);
@@ -324,6 +341,11 @@ __device__ __forceinline__ FastClosest fast_closest_tuple(const FastLds& S, cons
 // |dL| + sqrt(dA^2 + dB^2) over the n2 listed candidates, ties to the higher index.  float32 first (lab32_of); the exact f64 scan
 // decides when the runner-up is within 2 NQ_FAST_NEAR_EPS.
 // float32 part: the argmin and whether it is safe (runner-up more than 2 NQ_FAST_NEAR_EPS behind)
+// the float32 distance of fast_nearest32 between a palette entry's Lab {L, A, B, -} and the colour's float32 Lab
+__device__ __forceinline__ float fast_near_d32(float4 l2, float L1, float A1, float B1) {
+    const float dA = l2.y - A1, dB = l2.z - B1;
+    return fabsf(l2.x - L1) + __builtin_amdgcn_sqrtf(__builtin_fmaf(dA, dA, dB * dB));
+}
 __device__ __forceinline__ int fast_nearest32(const FastLds& S, const FastLookup& X, int c, uint4 na, int n2, int cell, bool& safe) {
     float L1, A1, B1;
     lab32_of(c, S.gamma32, L1, A1, B1);
@@ -338,8 +360,7 @@ __device__ __forceinline__ int fast_nearest32(const FastLds& S, const FastLookup
 #pragma unroll
         for (int j = 0; j < 8; ++j)
             if (j < n2) {
-                const float dA = ll[j].y - A1, dB = ll[j].z - B1;
-                const float d = fabsf(ll[j].x - L1) + __builtin_amdgcn_sqrtf(__builtin_fmaf(dA, dA, dB * dB));
+                const float d = fast_near_d32(ll[j], L1, A1, B1);
                 const bool lt = d < d1;
                 d2 = lt ? d1 : fminf(d2, d);
                 k1 = lt ? kk[j] : k1;
@@ -359,8 +380,7 @@ __device__ __forceinline__ int fast_nearest32(const FastLds& S, const FastLookup
             if (i == 14 && n2 > 15) { const uint4 m = X.cont[65536 + cell]; w0 = m.x; w1 = m.y; w2 = m.z; w3 = m.w; }
             k_next = (int) (w0 & 0xFF);
             l_next = S.lab[k_next];
-            const float dA = l2.y - A1, dB = l2.z - B1;
-            const float d = fabsf(l2.x - L1) + __builtin_amdgcn_sqrtf(__builtin_fmaf(dA, dA, dB * dB));
+            const float d = fast_near_d32(l2, L1, A1, B1);
             const bool lt = d < d1;
             d2 = lt ? d1 : fminf(d2, d);
             k1 = lt ? k : k1;
@@ -409,18 +429,17 @@ __device__ __forceinline__ int fast_nearest_rgb(const FastLds& S, double pa, dou
 
 // which of the two closest candidates (NQ/PnnLABQuantizer.java:465-468): 0 when closest[2] == 0 or
 // random.nextInt(32767) % (closest[3] + closest[2]) <= closest[3], else 1; draws from `rng` exactly when the reference does
-__device__ __forceinline__ int fast_closest_pick(const FastClosest& t, long long& rng) {
-    if (t.e0 == 0) return 0;
-    // random.nextInt(32767): next(31), then the rejection loop of the non-power-of-two bound (taken with probability 1e-9)
-    int r;
-    for (;;) {
-        const int uu = jr_next(rng, 31);
-        int v = (uu >> 15) + (uu & 32767);                  // 32768 == 1 (mod 32767)
-        v = (v >> 15) + (v & 32767);
-        r = v >= 32767 ? v - 32767 : v;
-        if ((int) ((unsigned) (uu - r) + 32766u) >= 0) break;
-    }
-    const int dsum = (int) ((unsigned) t.e1 + (unsigned) t.e0);
+// one draw uu = next(31) of random.nextInt(32767): uu % 32767 without a division, and whether the rejection loop of the
+// non-power-of-two bound accepts it
+__device__ __forceinline__ int fast_nextint_fold(int uu, bool& accept) {
+    int v = (uu >> 15) + (uu & 32767);                  // 32768 == 1 (mod 32767)
+    v = (v >> 15) + (v & 32767);
+    const int r = v >= 32767 ? v - 32767 : v;
+    accept = (int) ((unsigned) (uu - r) + 32766u) >= 0;
+    return r;
+}
+// r % dsum as the pick below needs it (0 <= r < 32767; dsum = closest[3] + closest[2], possibly wrapped)
+__device__ __forceinline__ int fast_pick_rem(int r, int dsum) {
     int rem = r;                                            // dsum < 0 (wrapped) or dsum > r: r % dsum == r
     if (dsum > 0 && dsum <= r) {
         // r < 2^15: the float quotient is within 0.01 of the true one
@@ -428,22 +447,43 @@ __device__ __forceinline__ int fast_closest_pick(const FastClosest& t, long long
         rem = r - qq * dsum;
         if (rem < 0) rem += dsum; else if (rem >= dsum) rem -= dsum;
     }
-    return rem <= t.e1 ? 0 : 1;
+    return rem;
+}
+__device__ __forceinline__ int fast_closest_pick(const FastClosest& t, long long& rng) {
+    if (t.e0 == 0) return 0;
+    // random.nextInt(32767): next(31), then the rejection loop of the non-power-of-two bound (taken with probability 1e-9)
+    int r;
+    for (;;) {
+        bool accept;
+        r = fast_nextint_fold(jr_next(rng, 31), accept);
+        if (accept) break;
+    }
+    const int dsum = (int) ((unsigned) t.e1 + (unsigned) t.e0);
+    return fast_pick_rem(r, dsum) <= t.e1 ? 0 : 1;
 }
 
 // Y_Diff(c1, c2) > thr (gt) or < thr (!gt), NQ/CIELABConvertor.java:215-227.  float32 first: each luminance is within 4e-7 of
-// its f64 value (table entries 6e-8 relative, three products, two sums, Y <= 1), the difference times 100 within 1e-4.
-__device__ __forceinline__ bool fast_ydiff_cmp(const FastLds& S, int c1, int c2, double thr, bool gt) {
+// its f64 value (table entries 6e-8 relative, three products, two sums, Y <= 1), the difference times 100 within 1e-4 (measured over
+// the colour cube against black, white and mid grey: 1.5e-5).  f64 decides within 2.2e-3 of the threshold: every pair whose exact
+// difference lies within 2e-3 of it goes there (2e-3 + 1e-4 + the rounding of thr32), which tests/test_gpu_fast_filters.py demands.
+// yd32 / f64 (self-test only): the float32 difference and whether the f64 path decided
+__device__ __forceinline__ bool fast_ydiff_cmp_x(const FastLds& S, int c1, int c2, double thr, bool gt, float& yd32, bool& f64) {
     const float* g = S.gamma32;
     const float y1 = __builtin_fmaf(g[c_blue(c1)], 0.0722f, __builtin_fmaf(g[c_green(c1)], 0.7152f, g[c_red(c1)] * 0.2126f));
     const float y2 = __builtin_fmaf(g[c_blue(c2)], 0.0722f, __builtin_fmaf(g[c_green(c2)], 0.7152f, g[c_red(c2)] * 0.2126f));
     const float yd = fabsf(y2 - y1) * 100.0f;
     const float thr32 = (float) thr;
     NQ_COUNT(FC_YDIFF, true);
-    NQ_COUNT(FC_YDIFF_F64, !(fabsf(yd - thr32) > 1e-3f));
-    if (fabsf(yd - thr32) > 1e-3f) return gt ? yd > thr32 : yd < thr32;
+    NQ_COUNT(FC_YDIFF_F64, !(fabsf(yd - thr32) > 2.2e-3f));
+    yd32 = yd;
+    f64 = !(fabsf(yd - thr32) > 2.2e-3f);
+    if (fabsf(yd - thr32) > 2.2e-3f) return gt ? yd > thr32 : yd < thr32;
     const double d = Y_Diff_y(color2Y_t(c1, S.gamma), color2Y_t(c2, S.gamma));
     return gt ? d > thr : d < thr;
+}
+__device__ __forceinline__ bool fast_ydiff_cmp(const FastLds& S, int c1, int c2, double thr, bool gt) {
+    float yd32; bool f64;
+    return fast_ydiff_cmp_x(S, c1, c2, thr, gt, yd32, f64);
 }
 
 // ditherPixel (NQ/GilbertCurve.java:125-185) for K > 32, up to its final lookup: returns the colour handed to it.
@@ -993,6 +1033,141 @@ __global__ void __launch_bounds__(256) fast_closest_tuple_kernel(DevParams P, Ce
         reinterpret_cast<int4*>(out4)[i] = make_int4(closest[0], closest[1], closest[2], closest[3]);
     }
 }
+// ------------------------------------------------------------------------------------------------
+// nq_selftest_fast: every float32 / integer filter above on its own, over inputs the host names (ranges are enumerated here, nothing of
+// 2^24 elements is uploaded).  It calls the device functions the kernels above call; modes (NQ_FAST_ST_*) and record layouts: include/nquant_abi.h.
+// ------------------------------------------------------------------------------------------------
+struct FastSelftestArgs {
+    int which;
+    long long first, n;      // range modes: elements first .. first + n - 1; explicit modes: n records behind `in`
+    long long a0, a1;        // mode's own arguments
+    const void* in;          // explicit records, or the thresholds of NQ_FAST_ST_YDIFF_RANGE
+    unsigned* out;
+};
+__device__ __forceinline__ void fast_selftest_closest(const FastLookup& X, int c, int c2, unsigned* __restrict__ o) {
+    const int cr = c_red(c), cg = c_green(c), cb = c_blue(c);
+    FastClosest t; t.c0 = t.c1 = 0; t.e0 = t.e1 = 2147483647;
+    fast_closest_step(t, 1, c2, (float) cr, (float) cg, (float) cb, cr, cg, cb, X.qa, X.qb, X.qc, X.wr, X.wg, X.wb, X.ratio);
+    float e32; bool exact;
+    (void) fast_closest_floor(2147483647, c2, (float) cr, (float) cg, (float) cb, cr, cg, cb, X.qa, X.qb, X.qc, X.wr, X.wg, X.wb, X.ratio, e32, exact);
+    o[0] = (unsigned) t.e0; o[1] = __float_as_uint(e32); o[2] = exact ? 1u : 0u;
+}
+__global__ void __launch_bounds__(256) fast_selftest_kernel(DevParams P, FastArgs F, const int* __restrict__ g_palette, FastSelftestArgs A) {
+    const FastLookupLds T = fast_stage_lookup(P, g_palette);
+    const FastLookup X = fast_lookup_ctx(P, F);
+    const FastLds& S = T.S;
+    const bool counting = A.which == NQ_FAST_ST_NEXTINT_COUNT || A.which == NQ_FAST_ST_REM_COUNT;
+    unsigned long long bad = 0ULL, first_bad = ~0ULL;
+    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < A.n; i += (long long) gridDim.x * blockDim.x) {
+        long long v = A.first + i;
+        if (A.which == NQ_FAST_ST_TANH_BITS) v = (long long) ((const unsigned*) A.in)[i];
+        if (A.which == NQ_FAST_ST_NEXTINT_LIST) v = (long long) (((const unsigned*) A.in)[i] & 0x7FFFFFFFu);
+        switch (A.which) {
+        case NQ_FAST_ST_TANH: case NQ_FAST_ST_TANH_BITS: {
+            bool library;
+            const float r = tanh_to_float_x(__uint_as_float((unsigned) v), library);
+            A.out[2 * i] = __float_as_uint(r); A.out[2 * i + 1] = library ? 1u : 0u;
+            break;
+        }
+        case NQ_FAST_ST_CLOSEST_ERR: {
+            // v = |dr| << 16 | |dg| << 8 | |db|; a0 bit 2 / 1 / 0: dr / dg / db negative (d = palette entry - colour)
+            int c = 0, c2 = 0;
+            for (int j = 0; j < 3; ++j) {
+                const int d = (int) ((v >> (8 * j)) & 0xFF);
+                if ((A.a0 >> j) & 1) c |= d << (8 * j); else c2 |= d << (8 * j);
+            }
+            fast_selftest_closest(X, (int) 0xFF000000 | c, (int) 0xFF000000 | c2, A.out + 3 * i);
+            break;
+        }
+        case NQ_FAST_ST_CLOSEST_ERR_PAIRS: {
+            const int* w = (const int*) A.in + 2 * i;
+            fast_selftest_closest(X, w[0], w[1], A.out + 3 * i);
+            break;
+        }
+        case NQ_FAST_ST_NEXTINT: case NQ_FAST_ST_NEXTINT_LIST: case NQ_FAST_ST_NEXTINT_COUNT: {
+            bool accept;
+            const int r = fast_nextint_fold((int) v, accept);
+            if (A.which != NQ_FAST_ST_NEXTINT_COUNT) A.out[i] = (unsigned) r | (accept ? 0x10000u : 0u);
+            else {
+                const long long rr = v % 32767;
+                const bool reject = v - rr + 32766 >= 2147483648LL;
+                if (rr != r || reject == accept) { ++bad; first_bad = first_bad < (unsigned long long) v ? first_bad : (unsigned long long) v; }
+            }
+            break;
+        }
+        case NQ_FAST_ST_REM: {
+            const int* w = (const int*) A.in + 2 * i;
+            A.out[i] = (unsigned) fast_pick_rem(w[0], w[1]);
+            break;
+        }
+        case NQ_FAST_ST_REM_COUNT: {
+            // v = r << 15 | dsum; the pairs 0 <= r < 32767, 1 <= dsum <= r count
+            const int r = (int) (v >> 15), dsum = (int) (v & 32767);
+            if (r < 32767 && dsum >= 1 && dsum <= r && fast_pick_rem(r, dsum) != r % dsum) {
+                ++bad; first_bad = first_bad < (unsigned long long) v ? first_bad : (unsigned long long) v;
+            }
+            break;
+        }
+        case NQ_FAST_ST_YDIFF: {
+            // record: {c1, c2, gt, 0, thr as f64}
+            const int* w = (const int*) A.in + 6 * i;
+            const double thr = *reinterpret_cast<const double*>(w + 4);
+            float yd; bool f64;
+            const bool dec = fast_ydiff_cmp_x(S, w[0], w[1], thr, w[2] != 0, yd, f64);
+            A.out[3 * i] = dec ? 1u : 0u; A.out[3 * i + 1] = __float_as_uint(yd); A.out[3 * i + 2] = f64 ? 1u : 0u;
+            break;
+        }
+        case NQ_FAST_ST_YDIFF_RANGE: {
+            // opaque colour v against the colour a0 under a1 >> 1 thresholds (<= 32), a1 & 1 = gt: decision / f64-path bit per threshold
+            const double* thr = (const double*) A.in;
+            const int nt = (int) (A.a1 >> 1);
+            float yd = 0.f;
+            unsigned decs = 0u, f64s = 0u;
+            for (int t = 0; t < nt; ++t) {
+                bool f64;
+                if (fast_ydiff_cmp_x(S, (int) 0xFF000000 | (int) v, (int) A.a0, thr[t], (A.a1 & 1) != 0, yd, f64)) decs |= 1u << t;
+                if (f64) f64s |= 1u << t;
+            }
+            A.out[3 * i] = __float_as_uint(yd); A.out[3 * i + 1] = decs; A.out[3 * i + 2] = f64s;
+            break;
+        }
+        case NQ_FAST_ST_LAB32: {
+            float L, A1, B1;
+            lab32_of((int) 0xFF000000 | (int) v, S.gamma32, L, A1, B1);
+            A.out[3 * i] = __float_as_uint(L); A.out[3 * i + 1] = __float_as_uint(A1); A.out[3 * i + 2] = __float_as_uint(B1);
+            break;
+        }
+        case NQ_FAST_ST_LAB64: {
+            const Lab l = RGB2LAB_fast((int) 0xFF000000 | (int) v, S.gamma);
+            A.out[3 * i] = __float_as_uint(l.L); A.out[3 * i + 1] = __float_as_uint(l.A); A.out[3 * i + 2] = __float_as_uint(l.B);
+            break;
+        }
+        case NQ_FAST_ST_NEAR_D32: case NQ_FAST_ST_NEAR_D32_PAIRS: {
+            const int* w = (const int*) A.in + 2 * i;
+            const int c = A.which == NQ_FAST_ST_NEAR_D32 ? ((int) 0xFF000000 | (int) v) : w[0];
+            const int k = (A.which == NQ_FAST_ST_NEAR_D32 ? (int) A.a0 : w[1]) & 255;
+            float L, A1, B1;
+            lab32_of(c, S.gamma32, L, A1, B1);
+            A.out[i] = __float_as_uint(fast_near_d32(S.lab[k], L, A1, B1));
+            break;
+        }
+        case NQ_FAST_ST_NEAR_SAFE: {
+            // record: {colour, ka | kb << 8}: fast_nearest32 over the two-entry list {ka, kb}
+            const int* w = (const int*) A.in + 2 * i;
+            uint4 na; na.x = (unsigned) w[1] & 0xFFFFu; na.y = na.z = na.w = 0u;
+            bool safe;
+            const int k1 = fast_nearest32(S, X, w[0], na, 2, 0, safe);
+            A.out[i] = (unsigned) k1 | (safe ? 0x10000u : 0u);
+            break;
+        }
+        default: break;
+        }
+    }
+    if (counting && bad) {          // out: {disagreements, first disagreeing input} as two 64-bit words (host: 0, ~0)
+        atomicAdd(reinterpret_cast<unsigned long long*>(A.out), bad);
+        atomicMin(reinterpret_cast<unsigned long long*>(A.out) + 1, first_bad);
+    }
+}
 } // namespace nq
 
 namespace nq {
@@ -1120,6 +1295,16 @@ void launch_fast_bluenoise(const DevParams& P, const ListsView& lv, const int* d
     const FastArgs F = fast_args(P, lv, d_packed, s);
     hipLaunchKernelGGL(fast_bluenoise_kernel, dim3(fast_grid((int64_t) width * height)), dim3(256), 0, s, P, to_lists_fast(lv), F, d_palette, d_pixels,
                        width, height, y_origin, weight, seed, d_index, d_argb);
+}
+
+// nq_selftest_fast: one launch of fast_selftest_kernel; qa / qb / qc from fast_args() as in every launch above
+void launch_fast_selftest(const DevParams& P, const int* d_palette, int which, const void* d_in, int64_t first, int64_t n, int64_t a0, int64_t a1,
+                          unsigned* d_out, hipStream_t s) {
+    ListsView lv; std::memset(&lv, 0, sizeof lv);
+    const FastArgs F = fast_args(P, lv, nullptr, s);
+    FastSelftestArgs A;
+    A.which = which; A.first = first; A.n = n; A.a0 = a0; A.a1 = a1; A.in = d_in; A.out = d_out;
+    hipLaunchKernelGGL(fast_selftest_kernel, dim3(fast_grid(n)), dim3(256), 0, s, P, F, d_palette, A);
 }
 
 } // namespace nq

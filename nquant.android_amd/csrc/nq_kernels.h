@@ -105,6 +105,10 @@ void launch_fast_lookup_only(const DevParams& P, const ListsView& lv, const int*
                              unsigned short* d_index, int* d_argb, unsigned* d_todo, hipStream_t s);
 void launch_fast_bluenoise(const DevParams& P, const ListsView& lv, const int* d_palette, void* d_packed, const int* d_pixels, int width, int height,
                            int y_origin, float weight, long long seed, unsigned short* d_index, int* d_argb, hipStream_t s);
+// nq_selftest_fast (include/nquant_abi.h): mode `which` (NQ_FAST_ST_*) of the dither kernel's filters over the range
+// [first, first + n) or over n explicit records at d_in; a0 / a1: the mode's own arguments; d_palette: P.K entries (null when P.K == 0)
+void launch_fast_selftest(const DevParams& P, const int* d_palette, int which, const void* d_in, int64_t first, int64_t n, int64_t a0, int64_t a1,
+                          unsigned* d_out, hipStream_t s);
 // BlueNoise.dither post-pass (NQ/BlueNoise.java:207-222); in-place on d_index, writes d_argb
 void launch_bluenoise(const DevParams& P, const int* d_palette, const ListsView& lv, const int* d_pixels, int width, int height,
                       int y_origin /* band start row in the whole image, 0 otherwise */,

@@ -19,6 +19,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 OPT_CELL_LISTS, OPT_FAST_DITHER, OPT_MERGE_WALL_SECONDS, OPT_DITHER_CHAIN = 1, 2, 3, 4
+# nq_selftest_fast modes (NQ_FAST_ST_*): name -> (code, output words per element; 0 = a counting form)
+FAST_ST = {"TANH": (0, 2), "CLOSEST_ERR": (1, 3), "CLOSEST_ERR_PAIRS": (2, 3), "NEXTINT": (3, 1), "NEXTINT_COUNT": (4, 0), "REM": (5, 1),
+           "REM_COUNT": (6, 0), "YDIFF": (7, 3), "YDIFF_RANGE": (8, 3), "LAB32": (9, 3), "LAB64": (10, 3), "NEAR_D32": (11, 1),
+           "NEAR_D32_PAIRS": (12, 1), "TANH_BITS": (13, 2), "NEXTINT_LIST": (14, 1),
+           "NEAR_SAFE": (15, 1)}
+YDIFF_RECORD = np.dtype([("c1", np.int32), ("c2", np.int32), ("gt", np.int32), ("pad", np.int32), ("thr", np.float64)])
 
 
 class NqError(RuntimeError):
@@ -78,6 +84,7 @@ _ABI = {
     "nq_get_device_bytes": (_i32, [_pi64]),
     "nq_set_band": (_i32, [_vp, _i32, _i32]),
     "nq_selftest_ciede": (_i32, [_vp, _vp, _i64, _vp]),
+    "nq_selftest_fast": (_i32, [_vp, _i32, _vp, _i64, _vp]),
     "nq_gilbert_dither": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, C.c_double, _i32, _i64, _i32, _vp, _vp]),
     "nq_bluenoise_dither": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, C.c_float, _i64, _i32, _vp]),
     "nq_band_color_presence_device": (_i32, [_vp, _vp, _i64, _vp, _i32, _pi64, _vp]),
@@ -388,6 +395,26 @@ class PnnQuantizer:
         self._check(self._L.nq_selftest_ciede(self._h, a.ctypes.data, a.shape[0], out.ctypes.data))
         self.ciede_quad_identical = (out[:, 8] >> 1) & 1     # the quad-parallel pass (merge loop) gave the same floats and flag
         return out[:, 0:4], out[:, 4:8], out[:, 8] & 1
+
+    def selftest_fast(self, mode, first=None, count=None, a0=0, thresholds=None, gt=False, records=None):
+        """One filter of the specialised dither kernel on its own (nq_selftest_fast).  Range modes: first, count (+ a0; YDIFF_RANGE: up to
+        32 float64 thresholds and gt); explicit modes: records (int32 (n, 2); TANH_BITS uint32 (n,); NEXTINT_LIST int32 (n,); YDIFF: YDIFF_RECORD).  Returns the (n, words) uint32 output, or
+        (disagreements, first disagreeing input or None) for the counting forms."""
+        which, words = FAST_ST[mode]
+        if records is None:
+            thr = np.zeros(0) if thresholds is None else np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+            a1 = (thr.size << 1 | int(bool(gt))) if mode == "YDIFF_RANGE" else 0
+            src = np.concatenate([np.array([first, count, a0, a1], np.int64), thr.view(np.int64)])
+            n = int(count)
+        else:
+            src = np.ascontiguousarray(records, YDIFF_RECORD if mode == "YDIFF" else np.uint32 if mode == "TANH_BITS" else np.int32)
+            n = src.shape[0]
+        out = np.zeros((n, words) if words else 4, np.uint32)
+        self._check(self._L.nq_selftest_fast(self._h, which, src.ctypes.data, n, out.ctypes.data))
+        if words:
+            return out
+        bad, where = (int(v) for v in out.view(np.uint64))
+        return bad, (None if where == 2 ** 64 - 1 else where)
 
     def nearestColorIndex(self, palette, colors):
         """short nearestColorIndex(palette, c, pos) on a cache miss, vectorised over `colors`."""

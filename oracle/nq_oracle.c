@@ -83,10 +83,14 @@ typedef struct { float alpha, A, B, L; } Lab;   /* NQ/CIELABConvertor.java:51-56
  * androidx.appcompat:appcompat:1.4.0-alpha03, nQuant.master/build.gradle:36) -- published algorithm restated:
  * RGBToXYZ (sRGB companding, D65 matrix x100) then XYZToLAB (white 95.047/100/108.883, eps .008856, kappa 903.3,
  * pivot by Math.pow(c, 1/3.0)).  Call site NQ/CIELABConvertor.java:58-69. */
-static double srgb_to_linear(int ch) {
+static double srgb_to_linear_eval(int ch) {
     double s = ch / 255.0;
     return s < 0.04045 ? s / 12.92 : pow((s + 0.055) / 1.055, 2.4);
 }
+/* both companding functions take a channel 0..255: their 256 values are evaluated once, when the library is loaded (the array
+ * exports below walk the whole colour cube) */
+static double g_srgb_to_linear[256], g_gamma_to_linear[256];
+static double srgb_to_linear(int ch) { return g_srgb_to_linear[ch]; }
 static double pivot_xyz(double c) { return c > 0.008856 ? pow(c, 1 / 3.0) : (903.3 * c + 16) / 116; }
 static Lab RGB2LAB(int32_t c1) {
     double sr = srgb_to_linear(c_red(c1)), sg = srgb_to_linear(c_green(c1)), sb = srgb_to_linear(c_blue(c1));
@@ -101,11 +105,17 @@ static Lab RGB2LAB(int32_t c1) {
     return lab;
 }
 void nqo_rgb2lab(int32_t c, float* o) { Lab l = RGB2LAB(c); o[0] = l.alpha; o[1] = l.L; o[2] = l.A; o[3] = l.B; }
+/* array form: out4[4 i + 0..3] = alpha, L, A, B of colors[i] */
+void nqo_rgb2lab_n(const int32_t* colors, int64_t n, float* out4) { for (int64_t i = 0; i < n; ++i) nqo_rgb2lab(colors[i], out4 + 4 * i); }
 
 /* NQ/CIELABConvertor.java:71-75 */
-static double gammaToLinear(int channel) {
+static double gammaToLinear_eval(int channel) {
     const double c = channel / 255.0;
     return c < 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4);
+}
+static double gammaToLinear(int channel) { return g_gamma_to_linear[channel]; }
+__attribute__((constructor)) static void init_companding_tables(void) {
+    for (int ch = 0; ch < 256; ++ch) { g_srgb_to_linear[ch] = srgb_to_linear_eval(ch); g_gamma_to_linear[ch] = gammaToLinear_eval(ch); }
 }
 
 /* ColorUtils.LABToColor = LABToXYZ + XYZToColor (published algorithm restated); NQ/CIELABConvertor.java:77-80.
@@ -258,6 +268,8 @@ static double color2U(int32_t c) { return -0.09991 * c_red(c) - 0.33609 * c_gree
 static double U_Diff(int32_t c1, int32_t c2) { return fabs(color2U(c2) - color2U(c1)); }
 double nqo_y_diff(int32_t c1, int32_t c2) { return Y_Diff(c1, c2); }
 double nqo_u_diff(int32_t c1, int32_t c2) { return U_Diff(c1, c2); }
+/* array form: out[i] = Y_Diff(c1[i], c2[i]) */
+void nqo_y_diff_n(const int32_t* c1, const int32_t* c2, int64_t n, double* out) { for (int64_t i = 0; i < n; ++i) out[i] = Y_Diff(c1[i], c2[i]); }
 
 /* NQ/BlueNoise.java:180-197 */
 static int32_t blue_diffuse(int32_t pixel, int32_t qPixel, float weight, float strength, int x, int y) {
@@ -1044,6 +1056,31 @@ static int16_t nearest_lab(nqo_quantizer* q, const int32_t* palette, int K, int3
 static int64_t g_dbg[16];
 void nqo_debug_counters(int64_t* out16, int reset) { if (out16) memcpy(out16, g_dbg, sizeof g_dbg); if (reset) memset(g_dbg, 0, sizeof g_dbg); }
 
+/* err of one palette entry c2 for the colour c, NQ/PnnLABQuantizer.java:421-445: the statement sequence with its gates.  A gate that
+ * fires (err >= limit = closest[3]) returns the partial sum, which neither branch of the caller then takes. */
+static double closest_lab_err(double PR, double PG, double PB, double PA, double ratio, int hasSemiTransparency, int32_t c2, int32_t c, double limit) {
+    double err = PR * (1 - ratio) * sqr(c_red(c2) - c_red(c));
+    if (err >= limit) return err;
+    err += PG * (1 - ratio) * sqr(c_green(c2) - c_green(c));
+    if (err >= limit) return err;
+    err += PB * (1 - ratio) * sqr(c_blue(c2) - c_blue(c));
+    if (err >= limit) return err;
+    if (hasSemiTransparency) err += PA * sqr(c_alpha(c2) - c_alpha(c));
+    for (int i = 0; i < 3; ++i) {
+        err += ratio * sqr(coeffs[i][0] * (c_red(c2) - c_red(c)));
+        if (err >= limit) break;
+        err += ratio * sqr(coeffs[i][1] * (c_green(c2) - c_green(c)));
+        if (err >= limit) break;
+        err += ratio * sqr(coeffs[i][2] * (c_blue(c2) - c_blue(c)));
+        if (err >= limit) break;
+    }
+    return err;
+}
+/* array form, no semi-transparency, no gate (limit = +inf): out[i] = the full err of the pair {colour, palette entry} = pairs[2 i], pairs[2 i + 1] */
+void nqo_closest_err_n(double PR, double PG, double PB, double ratio, const int32_t* pairs, int64_t n, double* out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = closest_lab_err(PR, PG, PB, 0, ratio, 0, pairs[2 * i + 1], pairs[2 * i], INFINITY);
+}
+
 /* NQ/PnnLABQuantizer.java:407-474 */
 static int16_t closest_lab(nqo_quantizer* q, const int32_t* palette, int K, int32_t c, int pos, int32_t* out4, int64_t* rng) {
     if (c_alpha(c) <= q->alphaThreshold) { if (out4) out4[0] = out4[1] = out4[2] = out4[3] = -1; return nearest_lab(q, palette, K, c, pos); }
@@ -1057,21 +1094,7 @@ static int16_t closest_lab(nqo_quantizer* q, const int32_t* palette, int K, int3
         const double PR = q->PR, PG = q->PG, PB = q->PB, PA = q->PA, ratio = q->ratio;
         for (int16_t k = 0; k < K; ++k) {
             int32_t c2 = palette[k];
-            double err = PR * (1 - ratio) * sqr(c_red(c2) - c_red(c));
-            if (err >= closest[3]) continue;
-            err += PG * (1 - ratio) * sqr(c_green(c2) - c_green(c));
-            if (err >= closest[3]) continue;
-            err += PB * (1 - ratio) * sqr(c_blue(c2) - c_blue(c));
-            if (err >= closest[3]) continue;
-            if (q->hasSemiTransparency) err += PA * sqr(c_alpha(c2) - c_alpha(c));
-            for (int i = 0; i < 3; ++i) {
-                err += ratio * sqr(coeffs[i][0] * (c_red(c2) - c_red(c)));
-                if (err >= closest[3]) break;
-                err += ratio * sqr(coeffs[i][1] * (c_green(c2) - c_green(c)));
-                if (err >= closest[3]) break;
-                err += ratio * sqr(coeffs[i][2] * (c_blue(c2) - c_blue(c)));
-                if (err >= closest[3]) break;
-            }
+            const double err = closest_lab_err(PR, PG, PB, PA, ratio, q->hasSemiTransparency, c2, c, closest[3]);
             if (err < closest[2]) {
                 closest[1] = closest[0]; closest[3] = closest[2];
                 closest[0] = k; closest[2] = j_d2i(err);
@@ -1327,6 +1350,9 @@ static int ditherPixel(GilbertCurve* g, int x, int y, int32_t c2, float beta) {
 }
 
 /* :187-280 */
+/* (float) Math.tanh((double) x), NQ/GilbertCurve.java:246 */
+static float limiter_tanh(float x) { return (float) tanh((double) x); }
+void nqo_limiter_tanh_n(const float* x, int64_t n, float* out) { for (int64_t i = 0; i < n; ++i) out[i] = limiter_tanh(x[i]); }
 static void diffusePixel(GilbertCurve* g, int x, int y) {
     const int bidx = x + y * g->width;
     const int32_t pixel = g->pixels[bidx];
@@ -1398,7 +1424,7 @@ static void diffusePixel(GilbertCurve* g, int x, int y) {
         if (fabsf(error.p[j]) >= g->ditherMax) {
             if (g->sortedByYDiff && sal != NULL) unaccepted = 1;
             if (diffuse)
-                error.p[j] = (float) tanh((double) (error.p[j] / maxErr * 20)) * (g->ditherMax - 1);
+                error.p[j] = limiter_tanh(error.p[j] / maxErr * 20) * (g->ditherMax - 1);
             else if (illusion)
                 error.p[j] = (float) ((double) (error.p[j] / maxErr) * error.yDiff) * (g->ditherMax - 1);
             else

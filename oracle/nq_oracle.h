@@ -101,6 +101,12 @@ int32_t nqo_lab2rgb(float alpha, float L, float A, float B);     /* :77-80 + Col
 float   nqo_ciede2000(const float* lab1_L_A_B, const float* lab2_L_A_B); /* :201-213 (squared deltaE00) */
 void    nqo_ciede_terms(const float* pairs6, int64_t n, float* out4);   /* L', C', H', R_T per pair, as find_nn obtains them (:93-110 of PnnLABQuantizer) */
 double  nqo_y_diff(int32_t c1, int32_t c2);                      /* :215-227 */
+/* array forms of single statements of the dither pass, each through the same static function the pass itself uses */
+void    nqo_y_diff_n(const int32_t* c1, const int32_t* c2, int64_t n, double* out);
+void    nqo_rgb2lab_n(const int32_t* colors, int64_t n, float* out_alpha_L_A_B);       /* four floats per colour */
+void    nqo_limiter_tanh_n(const float* x, int64_t n, float* out);                    /* (float) Math.tanh((double) x), NQ/GilbertCurve.java:246 */
+/* err of closestColorIndex (NQ/PnnLABQuantizer.java:421-445, no semi-transparency, no gate) per pair {colour, palette entry} */
+void    nqo_closest_err_n(double PR, double PG, double PB, double ratio, const int32_t* pairs, int64_t n, double* out);
 double  nqo_u_diff(int32_t c1, int32_t c2);                      /* :229-238 */
 int32_t nqo_blue_diffuse(int32_t pixel, int32_t qPixel, float weight, float strength, int x, int y); /* NQ/BlueNoise.java:180-197 */
 int8_t  nqo_blue_noise(int i);                                   /* TELL_BLUE_NOISE[i & 4095] */

@@ -68,6 +68,14 @@ def lib():
     L.nqo_debug_virtual_merge.restype = None
     L.nqo_y_diff.restype = C.c_double
     L.nqo_y_diff.argtypes = [C.c_int32, C.c_int32]
+    L.nqo_y_diff_n.restype = None
+    L.nqo_y_diff_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.nqo_rgb2lab_n.restype = None
+    L.nqo_rgb2lab_n.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.nqo_limiter_tanh_n.restype = None
+    L.nqo_limiter_tanh_n.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.nqo_closest_err_n.restype = None
+    L.nqo_closest_err_n.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]
     L.nqo_u_diff.restype = C.c_double
     L.nqo_u_diff.argtypes = [C.c_int32, C.c_int32]
     L.nqo_blue_diffuse.restype = C.c_int32
@@ -246,3 +254,35 @@ def ciede2000_sq(lab1, lab2):
     a = (C.c_float * 3)(*lab1)
     b = (C.c_float * 3)(*lab2)
     return lib().nqo_ciede2000(a, b)
+
+
+def limiter_tanh_n(x):
+    """(float) Math.tanh((double) x) of every float32 in x (the limiter statement of the oracle's dither pass)."""
+    a = np.ascontiguousarray(x, np.float32).ravel()
+    out = np.empty(a.size, np.float32)
+    lib().nqo_limiter_tanh_n(a.ctypes.data, a.size, out.ctypes.data)
+    return out
+
+
+def closest_err_n(PR, PG, PB, ratio, pairs):
+    """f64 err of closestColorIndex for (n, 2) int32 pairs {colour, palette entry}."""
+    a = _i32(pairs).reshape(-1, 2)
+    out = np.empty(a.shape[0], np.float64)
+    lib().nqo_closest_err_n(float(PR), float(PG), float(PB), float(ratio), a.ctypes.data, a.shape[0], out.ctypes.data)
+    return out
+
+
+def y_diff_n(c1, c2):
+    a, b = _i32(c1).ravel(), _i32(c2).ravel()
+    assert a.size == b.size
+    out = np.empty(a.size, np.float64)
+    lib().nqo_y_diff_n(a.ctypes.data, b.ctypes.data, a.size, out.ctypes.data)
+    return out
+
+
+def rgb2lab_n(colors):
+    """(n, 4) float32 {alpha, L, A, B} of every colour."""
+    a = _i32(colors).ravel()
+    out = np.empty((a.size, 4), np.float32)
+    lib().nqo_rgb2lab_n(a.ctypes.data, a.size, out.ctypes.data)
+    return out

@@ -16,7 +16,7 @@ from conftest import ROOT
 GETTERS_AND_SETTERS = {
     "nq_create", "nq_destroy", "nq_last_error", "nq_get_params", "nq_set_params", "nq_set_stream", "nq_set_tile", "nq_set_option", "nq_set_band",
     "nq_get_stage_ms", "nq_get_merge_stats", "nq_get_team_stats", "nq_get_merge_variant", "nq_get_batch_phase_ms", "nq_get_dither_path",
-    "nq_get_list_counts", "nq_selftest_ciede",
+    "nq_get_list_counts", "nq_selftest_ciede", "nq_selftest_fast",
 }
 # ops with no twin of the other form, each for its reason
 DEVICE_ONLY = {
