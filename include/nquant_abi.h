@@ -941,6 +941,62 @@ int nq_compare_frames(int device, int n, const uint32_t* const* src, const uint3
 int nq_compare_indexed(int device, int n, const uint32_t* const* src, const uint16_t* const* index, const uint32_t* palette, int K,
                        const int32_t* widths, const int32_t* heights, int flags, int64_t* result);
 
+/* ---- WebP encoding: n index maps of one size over one palette to ONE lossless WebP file (VP8L): a still image for n = 1, an
+ *      animation whose frames store only what changed for n > 1, with all 8 bits of the palette's alpha.  All n frames are width x height
+ *      uint16 index maps over the K <= 256 ARGB entries of `palette` (what nq_convert_frames returns).  The calls take no handle: a
+ *      device ordinal and, in the device form, a stream, like the quality measurement above.
+ *  * n = 1: `RIFF` size `WEBP`, one `VP8L` chunk, padded to even.  out_rects = {0, 0, width, height}.
+ *  * n > 1: `RIFF` size `WEBP`; `VP8X` (flags 0x02 = animation, | 0x10 when any palette alpha != 255; three zero bytes; width - 1 and
+ *    height - 1 as 24 bits, little-endian like every number of the container); `ANIM` (background 0, loop_count as 16 bits, 0 = for
+ *    ever); n `ANMF` chunks: x / 2, y / 2, w - 1, h - 1 of the rectangle as 24 bits each, the duration 10 * delays_cs[i] ms (NULL: 0)
+ *    as 24 bits, the flags byte 0x02 (do not blend, dispose none), then the rectangle's `VP8L` chunk.
+ *  * Rectangle: frame 0 whole.  delta = 0: every frame whole.  delta = 1: frame i >= 1 is the bounding box of the pixels with
+ *    index_i != index_(i-1), its left and top rounded DOWN to even (the container stores them halved); 1 x 1 at (0, 0) when nothing
+ *    differs.  The rectangle holds frame i's own indices and replaces what was there whatever the alpha is: no mark index, no mode.
+ *    It is read in place from the frame's map.  n = 1 ignores delta.
+ *  * A VP8L chunk (bits go into bytes least significant first; prefix codes are canonical and go most significant bit first):
+ *    byte 0x2f; 14 bits w - 1; 14 bits h - 1; 1 bit "alpha used" (any palette alpha != 255); 3 bits 0.  One transform: bit 1, type 3
+ *    (colour indexing), 8 bits K - 1, the colour table as a K x 1 image (cache bit 0, five prefix codes, K pixels: each entry the
+ *    per-channel difference to the entry before it mod 256, coded green, red, blue, alpha; all literals); bit 0.  Indices are
+ *    bundled 8 / 4 / 2 / 1 per packed pixel at K <= 2 / <= 4 / <= 16 / more, index x in bits (x mod per) * (8 / per) of packed pixel
+ *    x / per (LOW bits first); pw = ceil(w / per).  Main image: cache bit 0; with more than one band the bit 1, 3 bits p - 2 and the
+ *    entropy image (cache bit 0, five codes, ceil(pw / 2^p) x ceil(h / 2^p) pixels, pixel (x, y) = group y: green y & 255, red
+ *    y >> 8; per row a literal and, when wider than 1, one copy of length ew - 1 at distance 1), else the bit 0; then five prefix
+ *    codes per group, group after group; then all pixels.
+ *  * Bands: a band is 2^p packed rows and one chain: it sees only its own packed pixels, has its own five codes and is encoded by
+ *    one wavefront.  band_bits = 0 selects the largest p in 2..9 with pw * 2^p <= 32768 (per rectangle); an explicit 2..9 must
+ *    satisfy that for the whole frame.  A frame with pw * 4 > 32768 (wider than 8192 packed pixels, larger than anything this
+ *    project measures) is refused.
+ *  * A band's tokens are those of nq_encode_png's chains on the band's packed pixels (greedy, hash of 3, matches 3..258).  A literal
+ *    is the green code of the packed pixel (red, blue and alpha are one-symbol codes: 0 bits).  A copy is green symbol 256 +
+ *    prefix(length), its extra bits, the distance symbol prefix(distance + 120), its extra bits -- distance + 120 steps over the 120
+ *    codes of the format's 2-D neighbourhood map.  A code with at most one used symbol is written in the simple form and costs
+ *    no bits in the data; every other code in the normal form with all its lengths (runs through the symbols 16, 17, 18).  Lengths
+ *    are limited to 15 by nq_encode_png's rule.
+ *  * nq_webp_max_bytes: an upper bound of the file size for any content and any K (pure arithmetic, no device): 44 bytes, and per
+ *    frame 33 bytes + ceil(bits / 8), bits = 30400 (header, transform, colour table) + [more than one band: 7700 + 64 per band]
+ *    + 4640 per band + 15 per packed pixel, the largest over the four bundlings the geometry allows.  Derived in DESIGN.md.
+ *  * out_rects (NULL: not wanted): 4 ints per frame, x, y, w, h of its rectangle, written on success.
+ *  * nq_encode_webp_device: index maps in DEVICE memory of `device` (2-byte aligned pointers suffice; never written), d_index itself
+ *    and everything else on the host.  The call works on hip_stream (NULL = the default stream), allocates its scratch, frees it
+ *    before it returns, and returns when `out` holds the file: nq_get_device_bytes is the same before and after.
+ *    nq_encode_webp: the same with index maps in HOST memory (they are uploaded first).
+ *  * Errors: status as elsewhere; the text is the thread's handle-free one, nq_last_error(NULL).  NQ_ERR_INVALID before any device
+ *    work (*out_size, out and out_rects stay untouched): n outside 1..65535, a side outside 1..16384, K outside 1..256, a delay or
+ *    loop_count outside 0..65535, delta not 0 / 1, band_bits not 0 / 2..9 or too large for the width, a NULL or odd index pointer, a
+ *    NULL table, palette or out_size, out NULL with cap > 0, cap < 0, a negative device.  Then NQ_ERR_NO_DEVICE (no usable device; a
+ *    device ordinal past the last one is NQ_ERR_INVALID) or NQ_ERR_HIP.  After the encoding, NQ_ERR_INVALID: an index >= K anywhere
+ *    in any frame (delta mode: also outside the rectangle), or cap smaller than the file (then *out_size holds the size and `out`
+ *    is untouched).
+ *  There is no Java method for this stage.  The bit-exact definition, the bound and the kernels: DESIGN.md "WebP encoder". ---- */
+int nq_webp_max_bytes(int n, int width, int height, int band_bits, int64_t* out_bytes);
+int nq_encode_webp_device(int device, void* hip_stream, int n, const uint16_t* const* d_index, int width, int height,
+                          const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int band_bits, int delta,
+                          uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
+int nq_encode_webp(int device, int n, const uint16_t* const* index, int width, int height,
+                   const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int band_bits, int delta,
+                   uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

@@ -21,6 +21,7 @@ from .ordered import convert_frames_ordered, dither_ordered, dither_ordered_devi
 from .yuv import frames_from_yuv, frames_from_yuv_device, resample_frames_yuv, resample_frames_yuv_device, yuv_planes
 from .orient import orient_frames, orient_frames_device, orientation, oriented_size, source_rect
 from .compare import Quality, choose_colors, compare_frames, compare_frames_device, compare_indexed, compare_indexed_device
+from .webp import convert_frames_to_webp, convert_to_webp, encode_webp, encode_webp_device, webp_max_bytes, write_webp
 from .build import build as build_library
 
 __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARALLEL_TILED", "MODE_LOOKUP_ONLY",
@@ -36,4 +37,5 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "dither_ordered", "dither_ordered_device", "convert_frames_ordered", "frames_from_yuv", "frames_from_yuv_device",
            "resample_frames_yuv", "resample_frames_yuv_device", "yuv_planes", "orient_frames", "orient_frames_device", "orientation",
            "oriented_size", "source_rect", "Quality", "choose_colors", "compare_frames", "compare_frames_device", "compare_indexed",
-           "compare_indexed_device"]
+           "compare_indexed_device", "webp_max_bytes", "encode_webp", "encode_webp_device", "write_webp", "convert_to_webp",
+           "convert_frames_to_webp"]

@@ -23,7 +23,8 @@ UNITS = {
     "nq_dither_fast.hip": ("device", ["nq_dither_fast.hip", "nq_device.h", "nq_kernels.h", os.path.join(INC, "nq_blue_noise_64x64.inc"),
                                       os.path.join(INC, "nquant_abi.h")]),
     "nq_gif.hip": ("device", ["nq_gif.hip", "nq_kernels.h"]),
-    "nq_png.hip": ("device", ["nq_png.hip", "nq_kernels.h"]),
+    "nq_png.hip": ("device", ["nq_png.hip", "nq_lz.inc", "nq_kernels.h"]),
+    "nq_webp.hip": ("device", ["nq_webp.hip", "nq_lz.inc", "nq_kernels.h"]),
     "nq_hold.hip": ("device", ["nq_hold.hip", "nq_kernels.h"]),
     "nq_shots.hip": ("device", ["nq_shots.hip", "nq_kernels.h"]),
     "nq_refine.hip": ("device", ["nq_refine.hip", "nq_kernels.h"]),

@@ -4308,3 +4308,481 @@ int nq_compare_indexed(int device, int n, const uint32_t* const* src, const uint
 }
 
 } // extern "C"
+
+// ---- WebP encoding (nq_webp.hip; include/nquant_abi.h "WebP encoding"): stateless calls like the quality measurement -- no handle, the
+// error text goes to the thread's handle-free string; all scratch lives for the call only ----
+namespace {
+
+constexpr int kWebpMaxChain = 32768, kWebpGreen = 280, kWebpDist = 40;
+// the bound's ingredients (DESIGN.md "WebP encoder"): the five code headers of a band; header, transform, colour table and the fixed
+// bits of the main image; the entropy image's codes and one of its rows
+constexpr long long kWebpHeadBits = 4640, kWebpTableBits = 30400, kWebpEntropyBits = 7700, kWebpEntropyRowBits = 64;
+// RIFF header, VP8X, ANIM | ANMF header, VP8L header
+constexpr long long kWebpFileLead = 12 + 18 + 14, kWebpFrameLead = 24 + 8;
+const int kWebpClOrderHost[19] = {17, 18, 0, 1, 2, 3, 4, 5, 16, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15};
+
+inline int webp_per(int K) { return K <= 2 ? 8 : K <= 4 ? 4 : K <= 16 ? 2 : 1; }
+// p: a band is 2^p packed rows; 0: none fits a chain at this packed width
+inline int webp_band_bits(int pw, int band_bits) {
+    if (band_bits) return ((long long) pw << band_bits) <= kWebpMaxChain ? band_bits : 0;
+    for (int p = 9; p >= 2; --p)
+        if (((long long) pw << p) <= kWebpMaxChain) return p;
+    return 0;
+}
+// most bytes of one frame's ANMF header and VP8L chunk, over every bundling the geometry allows; 0: it allows none
+long long webp_frame_max(int w, int h, int band_bits) {
+    long long worst = 0;
+    for (int per = 1; per <= 8; per *= 2) {
+        const int pw = (w + per - 1) / per, p = webp_band_bits(pw, band_bits);
+        if (!p) continue;
+        const long long nb = (h + (1 << p) - 1) >> p;
+        const long long bits = kWebpTableBits + (nb > 1 ? kWebpEntropyBits + kWebpEntropyRowBits * nb : 0) + nb * kWebpHeadBits + 15ll * pw * h;
+        worst = std::max(worst, (bits + 7) / 8);
+    }
+    return worst ? kWebpFrameLead + worst + 1 : 0;
+}
+
+// the arguments nq_webp_max_bytes takes; false + the reason otherwise
+bool webp_check_shape(int n, int width, int height, int band_bits, char* why, size_t len) {
+    if (n < 1 || n > 65535) { std::snprintf(why, len, "n = %d: 1..65535 frames", n); return false; }
+    if (width < 1 || width > 16384 || height < 1 || height > 16384) {
+        std::snprintf(why, len, "%d x %d: sides must be 1..16384", width, height); return false;
+    }
+    if (band_bits != 0 && (band_bits < 2 || band_bits > 9)) { std::snprintf(why, len, "band_bits = %d: must be 0 or 2..9", band_bits); return false; }
+    if (!webp_frame_max(width, height, band_bits)) {
+        std::snprintf(why, len, "width %d at band_bits = %d: no band of 2^p packed rows fits a chain of %d packed pixels", width, band_bits, kWebpMaxChain);
+        return false;
+    }
+    return true;
+}
+
+// a bit string, first bit in bit 0 of word 0
+struct WebpBits {
+    std::vector<uint32_t> w;
+    long long nb = 0;
+    void put(uint32_t v, int b) {                    // b <= 32
+        for (int done = 0; done < b;) {
+            const int sh = (int) (nb & 31);
+            if (!sh) w.push_back(0);
+            const int take = std::min(32 - sh, b - done);
+            w.back() |= (uint32_t) (((uint64_t) (v >> done) & ((1ull << take) - 1)) << sh);
+            nb += take; done += take;
+        }
+    }
+    void append(const WebpBits& o) {
+        for (long long i = 0; i < o.nb; i += 32) put(o.w[(size_t) (i >> 5)], (int) std::min<long long>(32, o.nb - i));
+    }
+};
+
+// build_code of nq_lz.inc on the host: lengths <= limit and the canonical codes, bit-reversed
+void webp_build_code(const std::vector<unsigned>& freq, int limit, std::vector<int>& lens, std::vector<unsigned>& codes) {
+    const int nsym = (int) freq.size();
+    std::vector<std::pair<unsigned, int>> used;
+    for (int s = 0; s < nsym; ++s)
+        if (freq[s]) used.push_back({freq[s], s});
+    std::sort(used.begin(), used.end());
+    const int n = (int) used.size();
+    lens.assign(nsym, 0);
+    if (n <= 1) lens[n ? used[0].second : 0] = 1;
+    else {
+        std::vector<unsigned long long> W(2 * n - 1, 0);
+        std::vector<int> parent(2 * n - 1, 0), depth(2 * n - 1, 0), cnt(limit + 1, 0);
+        for (int i = 0; i < n; ++i) W[i] = used[i].first;
+        int i = 0, j = n;
+        for (int k = n; k < 2 * n - 1; ++k)
+            for (int r = 0; r < 2; ++r) {
+                int t;
+                if (i < n && (j >= k || W[i] <= W[j])) t = i++; else t = j++;
+                W[k] += W[t];
+                parent[t] = k;
+            }
+        for (int t = 2 * n - 3; t >= 0; --t) {
+            depth[t] = depth[parent[t]] + 1;
+            if (t < n) cnt[std::min(depth[t], limit)]++;
+        }
+        unsigned long long total = 0;
+        for (int l = 1; l <= limit; ++l) total += (unsigned long long) cnt[l] << (limit - l);
+        for (; total > (1ull << limit); --total) {
+            cnt[limit]--;
+            int l = limit - 1;
+            while (l > 1 && cnt[l] == 0) --l;
+            cnt[l]--;
+            cnt[l + 1] += 2;
+        }
+        int t = 0;
+        for (int l = limit; l >= 1; --l)
+            for (int c = cnt[l]; c > 0 && t < n; --c) lens[used[t++].second] = l;
+    }
+    std::vector<unsigned> count(limit + 2, 0), next(limit + 2, 0);
+    for (int s = 0; s < nsym; ++s) count[lens[s]]++;
+    count[0] = 0;
+    unsigned code = 0;
+    for (int l = 1; l <= limit; ++l) {
+        code = (code + count[l - 1]) << 1;
+        next[l] = code;
+    }
+    codes.assign(nsym, 0);
+    for (int s = 0; s < nsym; ++s) {
+        const int l = lens[s];
+        if (!l) continue;
+        unsigned c = next[l]++, rev = 0;
+        for (int b = 0; b < l; ++b) rev |= ((c >> b) & 1u) << (l - 1 - b);
+        codes[s] = rev;
+    }
+}
+
+struct WebpCode {
+    std::vector<int> len;
+    std::vector<unsigned> code;
+    void put(WebpBits& o, int s) const { o.put(code[s], len[s]); }
+};
+
+// emit_code of nq_webp.hip on the host: the prefix code of the symbols counted in freq, written to o
+WebpCode webp_put_code(WebpBits& o, const std::vector<unsigned>& freq) {
+    const int nsym = (int) freq.size();
+    WebpCode c;
+    int used = 0, only = 0;
+    for (int s = nsym - 1; s >= 0; --s)
+        if (freq[s]) { ++used; only = s; }
+    if (used <= 1) {                                 // the simple form; the symbol costs no bits
+        o.put(1, 1); o.put(0, 1);
+        if (only < 2) { o.put(0, 1); o.put((uint32_t) only, 1); }
+        else { o.put(1, 1); o.put((uint32_t) only & 255u, 8); }
+        c.len.assign(nsym, 0); c.code.assign(nsym, 0);
+        return c;
+    }
+    webp_build_code(freq, 15, c.len, c.code);
+    std::vector<std::pair<int, int>> cls;            // code-length symbol, extra value
+    std::vector<unsigned> cf(19, 0);
+    auto put = [&](int sym, int extra) { cls.push_back({sym, extra}); cf[sym]++; };
+    for (int i = 0; i < nsym;) {
+        const int v = c.len[i];
+        int r = 1;
+        while (i + r < nsym && c.len[i + r] == v) ++r;
+        i += r;
+        if (v == 0) {
+            while (r >= 11) { const int k = std::min(r, 138); put(18, k - 11); r -= k; }
+            if (r >= 3) { put(17, r - 3); r = 0; }
+        } else {
+            put(v, 0); --r;
+            while (r >= 3) { const int k = std::min(r, 6); put(16, k - 3); r -= k; }
+        }
+        for (; r > 0; --r) put(v, 0);
+    }
+    std::vector<int> cl;
+    std::vector<unsigned> cc;
+    webp_build_code(cf, 7, cl, cc);
+    int ncl = 19;
+    while (ncl > 4 && cl[kWebpClOrderHost[ncl - 1]] == 0) --ncl;
+    o.put(0, 1); o.put((uint32_t) (ncl - 4), 4);
+    for (int i = 0; i < ncl; ++i) o.put((uint32_t) cl[kWebpClOrderHost[i]], 3);
+    o.put(0, 1);                                     // all lengths follow
+    for (const auto& e : cls) {
+        o.put(cc[e.first], cl[e.first]);
+        o.put((uint32_t) e.second, e.first == 16 ? 2 : e.first == 17 ? 3 : e.first == 18 ? 7 : 0);
+    }
+    return c;
+}
+
+WebpCode webp_put_single(WebpBits& o, int symbol) {
+    std::vector<unsigned> f(256, 0);
+    f[symbol] = 1;
+    return webp_put_code(o, f);
+}
+
+// {prefix symbol, extra bits, extra value} of a length or distance code v >= 1
+inline void webp_prefix(unsigned v, int& sym, int& eb, unsigned& ev) {
+    const unsigned d = v - 1;
+    if (d < 4) { sym = (int) d; eb = 0; ev = 0; return; }
+    int hb = 31;
+    while (!((d >> hb) & 1u)) --hb;
+    eb = hb - 1;
+    sym = 2 * hb + (int) ((d >> eb) & 1u);
+    ev = d & ((1u << eb) - 1u);
+}
+
+// the colour-indexing transform with its table: a K x 1 image of per-channel differences, all literals
+void webp_color_table(WebpBits& o, const uint32_t* pal, int K) {
+    static const int shift[4] = {8, 16, 0, 24};      // a pixel is coded green, red, blue, alpha
+    std::vector<unsigned> f[4] = {std::vector<unsigned>(kWebpGreen, 0), std::vector<unsigned>(256, 0), std::vector<unsigned>(256, 0),
+                                  std::vector<unsigned>(256, 0)};
+    std::vector<uint8_t> px(4 * (size_t) K);
+    for (int k = 0; k < K; ++k)
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t prev = k ? pal[k - 1] : 0u;
+            px[4 * (size_t) k + c] = (uint8_t) (((pal[k] >> shift[c]) & 255u) - ((prev >> shift[c]) & 255u));
+            f[c][px[4 * (size_t) k + c]]++;
+        }
+    o.put(1, 1); o.put(3, 2); o.put((uint32_t) (K - 1), 8);
+    o.put(0, 1);                                     // no colour cache
+    WebpCode code[4];
+    for (int c = 0; c < 4; ++c) code[c] = webp_put_code(o, f[c]);
+    webp_put_code(o, std::vector<unsigned>(kWebpDist, 0));
+    for (int k = 0; k < K; ++k)
+        for (int c = 0; c < 4; ++c) code[c].put(o, px[4 * (size_t) k + c]);
+    o.put(0, 1);                                     // no more transforms
+}
+
+// the entropy image, ew x eh: pixel (x, y) names group y.  Per row a literal, then, when it is wider than 1, one copy of length
+// ew - 1 at distance 1.
+void webp_entropy_image(WebpBits& o, int ew, int eh) {
+    std::vector<unsigned> fg(kWebpGreen, 0), fr(256, 0), fd(kWebpDist, 0);
+    int ls, lb, ds, db;
+    unsigned le, de;
+    webp_prefix((unsigned) std::max(ew - 1, 1), ls, lb, le);
+    webp_prefix(1 + 120, ds, db, de);
+    for (int y = 0; y < eh; ++y) {
+        fg[y & 255]++; fr[y >> 8]++;
+        if (ew > 1) { fg[256 + ls]++; fd[ds]++; }
+    }
+    o.put(0, 1);                                     // no colour cache
+    const WebpCode g = webp_put_code(o, fg), r = webp_put_code(o, fr);
+    webp_put_single(o, 0);
+    webp_put_single(o, 255);
+    const WebpCode d = webp_put_code(o, fd);
+    for (int y = 0; y < eh; ++y) {
+        g.put(o, y & 255); r.put(o, y >> 8);
+        if (ew > 1) {
+            g.put(o, 256 + ls); o.put(le, lb);
+            d.put(o, ds); o.put(de, db);
+        }
+    }
+}
+
+struct WebpCall {
+    int device, n;
+    const uint16_t* const* index;
+    int width, height;
+    const uint32_t* palette; int K;
+    const int32_t* delays_cs; int loop_count, band_bits, delta;
+    uint8_t* out; int64_t cap; int64_t* out_size; int32_t* out_rects;
+};
+
+// NQ_ERR_INVALID of both entry points, before any device is touched (the maps may be host or device addresses alike)
+int webp_check(const WebpCall& c) {
+    char why[256];
+    if (c.device < 0) NQ_CMP_FAIL(NQ_ERR_INVALID, "device = %d: a device ordinal is not negative", c.device);
+    if (!webp_check_shape(c.n, c.width, c.height, c.band_bits, why, sizeof why)) NQ_CMP_FAIL(NQ_ERR_INVALID, "%s", why);
+    if (c.K < 1 || c.K > 256) NQ_CMP_FAIL(NQ_ERR_INVALID, "K = %d: a palette has 1..256 entries", c.K);
+    const int pw = (c.width + webp_per(c.K) - 1) / webp_per(c.K);
+    if (!webp_band_bits(pw, c.band_bits))
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "packed width %d at band_bits = %d: a band of 2^p packed rows must fit %d packed pixels", pw, c.band_bits, kWebpMaxChain);
+    if (c.delta != 0 && c.delta != 1) NQ_CMP_FAIL(NQ_ERR_INVALID, "delta = %d: must be 0 or 1", c.delta);
+    if (c.loop_count < 0 || c.loop_count > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "loop_count = %d: must be 0..65535 (0 = for ever)", c.loop_count);
+    if (c.delays_cs)
+        for (int i = 0; i < c.n; ++i)
+            if (c.delays_cs[i] < 0 || c.delays_cs[i] > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: delay %d outside 0..65535", i, c.delays_cs[i]);
+    if (!c.palette || !c.out_size) NQ_CMP_FAIL(NQ_ERR_INVALID, "palette / out_size is NULL");
+    if (c.cap < 0 || (!c.out && c.cap > 0)) NQ_CMP_FAIL(NQ_ERR_INVALID, "out is NULL or cap < 0");
+    if (!c.index) NQ_CMP_FAIL(NQ_ERR_INVALID, "index is NULL");
+    for (int i = 0; i < c.n; ++i)
+        if (!c.index[i] || ((uintptr_t) c.index[i] & 1)) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: index pointer NULL or not 2-byte aligned", i);
+    return NQ_OK;
+}
+
+void webp_u24(std::vector<uint8_t>& b, uint32_t v) { for (int k = 0; k < 3; ++k) b.push_back((uint8_t) (v >> (8 * k))); }
+void webp_u32(std::vector<uint8_t>& b, uint32_t v) { for (int k = 0; k < 4; ++k) b.push_back((uint8_t) (v >> (8 * k))); }
+void webp_tag(std::vector<uint8_t>& b, const char* t) { b.insert(b.end(), t, t + 4); }
+
+// after the checks, on device c.device: c.index are device maps; everything runs on s and is freed before the return
+int webp_encode(const WebpCall& c, hipStream_t s) {
+    const int n = c.n, W = c.width, H = c.height, K = c.K, per = webp_per(K);
+    int cus = 0;
+    NQ_CMP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
+    // ---- rectangles: one difference pass over all frames, which also finds an index >= K anywhere ----
+    std::vector<GifRect> rects(n, GifRect{0, 0, W, H});
+    const bool diff = n > 1 && c.delta;
+    if (diff) {
+        DevBuf<const unsigned short*> d_ptrs;
+        DevBuf<int> d_box;
+        std::vector<int> box(4 * (size_t) (n - 1) + 1, 0);
+        for (int i = 0; i < n - 1; ++i) { box[4 * i] = box[4 * i + 1] = INT_MAX; box[4 * i + 2] = box[4 * i + 3] = -1; }
+        NQ_CMP_HIP(d_ptrs.reserve(n));
+        NQ_CMP_HIP(d_box.reserve(box.size()));
+        NQ_CMP_HIP(hipMemcpyAsync(d_ptrs.p, c.index, n * sizeof(*c.index), hipMemcpyHostToDevice, s));
+        NQ_CMP_HIP(hipMemcpyAsync(d_box.p, box.data(), box.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        launch_gif_diff(d_ptrs.p, n, W, H, K, d_box.p, d_box.p + 4 * (size_t) (n - 1), s);
+        NQ_CMP_HIP(launch_status());
+        NQ_CMP_HIP(hipMemcpyAsync(box.data(), d_box.p, box.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        NQ_CMP_HIP(hipStreamSynchronize(s));
+        if (box[4 * (size_t) (n - 1)]) NQ_CMP_FAIL(NQ_ERR_INVALID, "an index map holds an index >= K = %d", K);
+        for (int i = 1; i < n; ++i) {
+            const int* b = &box[4 * (size_t) (i - 1)];
+            GifRect& r = rects[i];
+            if (b[2] < 0) r = {0, 0, 1, 1};             // nothing changed
+            else {                                      // the container stores offsets halved: left and top go down to even
+                const int x = b[0] & ~1, y = b[1] & ~1;
+                r = {x, y, b[2] - x + 1, b[3] - y + 1};
+            }
+            if (r.x < 0 || r.y < 0 || r.w < 1 || r.h < 1 || r.x + r.w > W || r.y + r.h > H)
+                NQ_CMP_FAIL(NQ_ERR_HIP, "frame %d: the difference pass returned the box %d %d %d %d", i, b[0], b[1], b[2], b[3]);
+        }
+    }
+    // ---- the images, their chains, and the bits the host writes (they depend on the palette and the geometry only) ----
+    bool alpha = false;
+    for (int i = 0; i < K; ++i) alpha = alpha || (c.palette[i] >> 24) != 255;
+    WebpBits table;
+    webp_color_table(table, c.palette, K);
+    std::vector<nq::WebpImage> img(n);
+    std::vector<uint32_t> pre;
+    long long chains = 0;
+    int max_len = 1;
+    for (int i = 0; i < n; ++i) {
+        nq::WebpImage& F = img[i];
+        const GifRect& r = rects[i];
+        std::memset(&F, 0, sizeof F);
+        F.index = c.index[i] + (size_t) r.y * W + r.x;
+        F.width = r.w; F.height = r.h; F.pitch = W; F.K = K; F.per = per; F.pw = (r.w + per - 1) / per;
+        const int p = webp_band_bits(F.pw, c.band_bits);             // (a rectangle is no wider than the frame: p exists)
+        F.band_rows = 1 << p; F.nbands = (r.h + F.band_rows - 1) >> p;
+        F.chain_base = chains; chains += F.nbands;
+        max_len = std::max(max_len, F.pw * std::min(F.band_rows, r.h));
+        WebpBits b;
+        b.put(0x2F, 8); b.put((uint32_t) (r.w - 1), 14); b.put((uint32_t) (r.h - 1), 14); b.put(alpha ? 1 : 0, 1); b.put(0, 3);
+        b.append(table);
+        b.put(0, 1);                                                 // no colour cache
+        if (F.nbands > 1) {
+            b.put(1, 1); b.put((uint32_t) (p - 2), 3);
+            webp_entropy_image(b, (F.pw + F.band_rows - 1) >> p, F.nbands);
+        } else b.put(0, 1);
+        F.pre_word = (long long) pre.size(); F.pre_bits = b.nb;
+        pre.insert(pre.end(), b.w.begin(), b.w.end());
+        pre.push_back(0); pre.push_back(0);                          // a reader may touch the word after the last bit
+    }
+    const long long cw = nq::webp_chain_words(max_len);
+    const int grid = (int) std::min<long long>(chains, 4ll * std::max(cus, 1));
+    DevBuf<nq::WebpImage> d_img;
+    DevBuf<uint32_t> d_pre, d_words, d_tokens;
+    DevBuf<unsigned long long> d_bits, d_off, d_res;
+    DevBuf<int> d_bad;
+    DevBuf<uint8_t> d_blob, d_file;
+    NQ_CMP_HIP(d_img.reserve(n));
+    NQ_CMP_HIP(d_pre.reserve(pre.size()));
+    NQ_CMP_HIP(d_words.reserve((size_t) (chains * cw)));
+    NQ_CMP_HIP(d_tokens.reserve((size_t) grid * max_len));
+    NQ_CMP_HIP(d_bits.reserve(2 * (size_t) chains));
+    NQ_CMP_HIP(d_off.reserve((size_t) n + 2 * (size_t) chains));
+    NQ_CMP_HIP(d_res.reserve(n));
+    NQ_CMP_HIP(d_bad.reserve(n));
+    NQ_CMP_HIP(hipMemcpyAsync(d_img.p, img.data(), n * sizeof(nq::WebpImage), hipMemcpyHostToDevice, s));
+    NQ_CMP_HIP(hipMemcpyAsync(d_pre.p, pre.data(), pre.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    NQ_CMP_HIP(hipMemsetAsync(d_bad.p, 0, n * sizeof(int), s));
+    NQ_CMP_HIP(launch_webp_chains(d_img.p, n, chains, max_len, grid, d_words.p, d_bits.p, d_tokens.p, d_bad.p, s));
+    launch_webp_scan(d_img.p, n, max_len, d_bits.p, d_off.p, d_res.p, s);
+    NQ_CMP_HIP(launch_status());
+    std::vector<unsigned long long> res(n);
+    std::vector<int> bad(n);
+    NQ_CMP_HIP(hipMemcpyAsync(res.data(), d_res.p, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    NQ_CMP_HIP(hipMemcpyAsync(bad.data(), d_bad.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    NQ_CMP_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i)
+        if (bad[i]) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: the index map holds an index >= K = %d", i, K);
+    // ---- the container: every image's chunk headers in one blob, then the file is gathered ----
+    std::vector<uint8_t> blob;
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        nq::WebpImage& F = img[i];
+        F.data_bytes = (long long) ((res[i] + 7) / 8);
+        total += (i == 0 ? (n > 1 ? kWebpFileLead : 12) : 0) + (n > 1 ? kWebpFrameLead : 8) + F.data_bytes + (F.data_bytes & 1);
+    }
+    long long at = 0;
+    for (int i = 0; i < n; ++i) {
+        nq::WebpImage& F = img[i];
+        const GifRect& r = rects[i];
+        const size_t start = blob.size();
+        const long long padded = F.data_bytes + (F.data_bytes & 1);
+        if (i == 0) {
+            webp_tag(blob, "RIFF"); webp_u32(blob, (uint32_t) (total - 8)); webp_tag(blob, "WEBP");
+            if (n > 1) {
+                webp_tag(blob, "VP8X"); webp_u32(blob, 10);
+                blob.push_back((uint8_t) (0x02 | (alpha ? 0x10 : 0))); blob.push_back(0); blob.push_back(0); blob.push_back(0);
+                webp_u24(blob, (uint32_t) (W - 1)); webp_u24(blob, (uint32_t) (H - 1));
+                webp_tag(blob, "ANIM"); webp_u32(blob, 6); webp_u32(blob, 0);
+                blob.push_back((uint8_t) c.loop_count); blob.push_back((uint8_t) (c.loop_count >> 8));
+            }
+        }
+        if (n > 1) {
+            webp_tag(blob, "ANMF"); webp_u32(blob, (uint32_t) (16 + 8 + padded));
+            webp_u24(blob, (uint32_t) (r.x / 2)); webp_u24(blob, (uint32_t) (r.y / 2));
+            webp_u24(blob, (uint32_t) (r.w - 1)); webp_u24(blob, (uint32_t) (r.h - 1));
+            webp_u24(blob, 10u * (uint32_t) (c.delays_cs ? c.delays_cs[i] : 0));
+            blob.push_back(0x02);                                    // do not blend, dispose none
+        }
+        webp_tag(blob, "VP8L"); webp_u32(blob, (uint32_t) F.data_bytes);
+        F.prefix_off = (long long) start; F.prefix_len = (int) (blob.size() - start);
+        F.file_off = at;
+        at += F.prefix_len + padded;
+    }
+    if (at != total) NQ_CMP_FAIL(NQ_ERR_HIP, "the container's %lld bytes are not the %lld counted", at, total);
+    if (total > 4294967295ll + 8) NQ_CMP_FAIL(NQ_ERR_INVALID, "the file's %lld bytes exceed what RIFF can hold", total);
+    *c.out_size = total;
+    if (c.cap < total) NQ_CMP_FAIL(NQ_ERR_INVALID, "cap = %lld bytes < the file's %lld", (long long) c.cap, total);
+    NQ_CMP_HIP(d_blob.reserve(blob.size()));
+    NQ_CMP_HIP(d_file.reserve((size_t) total));
+    NQ_CMP_HIP(hipMemcpyAsync(d_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+    NQ_CMP_HIP(hipMemcpyAsync(d_img.p, img.data(), n * sizeof(nq::WebpImage), hipMemcpyHostToDevice, s));
+    launch_webp_gather(d_img.p, n, max_len, d_words.p, d_pre.p, d_bits.p, d_off.p, d_blob.p, d_file.p, total, s);
+    NQ_CMP_HIP(launch_status());
+    NQ_CMP_HIP(hipMemcpyAsync(c.out, d_file.p, (size_t) total, hipMemcpyDeviceToHost, s));
+    NQ_CMP_HIP(hipStreamSynchronize(s));
+    if (c.out_rects)
+        for (int i = 0; i < n; ++i) { c.out_rects[4 * i] = rects[i].x; c.out_rects[4 * i + 1] = rects[i].y; c.out_rects[4 * i + 2] = rects[i].w; c.out_rects[4 * i + 3] = rects[i].h; }
+    return NQ_OK;
+}
+
+// the work of a call, then the stream drained whatever happened: the scratch is freed on return
+int webp_run(const WebpCall& c, hipStream_t s) {
+    const int rc = webp_encode(c, s);
+    if (rc) (void) hipStreamSynchronize(s);
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_webp_max_bytes(int n, int width, int height, int band_bits, int64_t* out_bytes) {
+    char why[256];
+    if (!out_bytes || !webp_check_shape(n, width, height, band_bits, why, sizeof why)) return NQ_ERR_INVALID;
+    *out_bytes = kWebpFileLead + (long long) n * webp_frame_max(width, height, band_bits);
+    return NQ_OK;
+}
+
+int nq_encode_webp_device(int device, void* hip_stream, int n, const uint16_t* const* d_index, int width, int height, const uint32_t* palette,
+                          int K, const int32_t* delays_cs, int loop_count, int band_bits, int delta, uint8_t* out, int64_t cap, int64_t* out_size,
+                          int32_t* out_rects) {
+    const WebpCall c{device, n, d_index, width, height, palette, K, delays_cs, loop_count, band_bits, delta, out, cap, out_size, out_rects};
+    int rc = webp_check(c);
+    if (rc) return rc;
+    rc = compare_use_device(device);
+    if (rc) return rc;
+    return webp_run(c, (hipStream_t) hip_stream);
+}
+
+int nq_encode_webp(int device, int n, const uint16_t* const* index, int width, int height, const uint32_t* palette, int K,
+                   const int32_t* delays_cs, int loop_count, int band_bits, int delta, uint8_t* out, int64_t cap, int64_t* out_size,
+                   int32_t* out_rects) {
+    WebpCall c{device, n, index, width, height, palette, K, delays_cs, loop_count, band_bits, delta, out, cap, out_size, out_rects};
+    int rc = webp_check(c);
+    if (rc) return rc;
+    rc = compare_use_device(device);
+    if (rc) return rc;
+    // the maps uploaded to one temporary buffer, every one at an even element
+    const size_t px = (size_t) width * height, stride = (px + 1) & ~(size_t) 1;
+    DevBuf<uint16_t> d_maps;
+    NQ_CMP_HIP(d_maps.reserve(stride * n));
+    std::vector<const uint16_t*> dev(n);
+    hipStream_t s = nullptr;
+    for (int i = 0; i < n; ++i) {
+        dev[i] = d_maps.p + stride * i;
+        const hipError_t e = hipMemcpyAsync(d_maps.p + stride * i, index[i], px * sizeof(uint16_t), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) {
+            (void) hipStreamSynchronize(s);
+            NQ_CMP_FAIL(NQ_ERR_HIP, "upload of frame %d failed: %s", i, hipGetErrorString(e));
+        }
+    }
+    c.index = dev.data();
+    return webp_run(c, s);
+}
+
+} // extern "C"

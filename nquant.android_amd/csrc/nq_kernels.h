@@ -295,6 +295,36 @@ void launch_png_gather(const PngImage* d_images, int n_images, const unsigned* d
                        const unsigned long long* d_seg_off, const unsigned long long* d_res, const unsigned char* d_blob, unsigned char* d_file,
                        long long total, long long n_crc_chunks, unsigned* d_crc, hipStream_t s);
 
+// ---- WebP encoding (nq_webp.hip): an image is one VP8L bit string: a frame, or the rectangle of a frame (rows `pitch` elements
+// apart, index points at its first pixel).  `per` indices make one packed pixel, pw packed pixels a row; band b (band_rows packed rows,
+// the last one shorter) is chain chain_base + b of the call.  Chain c writes two bit strings: its five code headers to
+// words[c * chain_words ...] and its pixel data to words[c * chain_words + WEBP_HEAD_WORDS ...]; bits[2 c] and bits[2 c + 1] are their
+// lengths.  The image's bit string is the host's pre_bits bits (d_pre[pre_word ...]: header, transform, colour table, entropy image),
+// the headers in band order, the data in band order: 1 + 2 nbands segments, whose offsets are d_off[image + 2 chain_base ...].
+// file_off .. data_bytes place the image in the file once the lengths are known: prefix_len bytes of the blob (container chunk
+// headers), data_bytes of the bit string, a zero byte when data_bytes is odd. ----
+struct WebpImage {
+    const unsigned short* index;   // 2-byte aligned
+    int width, height, pitch, K, per, pw, band_rows, nbands, prefix_len;
+    long long chain_base, pre_word, pre_bits;
+    long long file_off, prefix_off, data_bytes;
+};
+constexpr int WEBP_HEAD_WORDS = 148;       // 4640 bits of code headers at most (DESIGN.md "WebP encoder"), and the words a reader may touch past them
+// words of a chain at this largest chain length: the headers, at most 15 bits per packed pixel, and the words a reader may touch past them
+inline long long webp_chain_words(int max_len) { return WEBP_HEAD_WORDS + (15ll * max_len + 31) / 32 + 2; }
+// dynamic LDS of one chain (= one workgroup of 64) at this largest chain length (<= 32768)
+size_t webp_chain_lds_bytes(int max_len);
+// `grid` chains at a time; d_tokens: grid * max_len words; d_bad[image] = 1 when an index >= K was met (zeroed by the caller)
+hipError_t launch_webp_chains(const WebpImage* d_images, int n_images, long long n_chains, int max_len, int grid, unsigned* d_words,
+                              unsigned long long* d_bits, unsigned* d_tokens, int* d_bad, hipStream_t s);
+// d_off: the segments' bit offsets inside their image; d_res[image] = the image's bit length
+void launch_webp_scan(const WebpImage* d_images, int n_images, int max_len, const unsigned long long* d_bits, unsigned long long* d_off,
+                      unsigned long long* d_res, hipStream_t s);
+// the file (total bytes) from the placed images
+void launch_webp_gather(const WebpImage* d_images, int n_images, int max_len, const unsigned* d_words, const unsigned* d_pre,
+                        const unsigned long long* d_bits, const unsigned long long* d_off, const unsigned char* d_blob, unsigned char* d_file,
+                        long long total, hipStream_t s);
+
 // ---- temporal hold (nq_hold.hip): d_src / d_idx / d_out are device arrays of n frame pointers (npix elements per frame; d_out null: no
 // ARGB stream), d_held n counters the caller zeroed (null: not counted).  Frames 1 .. n - 1 of idx (and out) are updated in place in one
 // launch.  vec: the 16-byte path -- the caller has checked that EVERY frame pointer of every stream is 16-byte aligned; otherwise the

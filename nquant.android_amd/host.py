@@ -144,6 +144,9 @@ _ABI = {
     "nq_compare_indexed_device": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "nq_compare_frames": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "nq_compare_indexed": (_i32, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "nq_webp_max_bytes": (_i32, [_i32, _i32, _i32, _i32, _pi64]),
+    "nq_encode_webp_device": (_i32, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _pi64, _vp]),
+    "nq_encode_webp": (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _pi64, _vp]),
 }
 
 
