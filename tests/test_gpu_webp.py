@@ -2,7 +2,8 @@
 the restatement in webp_ref.py, through the host form and through the device form on a caller's stream, with nq_get_device_bytes the
 same before and after; n = 1 ignores delta; an index >= K is reported, also outside the rectangle; a too-small cap reports the size
 and leaves `out` alone; calls of different geometry do not see each other; convert_frames_to_webp composes back to the converter's
-ARGB output.  No case is above 300 x 250."""
+ARGB output.  The limit cases of webp_cases.py (full chains, the farthest copy, items of up to 46 bits, more chains than the grid holds,
+more segments than a round of the scan, a file past the gather's one pass) run through the same test as the small ones."""
 import ctypes as C
 
 import numpy as np
@@ -60,6 +61,26 @@ def test_bytes_and_rectangles_equal_the_restatement(nq, stream, name):
     assert rects.tolist() == _want_rects(frames, kw), name
     assert got == want, (name, len(got), len(want))
     assert (buf.cpu().numpy().view(np.uint16) == host).all()                 # the maps are never written
+
+
+def test_more_chains_than_the_grid_holds(nq):
+    """The many_bands and many_frames cases are there for a workgroup's second chain: they must hold more chains than the grid of
+    4 workgroups per compute unit of this device, whatever its size."""
+    import torch
+    grid = 4 * torch.cuda.get_device_properties(0).multi_processor_count
+    for name in ("many_bands_K2", "many_bands_K256", "many_frames"):
+        chains = sum(len(image) for image in webp_cases.restated(name)[1])
+        print(name, chains, grid)
+        assert chains > grid, (name, chains, grid)
+
+
+def test_a_refused_width_leaves_the_next_call_what_it_was(nq):
+    """16384 wide is the limit at K = 16 and past it at K = 17: NQ_ERR_INVALID, and the same map at K = 16 encodes as before."""
+    _, frames, pal, kw = webp_cases.case("full_chain_K16")
+    with pytest.raises(nq.NqError) as e:
+        nq.encode_webp(frames, np.concatenate([pal, pal[:1]]), **kw)
+    assert e.value.status == -1 and "packed width 16384" in str(e.value)
+    assert nq.encode_webp(frames, pal, **kw) == webp_cases.restated("full_chain_K16")[0]
 
 
 def test_one_frame_ignores_delta(nq):

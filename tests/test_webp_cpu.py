@@ -92,6 +92,96 @@ def test_the_fibonacci_map_needs_the_length_limit():
     assert sum(2.0 ** -l for l in cut if l) == 1.0
 
 
+# ---- the limit cases reach their limits (DESIGN.md "WebP encoder", the limit cases): asserted from the restatement's statistics, so
+# that an edit of a case cannot quietly stop reaching what it was made for ----
+def _bands(name):
+    return [b for image in webp_cases.restated(name)[1] for b in image]
+
+
+def test_the_old_cases_reach_none_of_the_limits():
+    """What the limit cases add: before them no item reached a third word of the emit window or went past 32 bits, no chain was
+    full, no call held more chains than a grid or more than 256 segments in an image."""
+    old = [c[0] for c in webp_cases.cases()]
+    bands = [b for name in old for b in _bands(name)]
+    assert max(b.item_bits for b in bands) == 28 and not any(b.third_word or b.wide_items for b in bands)
+    assert max(b.length for b in bands) < webp_ref.MAX_CHAIN and max(b.distance for b in bands) < 1 << 14
+    assert max(b.green_depth for b in bands) == 15 and max(b.dist_depth for b in bands) == 5
+    assert max(sum(len(image) for image in webp_cases.restated(name)[1]) for name in old) <= 5
+
+
+@pytest.mark.parametrize("name,shape,nbands", [("full_chain_K17", (5, 8192), 2), ("full_chain_K16", (9, 16384), 3)])
+def test_a_full_chain(name, shape, nbands):
+    _, frames, pal, kw = webp_cases.case(name)
+    bands = _bands(name)
+    assert frames[0].shape == shape and len(bands) == nbands
+    assert [b.length for b in bands] == [webp_ref.MAX_CHAIN] * (nbands - 1) + [8192]      # the last band is one packed row
+    assert all(b[0] > 0 and b[1] > 0 for b in bands[:-1])                  # literals and copies in every full band
+    assert webp_ref.pack(frames[0], len(pal)).shape[1] == 8192             # the widest packed row there is
+
+
+def test_the_far_copy():
+    band, = _bands("far_copy")
+    assert band.length == webp_ref.MAX_CHAIN and band.distance == 32765
+    assert webp_ref.prefix_of(band.distance + 120) == (30, 32765 + 119 - (1 << 15), 14)     # the top prefix pair, 14 extra bits
+    assert band.distance >= 32649 and band.distance >> 14 == 1              # (a token that kept 14 bits of it would lose one)
+
+
+def test_the_wide_items():
+    """The committed map's reach, exactly: 46 of the 51 bits an item can have -- 12 + 7 of the length, 14 + 13 of the
+    distance."""
+    band, = _bands("wide_items")
+    assert band.length == webp_ref.MAX_CHAIN
+    assert (band.item_bits, band.green_depth, band.dist_depth) == (46, 12, 14)
+    assert band.wide_items == 3                                            # items over 32 bits
+    assert band.third_word == 2 and band.third_word_set == 2               # both put a 1 into the third word they reach
+    assert band.distance >= 32649 and band.copy == 258
+
+
+@pytest.mark.parametrize("name", ["many_bands_K2", "many_bands_K256"])
+def test_many_bands(name):
+    _, frames, pal, kw = webp_cases.case(name)
+    stats = webp_cases.restated(name)[1]
+    nbands = len(stats[0])
+    assert len(stats) == 1 and nbands == 1025
+    assert nbands > 256 and len({y >> 8 for y in range(nbands)}) >= 5      # the entropy image's red channel takes five values
+    assert 1 + 2 * nbands > 2048                                           # nine rounds of the scan
+    assert nbands > 1024                                                   # more chains than a grid of 4 x 256 workgroups
+    assert webp_ref.pack(frames[0], len(pal)).shape[1] == 8 and all(b.length == 32 for b in stats[0][:-1])
+    assert sum(1 for b in stats[0] if b[1]) > 100                          # bands with copies among them
+
+
+def test_many_frames():
+    _, frames, pal, kw = webp_cases.case("many_frames")
+    data, stats = webp_cases.restated("many_frames")
+    assert len(frames) == 1100 and len({id(f) for f in frames}) == 6 and not kw["delta"]
+    assert len(data) > 4194304                                             # the gather's grid cap: 16384 x 256 bytes in one pass
+    assert sum(len(image) for image in stats) == 4400 and all(len(image) == 4 for image in stats)
+    assert len(set(kw["delays_cs"])) > 2
+
+
+def test_many_frames_delta():
+    _, frames, pal, kw = webp_cases.case("many_frames_delta")
+    stats = webp_cases.restated("many_frames_delta")[1]
+    rects = webp_ref.rectangles(frames, True)
+    heights = [1 << webp_ref.band_bits_of(webp_ref.pack(np.zeros((1, w), np.int64), len(pal)).shape[1]) for _, _, w, _ in rects]
+    print(sorted(set(heights)), sorted({len(image) for image in stats}))
+    assert len(frames) == 300 and len(set(heights)) >= 3                   # images of one call with different band heights
+    assert {len(image) for image in stats} == {1, 2}                       # and band counts
+    longest = [max(b.length for b in image) for image in stats]
+    assert sorted(longest)[-1] > sorted(longest)[-2]                       # one image alone sets the call's largest chain
+
+
+def test_the_memo_of_vp8l_returns_what_it_computes():
+    """vp8l is memoised by content: the 1100 frames of many_frames cost six restatements."""
+    _, frames, pal, kw = webp_cases.case("many_frames")
+    data, _ = webp_cases.restated("many_frames")
+    key = tuple(int(c) for c in pal)
+    assert sum(1 for k in webp_ref._VP8L if k[3] == key) == 6
+    # the memo returns what the restatement computes: one frame restated afresh
+    assert webp_ref._vp8l(np.asarray(frames[1]), list(key), 4)[0] == webp_ref.vp8l(frames[1], list(key), 4)
+    assert data.endswith(webp_ref.chunk(b"VP8L", webp_ref._vp8l(np.asarray(frames[1099]), list(key), 4)[0]))
+
+
 def test_a_single_length_symbol_never_stands_alone():
     """A band's first token is a literal (no match reaches before the band), so a green code that holds a length symbol holds a literal
     too: a code with one used symbol has a symbol below 256 and fits the simple form."""
@@ -203,6 +293,7 @@ def _spoilers():
             ("band_bits 1", setter(band_bits=1)), ("band_bits 10", setter(band_bits=10)), ("band_bits -2", setter(band_bits=-2)),
             ("band_bits 9 at 100 packed pixels", setter(w=100, K=17, band_bits=9)),
             ("8193 packed pixels", setter(w=8193, K=17)), ("16384 packed pixels at K = 256", setter(w=16384, K=256)),
+            ("16384 packed pixels at K = 17", setter(w=16384, K=17)),
             ("NULL table", setter(table=False)), ("NULL frame", pointer(1, None)), ("odd frame pointer", pointer(0, 1)),
             ("NULL palette", setter(p_pal=None)), ("NULL out_size", setter(p_size=None)), ("NULL out", setter(p_out=None)),
             ("cap < 0", setter(cap=-1)), ("negative device", setter(device=-1))]
@@ -234,6 +325,29 @@ def test_the_widest_frames_the_bundling_allows_pass_the_checks(nq):
         c.pal = np.full(K, 0xFF000000, np.uint32)
         c.p_pal = c.pal.ctypes.data
         assert c.run(L, "nq_encode_webp") == -5 and c.untouched()
+
+
+def test_the_widest_frame_one_palette_entry_too_many_is_refused_and_the_next_call_is_what_it_was(nq):
+    """full_chain_K16 is 16384 wide at K = 16; at K = 17 nothing is bundled and the same width is 16384 packed pixels.  The refusal
+    leaves no state behind: the same call at K = 16 gets as far as it did before (here: to the device that is not there;
+    tests/test_gpu_webp.py encodes it)."""
+    L = nq.load_library()
+    _, frames, _, _ = webp_cases.case("full_chain_K16")
+
+    def call(K):
+        c = _Call()
+        c.w, c.h, c.K, c.n = 16384, 9, K, 1
+        c.maps = [np.ascontiguousarray(frames[0], np.uint16)]
+        c.ptrs = [c.maps[0].ctypes.data]
+        c.pal = np.full(K, 0xFF000000, np.uint32)
+        c.p_pal = c.pal.ctypes.data
+        return c.run(L, "nq_encode_webp"), c
+
+    rc, c = call(17)
+    assert rc == -1 and c.untouched() and b"packed width 16384" in L.nq_last_error(None)
+    if not conftest.HAS_GPU:
+        rc, c = call(16)
+        assert rc == -5 and c.untouched()
 
 
 def test_max_bytes_refuses_bad_shapes(nq):

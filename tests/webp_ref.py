@@ -2,6 +2,7 @@
 independent of the library, and an independent reader of such files.
   encode()    the encoder bit for bit: bundling, bands, the per-band parse (png_ref.tokens_of: the PNG encoder's), the code lengths
               (png_ref.code_lengths), the code headers, the entropy image, the colour table, the RIFF container
+              with stats=[]: per image and band a Band -- (literals, copies), and what the band reaches of the encoder's limits
   read()      RIFF / VP8X / ANIM / ANMF / VP8L as far as the encoder uses them, with a Huffman decoder of its own (it shares nothing
               with the writer but the bit order); per frame also how many literals and copies every band held
   compose()   the n displayed RGBA canvases of a file
@@ -167,8 +168,26 @@ def entropy_image_bits(w, ew, eh):
             w.put(de, db)
 
 
+class Band(tuple):
+    """What `stats` holds per band: the pair (literals, copies), which it compares equal to, and as attributes what the band reaches:
+      length           L, the band's packed pixels (the chain length)
+      item_bits        the largest data item (one token: green code + length extra bits + distance code + distance extra bits)
+      third_word       items with (bit offset in the band's data string) % 32 + bits > 64: they reach a third 32-bit word
+      third_word_set   those of them that have a 1 among the bits in that third word
+      wide_items       items of more than 32 bits
+      green_depth, dist_depth   the longest code of the band's green and distance code (0: the one-symbol form)
+      distance, copy   the largest copy distance and copy length (0: no copy)"""
+    FIELDS = ("length", "item_bits", "third_word", "third_word_set", "wide_items", "green_depth", "dist_depth", "distance", "copy")
+
+    def __new__(cls, literals, copies, **reach):
+        self = super().__new__(cls, (literals, copies))
+        assert sorted(reach) == sorted(cls.FIELDS)
+        self.__dict__.update(reach)
+        return self
+
+
 def band_bits_strings(seg):
-    """(code header, data) bit strings of one band, and its tokens."""
+    """(code header, data) bit strings of one band, and its Band."""
     toks = png_ref.tokens_of(seg)
     fg, fd = [0] * GREEN_SYMBOLS, [0] * DIST_SYMBOLS
     for t in toks:
@@ -183,7 +202,9 @@ def band_bits_strings(seg):
     put_simple_zero(head, 0)
     put_simple_zero(head, 255)
     dl, dc = put_code(head, fd)
+    item_bits = third_word = third_word_set = wide_items = 0
     for t in toks:
+        at = data.nb
         if isinstance(t, tuple):
             s, e, eb = prefix_of(t[0])
             data.put(gc[256 + s], gl[256 + s])
@@ -193,7 +214,19 @@ def band_bits_strings(seg):
             data.put(e, eb)
         else:
             data.put(gc[t], gl[t])
-    return head, data, toks
+        bits = data.nb - at
+        item_bits = max(item_bits, bits)
+        wide_items += bits > 32
+        if at % 32 + bits > 64:
+            third_word += 1
+            third_word_set += (data.val >> (at - at % 32 + 64)) != 0
+    copies = [t for t in toks if isinstance(t, tuple)]
+    return head, data, Band(len(toks) - len(copies), len(copies), length=len(seg), item_bits=item_bits, third_word=third_word,
+                            third_word_set=third_word_set, wide_items=wide_items, green_depth=max(gl), dist_depth=max(dl),
+                            distance=max((d for _, d in copies), default=0), copy=max((n for n, _ in copies), default=0))
+
+
+_VP8L = {}                # vp8l's results by content: an animation that repeats frames restates each distinct one once
 
 
 def vp8l(index, pal, band_bits=0, stats=None):
@@ -202,6 +235,18 @@ def vp8l(index, pal, band_bits=0, stats=None):
     h, w = index.shape
     K = len(pal)
     assert index.min() >= 0 and index.max() < K
+    key = (index.astype(np.uint8).tobytes(), h, w, tuple(pal), band_bits)
+    if key not in _VP8L:
+        _VP8L[key] = _vp8l(index, pal, band_bits)
+    data, bands = _VP8L[key]
+    if stats is not None:
+        stats.append(list(bands))
+    return data
+
+
+def _vp8l(index, pal, band_bits):
+    h, w = index.shape
+    K = len(pal)
     alpha = any((c >> 24) != 255 for c in pal)
     packed = pack(index, K)
     pw = packed.shape[1]
@@ -231,9 +276,7 @@ def vp8l(index, pal, band_bits=0, stats=None):
         o.extend(head)
     for _, data, _ in parts:
         o.extend(data)
-    if stats is not None:
-        stats.append([(sum(1 for t in toks if not isinstance(t, tuple)), sum(1 for t in toks if isinstance(t, tuple))) for _, _, toks in parts])
-    return o.tobytes()
+    return o.tobytes(), [band for _, _, band in parts]
 
 
 def chunk(kind, data):
@@ -427,8 +470,18 @@ def read_groups(r, count):
     return [[read_code(r, GREEN_SYMBOLS)] + [read_code(r, 256) for _ in range(3)] + [read_code(r, DIST_SYMBOLS)] for _ in range(count)]
 
 
+_READ = {}                # read_vp8l's results by payload
+
+
 def read_vp8l(data):
     """(index map (h, w), palette words, alpha bit, [(literals, copies)] per band) of a VP8L payload as the encoder writes it."""
+    if data not in _READ:
+        _READ[data] = _read_vp8l(data)
+    index, pal, alpha, bands = _READ[data]
+    return index.copy(), list(pal), alpha, list(bands)
+
+
+def _read_vp8l(data):
     r = Reader(data)
     assert r.bits(8) == 0x2F
     w, h = r.bits(14) + 1, r.bits(14) + 1
