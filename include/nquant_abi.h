@@ -997,6 +997,103 @@ int nq_encode_webp(int device, int n, const uint16_t* const* index, int width, i
                    const uint32_t* palette, int K, const int32_t* delays_cs, int loop_count, int band_bits, int delta,
                    uint8_t* out, int64_t cap, int64_t* out_size, int32_t* out_rects);
 
+/* ---- 10-bit YUV input: 10-bit YUV 4:2:0 frames in 16-bit words (P010: what a 10-bit MediaCodec hands out as COLOR_FormatYUVP010
+ *      and the camera as ImageFormat.YCBCR_P010; I010: the planar form) in front of the frame path, in SDR, PQ (SMPTE ST 2084) or HLG
+ *      (BT.2100).  nq_frames_from_yuv16* converts a sequence 1:1 to ARGB_8888 words (8-bit sRGB); nq_resample_frames_yuv16* converts
+ *      and reduces it in one step, without the full-size ARGB frames ever existing.  All arithmetic is integer and two committed
+ *      tables: the result is deterministic and can be restated bit for bit (tests/yuv16_ref.py).  The calls take NO handle: a device
+ *      ordinal and, in the device forms, a stream, as nq_compare_* do; the error text is the thread's, nq_last_error(NULL).
+ *  * The frame: the geometry of "YUV input" with every stride and step counted in 16-bit SAMPLES.  width x height, both 1..65535, and
+ *    three pointers to 16-bit little-endian words y, u, v.  Luma of pixel (x, y) is y[y * y_stride + x]; the chroma planes are
+ *    cw2 = (width + 1) >> 1 by ch2 = (height + 1) >> 1 samples, and the chroma of pixel (x, y) is
+ *    u[(y >> 1) * c_stride + (x >> 1) * c_step], likewise v (sample replication).  c_step is 1 (planar) or 2 (interleaved):
+ *        P010                     u = uv, v = uv + 1     c_step 2
+ *        P010, v first            v = vu, u = vu + 1     c_step 2
+ *        I010 / YV12 at 10 bits   two planes             c_step 1
+ *    All n frames of a call share width, height, y_stride, c_stride, c_step and the flag word.
+ *  * yuv16_flags:
+ *        NQ_YUV_BT709        1   the BT.709 matrix (BT.601 when no matrix bit is set)
+ *        NQ_YUV_FULL_RANGE   2   full range (otherwise limited range)
+ *        NQ_YUV16_BT2020     4   the BT.2020 non-constant-luminance matrix, Kr = 0.2627, Kb = 0.0593; exclusive with bit 1
+ *        NQ_YUV16_MSB        8   sample = word >> 6 (P010); otherwise sample = word & 1023 (I010).  The other 6 bits are ignored.
+ *        NQ_YUV16_PQ        16   PQ transfer; exclusive with HLG
+ *        NQ_YUV16_HLG       32   HLG transfer; exclusive with PQ
+ *    Neither transfer bit: SDR.
+ *  * Step 1, every mode: R'G'B' on a 12-bit scale.  yo = 64 in limited range, 0 in full range; the chroma centre is 512.
+ *    Coefficients: floor(16384 e + 1/2) of the rationals e of "YUV input" (cy = sy, crv = sc 2 (1 - Kr), cgu = sc 2 (1 - Kb) Kb / Kg,
+ *    cgv = sc 2 (1 - Kr) Kr / Kg, cbu = sc 2 (1 - Kb)) with sy = 4095/876 and sc = 4095/896 in limited range, both 4095/1023 in full
+ *    range:
+ *                          cy      crv     cgu     cgv     cbu
+ *        601 limited     76590   104982   25769   53475  132687
+ *        601 full        65584    91949   22570   46836  116215
+ *        709 limited     76590   117921   14027   35053  138947
+ *        709 full        65584   103282   12285   30701  121698
+ *        2020 limited    76590   110418   12322   42783  140879
+ *        2020 full       65584    96710   10792   37472  123390
+ *        R' = clamp((cy (Y - yo) + crv (V - 512) + 8192) >> 14, 0, 4095)
+ *        G' = clamp((cy (Y - yo) - cgu (U - 512) - cgv (V - 512) + 8192) >> 14, 0, 4095)
+ *        B' = clamp((cy (Y - yo) + cbu (U - 512) + 8192) >> 14, 0, 4095)
+ *    >> is the arithmetic shift of a signed 32-bit value (a floor).  Every intermediate is below 1.6e8 in magnitude.
+ *  * Step 2, SDR: channel = (c' * 255 + 2047) / 4095 (integer division).  DEVIATION: there is no gamut change, with the BT.2020
+ *    matrix too -- wide-gamut SDR comes out with its primaries read as BT.709's.  Each channel is within one level of round-half-up
+ *    of the exact real formula.
+ *  * Step 2, PQ / HLG: through the two tables of the transfer in include/nq_hdr_luts.inc (normative; tools/make_hdr_luts.py wrote it).
+ *      - E[4096], unsigned 16 bit: the 12-bit signal to linear light with 8192 = reference white.
+ *          PQ   min(65535, floor(8192 * 10000 * pq_eotf(i / 4095) / 203 + 1/2)): the ST 2084 EOTF with 203 nits for white
+ *               (BT.2408); it saturates near 1624 nits.
+ *          HLG  floor(8192 * h(i / 4095) / h(0.75) + 1/2), h the inverse OETF of BT.2100: h(x) = x^2 / 3 for x <= 1/2, otherwise
+ *               (exp((x - c) / a) + b) / 12 with a = 0.17883277, b = 0.28466892, c = 0.55991073.  System gamma 1: no OOTF.
+ *      - Gamut, BT.2020 -> BT.709 at 2^12: l_c = clamp((row . (E[R'], E[G'], E[B']) + 2048) >> 12, 0, 65535) with the rows
+ *          r: (6801, -2407, -298)    g: (-510, 4640, -34)    b: (-75, -412, 4583)
+ *        Each row sums to 4096: grey stays grey.  Every term stays below 4.5e8 in magnitude: signed 32 bits suffice.
+ *      - O[1280], unsigned 8 bit: the per-channel tone curve and the sRGB encoding behind one logarithmic index.  For l < 256
+ *        idx = l; otherwise, with e = 31 - clz(l), idx = 256 + 128 (e - 8) + ((l >> (e - 7)) & 127).  The representative of an index
+ *        is l itself below 256, otherwise the bucket's lower bound plus half its width, 2^(e - 8).
+ *        O[idx] = floor(255 s(t(x / 8192)) + 1/2) with t(x) = min(1, x (1 + x / p^2) / (1 + x)) (extended Reinhard; p = 65535 / 8192
+ *        for PQ, E_HLG[4095] / 8192 for HLG) and s the sRGB encoding function.  The bucketed O stays within 0.68 of a level of the
+ *        unbucketed curve over all 65536 inputs.
+ *    The matrix bit is honoured as given; PQ and HLG footage carries BT.2020 (NQ_YUV16_BT2020), and the gamut rows assume it.
+ *  * The word is 0xFF << 24 | R << 16 | G << 8 | B in every mode.
+ *  * nq_frames_from_yuv16_device: d_y, d_u, d_v, d_dst are host arrays of n DEVICE pointers; output i is width x height words, rows
+ *    contiguous.  nq_resample_frames_yuv16_device is DEFINED as that call followed by nq_resample_frames_device with the same crop,
+ *    target and flags ("frame reduction"), bit for bit; output i is dst_width x dst_height words; it needs no scratch.  The chroma of
+ *    crop pixel (j, i) is the frame's sample ((crop_x + j) >> 1, (crop_y + i) >> 1).  For sideways footage reduce first and turn the
+ *    small result with nq_orient_frames: exact, because orientation moves words and the reducer is symmetric ("orientation").
+ *    Both calls are asynchronous on hip_stream (NULL: the default stream) of `device`; the frames of a launch travel in its arguments,
+ *    16 to a launch, so the calls allocate nothing and wait for nothing.  They never write the sources and write nothing outside the n
+ *    outputs.  Sample pointers need 2-byte alignment, outputs 4-byte alignment.  When width is a multiple of 4, every y pointer is
+ *    8-byte aligned, y_stride is a multiple of 4 and the chroma is either interleaved (c_step 2, u and v one sample apart in the same
+ *    order in every frame of a launch, the lower one 8-byte aligned and c_stride a multiple of 4) or planar with u and v 4-byte aligned
+ *    and c_stride even (and, 1:1, every output is 16-byte aligned), the kernels load 8 luma bytes per access and store 16; otherwise
+ *    one pixel per access, with the same results.
+ *    nq_frames_from_yuv16 / nq_resample_frames_yuv16: the same with HOST buffers.  Per frame the luma span and the chroma spans are
+ *    uploaded -- one span where u's and v's overlap or touch --, the device form runs, the n outputs are copied back and every
+ *    temporary buffer is freed; the call returns when the outputs are there.  nq_get_device_bytes is the same before and after.
+ *  * NQ_ERR_INVALID before any device is touched, every buffer untouched: n outside 1..65535, a side outside 1..65535,
+ *    y_stride < width, c_step not 1 or 2, c_stride < c_step (cw2 - 1) + 1, unknown bits in either flag word, both matrix bits, both
+ *    transfer bits, a negative device, a NULL pointer array or entry, a sample pointer that is not 2-byte aligned, an output pointer
+ *    that is not 4-byte aligned, n width height above 2^31 - 1, the crop and target errors of nq_resample_frames, an output that
+ *    overlaps a source span or another output.  Then NQ_ERR_NO_DEVICE (no usable device; a device ordinal past the last one is
+ *    NQ_ERR_INVALID) or NQ_ERR_HIP.
+ *  Out of scope: 12-bit samples, 4:2:2 and 4:4:4, Dolby Vision and HDR10+ metadata.  The kernels: DESIGN.md 5g2 "10-bit YUV input". ---- */
+#define NQ_YUV16_BT2020 4
+#define NQ_YUV16_MSB 8
+#define NQ_YUV16_PQ 16
+#define NQ_YUV16_HLG 32
+int nq_frames_from_yuv16_device(int device, void* hip_stream, int n, const uint16_t* const* d_y, const uint16_t* const* d_u,
+                                const uint16_t* const* d_v, int width, int height, int y_stride, int c_stride, int c_step,
+                                int yuv16_flags, uint32_t* const* d_dst);
+int nq_frames_from_yuv16(int device, int n, const uint16_t* const* y, const uint16_t* const* u, const uint16_t* const* v,
+                         int width, int height, int y_stride, int c_stride, int c_step, int yuv16_flags, uint32_t* const* dst);
+int nq_resample_frames_yuv16_device(int device, void* hip_stream, int n, const uint16_t* const* d_y, const uint16_t* const* d_u,
+                                    const uint16_t* const* d_v, int src_width, int src_height, int y_stride, int c_stride, int c_step,
+                                    int yuv16_flags, int crop_x, int crop_y, int crop_w, int crop_h,
+                                    uint32_t* const* d_dst, int dst_width, int dst_height, int flags);
+int nq_resample_frames_yuv16(int device, int n, const uint16_t* const* y, const uint16_t* const* u, const uint16_t* const* v,
+                             int src_width, int src_height, int y_stride, int c_stride, int c_step, int yuv16_flags,
+                             int crop_x, int crop_y, int crop_w, int crop_h,
+                             uint32_t* const* dst, int dst_width, int dst_height, int flags);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

@@ -85,7 +85,7 @@ def write_apng(path, frames, palette, delays_cs=None, loop=0, segment_bytes=0, d
 
 def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, seeds=None, tile=None, segment_bytes=0, device=0,
                            mode=MODE_PARALLEL_TILED, return_rects=False, hold=None, refine=0, size=None, crop=None, linear_resample=True,
-                           ordered=None, yuv=None, orient=1):
+                           ordered=None, yuv=None, orient=1, yuv16=None):
     """convert_frames (one shared palette for the ARGB frames, which must have one size) followed by encode_apng of the index maps on
     the same handle.  nMaxColors <= 256.  Seeds are passed on as given: regions that do not move repeat in the index maps, and so drop
     out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.  hold (None: no such pass): an integer
@@ -100,7 +100,13 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
     YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
     orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
     converting kernel --; size and crop are then those of the oriented frames.
+    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
+    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
+    with orient: then turned -- before anything else runs.
     Returns (file bytes, palette); with return_rects=True (file bytes, palette, rectangles)."""
+    if yuv16 is not None:
+        from .yuv16 import _converter_frames
+        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a PNG palette holds at most 256 entries")
     if yuv is None and len({np.asarray(f).shape for f in frames}) > 1:

@@ -4786,3 +4786,230 @@ int nq_encode_webp(int device, int n, const uint16_t* const* index, int width, i
 }
 
 } // extern "C"
+
+// ---- 10-bit YUV input (nq_yuv16.hip; include/nquant_abi.h "10-bit YUV input"): stateless calls like the quality measurement -- no
+// handle, the error text goes to the thread's handle-free string; the frames of a launch travel in its arguments, so the device forms
+// allocate nothing and wait for nothing ----
+namespace {
+
+// the n frames of a call: plane pointers (host arrays), one geometry (strides and step in samples) and one flag word
+struct Yuv16Frames {
+    int device, n;
+    const uint16_t* const* y; const uint16_t* const* u; const uint16_t* const* v;
+    int width, height, y_stride, c_stride, c_step, flags;
+    // bytes from a plane's first sample to one past its last
+    uintptr_t y_span() const { return ((uintptr_t) (height - 1) * (uintptr_t) y_stride + (uintptr_t) width) * sizeof(uint16_t); }
+    uintptr_t c_span() const {
+        return ((uintptr_t) ((height + 1) / 2 - 1) * (uintptr_t) c_stride + (uintptr_t) ((width + 1) / 2 - 1) * (uintptr_t) c_step + 1) *
+               sizeof(uint16_t);
+    }
+};
+
+// floor(16384 e + 1/2) of the rationals of include/nquant_abi.h "10-bit YUV input", by matrix and range: {cy, crv, cgu, cgv, cbu, yo}
+const YuvCoef YUV16_COEF[3][2] = {
+    {{76590, 104982, 25769, 53475, 132687, 64}, {65584, 91949, 22570, 46836, 116215, 0}},       // BT.601: limited, full
+    {{76590, 117921, 14027, 35053, 138947, 64}, {65584, 103282, 12285, 30701, 121698, 0}},      // NQ_YUV_BT709
+    {{76590, 110418, 12322, 42783, 140879, 64}, {65584, 96710, 10792, 37472, 123390, 0}},       // NQ_YUV16_BT2020
+};
+
+constexpr int kYuv16Flags = NQ_YUV_BT709 | NQ_YUV_FULL_RANGE | NQ_YUV16_BT2020 | NQ_YUV16_MSB | NQ_YUV16_PQ | NQ_YUV16_HLG;
+
+// every argument of the four entry points, from the host arrays alone (no device work).  nq_frames_from_yuv16* pass the whole frame
+// as crop and target, and flags 0.
+int yuv16_check(const Yuv16Frames& a, int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* dst, int dst_width, int dst_height,
+                int flags) {
+    const int n = a.n;
+    if (n < 1 || n > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "n = %d: 1..65535 frames", n);
+    if (a.width < 1 || a.width > 65535 || a.height < 1 || a.height > 65535)
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "%d x %d: source sides must be 1..65535", a.width, a.height);
+    if (a.y_stride < a.width) NQ_CMP_FAIL(NQ_ERR_INVALID, "y_stride = %d: shorter than a row of %d samples", a.y_stride, a.width);
+    if (a.c_step != 1 && a.c_step != 2) NQ_CMP_FAIL(NQ_ERR_INVALID, "c_step = %d: must be 1 or 2", a.c_step);
+    if (a.c_stride < a.c_step * ((a.width + 1) / 2 - 1) + 1)
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "c_stride = %d: shorter than a chroma row of %d samples %d apart", a.c_stride, (a.width + 1) / 2, a.c_step);
+    if (a.flags & ~kYuv16Flags) NQ_CMP_FAIL(NQ_ERR_INVALID, "yuv16_flags = 0x%x: unknown bits", (unsigned) a.flags);
+    if ((a.flags & NQ_YUV_BT709) && (a.flags & NQ_YUV16_BT2020)) NQ_CMP_FAIL(NQ_ERR_INVALID, "yuv16_flags = 0x%x: two matrices", (unsigned) a.flags);
+    if ((a.flags & NQ_YUV16_PQ) && (a.flags & NQ_YUV16_HLG)) NQ_CMP_FAIL(NQ_ERR_INVALID, "yuv16_flags = 0x%x: two transfers", (unsigned) a.flags);
+    if (a.device < 0) NQ_CMP_FAIL(NQ_ERR_INVALID, "device = %d: a device ordinal is not negative", a.device);
+    if (!a.y || !a.u || !a.v || !dst) NQ_CMP_FAIL(NQ_ERR_INVALID, "an array of plane / output pointers is NULL");
+    for (int i = 0; i < n; ++i) {
+        if (!a.y[i] || !a.u[i] || !a.v[i]) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: a plane pointer is NULL", i);
+        if (((uintptr_t) a.y[i] | (uintptr_t) a.u[i] | (uintptr_t) a.v[i]) & 1)
+            NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: a plane pointer is not 2-byte aligned", i);
+        if (!dst[i] || ((uintptr_t) dst[i] & 3)) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: output pointer NULL or not 4-byte aligned", i);
+    }
+    if ((long long) n * a.width * a.height > 2147483647ll)
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "%d frames of %d x %d: more than 2^31 - 1 pixels", n, a.width, a.height);
+    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > a.width - crop_w || crop_y > a.height - crop_h)
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "crop %d x %d at (%d, %d): empty or outside the %d x %d frame", crop_w, crop_h, crop_x, crop_y, a.width,
+                    a.height);
+    if (dst_width < 1 || dst_width > crop_w || dst_height < 1 || dst_height > crop_h)
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "target %d x %d: sides must be 1 .. the crop's (%d x %d); this call only reduces", dst_width, dst_height,
+                    crop_w, crop_h);
+    if (flags & ~NQ_RESAMPLE_LINEAR) NQ_CMP_FAIL(NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) flags);
+    // no output may overlap a plane's span or another output (yuv_check's sweep)
+    struct Span { uintptr_t begin, end; bool out; };
+    std::vector<Span> spans;
+    spans.reserve(4 * (size_t) n);
+    const uintptr_t dst_bytes = (uintptr_t) dst_width * dst_height * sizeof(uint32_t);
+    for (int i = 0; i < n; ++i) {
+        spans.push_back({(uintptr_t) a.y[i], (uintptr_t) a.y[i] + a.y_span(), false});
+        spans.push_back({(uintptr_t) a.u[i], (uintptr_t) a.u[i] + a.c_span(), false});
+        spans.push_back({(uintptr_t) a.v[i], (uintptr_t) a.v[i] + a.c_span(), false});
+        spans.push_back({(uintptr_t) dst[i], (uintptr_t) dst[i] + dst_bytes, true});
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span& p, const Span& q) { return p.begin < q.begin; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const Span& sp : spans) {
+        if (sp.begin < (sp.out ? end_any : end_out)) NQ_CMP_FAIL(NQ_ERR_INVALID, "an output overlaps a source plane or another output");
+        end_any = std::max(end_any, sp.end);
+        if (sp.out) end_out = std::max(end_out, sp.end);
+    }
+    return NQ_OK;
+}
+
+struct Yuv16Geometry { bool fused; int crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags; };
+
+// after the checks, for DEVICE frames `a` and outputs d_dst: one launch per YUV16_FRAMES_PER_LAUNCH frames, all on s.  The wide paths
+// need, for EVERY frame of a launch: width and y_stride multiples of 4, y 8-byte aligned (1:1: and the output 16-byte aligned), and
+// either c_step 2 with u and v one sample apart in the same order, the lower one 8-byte aligned and c_stride a multiple of 4
+// (interleaved: P010 and its chroma-swapped form), or c_step 1 with u and v 4-byte aligned and c_stride even (planar: I010, YV12 at ten
+// bits).  Everything else takes the one-pixel path.
+int yuv16_launches(const Yuv16Frames& a, uint32_t* const* d_dst, const Yuv16Geometry& g, hipStream_t s) {
+    const int matrix = (a.flags & NQ_YUV16_BT2020) ? 2 : (a.flags & NQ_YUV_BT709) ? 1 : 0;
+    for (int first = 0; first < a.n; first += YUV16_FRAMES_PER_LAUNCH) {
+        const int count = std::min(a.n - first, (int) YUV16_FRAMES_PER_LAUNCH);
+        Yuv16Launch l;
+        std::memset(&l, 0, sizeof l);
+        bool wide = a.width % 4 == 0 && a.y_stride % 4 == 0;
+        bool inter = a.c_step == 2 && a.c_stride % 4 == 0, planar = a.c_step == 1 && a.c_stride % 2 == 0;
+        int order = 0;                              // +1: u is the lower pointer of every frame so far, -1: v is
+        for (int i = first; i < first + count; ++i) {
+            const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i];
+            wide = wide && !((uintptr_t) a.y[i] & 7) && !(!g.fused && ((uintptr_t) d_dst[i] & 15));
+            const int o = v == u + sizeof(uint16_t) ? 1 : u == v + sizeof(uint16_t) ? -1 : 0;
+            inter = inter && o != 0 && (order == 0 || order == o) && !(std::min(u, v) & 7);
+            if (o) order = o;
+            planar = planar && !((u | v) & 3);
+        }
+        l.path = wide && inter ? YUV_WIDE_INTERLEAVED : wide && planar ? YUV_WIDE_PLANAR : YUV_BYTE;
+        for (int i = 0; i < count; ++i) {
+            const int j = first + i;
+            l.frame[i] = {a.y[j], l.path == YUV_WIDE_INTERLEAVED ? std::min(a.u[j], a.v[j]) : a.u[j], a.v[j], d_dst[j]};
+        }
+        l.count = count;
+        l.y_stride = a.y_stride; l.c_stride = a.c_stride; l.c_step = a.c_step;
+        l.swap = order < 0 ? 1 : 0;
+        l.shift = (a.flags & NQ_YUV16_MSB) ? 6 : 0;
+        l.transfer = (a.flags & NQ_YUV16_PQ) ? YUV16_PQ : (a.flags & NQ_YUV16_HLG) ? YUV16_HLG : YUV16_SDR;
+        l.k = YUV16_COEF[matrix][(a.flags & NQ_YUV_FULL_RANGE) ? 1 : 0];
+        if (g.fused)
+            launch_resample_yuv16(l, g.crop_x, g.crop_y, g.crop_w, g.crop_h, g.dst_width, g.dst_height, (g.flags & NQ_RESAMPLE_LINEAR) != 0, s);
+        else
+            launch_yuv16_argb(l, a.width, a.height, s);
+    }
+    NQ_CMP_HIP(launch_status());
+    return NQ_OK;
+}
+
+int yuv16_device_form(const Yuv16Frames& a, uint32_t* const* d_dst, const Yuv16Geometry& g, void* hip_stream) {
+    int rc = yuv16_check(a, g.crop_x, g.crop_y, g.crop_w, g.crop_h, d_dst, g.dst_width, g.dst_height, g.flags);
+    if (rc) return rc;
+    rc = compare_use_device(a.device);
+    if (rc) return rc;
+    return yuv16_launches(a, d_dst, g, (hipStream_t) hip_stream);
+}
+
+// The host forms: per frame the luma span and the chroma spans go up into one temporary buffer -- ONE span where u's and v's overlap
+// or touch (the interleaved layouts, and planes that follow each other) -- each at a 16-byte boundary, which keeps what the wide paths
+// need of a layout that has it; the outputs are staged 16-byte aligned.  The device form runs on the staged copies, the outputs are
+// copied back, and everything is freed when the call returns.
+int yuv16_host_form(const Yuv16Frames& a, uint32_t* const* dst, const Yuv16Geometry& g) {
+    int rc = yuv16_check(a, g.crop_x, g.crop_y, g.crop_w, g.crop_h, dst, g.dst_width, g.dst_height, g.flags);
+    if (rc) return rc;
+    rc = compare_use_device(a.device);
+    if (rc) return rc;
+    const int n = a.n;
+    const size_t up16 = 15, out_px = (size_t) g.dst_width * g.dst_height;
+    const uintptr_t yb = a.y_span(), cb = a.c_span();
+    struct Place { size_t y, lo, hi; bool joined; };          // offsets in the buffer: luma, the lower chroma span, the other one
+    std::vector<Place> at(n);
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i], lo = std::min(u, v), hi = std::max(u, v);
+        at[i].y = total; total += (yb + up16) & ~up16;
+        at[i].joined = hi <= lo + cb;
+        at[i].lo = total;
+        if (at[i].joined) { at[i].hi = total + (hi - lo); total += (hi - lo + cb + up16) & ~up16; }
+        else { total += (cb + up16) & ~up16; at[i].hi = total; total += (cb + up16) & ~up16; }
+    }
+    const size_t dpitch = (out_px + 3) & ~(size_t) 3;
+    DevBuf<unsigned char> d_in;
+    DevBuf<uint32_t> d_out;
+    hipStream_t s = nullptr;
+    auto body = [&]() -> int {
+        NQ_CMP_HIP(d_in.reserve(total));
+        NQ_CMP_HIP(d_out.reserve(n * dpitch));
+        std::vector<const uint16_t*> dy(n), du(n), dv(n);
+        std::vector<uint32_t*> d_dst(n);
+        unsigned char* base = d_in.p;
+        for (int i = 0; i < n; ++i) {
+            const bool u_low = a.u[i] <= a.v[i];
+            const unsigned char* lo = reinterpret_cast<const unsigned char*>(u_low ? a.u[i] : a.v[i]);
+            const unsigned char* hi = reinterpret_cast<const unsigned char*>(u_low ? a.v[i] : a.u[i]);
+            dy[i] = reinterpret_cast<const uint16_t*>(base + at[i].y); d_dst[i] = d_out.p + i * dpitch;
+            (u_low ? du : dv)[i] = reinterpret_cast<const uint16_t*>(base + at[i].lo);
+            (u_low ? dv : du)[i] = reinterpret_cast<const uint16_t*>(base + at[i].hi);
+            NQ_CMP_HIP(hipMemcpyAsync(base + at[i].y, a.y[i], yb, hipMemcpyHostToDevice, s));
+            if (at[i].joined) {
+                NQ_CMP_HIP(hipMemcpyAsync(base + at[i].lo, lo, (size_t) (hi - lo) + cb, hipMemcpyHostToDevice, s));
+            } else {
+                NQ_CMP_HIP(hipMemcpyAsync(base + at[i].lo, lo, cb, hipMemcpyHostToDevice, s));
+                NQ_CMP_HIP(hipMemcpyAsync(base + at[i].hi, hi, cb, hipMemcpyHostToDevice, s));
+            }
+        }
+        Yuv16Frames d = a;
+        d.y = dy.data(); d.u = du.data(); d.v = dv.data();
+        const int rc2 = yuv16_launches(d, d_dst.data(), g, s);
+        if (rc2) return rc2;
+        for (int i = 0; i < n; ++i) NQ_CMP_HIP(hipMemcpyAsync(dst[i], d_dst[i], out_px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        NQ_CMP_HIP(hipStreamSynchronize(s));
+        return NQ_OK;
+    };
+    rc = body();
+    if (rc) (void) hipStreamSynchronize(s);
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_frames_from_yuv16_device(int device, void* hip_stream, int n, const uint16_t* const* d_y, const uint16_t* const* d_u,
+                                const uint16_t* const* d_v, int width, int height, int y_stride, int c_stride, int c_step, int yuv16_flags,
+                                uint32_t* const* d_dst) {
+    return yuv16_device_form({device, n, d_y, d_u, d_v, width, height, y_stride, c_stride, c_step, yuv16_flags}, d_dst,
+                             {false, 0, 0, width, height, width, height, 0}, hip_stream);
+}
+
+int nq_frames_from_yuv16(int device, int n, const uint16_t* const* y, const uint16_t* const* u, const uint16_t* const* v, int width,
+                         int height, int y_stride, int c_stride, int c_step, int yuv16_flags, uint32_t* const* dst) {
+    return yuv16_host_form({device, n, y, u, v, width, height, y_stride, c_stride, c_step, yuv16_flags}, dst,
+                           {false, 0, 0, width, height, width, height, 0});
+}
+
+int nq_resample_frames_yuv16_device(int device, void* hip_stream, int n, const uint16_t* const* d_y, const uint16_t* const* d_u,
+                                    const uint16_t* const* d_v, int src_width, int src_height, int y_stride, int c_stride, int c_step,
+                                    int yuv16_flags, int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* d_dst, int dst_width,
+                                    int dst_height, int flags) {
+    return yuv16_device_form({device, n, d_y, d_u, d_v, src_width, src_height, y_stride, c_stride, c_step, yuv16_flags}, d_dst,
+                             {true, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags}, hip_stream);
+}
+
+int nq_resample_frames_yuv16(int device, int n, const uint16_t* const* y, const uint16_t* const* u, const uint16_t* const* v, int src_width,
+                             int src_height, int y_stride, int c_stride, int c_step, int yuv16_flags, int crop_x, int crop_y, int crop_w,
+                             int crop_h, uint32_t* const* dst, int dst_width, int dst_height, int flags) {
+    return yuv16_host_form({device, n, y, u, v, src_width, src_height, y_stride, c_stride, c_step, yuv16_flags}, dst,
+                           {true, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags});
+}
+
+} // extern "C"

@@ -416,4 +416,26 @@ struct CompareLaunch { CompareFrame frame[COMPARE_FRAMES_PER_LAUNCH]; long long*
 int compare_grid(int width, int height);
 void launch_compare(const CompareLaunch& a, int count, bool vec, bool indexed, const unsigned* palette, int K, int* d_bad, hipStream_t s);
 
+// ---- 10-bit YUV 4:2:0 input (nq_yuv16.hip; include/nquant_abi.h "10-bit YUV input"): `count` frames (1 .. YUV16_FRAMES_PER_LAUNCH) go
+// to the kernel BY VALUE, so a launch needs no table in device memory.  Planes hold 16-bit words; strides and the chroma step count
+// samples.  A sample is (word >> shift) & 1023 (shift 6: the high ten bits, 0: the low ten).  k: the 2^14 coefficients of the flag
+// word; transfer: YUV16_SDR, YUV16_PQ or YUV16_HLG (the tables of include/nq_hdr_luts.inc).  path: YUV_BYTE takes any (2-byte aligned)
+// pointers and strides, one pixel per access.  The wide paths -- the caller has checked for EVERY frame of the launch: width a multiple
+// of 4, y 8-byte aligned and y_stride a multiple of 4, and YUV_WIDE_INTERLEAVED: c_step 2, the two chroma pointers one sample apart,
+// the lower one (it goes into the u slot; swap: it is v's) 8-byte aligned and c_stride a multiple of 4; YUV_WIDE_PLANAR: c_step 1, u
+// and v 4-byte aligned, c_stride even.  launch_yuv16_argb converts 1:1 into tight width x height outputs; its wide paths also need
+// every output 16-byte aligned.  launch_resample_yuv16 is launch_resample on the converted frames, bit for bit, without forming them
+// (outputs: 4-byte alignment).  Nothing but the outputs is written. ----
+constexpr int YUV16_FRAMES_PER_LAUNCH = 16;
+enum { YUV16_SDR = 0, YUV16_PQ = 1, YUV16_HLG = 2 };
+struct Yuv16Frame { const void* y; const void* u; const void* v; void* dst; };
+struct Yuv16Launch {
+    Yuv16Frame frame[YUV16_FRAMES_PER_LAUNCH];
+    int count, y_stride, c_stride, c_step, path, swap, shift, transfer;
+    YuvCoef k;
+};
+void launch_yuv16_argb(const Yuv16Launch& a, int width, int height, hipStream_t s);
+void launch_resample_yuv16(const Yuv16Launch& a, int crop_x, int crop_y, int crop_w, int crop_h, int dst_width, int dst_height, bool linear,
+                           hipStream_t s);
+
 } // namespace nq

@@ -63,10 +63,16 @@ def dither_ordered_device(q, d_pixels, widths, heights, palette, limit, d_out_in
                    None if d_out_argb is None else list(d_out_argb), return_stats)
 
 
-def convert_frames_ordered(kind, frames, nMaxColors, limit, refine=0, device=0, size=None, crop=None, linear_resample=True, yuv=None, orient=1):
+def convert_frames_ordered(kind, frames, nMaxColors, limit, refine=0, device=0, size=None, crop=None, linear_resample=True, yuv=None, orient=1, yuv16=None):
     """nq_convert_frames_ordered on host arrays: one shared palette for the frames (convert_frames' palette), `refine` (0..64) k-means
     passes on it over the same frames (refine.py), then the ordered dither with `limit` (0..255).  nMaxColors <= 256.
-    size / crop / linear_resample / yuv / orient as for convert_frames_refined.  Returns what convert_frames returns: (palette, [QuantizedImage per frame])."""
+    size / crop / linear_resample / yuv / orient as for convert_frames_refined.  Returns what convert_frames returns: (palette, [QuantizedImage per frame]).
+    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
+    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
+    with orient: then turned -- before anything else runs."""
+    if yuv16 is not None:
+        from .yuv16 import _converter_frames
+        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
     if not 0 <= int(refine) <= 64:
         raise ValueError("refine must be 0..64, got %r" % (refine,))
     from .orient import _code as _orient_code

@@ -70,7 +70,7 @@ def palette_error(frames, palette, device=0):
 
 
 def convert_frames_refined(kind, frames, nMaxColors, dither, refine, device=0, mode=MODE_PARALLEL_TILED, seeds=None, tile=None, size=None,
-                           crop=None, linear_resample=True, yuv=None, orient=1):
+                           crop=None, linear_resample=True, yuv=None, orient=1, yuv16=None):
     """nq_convert_frames_refined on host arrays: convert_frames with `refine` (0..64) k-means passes on the shared palette, over the
     same frames, between the palette and the dither.  nMaxColors <= 256 unless refine is 0, which gives convert_frames' results.
     size / crop / linear_resample: with size=(width, height) or crop=(x, y, width, height) given, the frames (then all of one size) are
@@ -79,7 +79,13 @@ def convert_frames_refined(kind, frames, nMaxColors, dither, refine, device=0, m
     YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
     orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
     converting kernel --; size and crop are then those of the oriented frames.
+    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
+    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
+    with orient: then turned -- before anything else runs.
     Returns (palette, [QuantizedImage per frame])."""
+    if yuv16 is not None:
+        from .yuv16 import _converter_frames
+        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
     if not 0 <= int(refine) <= 64:
         raise ValueError("refine must be 0..64, got %r" % (refine,))
     from .orient import _code as _orient_code

@@ -101,13 +101,19 @@ def convert_to_webp(kind, image, nMaxColors, dither, band_bits=0, device=0, mode
 
 def convert_frames_to_webp(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, seeds=None, tile=None, band_bits=0, device=0,
                            mode=MODE_PARALLEL_TILED, return_rects=False, hold=None, refine=0, size=None, crop=None, linear_resample=True,
-                           ordered=None, yuv=None, orient=1, delta=True):
+                           ordered=None, yuv=None, orient=1, delta=True, yuv16=None):
     """convert_frames (one shared palette for the ARGB frames, which must have one size) followed by encode_webp of the index maps on
     the same device.  nMaxColors <= 256.  The keywords are convert_frames_to_apng's (apng.py), with band_bits in place of
     segment_bytes and delta (True: every later frame stores its changed rectangle only) in addition: seeds, tile and mode go to the
     dither; hold runs the temporal hold between the two steps; refine the k-means passes on the palette; size / crop /
     linear_resample the reducer; ordered the ordered dither; yuv takes (y, u, v) planes; orient turns / mirrors the frames first.
+    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
+    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
+    with orient: then turned -- before anything else runs.
     Returns (file bytes, palette); with return_rects=True (file bytes, palette, rectangles)."""
+    if yuv16 is not None:
+        from .yuv16 import _converter_frames
+        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("the colour table of a lossless WebP holds at most 256 entries")
     if yuv is None and len({np.asarray(f).shape for f in frames}) > 1:
