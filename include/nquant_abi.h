@@ -113,7 +113,11 @@ int nq_set_band(nq_handle* h, int y0, int image_height);
 #define NQ_OPT_FAST_DITHER 2
 /* NQ_OPT_DITHER_CHAIN (default 0 = automatic): the specialised kernel first walks a wavefront's tiles without the error-diffusion chain
  * wherever ditherPixel replaces the accumulated colour by a colour of the source pixel (LAB, dither, saliencies, 2 * acceptedDiff > 100),
- * and starts over with the chain only when a step needs it (direct branch, second stage); 1 = every step runs the chain.  Same results. */
+ * and starts over with the chain only when a step needs it (direct branch, second stage); 1 = every step runs the chain.  Same results.
+ * 2 = that fused single-kernel light walk wherever it applies; 3 = the split form wherever it applies: a light kernel of its own (87
+ * registers and, at 8x8 tiles, 32 KB of LDS: at least four wavefronts per SIMD) lists the TILES that need the chain, the full walk then runs over that list.  0 picks the split form in the finish
+ * phase of nq_convert_batch[_device], where the chain pass of image i runs on a side stream beside the light kernel of image i + 1, and the
+ * fused form in every other entry point. */
 #define NQ_OPT_DITHER_CHAIN 4
 /* NQ_OPT_MERGE_WALL_SECONDS (default 0 = automatic: 60 s + 1 ms per histogram bin and per merge loop sharing a compute unit with it):
  * seconds of residency after which a merge loop of this handle's calls gives up with NQ_ERR_TIME_LIMIT.  Every loop of the persistent
@@ -123,6 +127,11 @@ int nq_set_option(nq_handle* h, int option, int value);
 /* Diagnostics of the last dither pass: out_fast = 1 if the specialised kernel ran; out_failed_tiles = tiles it handed back to
  * the generic kernel (synchronises the handle's stream). */
 int nq_get_dither_path(nq_handle* h, int32_t* out_fast, int32_t* out_failed_tiles);
+/* Diagnostics, process-wide, cumulative: out3[0] = dither passes that took the split form (NQ_OPT_DITHER_CHAIN), out3[1] = those of them
+ * whose chain pass went onto the side stream of a batch call, out3[2] = tiles their light kernels listed for the chain pass (the lengths
+ * of the need lists).  A pass's need list lives in device memory: its length enters out3[2] when nq_get_dither_path is asked for the
+ * hand-back count of that pass (the two counts are read back together), once per pass. */
+int nq_get_dither_split_stats(int64_t* out3);
 /* Diagnostics: length of every cell's candidate list of the last dither/lookup call (255 = full scan), 65536 bytes each. */
 int nq_get_list_counts(nq_handle* h, uint8_t* closest_counts, uint8_t* nearest_counts);
 /* Self-test hook of the branch-free CIEDE2000 evaluation inside find_nn (csrc/nq_device.h: ciede_terms_fast): for n pairs
@@ -1167,7 +1176,10 @@ int nq_band_color_presence_device(nq_handle* h, const uint32_t* d_argb, int64_t 
  * Batch entry points: an event record costs the GPU ~3 us of queue time, so only the first SIXTEEN handles of a batch record all
  * eight boundaries; for the others {prescan, histogram, nn_init, merge, palette_fill, bluenoise} are reported as -1 (not recorded),
  * `dither` is the per-pixel pass as for every handle, and `total` spans from the start of the image's pre-scan to the END OF THE
- * DITHER PASS -- it leaves out the BlueNoise post-pass of convert(n, false).  nq_get_batch_phase_ms gives the amortised phases. */
+ * DITHER PASS -- it leaves out the BlueNoise post-pass of convert(n, false).  nq_get_batch_phase_ms gives the amortised phases.
+ * `dither` in a batch call whose dither passes take the split form (NQ_OPT_DITHER_CHAIN): the span ends behind the LIGHT kernel on the
+ * launch stream; the image's chain pass and hand-back pass run on a side stream beside the next image and are not inside it (their
+ * time shows in the finish phase of nq_get_batch_phase_ms, which waits for them).  Everywhere else it is the whole per-pixel pass. */
 #define NQ_N_STAGES 8
 int nq_get_stage_ms(const nq_handle* h, float* out8);
 /* Counters of the last merge loop (diagnostics), 16 values: {find_nn calls, merges, 100 MHz ticks inside find_nn, ticks in

@@ -189,11 +189,19 @@ struct nq_handle {
     DevBuf<float> d_user_sal;
     int band_y0 = 0, band_image_h = 0; // nq_set_band: this handle dithers a row band of a larger image (0, 0 = a whole image)
     int use_fast_dither = 1;          // NQ_OPT_FAST_DITHER: the specialised dither kernel where the configuration allows it
-    int dither_chain_always = 0;      // NQ_OPT_DITHER_CHAIN: 1 = the specialised kernel runs the error chain in every step (no light walk)
+    // NQ_OPT_DITHER_CHAIN: 0 automatic, 1 the error chain in every step, 2 the fused light walk, 3 the split form (a new handle starts from
+    // the environment's NQ_DITHER_CHAIN = 0..3: whole-suite runs under one form, tests/fuzz_parity.py)
+    int dither_chain = [] { const char* e = std::getenv("NQ_DITHER_CHAIN"); const int v = e ? std::atoi(e) : 0; return v >= 0 && v <= 3 ? v : 0; }();
+    // batch entry points, finish phase: the image's chain pass and hand-back pass go onto chain_stream (the split form is "automatic"
+    // there); chain_gate: behind the light kernel on the main stream, chain_done: behind the image's last kernel on chain_stream
+    hipStream_t chain_stream = nullptr;
+    hipEvent_t chain_gate = nullptr, chain_done = nullptr;
+    bool chain_on_side = false;       // the last dither pass ended on chain_stream (chain_done was recorded there)
     bool dither_events_fresh = false; // the last call on the handle was a stand-alone dither (events 5..7 are newer than stage_ms)
     int last_dither_fast = 0;         // diagnostics: 1 if the last dither pass ran gilbert_fast_kernel
+    bool split_uncounted = false;     // ... it took the split form and its need count is not yet in nq_get_dither_split_stats
     int last_dither_failed_tiles = 0; // ... and how many tiles it handed back to the generic kernel (read lazily)
-    DevBuf<int> d_failed;             // {count, tile indices...} of those tiles
+    DevBuf<int> d_failed;             // {need count, count, tile indices..., need list...}: failed_list(), launch_gilbert_fast (nq_kernels.h)
     DevBuf<float> scan_f;             // merge loop: position-indexed scan arrays (two generations)
     DevBuf<int> scan_i;
     DevBuf<float> scan_box;           // merge loop: bounding boxes of the 64-position blocks (1024 x 8 floats)
@@ -318,6 +326,8 @@ struct nq_handle {
         for (auto& e : ev) if (e) (void) hipEventDestroy(e);
         for (auto& e : bev) if (e) (void) hipEventDestroy(e);
         if (lane_gate) (void) hipEventDestroy(lane_gate);
+        if (chain_gate) (void) hipEventDestroy(chain_gate);
+        if (chain_done) (void) hipEventDestroy(chain_done);
         if (copy_stream) (void) hipStreamDestroy(copy_stream);
         if (lane_stream) (void) hipStreamDestroy(lane_stream);
         for (auto& ls : more_lanes) if (ls) (void) hipStreamDestroy(ls);
@@ -395,6 +405,12 @@ int upload_palette(nq_handle* h, const uint32_t* palette, int K) {
     h->palette_stream = h->stream; h->palette_synced = false;
     return NQ_OK;
 }
+// nq_get_dither_split_stats: split-form dither passes of this process / of those, with the chain pass on a side stream / tiles their light
+// kernels listed, counted when nq_get_dither_path reads a pass's counts back (once per pass)
+static std::atomic<long long> g_split_passes{0}, g_split_side{0}, g_split_listed{0};
+// the hand-back list of launch_gilbert_fast inside d_failed (one word in front of it: the need count of the split form, nq_kernels.h)
+int* failed_list(nq_handle* h) { return h->d_failed.p + 1; }
+size_t failed_words(const nq::TileGeom& T) { return 2 * ((size_t) T.tiles_x * T.tiles_y + 1); }
 void* packed_lists(nq_handle* h) { return h->sc->cell_lists.p + 2 * (size_t) 65536 * 32 + 2 * 65536; }
 
 // candidate lists per colour cell for this palette (nq_lists.inc); empty view = full scans
@@ -1089,8 +1105,8 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
     // (the specialised dither kernel's hand-back list is sized here, so that the builders' launch can clear its count)
     const bool maybe_fast = !ov.blue_only && !sequential && h->use_fast_dither && K > 32 && K <= 256;
     bool failed_cleared = false;
-    if (maybe_fast) NQ_HIP(h, h->d_failed.reserve((size_t) T.tiles_x * T.tiles_y + 1));
-    { int rcl = lists_for_call(h, P, &lv, want_sal ? (const int*) d_argb : nullptr, n, salSubst ? 1 : 0, &sal_done, maybe_fast ? h->d_failed.p : nullptr,
+    if (maybe_fast) NQ_HIP(h, h->d_failed.reserve(failed_words(T)));
+    { int rcl = lists_for_call(h, P, &lv, want_sal ? (const int*) d_argb : nullptr, n, salSubst ? 1 : 0, &sal_done, maybe_fast ? failed_list(h) : nullptr,
                                &failed_cleared); if (rcl) return rcl; }
     const float* d_sal = nullptr;
     if (staged) d_sal = hasSal ? ov.d_sal : nullptr;
@@ -1111,22 +1127,37 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
         NQ_HIP(h, hipMemsetAsync(h->d_seqseen.p, 0, (size_t) K, h->stream));
     }
     const int* d_tile_list = nullptr;
+    hipStream_t tail_stream = h->stream;          // where the dither pass ends: the side stream once a chain pass went there
+    h->chain_on_side = false;
     h->last_dither_fast = 0;
+    h->split_uncounted = false;
     if (ov.blue_only) { /* BlueNoise.dither alone: the indices are already in d_out_index */ }
     else {
     if (!sequential && h->use_fast_dither && gilbert_fast_eligible(P, G, T, lv)) {
         // production path (nq_dither_fast.hip); the tiles it cannot finish come back as a list for the generic kernel below
-        NQ_HIP(h, h->d_failed.reserve((size_t) T.tiles_x * T.tiles_y + 1));
+        NQ_HIP(h, h->d_failed.reserve(failed_words(T)));
+        // NQ_OPT_DITHER_CHAIN.  Automatic: the split form with the chain pass on the side stream in the finish phase of a batch (chain_stream
+        // set), the fused light walk everywhere else
+        int chain_mode = nq::FAST_CHAIN_FUSED;
+        if (h->dither_chain == 1) chain_mode = nq::FAST_CHAIN_ALWAYS;
+        else if (h->dither_chain == 3 || (h->dither_chain == 0 && h->chain_stream)) chain_mode = nq::FAST_CHAIN_SPLIT;
+        const bool split = chain_mode == nq::FAST_CHAIN_SPLIT && nq::gilbert_fast_split_eligible(P, G);
+        const bool side = split && h->chain_stream && h->chain_stream != h->stream;
+        if (split) ++g_split_passes;
+        if (side) ++g_split_side;
+        h->split_uncounted = split;
         NQ_HIP(h, launch_gilbert_fast(P, G, T, lv, (const int*) d_argb, d_sal, h->d_palette.p, (long long) seed, d_out_index,
-                                      post ? nullptr : (int*) d_out_argb, h->d_failed.p, packed_lists(h), h->stream, failed_cleared,
-                                      h->dither_chain_always != 0));
-        d_tile_list = h->d_failed.p;
+                                      post ? nullptr : (int*) d_out_argb, failed_list(h), packed_lists(h), h->stream, failed_cleared,
+                                      chain_mode, side ? h->chain_stream : nullptr, side ? h->chain_gate : nullptr));
+        if (side) tail_stream = h->chain_stream;
+        d_tile_list = failed_list(h);
         h->last_dither_fast = 1;
     }
     launch_gilbert(P, G, T, lv, (const int*) d_argb, d_sal, h->d_palette.p, h->d_bincache.p, (long long) seed, sequential ? 1 : 0,
                    h->d_scalars.p, d_out_index, post ? nullptr : (int*) d_out_argb,
                    seq_lab_post ? h->d_seqlog.p : nullptr, seq_lab_post ? h->d_seqlog.p + log_cap : nullptr,
-                   seq_lab_post ? h->d_seqseen.p : nullptr, log_cap, d_tile_list, h->stream);
+                   seq_lab_post ? h->d_seqseen.p : nullptr, log_cap, d_tile_list, tail_stream);
+    if (tail_stream != h->stream) { NQ_HIP(h, hipEventRecord(h->chain_done, tail_stream)); h->chain_on_side = true; }
     }
     rec(h, 6);
     if (seq_lab_post) {
@@ -1363,9 +1394,11 @@ struct BatchGuard {
     nq_handle* const* hs; int n;
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> events;
+    hipStream_t side = nullptr;          // the finish phase's side stream, once work may be on it
     BatchGuard(nq_handle* const* hh, int nn) : hs(hh), n(nn) { for (int i = 0; i < n; ++i) streams.push_back(hs[i]->stream); }
     ~BatchGuard() {
-        for (int i = 0; i < n; ++i) { hs[i]->stream = streams[i]; hs[i]->sc = &hs[i]->own; hs[i]->light_events = false; }
+        if (side) (void) hipStreamSynchronize(side);        // (a chain pass of a call that failed half-way may still run there)
+        for (int i = 0; i < n; ++i) { hs[i]->stream = streams[i]; hs[i]->sc = &hs[i]->own; hs[i]->light_events = false; hs[i]->chain_stream = nullptr; }
         for (hipEvent_t e : events) (void) hipEventDestroy(e);
     }
 };
@@ -1468,7 +1501,7 @@ int nq_set_option(nq_handle* h, int option, int value) {
     if (!h) return NQ_ERR_INVALID;
     if (option == NQ_OPT_CELL_LISTS) { h->use_lists = value != 0; return NQ_OK; }
     if (option == NQ_OPT_FAST_DITHER) { h->use_fast_dither = value != 0; return NQ_OK; }
-    if (option == NQ_OPT_DITHER_CHAIN) { h->dither_chain_always = value != 0; return NQ_OK; }
+    if (option == NQ_OPT_DITHER_CHAIN) { h->dither_chain = value >= 0 && value <= 3 ? (int) value : 1; return NQ_OK; }
     if (option == NQ_OPT_MERGE_WALL_SECONDS) { h->merge_wall_s = value > 0 ? value : 0; return NQ_OK; }
     NQ_FAIL(h, NQ_ERR_INVALID, "unknown option %d", option);
 }
@@ -1541,11 +1574,17 @@ int nq_get_dither_path(nq_handle* h, int32_t* out_fast, int32_t* out_failed_tile
         *out_failed_tiles = 0;
         if (h->last_dither_fast && h->d_failed.p) {
             NQ_HIP(h, hipStreamSynchronize(h->stream));
-            int cnt = 0;
-            NQ_HIP(h, hipMemcpy(&cnt, h->d_failed.p, sizeof(int), hipMemcpyDeviceToHost));
-            *out_failed_tiles = cnt;
+            int cnt[2] = {0, 0};                   // {need count of the split form, hand-back count}
+            NQ_HIP(h, hipMemcpy(cnt, h->d_failed.p, sizeof(cnt), hipMemcpyDeviceToHost));
+            *out_failed_tiles = cnt[1];
+            if (h->split_uncounted) { g_split_listed += cnt[0]; h->split_uncounted = false; }
         }
     }
+    return NQ_OK;
+}
+int nq_get_dither_split_stats(int64_t* out3) {
+    if (!out3) return NQ_ERR_INVALID;
+    out3[0] = g_split_passes.load(); out3[1] = g_split_side.load(); out3[2] = g_split_listed.load();
     return NQ_OK;
 }
 int nq_get_params(const nq_handle* h, nq_params* out) {
@@ -1803,6 +1842,27 @@ int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const in
     return nq_convert_frames_refined(h, n, argb, widths, heights, nMaxColors, 0, dither, rng_seeds, mode, out_argb, out_index, out_palette, out_K);
 }
 
+// Finish phase of the batch entry points: every handle's chain_stream for the dither passes that follow.  *side: the side stream (then the
+// caller alternates two scratch sets and orders the streams by chain_done), or null with NQ_DITHER_SIDE_STREAM=0 (A/B timing): the split
+// form in plain serial order on the main stream.  The BatchGuard of the call takes chain_stream back.
+int finish_side_stream(nq_handle* h0, nq_handle* const* hs, int n, hipStream_t* side) {
+    *side = nullptr;
+    bool use_side = true;
+    if (const char* e = std::getenv("NQ_DITHER_SIDE_STREAM")) use_side = std::atoi(e) != 0;
+    if (!use_side) {
+        for (int i = 0; i < n; ++i) hs[i]->chain_stream = hs[i]->stream;
+        return NQ_OK;
+    }
+    if (!h0->lane_stream) NQ_HIP(h0, hipStreamCreateWithFlags(&h0->lane_stream, hipStreamNonBlocking));
+    for (int i = 0; i < n; ++i) {
+        if (!hs[i]->chain_gate) NQ_HIP(h0, hipEventCreateWithFlags(&hs[i]->chain_gate, hipEventDisableTiming));
+        if (!hs[i]->chain_done) NQ_HIP(h0, hipEventCreateWithFlags(&hs[i]->chain_done, hipEventDisableTiming));
+        hs[i]->chain_stream = h0->lane_stream;
+    }
+    *side = h0->lane_stream;
+    return NQ_OK;
+}
+
 int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* d_argb, const int32_t* widths, const int32_t* heights,
                             int nMaxColors, int dither, const int64_t* rng_seeds, int mode,
                             uint32_t* const* d_out_argb, uint16_t* const* d_out_index,
@@ -1926,12 +1986,26 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
             rc = palette_check(hs[i], jobs[i], out_K + i);
             if (rc) return batch_fail(h0, hs[i], rc);
         }
+    // The chain pass and the hand-back pass of image i (a few wavefronts, one chain's latency) run on a side stream beside the lists,
+    // saliency map and light kernel of image i + 1 (dither_device, chain_stream).  What they read of the per-image scratch -- saliency plane,
+    // list records -- alternates between two sets by image parity; the main stream waits for image i's side work before image i + 2
+    // reuses its set, and at the end of the phase.
+    hipStream_t side = nullptr;
+    rc = finish_side_stream(h0, hs, n, &side);
+    if (rc) return batch_fail(h0, h0, rc);
+    guard.side = side;
     for (int i = 0; i < n; ++i) {
         uint32_t* pal = out_palettes + (size_t) i * palette_stride;
+        if (side) {
+            hs[i]->sc = lane_sc[i & 1];
+            if (i >= 2 && hs[i - 2]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(lane_s[0], hs[i - 2]->chain_done, 0));
+        }
         rc = dither_device(hs[i], d_argb[i], widths[i], heights[i], pal, out_K[i], dither, rng_seeds[i], mode, d_out_argb[i],
                            d_out_index ? d_out_index[i] : nullptr);
         if (rc) return batch_fail(h0, hs[i], rc);
     }
+    for (int i = std::max(0, n - 2); i < n; ++i)
+        if (hs[i]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(lane_s[0], hs[i]->chain_done, 0));
     (void) hipEventRecord(h0->bev[3], lane_s[0]);
     NQ_HIP(h0, hipStreamSynchronize(lane_s[0]));
     for (int i = 0; i < n; ++i) finish_timing(hs[i]);
@@ -1996,6 +2070,11 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
     if (rc) return rc;
     (void) hipEventRecord(h0->bev[2], h0->stream);
     for (int i = 0; i < n; ++i) if (jobs[i].merge) rec(hs[i], 4);
+    // (the chain pass of image i beside the light kernel of image i + 1, two scratch sets by parity: as in nq_convert_batch_device)
+    hipStream_t side = nullptr;
+    rc = finish_side_stream(h0, hs, n, &side);
+    if (rc) return batch_fail(h0, h0, rc);
+    guard.side = side;
     for (int i = 0; i < n; ++i) {
         uint32_t* pal = out_palettes + (size_t) i * palette_stride;
         if (jobs[i].merge) {
@@ -2004,17 +2083,24 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
         }
         const int r = i % RING;
         if (i >= RING) NQ_HIP(h0, hipStreamWaitEvent(h0->stream, ev_dl[i - RING], 0));     // the slot's previous result has left
+        if (side) {
+            hs[i]->sc = (i & 1) && n > 1 ? &hs[1]->own : &h0->own;
+            if (i >= 2 && hs[i - 2]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(h0->stream, hs[i - 2]->chain_done, 0));
+        }
         rc = dither_device(hs[i], hs[i]->d_in.p, widths[i], heights[i], pal, out_K[i], dither, rng_seeds[i], mode,
                            (uint32_t*) h0->ring_argb[r].p, h0->ring_index[r].p);
         if (rc) return batch_fail(h0, hs[i], rc);
         NQ_HIP(h0, hipEventRecord(ev_done[i], h0->stream));
         NQ_HIP(h0, hipStreamWaitEvent(cs, ev_done[i], 0));
+        if (hs[i]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(cs, hs[i]->chain_done, 0));
         const size_t px = (size_t) widths[i] * heights[i];
         NQ_HIP(h0, hipMemcpyAsync(out_argb[i], h0->ring_argb[r].p, px * sizeof(int), hipMemcpyDeviceToHost, cs));
         if (out_index && out_index[i])
             NQ_HIP(h0, hipMemcpyAsync(out_index[i], h0->ring_index[r].p, px * sizeof(uint16_t), hipMemcpyDeviceToHost, cs));
         NQ_HIP(h0, hipEventRecord(ev_dl[i], cs));
     }
+    for (int i = std::max(0, n - 2); i < n; ++i)
+        if (hs[i]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(h0->stream, hs[i]->chain_done, 0));
     (void) hipEventRecord(h0->bev[3], h0->stream);
     NQ_HIP(h0, hipStreamSynchronize(h0->stream));
     NQ_HIP(h0, hipStreamSynchronize(cs));

@@ -189,8 +189,9 @@ __global__ void __launch_bounds__(256) build_lab_lists_kernel(DevParams P, const
                                                               void* packed, int* failed) {
     extern __shared__ __align__(16) unsigned char smem[];
     // packed (nullable): each builder also writes its half of the specialised kernels' records; failed (nullable): the hand-back count of
-    // the dither kernel that follows on the stream starts at zero (one fill per image less)
-    if (failed && blockIdx.x == 0 && threadIdx.x == 0) failed[0] = 0;
+    // the dither kernel that follows on the stream starts at zero (one fill per image less), and the need count of its split form, the
+    // word in front of it (launch_gilbert_fast, nq_kernels.h)
+    if (failed && blockIdx.x == 0 && threadIdx.x == 0) { failed[-1] = 0; failed[0] = 0; }
     if (blockIdx.x < 256) closest_lists_body(P, g_palette, wA, wR, wG, wB, closest, closestCount, (int) blockIdx.x, packed);
     else if (blockIdx.x < 512) nearest_lists_body(P, g_palette, kstart, box, nearest, nearestCount, (int) blockIdx.x - 256, smem, packed);
     else saliency_body(P, sal.salSubst, sal.pixels, sal.N, sal.out, sal.vec4, (int) blockIdx.x - 512, sal.blocks, reinterpret_cast<double*>(smem));

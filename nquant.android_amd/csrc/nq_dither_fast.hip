@@ -3,6 +3,7 @@
 #include "nq_device.h"
 #include "nq_kernels.h"
 #include "../../include/nquant_abi.h"      // NQ_FAST_ST_*: the modes of nq_selftest_fast
+#include <algorithm>
 #include <cstring>
 #include <cmath>
 #include <cstdlib>
@@ -48,6 +49,11 @@ struct FastArgs {
     const uint4* cont;       // [2][65536]: candidates 15..30 of the closest / nearest lists
     int debug;               // timing experiments only (builds with -DNQ_FAST_KNOCKOUT): bit mask of stages to leave out
     int chainAlways;         // NQ_OPT_DITHER_CHAIN = 1: every wavefront runs the error chain (no light walk)
+    // the split form (gilbert_light_kernel, then gilbert_fast_kernel over the tiles it listed): the need list is a count plus up to
+    // failedCap tile numbers, filled by the light kernel; `listed` makes gilbert_fast_kernel a chain pass: slot i of the grid walks tile needTiles[i]
+    int* needCount;
+    int* needTiles;
+    int listed;
 };
 // instruction budget by block (tools/fast_budget.py compiles this file with -DNQ_FAST_MARKS and counts between the markers)
 #ifdef NQ_FAST_MARKS
@@ -579,6 +585,49 @@ __device__ __forceinline__ int fast_lab_index(const FastLds& S, const FastLookup
     return qidx;
 }
 
+// write-out of gilbert_fast_kernel / gilbert_light_kernel (behind the barrier that ends the walks): the wave's 64 tiles leave row by row; a
+// tile whose tileinfo extent is zero (dead lane, or a tile the light kernel left to the chain pass) writes nothing
+__device__ __forceinline__ void fast_write_out(const FastLds& S, const FastArgs& F, const TileGeom& T, int tid, int width,
+                                               unsigned short* __restrict__ out_index, int* __restrict__ out_argb) {
+    // lane l handles group it * 64 + l of every tile row
+    {
+        const int wave = tid >> 6, lane = tid & 63;
+        const unsigned char* wstage = S.stage + (size_t) (wave * 64) * F.strideBytes;
+        const int4* winfo = S.tileinfo + wave * 64;
+        const int tw = T.tile_w, th = T.tile_h;
+        if (F.vecOut) {
+            const int gpr = tw >> 2;                    // 4-pixel groups per tile row
+            for (int r = 0; r < th; ++r)
+                for (int it = 0; it < gpr; ++it) {
+                    const int g = it * 64 + lane;
+                    const int t = g / gpr, cgrp = (g - t * gpr) * 4;
+                    const int4 ti = winfo[t];
+                    if (r < ti.w && cgrp < ti.z) {          // ti.z = tile width (multiple of 4 here), ti.w = tile height
+                        const unsigned kk = *reinterpret_cast<const unsigned*>(wstage + (size_t) t * F.strideBytes + r * tw + cgrp);
+                        const long long bidx = (long long) (ti.y + r) * width + ti.x + cgrp;
+                        const unsigned k0 = kk & 0xFF, k1 = (kk >> 8) & 0xFF, k2 = (kk >> 16) & 0xFF, k3 = kk >> 24;
+                        uint2 iv; iv.x = k0 | (k1 << 16); iv.y = k2 | (k3 << 16);
+                        *reinterpret_cast<uint2*>(out_index + bidx) = iv;
+                        if (out_argb) *reinterpret_cast<int4*>(out_argb + bidx) = make_int4(S.argb[k0], S.argb[k1], S.argb[k2], S.argb[k3]);
+                    }
+                }
+        } else {
+            for (int r = 0; r < th; ++r)
+                for (int it = 0; it < tw; ++it) {
+                    const int g = it * 64 + lane;
+                    const int t = g / tw, cc = g - t * tw;
+                    const int4 ti = winfo[t];
+                    if (r < ti.w && cc < ti.z) {
+                        const int k = wstage[(size_t) t * F.strideBytes + r * tw + cc];
+                        const long long bidx = (long long) (ti.y + r) * width + ti.x + cc;
+                        out_index[bidx] = (unsigned short) k;
+                        if (out_argb) out_argb[bidx] = S.argb[k];
+                    }
+                }
+        }
+    }
+}
+
 // KIND 1: PnnLABQuantizer (the family described at the top).  KIND 0: PnnQuantizer with dither = true, 32 < K <= 256, an image without
 // transparency: GilbertCurve has no saliencies there, so a step is accumulate -> nearestColorIndex(c2) -> limiter -> queue
 // (NQ/GilbertCurve.java:212-229 takes the plain lookup; NQ/PnnQuantizer.java:377-391 getDitherFn(true) = nearestColorIndex).
@@ -589,6 +638,13 @@ __global__ void __launch_bounds__(256, MINWAVES) gilbert_fast_kernel(DevParams P
                                                                       unsigned short* __restrict__ out_index, int* __restrict__ out_argb) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tilepx = T.tile_w * T.tile_h;
+    const int ntiles = T.tiles_x * T.tiles_y;
+    // chain pass of the split form: the grid covers every tile, the workgroups beyond the need list leave before any barrier
+    int nlisted = 0;
+    if (F.listed) {
+        nlisted = min(*F.needCount, min(F.failedCap, ntiles));
+        if ((int) blockIdx.x * 256 >= nlisted) return;
+    }
     FastLds S;
     {
         unsigned char* p = smem;
@@ -619,9 +675,14 @@ __global__ void __launch_bounds__(256, MINWAVES) gilbert_fast_kernel(DevParams P
             for (int i = tid; i < tilepx; i += 256) pp[s * tilepx + i] = i < T.path_len[s] ? T.path[s][i] : 0u;
     }
 
-    const int ntiles = T.tiles_x * T.tiles_y;
-    const int tile = blockIdx.x * 256 + tid;
-    const bool live = tile < ntiles;
+    const int slot = blockIdx.x * 256 + tid;
+    int tile = slot;
+    bool live = slot < ntiles;
+    if (F.listed) {
+        live = slot < nlisted;
+        tile = live ? F.needTiles[slot] : 0;
+        live = live && tile >= 0 && tile < ntiles;
+    }
     const int ty = live ? tile / T.tiles_x : 0, tx = live ? tile - ty * T.tiles_x : 0;
     const int shape = (tx == T.tiles_x - 1 ? 1 : 0) | (ty == T.tiles_y - 1 ? 2 : 0);
     const int steps = live ? T.path_len[shape] : 0;
@@ -817,45 +878,116 @@ __global__ void __launch_bounds__(256, MINWAVES) gilbert_fast_kernel(DevParams P
     }
     __syncthreads();
 
-    // write-out: the wave's 64 tiles leave row by row; lane l handles group it * 64 + l of every tile row
-    {
-        const int wave = tid >> 6, lane = tid & 63;
-        const unsigned char* wstage = S.stage + (size_t) (wave * 64) * F.strideBytes;
-        const int4* winfo = S.tileinfo + wave * 64;
-        const int tw = T.tile_w, th = T.tile_h;
-        if (F.vecOut) {
-            const int gpr = tw >> 2;                    // 4-pixel groups per tile row
-            for (int r = 0; r < th; ++r)
-                for (int it = 0; it < gpr; ++it) {
-                    const int g = it * 64 + lane;
-                    const int t = g / gpr, cgrp = (g - t * gpr) * 4;
-                    const int4 ti = winfo[t];
-                    if (r < ti.w && cgrp < ti.z) {          // ti.z = tile width (multiple of 4 here), ti.w = tile height
-                        const unsigned kk = *reinterpret_cast<const unsigned*>(wstage + (size_t) t * F.strideBytes + r * tw + cgrp);
-                        const long long bidx = (long long) (ti.y + r) * width + ti.x + cgrp;
-                        const unsigned k0 = kk & 0xFF, k1 = (kk >> 8) & 0xFF, k2 = (kk >> 16) & 0xFF, k3 = kk >> 24;
-                        uint2 iv; iv.x = k0 | (k1 << 16); iv.y = k2 | (k3 << 16);
-                        *reinterpret_cast<uint2*>(out_index + bidx) = iv;
-                        if (out_argb) *reinterpret_cast<int4*>(out_argb + bidx) = make_int4(S.argb[k0], S.argb[k1], S.argb[k2], S.argb[k3]);
-                    }
-                }
-        } else {
-            for (int r = 0; r < th; ++r)
-                for (int it = 0; it < tw; ++it) {
-                    const int g = it * 64 + lane;
-                    const int t = g / tw, cc = g - t * tw;
-                    const int4 ti = winfo[t];
-                    if (r < ti.w && cc < ti.z) {
-                        const int k = wstage[(size_t) t * F.strideBytes + r * tw + cc];
-                        const long long bidx = (long long) (ti.y + r) * width + ti.x + cc;
-                        out_index[bidx] = (unsigned short) k;
-                        if (out_argb) out_argb[bidx] = S.argb[k];
-                    }
-                }
-        }
-    }
+    fast_write_out(S, F, T, tid, width, out_index, out_argb);
 }
 
+// The light walk as a kernel of its own (the split form): what gilbert_fast_kernel's light walk does, without the full
+// walk's 29 x 4 register window behind it: 87 VGPRs, and at 8x8 tiles 32 KB of LDS, so up to five wavefronts per SIMD fit instead of two
+// (the launch bounds guarantee four, and a 4096 x 4096 launch is four per SIMD; larger tiles are bounded by their LDS block).  Same device functions, same Random
+// per tile, same draw order.  The exit is per TILE: a lane whose step needs the error chain appends its tile to the need list, gives its
+// tileinfo entry a zero extent (the write-out then skips the tile) and goes idle; the others walk on.  gilbert_fast_kernel with
+// FastArgs::listed then walks the listed tiles with the chain.  A tile listed here is handed back (FastArgs::failed) by the chain pass
+// alone, if at all: no tile enters that list twice.  LDS: the f64 gamma table stays in constant memory (only the rare exact paths read it).
+__host__ __device__ __forceinline__ size_t light_lds_bytes(int tilepx, int strideBytes) { return fast_lds_bytes(tilepx, strideBytes) - 256 * 8; }
+__global__ void __launch_bounds__(256, 4) gilbert_light_kernel(DevParams P, GilbertConsts G, TileGeom T, FastArgs F,
+                                                               const int* __restrict__ pixels, const float* __restrict__ saliency,
+                                                               const int* __restrict__ g_palette, long long seed,
+                                                               unsigned short* __restrict__ out_index, int* __restrict__ out_argb) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tilepx = T.tile_w * T.tile_h;
+    FastLds S;
+    {
+        unsigned char* p = smem;
+        S.argb = (const int*) p; p += 256 * 4;
+        S.lab = (const float4*) p; p += 256 * 16;
+        S.gamma = g_tab.gamma;
+        S.gamma32 = (const float*) p; p += 256 * 4;
+        S.blue = (const signed char*) p; p += 4096;
+        S.path = (const unsigned*) p; p += (size_t) 4 * tilepx * 4;
+        S.tileinfo = (int4*) p; p += 256 * 16;
+        S.stage = p;
+    }
+    const int K = P.K;
+    const int tid = threadIdx.x;
+    {
+        int* a = (int*) S.argb; float4* l = (float4*) S.lab; float* g32 = (float*) S.gamma32;
+        const int c2 = tid < K ? g_palette[tid] : 0;
+        a[tid] = c2;
+        const Lab l2 = RGB2LAB(c2);                    // getLab(palette[i]) (NQ/PnnLABQuantizer.java:352)
+        l[tid] = make_float4(l2.L, l2.A, l2.B, 0.f);
+        g32[tid] = (float) g_tab.gamma[tid];
+        for (int i = tid; i < 1024; i += 256) ((int*) S.blue)[i] = ((const int*) g_tab.blue)[i];
+        unsigned* pp = (unsigned*) S.path;
+        for (int s = 0; s < 4; ++s)
+            for (int i = tid; i < tilepx; i += 256) pp[s * tilepx + i] = i < T.path_len[s] ? T.path[s][i] : 0u;
+    }
+    const int ntiles = T.tiles_x * T.tiles_y;
+    const int tile = blockIdx.x * 256 + tid;
+    const bool live = tile < ntiles;
+    const int ty = live ? tile / T.tiles_x : 0, tx = live ? tile - ty * T.tiles_x : 0;
+    const int shape = (tx == T.tiles_x - 1 ? 1 : 0) | (ty == T.tiles_y - 1 ? 2 : 0);
+    const int steps = live ? T.path_len[shape] : 0;
+    const int x0 = tx * T.tile_w, y0 = ty * T.tile_h;
+    S.tileinfo[tid] = make_int4(x0, y0, live ? T.shape_w[shape] : 0, live ? T.shape_h[shape] : 0);
+    __syncthreads();
+
+    const unsigned* __restrict__ path = S.path + shape * tilepx;
+    unsigned char* stage = S.stage + (size_t) tid * F.strideBytes;
+    const int width = T.width;
+    long long rng = jr_seed((long long) mix64((unsigned long long) seed + (unsigned long long) (T.tile_base + tile)));
+    FastLookup X;
+    X.packed = F.packed; X.cont = F.cont; X.qa = F.qa; X.qb = F.qb; X.qc = F.qc;
+    X.ratio = P.ratio; X.wr = P.PR * (1 - P.ratio); X.wg = P.PG * (1 - P.ratio); X.wb = P.PB * (1 - P.ratio);
+    X.kfirst = P.hasAlpha ? 1 : 0;
+    bool failed = false, listed = false;
+    int left = steps;                           // steps this lane still walks: 0 once its tile is listed
+    unsigned d_next = 0;
+    int bidx_next = 0, pixel_next = 0;
+    float sal_next = 0.f;
+    const int maxsteps = T.path_len[0];
+    if (steps > 0) {
+        d_next = path[0];
+        bidx_next = (x0 + (int) (d_next & 0xFFFFu)) + (y0 + (int) (d_next >> 16)) * width;
+        pixel_next = pixels[bidx_next];
+        sal_next = saliency[bidx_next];
+    }
+    for (int s = 0; s < maxsteps; ++s) {
+        if (s < left) {
+            const int pixel = pixel_next;
+            const float sal = sal_next;
+            const int dxx = (int) (d_next & 0xFFFFu), dyy = (int) (d_next >> 16);
+            const int xx = x0 + dxx, yy = y0 + dyy + T.y_origin;
+            const int pos = dyy * T.tile_w + dxx;
+            if (s + 1 < steps) {
+                d_next = path[s + 1];
+                bidx_next = (x0 + (int) (d_next & 0xFFFFu)) + (y0 + (int) (d_next >> 16)) * width;
+                pixel_next = pixels[bidx_next];
+                sal_next = saliency[bidx_next];
+            }
+            bool need = K >= 256 && sal > .99f;
+            int c = 0;
+            if (!need) c = fast_dither_color<true>(S, G, K, xx, yy, 0, pixel, sal, need);
+            if (need) { listed = true; left = 0; }
+            else {
+                const int qidx = fast_lab_index<true>(S, X, F, K, c, rng, failed);
+                stage[pos] = (unsigned char) qidx;
+            }
+        }
+    }
+    NQ_COUNT_SUM(FC_CHAIN_LIGHT, live && !listed, 1);
+    NQ_COUNT_SUM(FC_CHAIN_REWALK, listed, 1);
+    if (listed) {
+        const int slot = atomicAdd(F.needCount, 1);
+        if (slot < F.failedCap) F.needTiles[slot] = tile;
+        S.tileinfo[tid] = make_int4(x0, y0, 0, 0);
+    }
+    else if (failed && live) {
+        const int slot = atomicAdd(F.failed, 1);
+        if (slot < F.failedCap) F.failed[1 + slot] = tile;
+    }
+    __syncthreads();
+    fast_write_out(S, F, T, tid, width, out_index, out_argb);
+}
 
 // ------------------------------------------------------------------------------------------------
 // The same two lookups as stand-alone kernels behind nq_nearest_index / nq_closest_tuple / LOOKUP_ONLY (BASELINE cfg 2): the
@@ -1201,6 +1333,10 @@ bool gilbert_fast_eligible(const DevParams& P, const GilbertConsts& G, const Til
     // PnnQuantizer: dither = true (nearestColorIndex), no transparent colour (the RGB nearest lists exist for such images only), no saliencies
     return common && G.dither && !P.hasAlpha && !G.hasSaliencies;
 }
+// the launches that take the light walk: those gilbert_light_kernel + chain pass can replace (FAST_CHAIN_SPLIT)
+bool gilbert_fast_split_eligible(const DevParams& P, const GilbertConsts& G) {
+    return P.kind == 1 && G.hasSaliencies && G.dither && 2 * std::max(2, P.K - G.margin) > 100;
+}
 // the packed records are needed by the LAB lookups and by the RGB dither kernel
 bool fast_pack_wanted(const DevParams& P, const ListsView& lv) {
     return fast_lookup_eligible(P, lv) || (P.kind == 0 && P.K > 32 && P.K <= 256 && !P.hasSemi && !P.hasAlpha && lv.nearest && lv.closest);
@@ -1227,7 +1363,8 @@ static FastArgs fast_args(const DevParams& P, const ListsView& lv, void* d_packe
 }
 hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv, const int* d_pixels,
                                const float* d_saliency, const int* d_palette, long long seed, unsigned short* d_index, int* d_argb,
-                               int* d_failed, void* d_packed, hipStream_t s, bool failed_cleared, bool chain_always) {
+                               int* d_failed, void* d_packed, hipStream_t s, bool failed_cleared, int chain_mode, hipStream_t chain_stream,
+                               hipEvent_t chain_gate) {
     const int ntiles = T.tiles_x * T.tiles_y;
     const int tilepx = T.tile_w * T.tile_h;
     FastArgs F = fast_args(P, lv, d_packed, s);
@@ -1235,15 +1372,47 @@ hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const
     F.strideBytes = fast_stride_bytes(tilepx);
     F.failedCap = ntiles;
     F.failed = d_failed;
-    F.chainAlways = chain_always ? 1 : 0;
+    F.chainAlways = chain_mode == FAST_CHAIN_ALWAYS ? 1 : 0;
+    F.needCount = d_failed - 1;
+    F.needTiles = d_failed + 1 + ntiles;
+    const bool split = chain_mode == FAST_CHAIN_SPLIT && gilbert_fast_split_eligible(P, G);
 #ifdef NQ_FAST_KNOCKOUT
     if (const char* e = std::getenv("NQ_FAST_DEBUG")) F.debug = std::atoi(e);
 #endif
     F.vecOut = (T.tile_w % 4 == 0) && (T.width % 4 == 0) && ((uintptr_t) d_index % 8 == 0) && (!d_argb || (uintptr_t) d_argb % 16 == 0);
-    hipError_t e = failed_cleared ? hipSuccess : hipMemsetAsync(d_failed, 0, sizeof(int), s);
+    hipError_t e = failed_cleared ? hipSuccess : hipMemsetAsync(d_failed - 1, 0, 2 * sizeof(int), s);      // {need count, hand-back count}
     if (e != hipSuccess) return e;
     const size_t lds = fast_lds_bytes(tilepx, F.strideBytes);
     const int grid = (ntiles + 255) / 256;
+    if (split) {
+        // light kernel, then the full walk over the tiles it listed (same stream, or the caller's side stream behind chain_gate)
+        // (32 KB at 8x8 tiles: five workgroups fit a CU; NQ_LIGHT_WAVES=4 pads the block so that four fit, for A/B timing: DESIGN.md section 6)
+        static const bool four = [] { const char* w = std::getenv("NQ_LIGHT_WAVES"); return w && std::atoi(w) == 4; }();
+        const size_t llds = light_lds_bytes(tilepx, F.strideBytes) + (four ? 256 * 8 : 0);
+        if (llds > 64 * 1024) {
+            e = hipFuncSetAttribute((const void*) gilbert_light_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(gilbert_light_kernel, dim3(grid), dim3(256), llds, s, P, G, T, F, d_pixels, d_saliency, d_palette, seed, d_index, d_argb);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipStream_t cs = s;
+        if (chain_stream && chain_stream != s) {
+            e = hipEventRecord(chain_gate, s);
+            if (e == hipSuccess) e = hipStreamWaitEvent(chain_stream, chain_gate, 0);
+            if (e != hipSuccess) return e;
+            cs = chain_stream;
+        }
+        F.listed = 1;
+        F.chainAlways = 1;
+        if (lds > 64 * 1024) {
+            e = hipFuncSetAttribute((const void*) gilbert_fast_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((gilbert_fast_kernel<2, 1>), dim3(grid), dim3(256), lds, cs, P, G, T, to_lists_fast(lv), F, d_pixels, d_saliency, d_palette,
+                           seed, d_index, d_argb);
+        return hipGetLastError();
+    }
     if (lds > 64 * 1024) {
         // more than 64 KB of dynamic LDS (16x16 tiles) needs the opt-in.  The attribute belongs to the function ON THE CURRENT DEVICE, so it
         // is set at every such launch (a host-side call, no process-wide flag: handles of several devices and threads stay independent)

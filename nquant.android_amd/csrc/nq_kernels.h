@@ -86,11 +86,20 @@ void launch_gilbert(const DevParams& P, const GilbertConsts& G, const TileGeom& 
 // nq_dither_fast.hip: the specialised kernel for 32 < K <= 256, no semi-transparency, DITHER_MAX 25, tiled: PnnLABQuantizer, and
 // PnnQuantizer with dither = true on images without transparency
 bool gilbert_fast_eligible(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv);
+// chain_mode: how the launches that can do without the error chain in most steps (gilbert_fast_split_eligible) run
+enum { FAST_CHAIN_FUSED = 0,      // one kernel: a wavefront walks without the chain and starts over with it when a lane needs it
+       FAST_CHAIN_ALWAYS = 1,     // NQ_OPT_DITHER_CHAIN = 1: no light walk, every step runs the error chain
+       FAST_CHAIN_SPLIT = 2 };    // gilbert_light_kernel (87 registers, four or more wavefronts per SIMD; per-tile need list), then the full walk over the listed tiles
+bool gilbert_fast_split_eligible(const DevParams& P, const GilbertConsts& G);
+// d_failed points at word 1 of an int[2 + 2 * tiles] block: d_failed[-1] = the need count of the split form, d_failed[0] = the hand-back
+// count, d_failed[1 .. tiles] the tiles handed back, d_failed[1 + tiles ..] the need list.  chain_stream (split form only, nullable): the chain
+// pass goes onto that stream behind chain_gate, recorded on s after the light kernel; the caller orders what follows (the generic kernel over
+// the hand-back list must run behind the chain pass)
 hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv, const int* d_pixels,
                                const float* d_saliency, const int* d_palette, long long seed, unsigned short* d_index, int* d_argb,
-                               int* d_failed /* int[1 + tiles] */, void* d_packed /* 65536 x 64 bytes */, hipStream_t s,
-                               bool failed_cleared = false /* d_failed[0] was zeroed by the launch_build_lists in front of this call */,
-                               bool chain_always = false /* NQ_OPT_DITHER_CHAIN = 1: no light walk, every step runs the error chain */);
+                               int* d_failed, void* d_packed /* 65536 x 64 bytes */, hipStream_t s,
+                               bool failed_cleared = false /* d_failed[-1..0] were zeroed by the launch_build_lists in front of this call */,
+                               int chain_mode = FAST_CHAIN_FUSED, hipStream_t chain_stream = nullptr, hipEvent_t chain_gate = nullptr);
 bool fast_lookup_eligible(const DevParams& P, const ListsView& lv);
 bool fast_pack_wanted(const DevParams& P, const ListsView& lv);     // the packed records are needed (LAB lookups, or the RGB dither kernel)
 // packs the two lists of every colour cell into the 32-byte records (+ continuations) the specialised kernels read; must follow

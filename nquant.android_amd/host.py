@@ -8,6 +8,7 @@ Reference interface mirrored (NQ/ = nQuant.master/src/main/java/com/android/nQua
 The file name argument is replaced by the decoded ARGB_8888 pixels (BitmapFactory is Android platform I/O and out
 of scope); a non-zero status raises NqError just as the reference's convert() `throws Exception`."""
 import ctypes as C
+import gc
 import os
 
 import numpy as np
@@ -81,6 +82,7 @@ _ABI = {
     "nq_get_team_stats": (_i32, [_vp, _pi64]),
     "nq_get_merge_variant": (_i32, [_vp, _pi32, _pi32]),
     "nq_get_dither_path": (_i32, [_vp, _pi32, _pi32]),
+    "nq_get_dither_split_stats": (_i32, [_pi64]),
     "nq_get_device_bytes": (_i32, [_pi64]),
     "nq_set_band": (_i32, [_vp, _i32, _i32]),
     "nq_selftest_ciede": (_i32, [_vp, _vp, _i64, _vp]),
@@ -159,7 +161,10 @@ def abi_symbols():
 
 
 def device_bytes():
-    """Bytes of device memory the library holds in this process, over all handles (nq_get_device_bytes)."""
+    """Bytes of device memory the library holds in this process, over all handles (nq_get_device_bytes).  Quantizers that are unreachable
+    but still wait for the garbage collector (a caught NqError's traceback holds its frame's locals in a cycle) are destroyed first, so
+    two readings differ only by what the calls between them did, not by when the collector happens to run."""
+    gc.collect()
     out = C.c_int64(0)
     rc = load_library().nq_get_device_bytes(C.byref(out))
     if rc != 0:
@@ -459,6 +464,15 @@ class PnnQuantizer:
                                              int(bool(dither)), int(self.seed if seed is None else seed),
                                              int(self.mode if mode is None else mode), C.c_void_p(d_out_argb),
                                              C.c_void_p(d_out_index or None)))
+
+
+def dither_split_stats():
+    """nq_get_dither_split_stats, cumulative over the process: (dither passes in the split form of OPT_DITHER_CHAIN, those with the chain
+    pass on a batch's side stream, tiles their light kernels listed -- of the passes whose dither_path() has been asked)."""
+    out = (C.c_int64 * 3)()
+    if load_library().nq_get_dither_split_stats(out) != 0:
+        raise RuntimeError("nq_get_dither_split_stats failed")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def convert_batch_host(quantizers, pixels, nMaxColors, dither, out_argb, out_index=None, mode=None, seeds=None):

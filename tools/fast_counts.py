@@ -50,6 +50,8 @@ def main():
         lines += ["", "per fast_nearest_exact call: %.2f lanes need it, mean n2 of those lanes %.2f, loop trips (largest n2) %.2f"
                   % (v[2] / v[1], v[3] / max(v[2], 1), v[4] / v[1]),
                   "share of fast_nearest wavefront-steps that call it: %.4f; share of lanes: %.5f" % (v[1] / max(v[0], 1), v[2] / (64.0 * max(v[0], 1)))]
+    # (a single convert runs the fused light walk, whose exit is per wavefront; in the split form -- NQ_OPT_DITHER_CHAIN = 3, or the finish
+    # phase of a batch -- the same two slots count TILES: finished by gilbert_light_kernel / listed for the chain pass)
     lines += ["", "light walk (NQ_OPT_DITHER_CHAIN = 0): %d wavefronts finished without the error chain, %d walked again with it (of %d)"
               % (v[13], v[14], W * H // 4096)]
     text = "\n".join(lines) + "\n"
