@@ -1103,6 +1103,65 @@ int nq_resample_frames_yuv16(int device, int n, const uint16_t* const* y, const 
                              int crop_x, int crop_y, int crop_w, int crop_h,
                              uint32_t* const* dst, int dst_width, int dst_height, int flags);
 
+/* ---- retiming: timestamps in, blended frames and their delays out (ffmpeg fps / framerate / tmix).  A phone records 30, 60 or 120
+ *      frames per second at a variable rate; a GIF is shown at 10 to 20 on a centisecond grid.  nq_retime_plan turns the source's
+ *      timestamps into output frames, each the weighted mean of a window of sources, and into the delays_cs every encoder above takes;
+ *      nq_retime_frames* forms the means: exact overlap weights, linear light through the table of "frame reduction", alpha
+ *      premultiplied, one rounding at the end -- that call's footprint sum with time in place of x and y.  All integers, so the result
+ *      can be restated bit for bit (tests/retime_ref.py).  None of the calls takes a handle; the error text is nq_last_error(NULL).
+ *  * nq_retime_plan (host arithmetic; no device): t_us holds n + 1 strictly increasing values in microseconds
+ *    (MediaCodec.BufferInfo.presentationTimeUs); source frame i is on display during [t[i], t[i + 1]), t[n] is the end of the clip,
+ *    D = t[n] - t[0].  period_us >= 1 is the output frame's duration, shutter_us in 1 .. min(period_us, 2^31 - 1) the part of it that
+ *    gathers light.  m = max(1, floor((2 D + period) / (2 period))) output frames: every one stands for at least half a period, and
+ *    (m - 1) period < D.
+ *      - The window of output j is [o_j, min(o_j + shutter, t[n])) with o_j = t[0] + j period; its length W_j is >= 1.  w(j, i) is the
+ *        length of its overlap with source i's interval; the intervals tile [t[0], t[n]), so the weights of one j sum to W_j exactly.
+ *      - The plan is in CSR form: out_offset has m + 1 entries, the pairs of output j are offset[j] .. offset[j + 1] - 1, with
+ *        out_source[k] ascending and out_weight[k] >= 1.  shutter <= period keeps the windows disjoint: pairs <= n + m - 1.
+ *      - out_delays_cs[j] = R(e_(j+1)) - R(e_j) with e_j = j period for j < m, e_m = D and R(x) = floor((x + 5000) / 10000): every
+ *        delay is >= 0 and within one centisecond of its interval, and they sum to R(D): no drift (15 fps gives 7, 6, 7, ...).
+ *      - shutter = 1 picks the frame on display at o_j.
+ *    *out_m and *out_pairs receive the counts.  With cap_m = cap_pairs = 0 and the four arrays NULL the call only counts; otherwise
+ *    the arrays hold cap_m + 1, cap_pairs, cap_pairs and cap_m entries, and a cap that is too small is NQ_ERR_INVALID with the counts
+ *    written.  NQ_ERR_INVALID with nothing written: n < 1, NULL t_us, out_m or out_pairs, timestamps not strictly increasing,
+ *    period < 1, shutter out of range, m or D / period above 2^31 - 1, a delay above 2^31 - 1, a NULL array where it is needed.
+ *  * nq_retime_frames_device takes ANY plan, not only one of nq_retime_plan's (a crossfade is a plan too): n sources and m outputs of
+ *    width x height words, rows contiguous; every source[k] in 0 .. n - 1 (indices may repeat and need not be consecutive); each
+ *    output has 1 .. NQ_RETIME_MAX_WINDOW pairs; weights may be 0; W_j, the sum of output j's weights, is in 1 .. 2^31 - 1.  flags:
+ *    bit 0 is NQ_RETIME_LINEAR.  Per output pixel, with T the table of "frame reduction" (that of include/nq_srgb_linear_16.inc with
+ *    the flag, 257 v without) and a, r, g, b the channels of the pixel in source[k]:
+ *        S_a = sum of w a            S_c = sum of w a T[c]    for c = r, g, b        (S_c < 2^31 255 65535 < 2^55; unsigned 64-bit)
+ *    S_a = 0 gives 0x00000000.  Otherwise A = floor((2 S_a + W_j) / (2 W_j)); per channel t = floor((2 S_c + S_a) / (2 S_a)) and the
+ *    stored value is the nearest table entry, ties to the smaller, as in "frame reduction"; the word is A << 24 | r << 16 | g << 8 | b.
+ *    Consequences: a window that lies in one source copies it exactly for every pixel with a > 0 (a = 0 becomes 0), in both modes; a
+ *    transparent source pixel contributes nothing to the colour; opaque input gives A = 255.
+ *    d_src and d_dst are host arrays of n and m DEVICE pointers; offset, source and weight are host arrays, and all five may be freed
+ *    when the call returns.  The call is asynchronous on hip_stream (NULL: the default stream) of `device`: frame pointers and weights
+ *    travel in the kernel arguments -- consecutive outputs are packed into a launch until one more would exceed 16 outputs or 64
+ *    pairs --, so it allocates nothing and waits for nothing.  Sources are never written; nothing outside the m outputs is written.
+ *    Pointers need 4-byte alignment; when every source and output pointer is 16-byte aligned the kernel moves 16 bytes per access,
+ *    otherwise one pixel, with the same results.
+ *    nq_retime_frames: the same with HOST buffers (every source is uploaded on a 16-byte boundary, the device form runs, the m outputs
+ *    are copied back, every temporary buffer is freed; the call returns when the outputs are there).
+ *  * NQ_ERR_INVALID before any device is touched, every buffer untouched: n or m outside 1..65535, a side outside 1..65535,
+ *    n width height or m width height above 2^31 - 1, unknown flag bits, a negative device, a NULL array or entry, a pointer that is
+ *    not 4-byte aligned, offsets that do not start at 0 or do not ascend, a window that is empty or longer than
+ *    NQ_RETIME_MAX_WINDOW pairs, a source index out of range, W_j outside 1 .. 2^31 - 1, an output that overlaps a source or another
+ *    output.  Then NQ_ERR_NO_DEVICE (no usable device; a device ordinal past the last one is NQ_ERR_INVALID) or NQ_ERR_HIP.
+ *  Out of scope: fusing the temporal sum into the spatial reducers (a 3-D box with one rounding is a different result), motion-
+ *  compensated interpolation, dropping near-duplicate frames, windows over more than 64 frames.  The kernel: DESIGN.md 5e2 "Retiming". ---- */
+#define NQ_RETIME_LINEAR 1
+#define NQ_RETIME_MAX_WINDOW 64
+int nq_retime_plan(int n, const int64_t* t_us, int64_t period_us, int64_t shutter_us, int32_t cap_m, int32_t cap_pairs,
+                   int32_t* out_m, int32_t* out_pairs, int32_t* out_offset, int32_t* out_source, uint32_t* out_weight,
+                   int32_t* out_delays_cs);
+int nq_retime_frames_device(int device, void* hip_stream, int n, const uint32_t* const* d_src, int width, int height,
+                            int m, const int32_t* offset, const int32_t* source, const uint32_t* weight,
+                            uint32_t* const* d_dst, int flags);
+int nq_retime_frames(int device, int n, const uint32_t* const* src, int width, int height,
+                     int m, const int32_t* offset, const int32_t* source, const uint32_t* weight,
+                     uint32_t* const* dst, int flags);
+
 /* ---- Integer[] pnnquan(int[] pixels, int nMaxColors) incl. the alpha pre-scan of convert()
  *      (NQ/PnnQuantizer.java:410-436,134-267; NQ/PnnLABQuantizer.java:131-327) ---- */
 int nq_pnnquan(nq_handle* h, const uint32_t* argb, int width, int height, int nMaxColors,

@@ -20,6 +20,7 @@ from .resample import fit_size, resample_frames, resample_frames_device
 from .ordered import convert_frames_ordered, dither_ordered, dither_ordered_device
 from .yuv import frames_from_yuv, frames_from_yuv_device, resample_frames_yuv, resample_frames_yuv_device, yuv_planes
 from .yuv16 import frames_from_yuv16, frames_from_yuv16_device, resample_frames_yuv16, resample_frames_yuv16_device, yuv16_planes
+from .retime import RetimePlan, retime_frames, retime_frames_device, retime_plan, timestamps_from_pts
 from .orient import orient_frames, orient_frames_device, orientation, oriented_size, source_rect
 from .compare import Quality, choose_colors, compare_frames, compare_frames_device, compare_indexed, compare_indexed_device
 from .webp import convert_frames_to_webp, convert_to_webp, encode_webp, encode_webp_device, webp_max_bytes, write_webp
@@ -40,4 +41,4 @@ __all__ = ["NQ_KIND_RGB", "NQ_KIND_LAB", "MODE_REFERENCE_SEQUENTIAL", "MODE_PARA
            "resample_frames_yuv16", "resample_frames_yuv16_device", "yuv16_planes", "orient_frames", "orient_frames_device", "orientation",
            "oriented_size", "source_rect", "Quality", "choose_colors", "compare_frames", "compare_frames_device", "compare_indexed",
            "compare_indexed_device", "webp_max_bytes", "encode_webp", "encode_webp_device", "write_webp", "convert_to_webp",
-           "convert_frames_to_webp"]
+           "convert_frames_to_webp", "RetimePlan", "retime_frames", "retime_frames_device", "retime_plan", "timestamps_from_pts"]

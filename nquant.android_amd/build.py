@@ -34,6 +34,7 @@ UNITS = {
     "nq_orient.hip": ("device", ["nq_orient.hip", "nq_yuv.inc", "nq_kernels.h"]),
     "nq_yuv16.hip": ("device", ["nq_yuv16.hip", "nq_yuv.inc", "nq_resample.inc", "nq_kernels.h", os.path.join(INC, "nq_srgb_linear_16.inc"),
                                 os.path.join(INC, "nq_hdr_luts.inc")]),
+    "nq_retime.hip": ("device", ["nq_retime.hip", "nq_resample.inc", "nq_kernels.h", os.path.join(INC, "nq_srgb_linear_16.inc")]),
     "nq_compare.hip": ("device", ["nq_compare.hip", "nq_kernels.h", os.path.join(INC, "nq_srgb_linear_16.inc")]),
     "nq_abi.cpp": ("host", ["nq_abi.cpp", "nq_kernels.h", os.path.join(INC, "nquant_abi.h")]),
 }

@@ -5099,3 +5099,186 @@ int nq_resample_frames_yuv16(int device, int n, const uint16_t* const* y, const 
 }
 
 } // extern "C"
+
+// ---- retiming (nq_retime.hip; include/nquant_abi.h "retiming"): the plan is host arithmetic; the mix is a stateless call like the
+// 10-bit YUV input -- no handle, the error text goes to the thread's handle-free string; the outputs of a launch and their windows
+// travel in its arguments, so the device form allocates nothing and waits for nothing ----
+namespace {
+
+typedef unsigned __int128 rt_u128;
+
+// R(x) = floor((x + 5000) / 10000): microseconds to the nearest centisecond, halves up
+inline rt_u128 retime_cs(rt_u128 x) { return (x + 5000) / 10000; }
+
+// every argument of both forms of nq_retime_frames, from the host arrays alone (no device work)
+int retime_check(int device, int n, const uint32_t* const* src, int width, int height, int m, const int32_t* offset, const int32_t* source,
+                 const uint32_t* weight, uint32_t* const* dst, int flags) {
+    if (n < 1 || n > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "n = %d: 1..65535 source frames", n);
+    if (m < 1 || m > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "m = %d: 1..65535 output frames", m);
+    if (width < 1 || width > 65535 || height < 1 || height > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "%d x %d: sides must be 1..65535", width, height);
+    if ((long long) n * width * height > 2147483647ll || (long long) m * width * height > 2147483647ll)
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "%d sources / %d outputs of %d x %d: more than 2^31 - 1 pixels", n, m, width, height);
+    if (flags & ~NQ_RETIME_LINEAR) NQ_CMP_FAIL(NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) flags);
+    if (device < 0) NQ_CMP_FAIL(NQ_ERR_INVALID, "device = %d: a device ordinal is not negative", device);
+    if (!src || !dst || !offset || !source || !weight) NQ_CMP_FAIL(NQ_ERR_INVALID, "an array of frame pointers or of the plan is NULL");
+    for (int i = 0; i < n; ++i)
+        if (!src[i] || ((uintptr_t) src[i] & 3)) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: source pointer NULL or not 4-byte aligned", i);
+    for (int j = 0; j < m; ++j)
+        if (!dst[j] || ((uintptr_t) dst[j] & 3)) NQ_CMP_FAIL(NQ_ERR_INVALID, "output %d: pointer NULL or not 4-byte aligned", j);
+    if (offset[0] != 0) NQ_CMP_FAIL(NQ_ERR_INVALID, "offset[0] = %d: the pairs begin at 0", (int) offset[0]);
+    for (int j = 0; j < m; ++j) {
+        const long long len = (long long) offset[j + 1] - offset[j];
+        if (len < 1 || len > NQ_RETIME_MAX_WINDOW)
+            NQ_CMP_FAIL(NQ_ERR_INVALID, "output %d: a window of %lld pairs: 1..%d", j, len, NQ_RETIME_MAX_WINDOW);
+        uint64_t W = 0;
+        for (int k = offset[j]; k < offset[j + 1]; ++k) {
+            if (source[k] < 0 || source[k] >= n) NQ_CMP_FAIL(NQ_ERR_INVALID, "pair %d: source %d is outside 0..%d", k, (int) source[k], n - 1);
+            W += weight[k];
+        }
+        if (W < 1 || W > 2147483647ull) NQ_CMP_FAIL(NQ_ERR_INVALID, "output %d: its weights sum to %llu: 1 .. 2^31 - 1", j, (unsigned long long) W);
+    }
+    // no output may overlap a source frame or another output (resample_check's sweep)
+    struct Span { uintptr_t begin, end; bool out; };
+    std::vector<Span> spans;
+    spans.reserve((size_t) n + m);
+    const uintptr_t bytes = (uintptr_t) width * height * sizeof(uint32_t);
+    for (int i = 0; i < n; ++i) spans.push_back({(uintptr_t) src[i], (uintptr_t) src[i] + bytes, false});
+    for (int j = 0; j < m; ++j) spans.push_back({(uintptr_t) dst[j], (uintptr_t) dst[j] + bytes, true});
+    std::sort(spans.begin(), spans.end(), [](const Span& p, const Span& q) { return p.begin < q.begin; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const Span& sp : spans) {
+        if (sp.begin < (sp.out ? end_any : end_out)) NQ_CMP_FAIL(NQ_ERR_INVALID, "an output overlaps a source frame or another output");
+        end_any = std::max(end_any, sp.end);
+        if (sp.out) end_out = std::max(end_out, sp.end);
+    }
+    return NQ_OK;
+}
+
+// after the checks, for DEVICE frames: consecutive outputs are packed into a launch until one more would exceed
+// RETIME_OUTPUTS_PER_LAUNCH outputs or RETIME_PAIRS_PER_LAUNCH pairs (a window has at most that many); all on s.  The 16-byte path
+// needs every source and output pointer of the call aligned to it.
+int retime_launches(int n, const uint32_t* const* d_src, int width, int height, int m, const int32_t* offset, const int32_t* source,
+                    const uint32_t* weight, uint32_t* const* d_dst, int flags, hipStream_t s) {
+    bool vec = true;
+    for (int i = 0; i < n; ++i) vec = vec && !((uintptr_t) d_src[i] & 15);
+    for (int j = 0; j < m; ++j) vec = vec && !((uintptr_t) d_dst[j] & 15);
+    for (int j = 0; j < m;) {
+        RetimeLaunch l;
+        std::memset(&l, 0, sizeof l);
+        int pairs = 0;
+        while (j < m && l.count < RETIME_OUTPUTS_PER_LAUNCH && pairs + (offset[j + 1] - offset[j]) <= RETIME_PAIRS_PER_LAUNCH) {
+            uint64_t W = 0;
+            for (int k = offset[j]; k < offset[j + 1]; ++k, ++pairs) {
+                l.src[pairs] = d_src[source[k]];
+                l.weight[pairs] = weight[k];
+                W += weight[k];
+            }
+            l.dst[l.count] = d_dst[j];
+            l.W[l.count] = (unsigned) W;
+            l.first[++l.count] = pairs;
+            ++j;
+        }
+        launch_retime(l, (long long) width * height, (flags & NQ_RETIME_LINEAR) != 0, vec, s);
+    }
+    NQ_CMP_HIP(launch_status());
+    return NQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int nq_retime_plan(int n, const int64_t* t_us, int64_t period_us, int64_t shutter_us, int32_t cap_m, int32_t cap_pairs, int32_t* out_m,
+                   int32_t* out_pairs, int32_t* out_offset, int32_t* out_source, uint32_t* out_weight, int32_t* out_delays_cs) {
+    if (n < 1) NQ_CMP_FAIL(NQ_ERR_INVALID, "n = %d: at least one frame", n);
+    if (!t_us || !out_m || !out_pairs) NQ_CMP_FAIL(NQ_ERR_INVALID, "t_us, out_m or out_pairs is NULL");
+    for (int i = 0; i < n; ++i)
+        if (t_us[i + 1] <= t_us[i]) NQ_CMP_FAIL(NQ_ERR_INVALID, "t_us[%d] = %lld is not above t_us[%d] = %lld", i + 1, (long long) t_us[i + 1], i, (long long) t_us[i]);
+    if (period_us < 1) NQ_CMP_FAIL(NQ_ERR_INVALID, "period_us = %lld: at least 1", (long long) period_us);
+    if (shutter_us < 1 || shutter_us > period_us || shutter_us > 2147483647ll)
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "shutter_us = %lld: 1 .. min(period_us, 2^31 - 1)", (long long) shutter_us);
+    // times relative to t_us[0]: exact in unsigned 64-bit whatever the signs (the true differences are below 2^64)
+    auto rel = [&](int i) { return (uint64_t) t_us[i] - (uint64_t) t_us[0]; };
+    const uint64_t D = rel(n), P = (uint64_t) period_us, H = (uint64_t) shutter_us;
+    const rt_u128 m128 = std::max<rt_u128>(1, (2 * (rt_u128) D + P) / (2 * (rt_u128) P));
+    if (m128 > 2147483647ull || D / P > 2147483647ull) NQ_CMP_FAIL(NQ_ERR_INVALID, "the clip is more than 2^31 - 1 periods long");
+    const int64_t m = (int64_t) m128;
+    // one walk over the outputs, twice: to count (and to see that every delay fits its word), then to write.  Source i is the one on
+    // display at lo when r[i] <= lo < r[i + 1]; the windows ascend, so i never goes back.
+    auto walk = [&](bool write) -> int64_t {
+        int64_t pairs = 0;
+        int i = 0;
+        for (int64_t j = 0; j < m; ++j) {
+            const uint64_t lo = (uint64_t) j * P;                                   // < D
+            const uint64_t hi = (uint64_t) std::min<rt_u128>((rt_u128) lo + H, D);
+            if (write) out_offset[j] = (int32_t) pairs;
+            while (rel(i + 1) <= lo) ++i;
+            for (int k = i; k < n && rel(k) < hi; ++k, ++pairs) {
+                if (!write) continue;
+                out_source[pairs] = k;
+                out_weight[pairs] = (uint32_t) (std::min(rel(k + 1), hi) - std::max(rel(k), lo));
+            }
+            const rt_u128 d = retime_cs(j + 1 < m ? (rt_u128) (j + 1) * P : (rt_u128) D) - retime_cs((rt_u128) j * P);
+            if (d > 2147483647ull) return -1;
+            if (write) out_delays_cs[j] = (int32_t) d;
+        }
+        if (write) out_offset[m] = (int32_t) pairs;
+        return pairs;
+    };
+    const int64_t pairs = walk(false);
+    if (pairs < 0) NQ_CMP_FAIL(NQ_ERR_INVALID, "a delay is above 2^31 - 1 centiseconds");
+    if (pairs > 2147483647ll) NQ_CMP_FAIL(NQ_ERR_INVALID, "more than 2^31 - 1 pairs");
+    const bool count_only = cap_m == 0 && cap_pairs == 0 && !out_offset && !out_source && !out_weight && !out_delays_cs;
+    if (!count_only && cap_m >= m && cap_pairs >= pairs && (!out_offset || !out_source || !out_weight || !out_delays_cs))
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "an output array is NULL");
+    *out_m = (int32_t) m;
+    *out_pairs = (int32_t) pairs;
+    if (count_only) return NQ_OK;
+    if (cap_m < m || cap_pairs < pairs)
+        NQ_CMP_FAIL(NQ_ERR_INVALID, "the plan has %lld outputs and %lld pairs, the arrays hold %d and %d", (long long) m, (long long) pairs, (int) cap_m, (int) cap_pairs);
+    walk(true);
+    return NQ_OK;
+}
+
+int nq_retime_frames_device(int device, void* hip_stream, int n, const uint32_t* const* d_src, int width, int height, int m,
+                            const int32_t* offset, const int32_t* source, const uint32_t* weight, uint32_t* const* d_dst, int flags) {
+    int rc = retime_check(device, n, d_src, width, height, m, offset, source, weight, d_dst, flags);
+    if (rc) return rc;
+    rc = compare_use_device(device);
+    if (rc) return rc;
+    return retime_launches(n, d_src, width, height, m, offset, source, weight, d_dst, flags, (hipStream_t) hip_stream);
+}
+
+// The host form: every source goes up on a 16-byte boundary of one temporary buffer, the outputs are staged likewise, the device form
+// runs on the copies, the m outputs are copied back, and everything is freed when the call returns.
+int nq_retime_frames(int device, int n, const uint32_t* const* src, int width, int height, int m, const int32_t* offset,
+                     const int32_t* source, const uint32_t* weight, uint32_t* const* dst, int flags) {
+    int rc = retime_check(device, n, src, width, height, m, offset, source, weight, dst, flags);
+    if (rc) return rc;
+    rc = compare_use_device(device);
+    if (rc) return rc;
+    const size_t px = (size_t) width * height, pitch = (px + 3) & ~(size_t) 3;
+    DevBuf<uint32_t> d_in, d_out;
+    hipStream_t s = nullptr;
+    auto body = [&]() -> int {
+        NQ_CMP_HIP(d_in.reserve(n * pitch));
+        NQ_CMP_HIP(d_out.reserve(m * pitch));
+        std::vector<const uint32_t*> d_src(n);
+        std::vector<uint32_t*> d_dst(m);
+        for (int i = 0; i < n; ++i) {
+            d_src[i] = d_in.p + i * pitch;
+            NQ_CMP_HIP(hipMemcpyAsync(d_in.p + i * pitch, src[i], px * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        }
+        for (int j = 0; j < m; ++j) d_dst[j] = d_out.p + j * pitch;
+        const int rc2 = retime_launches(n, d_src.data(), width, height, m, offset, source, weight, d_dst.data(), flags, s);
+        if (rc2) return rc2;
+        for (int j = 0; j < m; ++j) NQ_CMP_HIP(hipMemcpyAsync(dst[j], d_dst[j], px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        NQ_CMP_HIP(hipStreamSynchronize(s));
+        return NQ_OK;
+    };
+    rc = body();
+    if (rc) (void) hipStreamSynchronize(s);
+    return rc;
+}
+
+} // extern "C"

@@ -447,4 +447,22 @@ void launch_yuv16_argb(const Yuv16Launch& a, int width, int height, hipStream_t 
 void launch_resample_yuv16(const Yuv16Launch& a, int crop_x, int crop_y, int crop_w, int crop_h, int dst_width, int dst_height, bool linear,
                            hipStream_t s);
 
+// ---- retiming (nq_retime.hip; include/nquant_abi.h "retiming"): `count` consecutive outputs (1 .. RETIME_OUTPUTS_PER_LAUNCH) with
+// their windows, at most RETIME_PAIRS_PER_LAUNCH (source, weight) pairs in all, go to the kernel BY VALUE, so a launch needs no table
+// in device memory.  Output o of the launch is dst[o]; its pairs are first[o] .. first[o + 1] - 1 (1..64 of them), pair k reads frame
+// src[k] with weight weight[k]; W[o] is the sum of its weights (1 .. 2^31 - 1).  Every frame is px words.  vec: the 16-byte path -- the
+// caller has checked that EVERY src and dst of the launch is 16-byte aligned; otherwise one pixel per access (4-byte alignment).  The
+// sources are never written; nothing but the px words of each output is. ----
+constexpr int RETIME_OUTPUTS_PER_LAUNCH = 16;
+constexpr int RETIME_PAIRS_PER_LAUNCH = 64;
+struct RetimeLaunch {
+    const void* src[RETIME_PAIRS_PER_LAUNCH];
+    void* dst[RETIME_OUTPUTS_PER_LAUNCH];
+    unsigned weight[RETIME_PAIRS_PER_LAUNCH];
+    unsigned W[RETIME_OUTPUTS_PER_LAUNCH];
+    int first[RETIME_OUTPUTS_PER_LAUNCH + 1];
+    int count;
+};
+void launch_retime(const RetimeLaunch& a, long long px, bool linear, bool vec, hipStream_t s);
+
 } // namespace nq

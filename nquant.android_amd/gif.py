@@ -302,7 +302,7 @@ def _shots(shot_starts, n):
 
 def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0,
                          mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None,
-                         linear_resample=True, ordered=None, yuv=None, orient=1, yuv16=None, delta=True):
+                         linear_resample=True, ordered=None, yuv=None, retime=None, orient=1, yuv16=None, delta=True):
     """One palette per shot: frames shot_starts[k] .. shot_starts[k + 1] - 1 are shot k and get a convert_frames palette of their own
     (shot_starts=range(n): one palette per frame), then encode_gif_local_delta (delta=False: encode_gif_local) writes all frames, each
     with its shot's palette as its local colour table.  hold (delta=True only) runs per shot and never across a cut: a held index means
@@ -317,7 +317,11 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
     yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
     of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
     with orient: then turned -- before anything else runs.
+    retime is refused here (ValueError): shot_starts name source frames, and retimed frames are other frames; convert_clip_to_gif
+    takes it.
     Returns (file bytes, list of per-shot palettes)."""
+    if retime is not None:
+        raise ValueError("retime changes the frames that shot_starts name: retime first (retime.py), or let convert_clip_to_gif find the cuts")
     if yuv16 is not None:
         from .yuv16 import _converter_frames
         frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
@@ -385,7 +389,7 @@ def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segm
 
 def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, delays_cs=None, loop=0, segment_pixels=0, device=0,
                         mode=MODE_PARALLEL_TILED, seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None,
-                        linear_resample=True, ordered=None, yuv=None, orient=1, yuv16=None, delta=True):
+                        linear_resample=True, ordered=None, yuv=None, retime=None, orient=1, yuv16=None, delta=True):
     """A list of frames in, an animation out: detect_shots (shots.py; cut in per mille, min_shot in frames) finds where the clip needs
     a new palette, then exactly convert_shots_to_gif with those starts -- both on one handle.  The frames must have one size (delta or
     not: a signature is compared between frames of one size).  With size or crop the frames are reduced first (resample.py) and the
@@ -393,7 +397,14 @@ def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, de
     yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
     of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
     with orient: then turned -- before anything else runs.
+    retime (None: the frames are shown as they are): a dict with the keys timestamps_us / period_us or fps / shutter_us / linear
+    (retime.py) blends the frames to that rate -- after the YUV, orient and reduce steps, which then run before anything else -- and
+    supplies delays_cs, which may not be given as well; seeds (one per frame) may not be given either.
     Returns (file bytes, list of per-shot palettes, shot_starts)."""
+    if retime is not None:
+        from .retime import _converter_frames as _retimed_frames
+        frames, delays_cs = _retimed_frames(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient, device)
+        yuv, yuv16, size, crop, orient = None, None, None, None, 1
     if yuv16 is not None:
         from .yuv16 import _converter_frames
         frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
@@ -451,7 +462,7 @@ def write_gif(path, indices, palette, delays_cs=None, loop=0, segment_pixels=0, 
 
 def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, segment_pixels=0, device=0, mode=MODE_PARALLEL_TILED,
                           seeds=None, tile=None, hold=None, lossy=0, refine=0, size=None, crop=None, linear_resample=True, ordered=None,
-                          yuv=None, orient=1, yuv16=None, delta=False):
+                          yuv=None, retime=None, orient=1, yuv16=None, delta=False):
     """convert_frames (one shared palette for the ARGB frames) followed by encode_gif of the index maps.  nMaxColors <= 256.
     delta=True: encode_gif_delta instead; the frames must have one size.  Seeds are passed on as given: regions that do not move repeat
     in the index maps, and so drop out of the file, when the frames are dithered with equal seeds in MODE_PARALLEL_TILED.
@@ -474,7 +485,14 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
     yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
     of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
     with orient: then turned -- before anything else runs.
+    retime (None: the frames are shown as they are): a dict with the keys timestamps_us / period_us or fps / shutter_us / linear
+    (retime.py) blends the frames to that rate -- after the YUV, orient and reduce steps, which then run before anything else -- and
+    supplies delays_cs, which may not be given as well; seeds (one per frame) may not be given either.
     Returns (file bytes, palette)."""
+    if retime is not None:
+        from .retime import _converter_frames as _retimed_frames
+        frames, delays_cs = _retimed_frames(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient, device)
+        yuv, yuv16, size, crop, orient = None, None, None, None, 1
     if yuv16 is not None:
         from .yuv16 import _converter_frames
         frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1

@@ -150,6 +150,9 @@ _ABI = {
     "nq_frames_from_yuv16": (_i32, [_i32, _i32, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     "nq_resample_frames_yuv16_device": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp] + [_i32] * 10 + [_vp, _i32, _i32, _i32]),
     "nq_resample_frames_yuv16": (_i32, [_i32, _i32, _vp, _vp, _vp] + [_i32] * 10 + [_vp, _i32, _i32, _i32]),
+    "nq_retime_plan": (_i32, [_i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nq_retime_frames_device": (_i32, [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
+    "nq_retime_frames": (_i32, [_i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
     "nq_webp_max_bytes": (_i32, [_i32, _i32, _i32, _i32, _pi64]),
     "nq_encode_webp_device": (_i32, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _pi64, _vp]),
     "nq_encode_webp": (_i32, [_i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _pi64, _vp]),

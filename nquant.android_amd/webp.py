@@ -101,7 +101,7 @@ def convert_to_webp(kind, image, nMaxColors, dither, band_bits=0, device=0, mode
 
 def convert_frames_to_webp(kind, frames, nMaxColors, dither, delays_cs=None, loop=0, seeds=None, tile=None, band_bits=0, device=0,
                            mode=MODE_PARALLEL_TILED, return_rects=False, hold=None, refine=0, size=None, crop=None, linear_resample=True,
-                           ordered=None, yuv=None, orient=1, delta=True, yuv16=None):
+                           ordered=None, yuv=None, retime=None, orient=1, delta=True, yuv16=None):
     """convert_frames (one shared palette for the ARGB frames, which must have one size) followed by encode_webp of the index maps on
     the same device.  nMaxColors <= 256.  The keywords are convert_frames_to_apng's (apng.py), with band_bits in place of
     segment_bytes and delta (True: every later frame stores its changed rectangle only) in addition: seeds, tile and mode go to the
@@ -110,7 +110,14 @@ def convert_frames_to_webp(kind, frames, nMaxColors, dither, delays_cs=None, loo
     yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
     of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
     with orient: then turned -- before anything else runs.
+    retime (None: the frames are shown as they are): a dict with the keys timestamps_us / period_us or fps / shutter_us / linear
+    (retime.py) blends the frames to that rate -- after the YUV, orient and reduce steps, which then run before anything else -- and
+    supplies delays_cs, which may not be given as well; seeds (one per frame) may not be given either.
     Returns (file bytes, palette); with return_rects=True (file bytes, palette, rectangles)."""
+    if retime is not None:
+        from .retime import _converter_frames as _retimed_frames
+        frames, delays_cs = _retimed_frames(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient, device)
+        yuv, yuv16, size, crop, orient = None, None, None, None, 1
     if yuv16 is not None:
         from .yuv16 import _converter_frames
         frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
