@@ -117,7 +117,9 @@ int nq_set_band(nq_handle* h, int y0, int image_height);
  * 2 = that fused single-kernel light walk wherever it applies; 3 = the split form wherever it applies: a light kernel of its own (87
  * registers and, at 8x8 tiles, 32 KB of LDS: at least four wavefronts per SIMD) lists the TILES that need the chain, the full walk then runs over that list.  0 picks the split form in the finish
  * phase of nq_convert_batch[_device], where the chain pass of image i runs on a side stream beside the light kernel of image i + 1, and the
- * fused form in every other entry point. */
+ * fused form in every other entry point.  4 = the split form with the light pass in its pixel form (gilbert_pixel_kernel: one lane per
+ * pixel instead of one per tile, the draws of a tile's Random by jump-ahead) for power-of-two tiles of 16, 32 or 64 pixels, and exactly 3
+ * for every other tile size; it counts as a split pass in every statistic.  0 takes 4 where it takes the split form. */
 #define NQ_OPT_DITHER_CHAIN 4
 /* NQ_OPT_MERGE_WALL_SECONDS (default 0 = automatic: 60 s + 1 ms per histogram bin and per merge loop sharing a compute unit with it):
  * seconds of residency after which a merge loop of this handle's calls gives up with NQ_ERR_TIME_LIMIT.  Every loop of the persistent
@@ -170,6 +172,9 @@ int nq_selftest_ciede(nq_handle* h, const float* lab_pairs, int64_t n, uint32_t*
  *   NEXTINT_LIST       int32 uu in [0, 2^31); out as NEXTINT.
  *   NEAR_SAFE          int32 {colour, ka | kb << 8}; out[i] = the index fast_nearest32 picks from the two-entry list {ka, kb} | safe << 16
  *                      (safe: the runner-up is more than 2 NQ_FAST_NEAR_EPS behind, so the exact scan is skipped).
+ *   JUMP               int64 Random state s0 (48 bits); out[66 i + n], n = 0..64 = next(31) of the draw that follows n earlier draws, from the
+ *                      jump table of the pixel-form light pass (state (A_{n+1} s0 + C_{n+1}) mod 2^48), | 1 << 31 when nextInt(32767) rejects
+ *                      it; out[66 i + 65] = how many of the 65 differ from the draw after n sequential steps of the generator (0).
  * tests/test_gpu_fast_filters.py holds each against the oracle over its whole domain. */
 #define NQ_FAST_ST_TANH 0
 #define NQ_FAST_ST_CLOSEST_ERR 1
@@ -187,7 +192,8 @@ int nq_selftest_ciede(nq_handle* h, const float* lab_pairs, int64_t n, uint32_t*
 #define NQ_FAST_ST_TANH_BITS 13
 #define NQ_FAST_ST_NEXTINT_LIST 14
 #define NQ_FAST_ST_NEAR_SAFE 15
-#define NQ_FAST_ST_MODES 16
+#define NQ_FAST_ST_JUMP 16
+#define NQ_FAST_ST_MODES 17
 int nq_selftest_fast(nq_handle* h, int which, const void* in, int64_t n, uint32_t* out);
 int nq_get_params(const nq_handle* h, nq_params* out);
 int nq_set_params(nq_handle* h, const nq_params* in);

@@ -189,9 +189,9 @@ struct nq_handle {
     DevBuf<float> d_user_sal;
     int band_y0 = 0, band_image_h = 0; // nq_set_band: this handle dithers a row band of a larger image (0, 0 = a whole image)
     int use_fast_dither = 1;          // NQ_OPT_FAST_DITHER: the specialised dither kernel where the configuration allows it
-    // NQ_OPT_DITHER_CHAIN: 0 automatic, 1 the error chain in every step, 2 the fused light walk, 3 the split form (a new handle starts from
-    // the environment's NQ_DITHER_CHAIN = 0..3: whole-suite runs under one form, tests/fuzz_parity.py)
-    int dither_chain = [] { const char* e = std::getenv("NQ_DITHER_CHAIN"); const int v = e ? std::atoi(e) : 0; return v >= 0 && v <= 3 ? v : 0; }();
+    // NQ_OPT_DITHER_CHAIN: 0 automatic, 1 the error chain in every step, 2 the fused light walk, 3 the split form, 4 the split form with the pixel-form light pass (a new handle starts from
+    // the environment's NQ_DITHER_CHAIN = 0..4: whole-suite runs under one form, tests/fuzz_parity.py)
+    int dither_chain = [] { const char* e = std::getenv("NQ_DITHER_CHAIN"); const int v = e ? std::atoi(e) : 0; return v >= 0 && v <= 4 ? v : 0; }();
     // batch entry points, finish phase: the image's chain pass and hand-back pass go onto chain_stream (the split form is "automatic"
     // there); chain_gate: behind the light kernel on the main stream, chain_done: behind the image's last kernel on chain_stream
     hipStream_t chain_stream = nullptr;
@@ -1137,11 +1137,12 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
         // production path (nq_dither_fast.hip); the tiles it cannot finish come back as a list for the generic kernel below
         NQ_HIP(h, h->d_failed.reserve(failed_words(T)));
         // NQ_OPT_DITHER_CHAIN.  Automatic: the split form with the chain pass on the side stream in the finish phase of a batch (chain_stream
-        // set), the fused light walk everywhere else
+        // set) -- with the pixel-form light pass where the tile size allows --, the fused light walk everywhere else
         int chain_mode = nq::FAST_CHAIN_FUSED;
         if (h->dither_chain == 1) chain_mode = nq::FAST_CHAIN_ALWAYS;
-        else if (h->dither_chain == 3 || (h->dither_chain == 0 && h->chain_stream)) chain_mode = nq::FAST_CHAIN_SPLIT;
-        const bool split = chain_mode == nq::FAST_CHAIN_SPLIT && nq::gilbert_fast_split_eligible(P, G);
+        else if (h->dither_chain == 3) chain_mode = nq::FAST_CHAIN_SPLIT;
+        else if (h->dither_chain == 4 || (h->dither_chain == 0 && h->chain_stream)) chain_mode = nq::FAST_CHAIN_PIXEL;
+        const bool split = (chain_mode == nq::FAST_CHAIN_SPLIT || chain_mode == nq::FAST_CHAIN_PIXEL) && nq::gilbert_fast_split_eligible(P, G);
         const bool side = split && h->chain_stream && h->chain_stream != h->stream;
         if (split) ++g_split_passes;
         if (side) ++g_split_side;
@@ -1394,10 +1395,10 @@ struct BatchGuard {
     nq_handle* const* hs; int n;
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> events;
-    hipStream_t side = nullptr;          // the finish phase's side stream, once work may be on it
+    hipStream_t side[3] = {nullptr, nullptr, nullptr};    // the finish phase's side streams, once work may be on them
     BatchGuard(nq_handle* const* hh, int nn) : hs(hh), n(nn) { for (int i = 0; i < n; ++i) streams.push_back(hs[i]->stream); }
     ~BatchGuard() {
-        if (side) (void) hipStreamSynchronize(side);        // (a chain pass of a call that failed half-way may still run there)
+        for (hipStream_t s : side) if (s) (void) hipStreamSynchronize(s);        // (a chain pass of a call that failed half-way may still run there)
         for (int i = 0; i < n; ++i) { hs[i]->stream = streams[i]; hs[i]->sc = &hs[i]->own; hs[i]->light_events = false; hs[i]->chain_stream = nullptr; }
         for (hipEvent_t e : events) (void) hipEventDestroy(e);
     }
@@ -1501,7 +1502,7 @@ int nq_set_option(nq_handle* h, int option, int value) {
     if (!h) return NQ_ERR_INVALID;
     if (option == NQ_OPT_CELL_LISTS) { h->use_lists = value != 0; return NQ_OK; }
     if (option == NQ_OPT_FAST_DITHER) { h->use_fast_dither = value != 0; return NQ_OK; }
-    if (option == NQ_OPT_DITHER_CHAIN) { h->dither_chain = value >= 0 && value <= 3 ? (int) value : 1; return NQ_OK; }
+    if (option == NQ_OPT_DITHER_CHAIN) { h->dither_chain = value >= 0 && value <= 4 ? (int) value : 1; return NQ_OK; }
     if (option == NQ_OPT_MERGE_WALL_SECONDS) { h->merge_wall_s = value > 0 ? value : 0; return NQ_OK; }
     NQ_FAIL(h, NQ_ERR_INVALID, "unknown option %d", option);
 }
@@ -1528,8 +1529,8 @@ int nq_selftest_fast(nq_handle* h, int which, const void* in, int64_t n, uint32_
     // words of a counting form), end of the range's domain
     static const struct { int rec_bytes, out_words; int64_t domain; } k_mode[] = {
         {0, 2, (int64_t) 1 << 32}, {0, 3, 1 << 24}, {8, 3, 0}, {0, 1, (int64_t) 1 << 31}, {0, 0, (int64_t) 1 << 31}, {8, 1, 0}, {0, 0, 1 << 30},
-        {24, 3, 0}, {0, 3, 1 << 24}, {0, 3, 1 << 24}, {0, 3, 1 << 24}, {0, 1, 1 << 24}, {8, 1, 0}, {4, 2, 0}, {4, 1, 0}, {8, 1, 0}};
-    static_assert(sizeof k_mode / sizeof k_mode[0] == NQ_FAST_ST_MODES && NQ_FAST_ST_MODES == NQ_FAST_ST_NEAR_SAFE + 1, "one row per NQ_FAST_ST_* mode, in their order");
+        {24, 3, 0}, {0, 3, 1 << 24}, {0, 3, 1 << 24}, {0, 3, 1 << 24}, {0, 1, 1 << 24}, {8, 1, 0}, {4, 2, 0}, {4, 1, 0}, {8, 1, 0}, {8, 66, 0}};
+    static_assert(sizeof k_mode / sizeof k_mode[0] == NQ_FAST_ST_MODES && NQ_FAST_ST_MODES == NQ_FAST_ST_JUMP + 1, "one row per NQ_FAST_ST_* mode, in their order");
     const auto& m = k_mode[which];
     const bool counting = m.out_words == 0;
     if (!counting && n > ((int64_t) 1 << 26)) NQ_FAIL(h, NQ_ERR_INVALID, "nq_selftest_fast: more than 2^26 elements in one call");
@@ -1842,24 +1843,35 @@ int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const in
     return nq_convert_frames_refined(h, n, argb, widths, heights, nMaxColors, 0, dither, rng_seeds, mode, out_argb, out_index, out_palette, out_K);
 }
 
-// Finish phase of the batch entry points: every handle's chain_stream for the dither passes that follow.  *side: the side stream (then the
-// caller alternates two scratch sets and orders the streams by chain_done), or null with NQ_DITHER_SIDE_STREAM=0 (A/B timing): the split
-// form in plain serial order on the main stream.  The BatchGuard of the call takes chain_stream back.
-int finish_side_stream(nq_handle* h0, nq_handle* const* hs, int n, hipStream_t* side) {
-    *side = nullptr;
+// Finish phase of the batch entry points: every handle's chain_stream for the dither passes that follow.  With S scratch sets (the per-pixel
+// scratch of the first S handles) image i takes set i % S and side stream i % (S - 1); the caller orders the main stream behind chain_done of
+// image i - S before image i reuses its set, and joins the last S images at the end of the phase.  S = 2, the default, is one side stream
+// and two sets by image parity; NQ_FINISH_SETS = 2..4 overrides, bounded by the number of handles (a single image has one set).  *sets = S and side[0 .. S - 2] = the side streams, or *sets = 0 with NQ_DITHER_SIDE_STREAM=0 (A/B
+// timing): the split form in plain serial order on the main stream.  The BatchGuard of the call takes chain_stream back.
+int finish_side_streams(nq_handle* h0, nq_handle* const* hs, int n, int* sets, hipStream_t side[3]) {
+    *sets = 0;
+    side[0] = side[1] = side[2] = nullptr;
     bool use_side = true;
     if (const char* e = std::getenv("NQ_DITHER_SIDE_STREAM")) use_side = std::atoi(e) != 0;
     if (!use_side) {
         for (int i = 0; i < n; ++i) hs[i]->chain_stream = hs[i]->stream;
         return NQ_OK;
     }
+    int S = 2;
+    if (const char* e = std::getenv("NQ_FINISH_SETS")) { const int v = std::atoi(e); if (v >= 2 && v <= 4) S = v; }
+    S = std::max(2, std::min(S, n));
     if (!h0->lane_stream) NQ_HIP(h0, hipStreamCreateWithFlags(&h0->lane_stream, hipStreamNonBlocking));
+    side[0] = h0->lane_stream;
+    for (int k = 1; k < S - 1; ++k) {
+        if (!h0->more_lanes[k - 1]) NQ_HIP(h0, hipStreamCreateWithFlags(&h0->more_lanes[k - 1], hipStreamNonBlocking));
+        side[k] = h0->more_lanes[k - 1];
+    }
     for (int i = 0; i < n; ++i) {
         if (!hs[i]->chain_gate) NQ_HIP(h0, hipEventCreateWithFlags(&hs[i]->chain_gate, hipEventDisableTiming));
         if (!hs[i]->chain_done) NQ_HIP(h0, hipEventCreateWithFlags(&hs[i]->chain_done, hipEventDisableTiming));
-        hs[i]->chain_stream = h0->lane_stream;
+        hs[i]->chain_stream = side[i % (S - 1)];
     }
-    *side = h0->lane_stream;
+    *sets = S;
     return NQ_OK;
 }
 
@@ -1988,23 +2000,22 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
         }
     // The chain pass and the hand-back pass of image i (a few wavefronts, one chain's latency) run on a side stream beside the lists,
     // saliency map and light kernel of image i + 1 (dither_device, chain_stream).  What they read of the per-image scratch -- saliency plane,
-    // list records -- alternates between two sets by image parity; the main stream waits for image i's side work before image i + 2
-    // reuses its set, and at the end of the phase.
-    hipStream_t side = nullptr;
-    rc = finish_side_stream(h0, hs, n, &side);
+    // list records -- rotates through S sets (finish_side_streams; two by default: image parity); the main stream waits for image i's side
+    // work before image i + S reuses its set, and at the end of the phase.
+    int S = 0;
+    rc = finish_side_streams(h0, hs, n, &S, guard.side);
     if (rc) return batch_fail(h0, h0, rc);
-    guard.side = side;
     for (int i = 0; i < n; ++i) {
         uint32_t* pal = out_palettes + (size_t) i * palette_stride;
-        if (side) {
-            hs[i]->sc = lane_sc[i & 1];
-            if (i >= 2 && hs[i - 2]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(lane_s[0], hs[i - 2]->chain_done, 0));
+        if (S) {
+            hs[i]->sc = &hs[n > 1 ? i % S : 0]->own;
+            if (i >= S && hs[i - S]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(lane_s[0], hs[i - S]->chain_done, 0));
         }
         rc = dither_device(hs[i], d_argb[i], widths[i], heights[i], pal, out_K[i], dither, rng_seeds[i], mode, d_out_argb[i],
                            d_out_index ? d_out_index[i] : nullptr);
         if (rc) return batch_fail(h0, hs[i], rc);
     }
-    for (int i = std::max(0, n - 2); i < n; ++i)
+    for (int i = std::max(0, n - std::max(S, 2)); i < n; ++i)
         if (hs[i]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(lane_s[0], hs[i]->chain_done, 0));
     (void) hipEventRecord(h0->bev[3], lane_s[0]);
     NQ_HIP(h0, hipStreamSynchronize(lane_s[0]));
@@ -2070,11 +2081,10 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
     if (rc) return rc;
     (void) hipEventRecord(h0->bev[2], h0->stream);
     for (int i = 0; i < n; ++i) if (jobs[i].merge) rec(hs[i], 4);
-    // (the chain pass of image i beside the light kernel of image i + 1, two scratch sets by parity: as in nq_convert_batch_device)
-    hipStream_t side = nullptr;
-    rc = finish_side_stream(h0, hs, n, &side);
+    // (the chain pass of image i beside the light kernel of image i + 1, S scratch sets in rotation: as in nq_convert_batch_device)
+    int S = 0;
+    rc = finish_side_streams(h0, hs, n, &S, guard.side);
     if (rc) return batch_fail(h0, h0, rc);
-    guard.side = side;
     for (int i = 0; i < n; ++i) {
         uint32_t* pal = out_palettes + (size_t) i * palette_stride;
         if (jobs[i].merge) {
@@ -2083,9 +2093,9 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
         }
         const int r = i % RING;
         if (i >= RING) NQ_HIP(h0, hipStreamWaitEvent(h0->stream, ev_dl[i - RING], 0));     // the slot's previous result has left
-        if (side) {
-            hs[i]->sc = (i & 1) && n > 1 ? &hs[1]->own : &h0->own;
-            if (i >= 2 && hs[i - 2]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(h0->stream, hs[i - 2]->chain_done, 0));
+        if (S) {
+            hs[i]->sc = &hs[n > 1 ? i % S : 0]->own;
+            if (i >= S && hs[i - S]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(h0->stream, hs[i - S]->chain_done, 0));
         }
         rc = dither_device(hs[i], hs[i]->d_in.p, widths[i], heights[i], pal, out_K[i], dither, rng_seeds[i], mode,
                            (uint32_t*) h0->ring_argb[r].p, h0->ring_index[r].p);
@@ -2099,7 +2109,7 @@ int nq_convert_batch(nq_handle* const* hs, int n, const uint32_t* const* argb, c
             NQ_HIP(h0, hipMemcpyAsync(out_index[i], h0->ring_index[r].p, px * sizeof(uint16_t), hipMemcpyDeviceToHost, cs));
         NQ_HIP(h0, hipEventRecord(ev_dl[i], cs));
     }
-    for (int i = std::max(0, n - 2); i < n; ++i)
+    for (int i = std::max(0, n - std::max(S, 2)); i < n; ++i)
         if (hs[i]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(h0->stream, hs[i]->chain_done, 0));
     (void) hipEventRecord(h0->bev[3], h0->stream);
     NQ_HIP(h0, hipStreamSynchronize(h0->stream));

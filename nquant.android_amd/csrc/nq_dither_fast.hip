@@ -54,6 +54,10 @@ struct FastArgs {
     int* needCount;
     int* needTiles;
     int listed;
+    // gilbert_pixel_kernel (the light pass, one lane per pixel): log2 of the pixels of a full tile (4, 5 or 6), tile groups (one wavefront
+    // iteration: 64 >> tileShift tiles) per workgroup, and the test switch NQ_LIGHT_REJECT (a draw whose bits under the mask are all zero counts as rejected; 0 = off)
+    int tileShift, pixelRun;
+    unsigned rejectMask;
 };
 // instruction budget by block (tools/fast_budget.py compiles this file with -DNQ_FAST_MARKS and counts between the markers)
 #ifdef NQ_FAST_MARKS
@@ -74,6 +78,7 @@ struct FastArgs {
 #ifdef NQ_FAST_COUNT
 enum { FC_NEAREST = 0, FC_NEAREST_EXACT, FC_NEAREST_EXACT_LANES, FC_NEAREST_EXACT_N2_SUM, FC_NEAREST_EXACT_N2_MAX, FC_NEAREST_TAIL, FC_CLOSEST,
        FC_CLOSEST_TAIL, FC_CLOSEST_EXACT, FC_YDIFF, FC_YDIFF_F64, FC_TANH, FC_TANH_LIBRARY, FC_CHAIN_LIGHT, FC_CHAIN_REWALK,
+       FC_PIXEL_NODRAW,       // gilbert_pixel_kernel: looked-up steps whose pick does not draw (closest[2] == 0)
        FC_SLOTS = 16 };
 __device__ unsigned long long g_fast_count[FC_SLOTS];
 __device__ __forceinline__ void fast_count_add(int slot, bool cond, unsigned long long v, bool use_max) {
@@ -560,29 +565,67 @@ __device__ __forceinline__ void fast_accumulate(const float (&q)[NQ_FQ][4], floa
 // Ditherable.nearestColorIndex(palette, c, bidx) = closestColorIndex (K > 4), NQ/PnnLABQuantizer.java:407-474: the step's lookup, shared by
 // the light walk and the full walk of the kernel below (LIGHT only names the markers of tools/fast_budget.py)
 #define NQ_MARK_L(name) do { if (LIGHT) NQ_MARK("light_" name); else NQ_MARK(name); } while (0)
+// The lookup in two halves around the pick, so that a caller can hand the pick's draw in (gilbert_pixel_kernel takes it from the jump
+// table).  Head: the cell's record and closest[] of a colour with alpha > 0xF; the pick draws exactly when t.e0 != 0.
+struct FastLabHead { FastClosest t; uint4 na; int n2, cell; };
+template <bool LIGHT>
+__device__ __forceinline__ FastLabHead fast_lab_head(const FastLds& S, const FastLookup& X, const FastArgs& F, int c, bool& failed) {
+    FastLabHead H;
+    H.cell = NQ_KO(1) ? 0 : cell_of(c);
+    const uint4 la = X.packed[2 * H.cell];
+    H.na = X.packed[2 * H.cell + 1];
+    const int ncl = (int) (la.w >> 24), nnr = (int) (H.na.w >> 24);
+    if (ncl == 255 || nnr == 255) failed = true;
+    const int n1 = (ncl == 255 || NQ_KO(16)) ? 0 : ncl;
+    H.n2 = nnr == 255 ? 0 : nnr;
+    NQ_MARK_L("lists_fetched");
+    H.t = fast_closest_tuple(S, X, c, la, n1, H.cell);
+    NQ_MARK_L("closest_done");
+    return H;
+}
+// Tail: idx = which of the two closest candidates the pick chose (:465-468), then the nearest fallback
+template <bool LIGHT>
+__device__ __forceinline__ int fast_lab_tail(const FastLds& S, const FastLookup& X, const FastArgs& F, int K, int c, const FastLabHead& H, int idx) {
+    const int ci = idx ? H.t.c1 : H.t.c0, ei = idx ? H.t.e1 : H.t.e0;
+    int qidx = ci;
+    NQ_MARK_L("picked");
+    if ((ei >= K || ci == 0 || c_alpha(S.argb[ci]) < c_alpha(c)) && !NQ_KO(2)) {
+        qidx = fast_nearest(S, X, c, H.na, H.n2, H.cell);
+    }
+    NQ_MARK_L("nearest_done");
+    return qidx;
+}
 template <bool LIGHT>
 __device__ __forceinline__ int fast_lab_index(const FastLds& S, const FastLookup& X, const FastArgs& F, int K, int c, long long& rng, bool& failed) {
     int qidx = 0;
     if (c_alpha(c) <= 0xF) failed = true;           // transparent colour: the generic kernel redoes this tile
     else {
-        const int cell = NQ_KO(1) ? 0 : cell_of(c);
-        const uint4 la = X.packed[2 * cell], na = X.packed[2 * cell + 1];
-        const int ncl = (int) (la.w >> 24), nnr = (int) (na.w >> 24);
-        if (ncl == 255 || nnr == 255) failed = true;
-        const int n1 = (ncl == 255 || NQ_KO(16)) ? 0 : ncl, n2 = nnr == 255 ? 0 : nnr;
-        NQ_MARK_L("lists_fetched");
-        const FastClosest t = fast_closest_tuple(S, X, c, la, n1, cell);
-        NQ_MARK_L("closest_done");
-        const int idx = fast_closest_pick(t, rng);              // :465-468
-        const int ci = idx ? t.c1 : t.c0, ei = idx ? t.e1 : t.e0;
-        qidx = ci;
-        NQ_MARK_L("picked");
-        if ((ei >= K || ci == 0 || c_alpha(S.argb[ci]) < c_alpha(c)) && !NQ_KO(2)) {
-            qidx = fast_nearest(S, X, c, na, n2, cell);
-        }
-        NQ_MARK_L("nearest_done");
+        const FastLabHead H = fast_lab_head<LIGHT>(S, X, F, c, failed);
+        qidx = fast_lab_tail<LIGHT>(S, X, F, K, c, H, fast_closest_pick(H.t, rng));
     }
     return qidx;
+}
+
+// ---- java.util.Random by jump-ahead.  The state after k draws is (A_k s0 + C_k) mod 2^48 with A_0 = 1, C_0 = 0, A_{k+1} = A_k * NQ_JR_MULT,
+// C_{k+1} = C_k * NQ_JR_MULT + 0xB: entry k of the table is {A_k, C_k}, k = 0 .. NQ_JUMP_MAX (a tile of 64 steps draws at most 64 times).
+#define NQ_JUMP_MAX 65
+struct __align__(16) JumpTable { unsigned long long ac[NQ_JUMP_MAX + 1][2]; };
+constexpr JumpTable make_jump_table() {
+    JumpTable t{};
+    unsigned long long a = 1ULL, c = 0ULL;
+    for (int k = 0; k <= NQ_JUMP_MAX; ++k) {
+        t.ac[k][0] = a; t.ac[k][1] = c;
+        a = (a * (unsigned long long) NQ_JR_MULT) & (unsigned long long) NQ_JR_MASK;
+        c = (c * (unsigned long long) NQ_JR_MULT + 0xBULL) & (unsigned long long) NQ_JR_MASK;
+    }
+    return t;
+}
+__device__ const JumpTable g_jump_table = make_jump_table();
+// next(31) of the draw that follows n earlier draws on the state s0 (jr_seed(...)): the n + 1-th state, its top 31 bits
+__device__ __forceinline__ int fast_jump_draw(const ulonglong2* __restrict__ tab, long long s0, int n) {
+    const ulonglong2 ac = tab[n + 1];
+    const unsigned long long st = (ac.x * (unsigned long long) s0 + ac.y) & (unsigned long long) NQ_JR_MASK;
+    return (int) (st >> 17);
 }
 
 // write-out of gilbert_fast_kernel / gilbert_light_kernel (behind the barrier that ends the walks): the wave's 64 tiles leave row by row; a
@@ -989,6 +1032,138 @@ __global__ void __launch_bounds__(256, 4) gilbert_light_kernel(DevParams P, Gilb
     fast_write_out(S, F, T, tid, width, out_index, out_argb);
 }
 
+// The light pass with one lane per PIXEL (the pixel form), for power-of-two tiles of 16, 32 or 64 pixels: lane l of a
+// wavefront is path step l % tilepx of tile l / tilepx of its tile group, so no lane waits on its own history and work comes in units of one
+// wavefront-step.  A light step is a pure function of the source pixel, its saliency and its position -- except the draw of the pick, and
+// java.util.Random is a 48-bit LCG: the draw a step sees is the (n + 1)-th state after the tile seed, n = the number of earlier steps of the
+// tile that drew (fast_closest_pick draws exactly when t.e0 != 0), a popcount over a ballot; the state comes from the jump table.  The
+// rejection loop of nextInt(32767) (2 of 2^31 values of next(31)) would shift every later draw of the tile: such a tile goes onto the need
+// list like one that needs the chain, and the chain pass walks it with the sequential Random.  Need / hand-back lists: the same sets, in
+// the same buffers, as gilbert_light_kernel (one lane per tile appends).  No staging: index and ARGB leave from registers; the four
+// wavefronts of a workgroup take neighbouring tile groups, so tile rows of one image row leave the CU together.  Pixel and saliency of the
+// wavefront's next group are requested before the current group's scans.  Not persistent: a workgroup walks F.pixelRun groups and retires,
+// so the chain pass and the hand-back pass of the previous image keep getting onto the chip.
+__global__ void __launch_bounds__(256, 5) gilbert_pixel_kernel(DevParams P, GilbertConsts G, TileGeom T, FastArgs F,
+                                                               const int* __restrict__ pixels, const float* __restrict__ saliency,
+                                                               const int* __restrict__ g_palette, long long seed,
+                                                               unsigned short* __restrict__ out_index, int* __restrict__ out_argb) {
+    __shared__ __align__(16) int s_argb[256];
+    __shared__ __align__(16) float4 s_lab[256];
+    __shared__ float s_gamma32[256];
+    __shared__ __align__(16) signed char s_blue[4096];
+    __shared__ unsigned s_path[4 * 64];
+    __shared__ __align__(16) ulonglong2 s_jump[NQ_JUMP_MAX + 1];
+    const int K = P.K;
+    const int tid = threadIdx.x;
+    const int sh = F.tileShift, tilepx = 1 << sh;
+    {
+        const int c2 = tid < K ? g_palette[tid] : 0;
+        s_argb[tid] = c2;
+        const Lab l2 = RGB2LAB(c2);                    // getLab(palette[i]) (NQ/PnnLABQuantizer.java:352)
+        s_lab[tid] = make_float4(l2.L, l2.A, l2.B, 0.f);
+        s_gamma32[tid] = (float) g_tab.gamma[tid];
+        for (int i = tid; i < 1024; i += 256) ((int*) s_blue)[i] = ((const int*) g_tab.blue)[i];
+        const int s = tid >> 6, i = tid & 63;
+        if (i < tilepx) s_path[s * tilepx + i] = i < T.path_len[s] ? T.path[s][i] : 0u;
+        if (tid <= NQ_JUMP_MAX) s_jump[tid] = make_ulonglong2(g_jump_table.ac[tid][0], g_jump_table.ac[tid][1]);
+    }
+    __syncthreads();
+    FastLds S;
+    S.argb = s_argb; S.lab = s_lab; S.gamma = g_tab.gamma; S.gamma32 = s_gamma32; S.blue = s_blue; S.path = s_path; S.tileinfo = nullptr; S.stage = nullptr;
+    FastLookup X;
+    X.packed = F.packed; X.cont = F.cont; X.qa = F.qa; X.qb = F.qb; X.qc = F.qc;
+    X.ratio = P.ratio; X.wr = P.PR * (1 - P.ratio); X.wg = P.PG * (1 - P.ratio); X.wb = P.PB * (1 - P.ratio);
+    X.kfirst = P.hasAlpha ? 1 : 0;
+
+    const int ntiles = T.tiles_x * T.tiles_y;
+    const int width = T.width;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int step = lane & (tilepx - 1), sub = lane >> sh;       // this lane: path step `step` of tile `sub` of the group
+    const int tpw = 64 >> sh;                                     // tiles per group
+    const int ngroups = (ntiles + tpw - 1) / tpw;
+    const int g_end = min((int) blockIdx.x * F.pixelRun + F.pixelRun, ngroups);
+    // the lanes of this lane's tile, and those of them below this lane
+    const unsigned long long tile_lanes = (sh == 6 ? ~0ULL : ((1ULL << tilepx) - 1ULL) << (sub << sh));
+    const unsigned long long below = tile_lanes & ((1ULL << lane) - 1ULL);
+
+    // geometry and fetch of this lane's step in group g: tile_n < 0 = a dead lane (no tile, or a step past the shape's path)
+    int tile_n = -1, xx_n = 0, yy_n = 0, bidx_n = 0, pixel_n = 0;
+    float sal_n = 0.f;
+    auto fetch = [&](int g) {
+        const int tile = g * tpw + sub;
+        tile_n = -1;
+        if (g < g_end && tile < ntiles) {
+            const int ty = tile / T.tiles_x, tx = tile - ty * T.tiles_x;
+            const int shape = (tx == T.tiles_x - 1 ? 1 : 0) | (ty == T.tiles_y - 1 ? 2 : 0);
+            if (step < T.path_len[shape]) {
+                const unsigned d = s_path[shape * tilepx + step];
+                const int x = tx * T.tile_w + (int) (d & 0xFFFFu), y = ty * T.tile_h + (int) (d >> 16);
+                tile_n = tile; xx_n = x; yy_n = y + T.y_origin;
+                bidx_n = x + y * width;
+                pixel_n = pixels[bidx_n];
+                sal_n = saliency[bidx_n];
+            }
+        }
+    };
+    int g = (int) blockIdx.x * F.pixelRun + wave;
+    fetch(g);
+    for (; g < g_end; g += 4) {
+        const int tile = tile_n, xx = xx_n, yy = yy_n, bidx = bidx_n, pixel = pixel_n;
+        const float sal = sal_n;
+        const bool active = tile >= 0;
+        fetch(g + 4);
+        bool need = false, failed = false, draws = false;
+        int c = 0, qidx = 0;
+        if (active) {
+            need = K >= 256 && sal > .99f;
+            if (!need) c = fast_dither_color<true>(S, G, K, xx, yy, 0, pixel, sal, need);
+        }
+        const bool look = active && !need && c_alpha(c) > 0xF;
+        if (active && !need && !look) failed = true;           // transparent colour: the generic kernel redoes this tile
+        FastLabHead H;
+        H.t.c0 = H.t.c1 = H.t.e0 = H.t.e1 = 0; H.na = make_uint4(0u, 0u, 0u, 0u); H.n2 = 0; H.cell = 0;
+        if (look) {
+            H = fast_lab_head<true>(S, X, F, c, failed);
+            draws = H.t.e0 != 0;
+        }
+        NQ_COUNT_SUM(FC_PIXEL_NODRAW, look && !draws, 1);
+        const unsigned long long dmask = __ballot(draws);
+        bool reject = false;
+        if (look) {
+            int idx = 0;
+            if (draws) {
+                // random.nextInt(32767) % (closest[3] + closest[2]) <= closest[3] (fast_closest_pick), the draw by jump-ahead
+                const long long s0 = jr_seed((long long) mix64((unsigned long long) seed + (unsigned long long) (T.tile_base + tile)));
+                const int uu = fast_jump_draw(s_jump, s0, __popcll(dmask & below));
+                bool accept;
+                const int r = fast_nextint_fold(uu, accept);
+                reject = !accept || (F.rejectMask && ((unsigned) uu & F.rejectMask) == 0u);
+                const int dsum = (int) ((unsigned) H.t.e1 + (unsigned) H.t.e0);
+                idx = fast_pick_rem(r, dsum) <= H.t.e1 ? 0 : 1;
+            }
+            qidx = fast_lab_tail<true>(S, X, F, K, c, H, idx);
+        }
+        const bool tile_listed = (__ballot(need || reject) & tile_lanes) != 0ULL;
+        const bool tile_failed = (__ballot(failed) & tile_lanes) != 0ULL;
+        NQ_COUNT_SUM(FC_CHAIN_LIGHT, active && step == 0 && !tile_listed, 1);
+        NQ_COUNT_SUM(FC_CHAIN_REWALK, active && step == 0 && tile_listed, 1);
+        if (active && !tile_listed) {
+            out_index[bidx] = (unsigned short) qidx;
+            if (out_argb) out_argb[bidx] = s_argb[qidx];
+        }
+        if (active && step == 0) {                  // (step 0 lies on every shape's path)
+            if (tile_listed) {
+                const int slot = atomicAdd(F.needCount, 1);
+                if (slot < F.failedCap) F.needTiles[slot] = tile;
+            }
+            else if (tile_failed) {
+                const int slot = atomicAdd(F.failed, 1);
+                if (slot < F.failedCap) F.failed[1 + slot] = tile;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // The same two lookups as stand-alone kernels behind nq_nearest_index / nq_closest_tuple / LOOKUP_ONLY (BASELINE cfg 2): the
 // pure functions of SURVEY 8b, so that the float32 filters of the dither kernel are checked against the oracle colour by colour
@@ -1292,6 +1467,22 @@ __global__ void __launch_bounds__(256) fast_selftest_kernel(DevParams P, FastArg
             A.out[i] = (unsigned) k1 | (safe ? 0x10000u : 0u);
             break;
         }
+        case NQ_FAST_ST_JUMP: {
+            // record: a 48-bit Random state s0.  out[66 i + n], n = 0..64: the draw fast_jump_draw gives after n earlier draws | 1 << 31 when
+            // fast_nextint_fold rejects it; out[66 i + 65]: how many of them differ from the draw after n sequential jr_next
+            long long seq = ((const long long*) A.in)[i] & NQ_JR_MASK;
+            const long long s0 = seq;
+            unsigned differ = 0u;
+            for (int n = 0; n <= 64; ++n) {
+                const int uu = fast_jump_draw(reinterpret_cast<const ulonglong2*>(g_jump_table.ac), s0, n);
+                if (uu != jr_next(seq, 31)) ++differ;
+                bool accept;
+                (void) fast_nextint_fold(uu, accept);
+                A.out[66 * i + n] = (unsigned) uu | (accept ? 0u : 0x80000000u);
+            }
+            A.out[66 * i + 65] = differ;
+            break;
+        }
         default: break;
         }
     }
@@ -1337,6 +1528,10 @@ bool gilbert_fast_eligible(const DevParams& P, const GilbertConsts& G, const Til
 bool gilbert_fast_split_eligible(const DevParams& P, const GilbertConsts& G) {
     return P.kind == 1 && G.hasSaliencies && G.dither && 2 * std::max(2, P.K - G.margin) > 100;
 }
+bool gilbert_pixel_eligible(const TileGeom& T) {
+    const int tilepx = T.tile_w * T.tile_h;
+    return (T.tile_w & (T.tile_w - 1)) == 0 && (T.tile_h & (T.tile_h - 1)) == 0 && (tilepx == 16 || tilepx == 32 || tilepx == 64);
+}
 // the packed records are needed by the LAB lookups and by the RGB dither kernel
 bool fast_pack_wanted(const DevParams& P, const ListsView& lv) {
     return fast_lookup_eligible(P, lv) || (P.kind == 0 && P.K > 32 && P.K <= 256 && !P.hasSemi && !P.hasAlpha && lv.nearest && lv.closest);
@@ -1375,7 +1570,8 @@ hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const
     F.chainAlways = chain_mode == FAST_CHAIN_ALWAYS ? 1 : 0;
     F.needCount = d_failed - 1;
     F.needTiles = d_failed + 1 + ntiles;
-    const bool split = chain_mode == FAST_CHAIN_SPLIT && gilbert_fast_split_eligible(P, G);
+    const bool split = (chain_mode == FAST_CHAIN_SPLIT || chain_mode == FAST_CHAIN_PIXEL) && gilbert_fast_split_eligible(P, G);
+    const bool pixel_form = split && chain_mode == FAST_CHAIN_PIXEL && gilbert_pixel_eligible(T);
 #ifdef NQ_FAST_KNOCKOUT
     if (const char* e = std::getenv("NQ_FAST_DEBUG")) F.debug = std::atoi(e);
 #endif
@@ -1389,11 +1585,25 @@ hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const
         // (32 KB at 8x8 tiles: five workgroups fit a CU; NQ_LIGHT_WAVES=4 pads the block so that four fit, for A/B timing: DESIGN.md section 6)
         static const bool four = [] { const char* w = std::getenv("NQ_LIGHT_WAVES"); return w && std::atoi(w) == 4; }();
         const size_t llds = light_lds_bytes(tilepx, F.strideBytes) + (four ? 256 * 8 : 0);
-        if (llds > 64 * 1024) {
-            e = hipFuncSetAttribute((const void*) gilbert_light_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-            if (e != hipSuccess) return e;
+        if (pixel_form) {
+            // NQ_PIXEL_RUN: tiles per workgroup (DESIGN.md section 6 has the measurements); NQ_LIGHT_REJECT=b: a draw whose low b bits are
+            // zero counts as rejected (tests: listing a tile is always safe).  Both are read at every launch.
+            int run_tiles = 64, reject_bits = 0;
+            if (const char* r = std::getenv("NQ_PIXEL_RUN")) { const int v = std::atoi(r); if (v >= 1) run_tiles = v; }
+            if (const char* r = std::getenv("NQ_LIGHT_REJECT")) { const int v = std::atoi(r); if (v >= 1 && v <= 30) reject_bits = v; }
+            F.tileShift = tilepx == 64 ? 6 : tilepx == 32 ? 5 : 4;
+            const int tpw = 64 / tilepx, ngroups = (ntiles + tpw - 1) / tpw;
+            F.pixelRun = std::max(1, std::min(run_tiles / tpw, ngroups));
+            F.rejectMask = reject_bits ? (1u << reject_bits) - 1u : 0u;
+            const int pgrid = (ngroups + F.pixelRun - 1) / F.pixelRun;
+            hipLaunchKernelGGL(gilbert_pixel_kernel, dim3(pgrid), dim3(256), 0, s, P, G, T, F, d_pixels, d_saliency, d_palette, seed, d_index, d_argb);
+        } else {
+            if (llds > 64 * 1024) {
+                e = hipFuncSetAttribute((const void*) gilbert_light_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
+                if (e != hipSuccess) return e;
+            }
+            hipLaunchKernelGGL(gilbert_light_kernel, dim3(grid), dim3(256), llds, s, P, G, T, F, d_pixels, d_saliency, d_palette, seed, d_index, d_argb);
         }
-        hipLaunchKernelGGL(gilbert_light_kernel, dim3(grid), dim3(256), llds, s, P, G, T, F, d_pixels, d_saliency, d_palette, seed, d_index, d_argb);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
         hipStream_t cs = s;

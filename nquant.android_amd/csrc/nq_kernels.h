@@ -89,8 +89,11 @@ bool gilbert_fast_eligible(const DevParams& P, const GilbertConsts& G, const Til
 // chain_mode: how the launches that can do without the error chain in most steps (gilbert_fast_split_eligible) run
 enum { FAST_CHAIN_FUSED = 0,      // one kernel: a wavefront walks without the chain and starts over with it when a lane needs it
        FAST_CHAIN_ALWAYS = 1,     // NQ_OPT_DITHER_CHAIN = 1: no light walk, every step runs the error chain
-       FAST_CHAIN_SPLIT = 2 };    // gilbert_light_kernel (87 registers, four or more wavefronts per SIMD; per-tile need list), then the full walk over the listed tiles
+       FAST_CHAIN_SPLIT = 2,      // gilbert_light_kernel (87 registers, four or more wavefronts per SIMD; per-tile need list), then the full walk over the listed tiles
+       FAST_CHAIN_PIXEL = 3 };    // the split form with gilbert_pixel_kernel (one lane per pixel, the draws by jump-ahead) as its light pass where the tile
+                                  // size allows (gilbert_pixel_eligible), with gilbert_light_kernel elsewhere
 bool gilbert_fast_split_eligible(const DevParams& P, const GilbertConsts& G);
+bool gilbert_pixel_eligible(const TileGeom& T);       // power-of-two tiles of 16, 32 or 64 pixels
 // d_failed points at word 1 of an int[2 + 2 * tiles] block: d_failed[-1] = the need count of the split form, d_failed[0] = the hand-back
 // count, d_failed[1 .. tiles] the tiles handed back, d_failed[1 + tiles ..] the need list.  chain_stream (split form only, nullable): the chain
 // pass goes onto that stream behind chain_gate, recorded on s after the light kernel; the caller orders what follows (the generic kernel over

@@ -24,7 +24,7 @@ OPT_CELL_LISTS, OPT_FAST_DITHER, OPT_MERGE_WALL_SECONDS, OPT_DITHER_CHAIN = 1, 2
 FAST_ST = {"TANH": (0, 2), "CLOSEST_ERR": (1, 3), "CLOSEST_ERR_PAIRS": (2, 3), "NEXTINT": (3, 1), "NEXTINT_COUNT": (4, 0), "REM": (5, 1),
            "REM_COUNT": (6, 0), "YDIFF": (7, 3), "YDIFF_RANGE": (8, 3), "LAB32": (9, 3), "LAB64": (10, 3), "NEAR_D32": (11, 1),
            "NEAR_D32_PAIRS": (12, 1), "TANH_BITS": (13, 2), "NEXTINT_LIST": (14, 1),
-           "NEAR_SAFE": (15, 1)}
+           "NEAR_SAFE": (15, 1), "JUMP": (16, 66)}
 YDIFF_RECORD = np.dtype([("c1", np.int32), ("c2", np.int32), ("gt", np.int32), ("pad", np.int32), ("thr", np.float64)])
 
 
@@ -413,7 +413,7 @@ class PnnQuantizer:
 
     def selftest_fast(self, mode, first=None, count=None, a0=0, thresholds=None, gt=False, records=None):
         """One filter of the specialised dither kernel on its own (nq_selftest_fast).  Range modes: first, count (+ a0; YDIFF_RANGE: up to
-        32 float64 thresholds and gt); explicit modes: records (int32 (n, 2); TANH_BITS uint32 (n,); NEXTINT_LIST int32 (n,); YDIFF: YDIFF_RECORD).  Returns the (n, words) uint32 output, or
+        32 float64 thresholds and gt); explicit modes: records (int32 (n, 2); TANH_BITS uint32 (n,); NEXTINT_LIST int32 (n,); JUMP int64 (n,); YDIFF: YDIFF_RECORD).  Returns the (n, words) uint32 output, or
         (disagreements, first disagreeing input or None) for the counting forms."""
         which, words = FAST_ST[mode]
         if records is None:
@@ -422,7 +422,7 @@ class PnnQuantizer:
             src = np.concatenate([np.array([first, count, a0, a1], np.int64), thr.view(np.int64)])
             n = int(count)
         else:
-            src = np.ascontiguousarray(records, YDIFF_RECORD if mode == "YDIFF" else np.uint32 if mode == "TANH_BITS" else np.int32)
+            src = np.ascontiguousarray(records, YDIFF_RECORD if mode == "YDIFF" else np.uint32 if mode == "TANH_BITS" else np.int64 if mode == "JUMP" else np.int32)
             n = src.shape[0]
         out = np.zeros((n, words) if words else 4, np.uint32)
         self._check(self._L.nq_selftest_fast(self._h, which, src.ctypes.data, n, out.ctypes.data))

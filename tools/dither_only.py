@@ -1,6 +1,6 @@
 """Runs the dither pass of the bench image `reps` times (for rocprofv3 --kernel-trace --stats / --pmc).
 Usage: python tools/dither_only.py [size] [reps] [tile] [fast 0|1] [dither 0|1] [mode 1 = PARALLEL_TILED | 2 = LOOKUP_ONLY]
-       [chain = NQ_OPT_DITHER_CHAIN: 0 automatic | 1 the error chain in every step | 2 the fused light walk | 3 the split form]"""
+       [chain = NQ_OPT_DITHER_CHAIN: 0 automatic | 1 the error chain in every step | 2 the fused light walk | 3 the split form | 4 the split form, pixel-form light pass]"""
 import os
 import sys
 

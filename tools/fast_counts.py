@@ -16,7 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 NAMES = ["fast_nearest", "fast_nearest_exact", "  lanes that needed it", "  sum of n2 over those lanes", "  sum of the largest n2 (trips of its loop)",
          "fast_nearest32 rolled tail (n2 > 8)", "fast_closest_tuple", "fast_closest_tuple rolled tail (n1 > 8)",
          "closest_err_exact (per candidate step)", "fast_ydiff_cmp", "f64 Y_Diff", "tanh_to_float", "tanh_library",
-         "wavefronts that finished in the light walk", "wavefronts that walked again with the chain"]
+         "wavefronts that finished in the light walk", "wavefronts that walked again with the chain",
+         "pixel-form light pass: steps without a draw (lanes)"]
 
 
 def main():
