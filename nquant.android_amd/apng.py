@@ -10,9 +10,10 @@ import ctypes as C
 
 import numpy as np
 
+from ._frames_in import _opened, _pre_steps
 from .gif import _Handle, _delays, _index_maps, _palette
 from .hold import _hold_host, _threshold
-from .host import MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frames_quantizer, _ordered_keyword, load_library
+from .host import MODE_PARALLEL_TILED, NqError, _convert_frames_on, _ordered_keyword, load_library
 
 
 def _one_size(maps):
@@ -92,28 +93,12 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
     0..255 runs the temporal hold (hold.py) with that threshold between the two steps, on the same handle, so that pixels whose source
     moved by no more than it keep their index (footage with sensor or codec noise); the index maps pass through host memory in between.
     refine (0..64): that many k-means passes on the palette over the frames before the dither (refine.py); 0 is the call without it.
-    size / crop / linear_resample: with size=(width, height) or crop=(x, y, width, height) given, the frames are first cropped and
-    area-averaged down to `size` (None: the crop's size) as resample_frames does it (resample.py), on the same handle.
     ordered (None: the error-diffusion dither): an integer 0..255 dithers the frames with the ordered dither (ordered.py) with that
     limit instead; dither, mode and tile then take no part, and seeds may not be given.
-    yuv (None: the frames are ARGB words): a dict with the keys bt709 / full_range says that `frames` are (y, u, v) tuples of 8-bit
-    YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
-    orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
-    converting kernel --; size and crop are then those of the oriented frames.
-    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
-    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
-    with orient: then turned -- before anything else runs.
-    retime (None: the frames are shown as they are): a dict with the keys timestamps_us / period_us or fps / shutter_us / linear
-    (retime.py) blends the frames to that rate -- after the YUV, orient and reduce steps, which then run before anything else -- and
-    supplies delays_cs, which may not be given as well; seeds (one per frame) may not be given either.
+    size / crop / linear_resample, yuv, orient, yuv16 and retime say what `frames` are and what is done to them first: _frames_in.py.
     Returns (file bytes, palette); with return_rects=True (file bytes, palette, rectangles)."""
-    if retime is not None:
-        from .retime import _converter_frames as _retimed_frames
-        frames, delays_cs = _retimed_frames(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient, device)
-        yuv, yuv16, size, crop, orient = None, None, None, None, 1
-    if yuv16 is not None:
-        from .yuv16 import _converter_frames
-        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
+    frames, delays_cs, yuv, size, crop, orient = _pre_steps(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient,
+                                                            device)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("a PNG palette holds at most 256 entries")
     if yuv is None and len({np.asarray(f).shape for f in frames}) > 1:
@@ -123,17 +108,7 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
         hold = _threshold(hold)
     from .orient import _code as _orient_code
     orient = _orient_code(orient)
-    if yuv is None:
-        frames, q = _frames_quantizer(kind, frames, device, mode, tile)
-    else:
-        from .yuv import _yuv_host, _yuv_quantizer
-        frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
-    try:
-        if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
-        elif size is not None or crop is not None or orient != 1:
-            from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
+    with _opened(kind, frames, yuv, size, crop, linear_resample, orient, device, mode, tile) as (q, frames):
         palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
         maps = _index_maps([o.index for o in outs])
         height, width = _one_size(maps)
@@ -141,6 +116,4 @@ def convert_frames_to_apng(kind, frames, nMaxColors, dither, delays_cs=None, loo
             _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
         data, rects = _encode(q._L, q._h, "nq_encode_apng", [a.ctypes.data for a in maps], width, height, palette, delays_cs, loop,
                               segment_bytes, q._check)
-    finally:
-        q.close()
     return (data, palette, rects) if return_rects else (data, palette)

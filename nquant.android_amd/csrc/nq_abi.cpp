@@ -343,9 +343,16 @@ static inline hipError_t launch_status() {
     return a != hipSuccess ? a : b;
 }
 
-#define NQ_FAIL(h, code, ...) do { char _b[512]; std::snprintf(_b, sizeof _b, __VA_ARGS__); (h)->err = _b; return (code); } while (0)
-#define NQ_HIP(h, call) do { hipError_t _e = (call); if (_e != hipSuccess) { \
-    NQ_FAIL(h, NQ_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); } } while (0)
+// The failing macros write the text into a std::string the caller names and return the code.  NQ_FAIL / NQ_HIP name a handle's err,
+// NQ_CMP_FAIL / NQ_CMP_HIP the thread's handle-free string (the stateless calls); code that serves both takes the string (*_TO).
+#define NQ_FAIL_TO(err, code, ...) do { char _b[512]; std::snprintf(_b, sizeof _b, __VA_ARGS__); (err) = _b; return (code); } while (0)
+#define NQ_HIP_TEXT(err, call, text) do { hipError_t _e = (call); if (_e != hipSuccess) { \
+    NQ_FAIL_TO(err, NQ_ERR_HIP, "%s failed: %s (%s:%d)", text, hipGetErrorString(_e), __FILE__, __LINE__); } } while (0)
+#define NQ_HIP_TO(err, call) NQ_HIP_TEXT(err, call, #call)
+#define NQ_FAIL(h, code, ...) NQ_FAIL_TO((h)->err, code, __VA_ARGS__)
+#define NQ_HIP(h, call) NQ_HIP_TEXT((h)->err, call, #call)
+#define NQ_CMP_FAIL(code, ...) NQ_FAIL_TO(g_create_error, code, __VA_ARGS__)
+#define NQ_CMP_HIP(call) NQ_HIP_TEXT(g_create_error, call, #call)
 
 namespace {
 
@@ -3192,6 +3199,199 @@ int nq_encode_apng(nq_handle* h, int n, const uint16_t* const* index, int width,
 
 } // extern "C"
 
+// ---- what the frame-input and frame-sequence stages share: every piece fails into the string it is given and enqueues
+// on the stream it is given, so the stages on a handle (h->err, h->stream) and the handle-free ones (g_create_error, their own
+// stream) use the same code ----
+namespace {
+
+// The tail of a stage's pointer table: the host vector `t` (kept in the handle) goes up into the device table `d`, grown first.
+// The call may return with this upload only enqueued, and the next call on the handle rewrites `t` and may regrow `d`.  Both are
+// safe for the reason the encoders' table uploads are: the runtime copies a small pageable source into its own staging memory before
+// hipMemcpyAsync returns, and DevBuf::reserve frees through hipFree, which waits for the device.  Held by tests/test_gpu_streams.py
+// (two asynchronous calls back to back behind a gated stream, the second with more frames): a runtime that read the source later
+// would fail there, and the tables would then need page-locked slots guarded by events.
+template <typename T> int upload_table(std::string& err, hipStream_t s, const std::vector<T>& t, DevBuf<T>& d) {
+    NQ_HIP_TO(err, d.reserve(t.size()));
+    NQ_HIP_TO(err, hipMemcpyAsync(d.p, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    return NQ_OK;
+}
+
+// A buffer of a call, [begin, end) in bytes; out: the call writes it.
+struct Span { uintptr_t begin, end; bool out; };
+
+// Whether an output overlaps a source or another output (the sources may overlap each other: they are only read; a buffer that
+// begins where another ends is apart from it): in the order of their first bytes, a buffer overlaps an earlier one exactly when it
+// begins before the furthest end seen so far.
+bool output_overlaps(std::vector<Span>& spans) {
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.begin < b.begin; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const Span& sp : spans) {
+        if (sp.begin < (sp.out ? end_any : end_out)) return true;
+        end_any = std::max(end_any, sp.end);
+        if (sp.out) end_out = std::max(end_out, sp.end);
+    }
+    return false;
+}
+
+// crop, target and flags of a reducing call on width x height frames
+int reduce_check(std::string& err, int width, int height, int crop_x, int crop_y, int crop_w, int crop_h, int dst_width, int dst_height,
+                 int flags) {
+    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > width - crop_w || crop_y > height - crop_h)
+        NQ_FAIL_TO(err, NQ_ERR_INVALID, "crop %d x %d at (%d, %d): empty or outside the %d x %d frame", crop_w, crop_h, crop_x, crop_y, width,
+                   height);
+    if (dst_width < 1 || dst_width > crop_w || dst_height < 1 || dst_height > crop_h)
+        NQ_FAIL_TO(err, NQ_ERR_INVALID, "target %d x %d: sides must be 1 .. the crop's (%d x %d); this call only reduces", dst_width, dst_height,
+                   crop_w, crop_h);
+    if (flags & ~NQ_RESAMPLE_LINEAR) NQ_FAIL_TO(err, NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) flags);
+    return NQ_OK;
+}
+
+// The host form of a stage over ARGB frames: the n sources of src_px words go up into d_in and the m outputs of out_px words are
+// staged in d_out, every frame a multiple of 4 words from the last (16-byte aligned: the vector paths); device(sources, outputs) runs
+// the device form on the staged copies; the outputs come back and are waited for.  On failure the stream is waited for too, so no
+// copy from or to the caller's buffers outlives the call.
+template <typename Device>
+int argb_host(std::string& err, hipStream_t s, DevBuf<uint32_t>& d_in, DevBuf<uint32_t>& d_out, int n, const uint32_t* const* src,
+              size_t src_px, int m, uint32_t* const* dst, size_t out_px, Device device) {
+    const size_t spitch = (src_px + 3) & ~(size_t) 3, dpitch = (out_px + 3) & ~(size_t) 3;
+    auto body = [&]() -> int {
+        NQ_HIP_TO(err, d_in.reserve(n * spitch));
+        NQ_HIP_TO(err, d_out.reserve(m * dpitch));
+        std::vector<const uint32_t*> d_src(n);
+        std::vector<uint32_t*> d_dst(m);
+        for (int i = 0; i < n; ++i) {
+            d_src[i] = d_in.p + i * spitch;
+            NQ_HIP_TO(err, hipMemcpyAsync(d_in.p + i * spitch, src[i], src_px * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        }
+        for (int j = 0; j < m; ++j) d_dst[j] = d_out.p + j * dpitch;
+        const int rc = device(d_src.data(), d_dst.data());
+        if (rc) return rc;
+        for (int j = 0; j < m; ++j) NQ_HIP_TO(err, hipMemcpyAsync(dst[j], d_dst[j], out_px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        NQ_HIP_TO(err, hipStreamSynchronize(s));
+        return NQ_OK;
+    };
+    const int rc = body();
+    if (rc) (void) hipStreamSynchronize(s);
+    return rc;
+}
+
+// The n frames of a YUV 4:2:0 call with samples of type S (uint8_t, or uint16_t for the 10-bit formats): plane pointers (host arrays),
+// one geometry (strides and step in samples) and one flag word.
+template <typename S> struct PlaneFrames {
+    int n;
+    const S* const* y; const S* const* u; const S* const* v;
+    int width, height, y_stride, c_stride, c_step, flags;
+    // bytes from a plane's first sample to one past its last
+    uintptr_t y_span() const { return ((uintptr_t) (height - 1) * (uintptr_t) y_stride + (uintptr_t) width) * sizeof(S); }
+    uintptr_t c_span() const {
+        return ((uintptr_t) ((height + 1) / 2 - 1) * (uintptr_t) c_stride + (uintptr_t) ((width + 1) / 2 - 1) * (uintptr_t) c_step + 1) * sizeof(S);
+    }
+    // the planes' spans and the outputs of dst_bytes each, for output_overlaps
+    std::vector<Span> spans(uint32_t* const* dst, uintptr_t dst_bytes) const {
+        std::vector<Span> sp;
+        sp.reserve(4 * (size_t) n);
+        for (int i = 0; i < n; ++i) {
+            sp.push_back({(uintptr_t) y[i], (uintptr_t) y[i] + y_span(), false});
+            sp.push_back({(uintptr_t) u[i], (uintptr_t) u[i] + c_span(), false});
+            sp.push_back({(uintptr_t) v[i], (uintptr_t) v[i] + c_span(), false});
+            sp.push_back({(uintptr_t) dst[i], (uintptr_t) dst[i] + dst_bytes, true});
+        }
+        return sp;
+    }
+};
+
+// The kernels' path for the DEVICE frames [first, first + count) of `a` and their outputs, and whether v is the lower pointer of the
+// interleaved pairs (*swap).  The wide paths need, for EVERY one of these frames: width and y_stride multiples of 4 samples and y
+// aligned to 4 samples (out16: and the output 16-byte aligned; rows4, the turning codes of nq_orient.hip: and height a multiple of
+// 4), and either c_step 2 with u and v one sample apart in the same order, the lower one aligned to 4 samples and c_stride a multiple
+// of 4 (interleaved: NV12, NV21, P010), or c_step 1 with u and v aligned to 2 samples and c_stride even (planar: I420, YV12, I010).
+// Everything else takes the one-sample path.
+template <typename S>
+int plane_path(const PlaneFrames<S>& a, uint32_t* const* d_dst, int first, int count, bool out16, bool rows4, bool* swap) {
+    const uintptr_t s4 = 4 * sizeof(S) - 1, s2 = 2 * sizeof(S) - 1;
+    bool wide = a.width % 4 == 0 && a.y_stride % 4 == 0 && !(rows4 && a.height % 4);
+    bool inter = a.c_step == 2 && a.c_stride % 4 == 0, planar = a.c_step == 1 && a.c_stride % 2 == 0;
+    int order = 0;                                  // +1: u is the lower pointer of every frame so far, -1: v is
+    for (int i = first; i < first + count; ++i) {
+        const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i];
+        wide = wide && !((uintptr_t) a.y[i] & s4) && !(out16 && ((uintptr_t) d_dst[i] & 15));
+        const int o = v == u + sizeof(S) ? 1 : u == v + sizeof(S) ? -1 : 0;
+        inter = inter && o != 0 && (order == 0 || order == o) && !(std::min(u, v) & s4);
+        if (o) order = o;
+        planar = planar && !((u | v) & s2);
+    }
+    *swap = order < 0;
+    return wide && inter ? YUV_WIDE_INTERLEAVED : wide && planar ? YUV_WIDE_PLANAR : YUV_BYTE;
+}
+
+// Where a frame's planes lie in the staging buffer of plane_host, in bytes: luma, the lower chroma span, the other one
+struct PlanePlace { size_t y, lo, hi; bool joined; };
+
+// ... for every frame of `a`, and the bytes they take together: per frame the luma span, then the chroma spans -- ONE span where u's
+// and v's overlap or touch (the interleaved layouts, and planes that follow each other) -- each at a 16-byte boundary, which keeps
+// what the wide paths need of a layout that has it
+template <typename S> size_t plane_places(const PlaneFrames<S>& a, std::vector<PlanePlace>& at) {
+    const size_t up16 = 15;
+    const uintptr_t yb = a.y_span(), cb = a.c_span();
+    at.resize(a.n);
+    size_t total = 0;
+    for (int i = 0; i < a.n; ++i) {
+        const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i], lo = std::min(u, v), hi = std::max(u, v);
+        at[i].y = total; total += (yb + up16) & ~up16;
+        at[i].joined = hi <= lo + cb;
+        at[i].lo = total;
+        if (at[i].joined) { at[i].hi = total + (hi - lo); total += (hi - lo + cb + up16) & ~up16; }
+        else { total += (cb + up16) & ~up16; at[i].hi = total; total += (cb + up16) & ~up16; }
+    }
+    return total;
+}
+
+// The host form of a stage over YUV frames: the planes go up into d_in as plane_places lays them out, the outputs (out_px words each)
+// are staged in d_out 16-byte aligned; device(frames, outputs) runs the device form on the staged copies; the outputs come back and
+// are waited for.  On failure the stream is waited for too.
+template <typename S, typename Device>
+int plane_host(std::string& err, hipStream_t s, DevBuf<unsigned char>& d_in, DevBuf<uint32_t>& d_out, const PlaneFrames<S>& a,
+               uint32_t* const* dst, size_t out_px, Device device) {
+    const int n = a.n;
+    const uintptr_t yb = a.y_span(), cb = a.c_span();
+    std::vector<PlanePlace> at;
+    const size_t total = plane_places(a, at), dpitch = (out_px + 3) & ~(size_t) 3;
+    auto body = [&]() -> int {
+        NQ_HIP_TO(err, d_in.reserve(total));
+        NQ_HIP_TO(err, d_out.reserve(n * dpitch));
+        std::vector<const S*> dy(n), du(n), dv(n);
+        std::vector<uint32_t*> d_dst(n);
+        unsigned char* base = d_in.p;
+        for (int i = 0; i < n; ++i) {
+            const bool u_low = a.u[i] <= a.v[i];
+            const unsigned char* lo = reinterpret_cast<const unsigned char*>(u_low ? a.u[i] : a.v[i]);
+            const unsigned char* hi = reinterpret_cast<const unsigned char*>(u_low ? a.v[i] : a.u[i]);
+            dy[i] = reinterpret_cast<const S*>(base + at[i].y); d_dst[i] = d_out.p + i * dpitch;
+            (u_low ? du : dv)[i] = reinterpret_cast<const S*>(base + at[i].lo);
+            (u_low ? dv : du)[i] = reinterpret_cast<const S*>(base + at[i].hi);
+            NQ_HIP_TO(err, hipMemcpyAsync(base + at[i].y, a.y[i], yb, hipMemcpyHostToDevice, s));
+            if (at[i].joined) {
+                NQ_HIP_TO(err, hipMemcpyAsync(base + at[i].lo, lo, (size_t) (hi - lo) + cb, hipMemcpyHostToDevice, s));
+            } else {
+                NQ_HIP_TO(err, hipMemcpyAsync(base + at[i].lo, lo, cb, hipMemcpyHostToDevice, s));
+                NQ_HIP_TO(err, hipMemcpyAsync(base + at[i].hi, hi, cb, hipMemcpyHostToDevice, s));
+            }
+        }
+        PlaneFrames<S> d = a;
+        d.y = dy.data(); d.u = du.data(); d.v = dv.data();
+        const int rc = device(d, d_dst.data());
+        if (rc) return rc;
+        for (int i = 0; i < n; ++i) NQ_HIP_TO(err, hipMemcpyAsync(dst[i], d_dst[i], out_px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        NQ_HIP_TO(err, hipStreamSynchronize(s));
+        return NQ_OK;
+    };
+    const int rc = body();
+    if (rc) (void) hipStreamSynchronize(s);
+    return rc;
+}
+
+} // namespace
+
 // ---- temporal hold (nq_hold.hip) ----
 namespace {
 
@@ -3228,14 +3428,9 @@ int hold_device(nq_handle* h, int n, const uint32_t* const* d_argb, uint16_t* co
         if (d_out_argb) t[2 * (size_t) n + i] = d_out_argb[i];
         vec = vec && !(((uintptr_t) d_argb[i] | (uintptr_t) d_index[i] | (uintptr_t) (d_out_argb ? d_out_argb[i] : nullptr)) & 15);
     }
-    NQ_HIP(h, h->hold_ptrs.reserve(t.size()));
     if (out_held) NQ_HIP(h, h->hold_held.reserve(n));
-    // With out_held == NULL the call returns with this upload only enqueued, and the next call on the handle rewrites `t` and may
-    // regrow hold_ptrs.  Both are safe for the reason the encoders' table uploads are: the runtime copies a small pageable source
-    // into its own staging memory before hipMemcpyAsync returns, and DevBuf::reserve frees through hipFree, which waits for the device.
-    // Held by tests/test_gpu_streams.py (two asynchronous calls back to back behind a gated stream, the second with more frames): a
-    // runtime that read the source later would fail there, and the tables would then need page-locked slots guarded by events.
-    NQ_HIP(h, hipMemcpyAsync(h->hold_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+    const int rc = upload_table(h->err, h->stream, t, h->hold_ptrs);      // (with out_held == NULL the call returns with it only enqueued)
+    if (rc) return rc;
     if (out_held) NQ_HIP(h, hipMemsetAsync(h->hold_held.p, 0, n * sizeof(unsigned long long), h->stream));
     launch_hold(reinterpret_cast<const unsigned* const*>(h->hold_ptrs.p), reinterpret_cast<unsigned short* const*>(h->hold_ptrs.p + n),
                 d_out_argb ? reinterpret_cast<unsigned* const*>(h->hold_ptrs.p + 2 * (size_t) n) : nullptr, n, (long long) width * height,
@@ -3370,9 +3565,9 @@ int signatures_device(nq_handle* h, int n, const uint32_t* const* d_argb, int wi
     bool vec = true;                                // the 16-byte path needs every frame aligned to it
     for (int i = 0; i < n; ++i) vec = vec && !((uintptr_t) d_argb[i] & 15);
     const size_t words = (size_t) n * NQ_SIG_WORDS;
-    NQ_HIP(h, h->sig_ptrs.reserve(n));
     NQ_HIP(h, h->d_sig.reserve(words));
-    NQ_HIP(h, hipMemcpyAsync(h->sig_ptrs.p, t.data(), n * sizeof(uint32_t*), hipMemcpyHostToDevice, h->stream));
+    const int rc = upload_table(h->err, h->stream, t, h->sig_ptrs);
+    if (rc) return rc;
     NQ_HIP(h, hipMemsetAsync(h->d_sig.p, 0, words * sizeof(uint32_t), h->stream));
     launch_signatures(reinterpret_cast<const unsigned* const*>(h->sig_ptrs.p), n, (long long) width * height, vec, h->n_cus, h->d_sig.p, h->stream);
     NQ_HIP(h, launch_status());
@@ -3471,13 +3666,8 @@ int resample_check(nq_handle* h, int n, const uint32_t* const* src, int src_widt
     if (n < 1) NQ_FAIL(h, NQ_ERR_INVALID, "n = %d: at least one frame", n);
     if (src_width < 1 || src_width > 65535 || src_height < 1 || src_height > 65535)
         NQ_FAIL(h, NQ_ERR_INVALID, "%d x %d: source sides must be 1..65535", src_width, src_height);
-    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > src_width - crop_w || crop_y > src_height - crop_h)
-        NQ_FAIL(h, NQ_ERR_INVALID, "crop %d x %d at (%d, %d): empty or outside the %d x %d frame", crop_w, crop_h, crop_x, crop_y, src_width,
-                src_height);
-    if (dst_width < 1 || dst_width > crop_w || dst_height < 1 || dst_height > crop_h)
-        NQ_FAIL(h, NQ_ERR_INVALID, "target %d x %d: sides must be 1 .. the crop's (%d x %d); this call only reduces", dst_width, dst_height,
-                crop_w, crop_h);
-    if (flags & ~NQ_RESAMPLE_LINEAR) NQ_FAIL(h, NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) flags);
+    const int rc = reduce_check(h->err, src_width, src_height, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags);
+    if (rc) return rc;
     if ((long long) n * src_width * src_height > 2147483647ll)
         NQ_FAIL(h, NQ_ERR_INVALID, "%d frames of %d x %d: more than 2^31 - 1 pixels", n, src_width, src_height);
     if (!src || !dst) NQ_FAIL(h, NQ_ERR_INVALID, "the array of source / output pointers is NULL");
@@ -3485,9 +3675,6 @@ int resample_check(nq_handle* h, int n, const uint32_t* const* src, int src_widt
         if (!src[i] || ((uintptr_t) src[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: source pointer NULL or not 4-byte aligned", i);
         if (!dst[i] || ((uintptr_t) dst[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: output pointer NULL or not 4-byte aligned", i);
     }
-    // no output may overlap a source frame or another output: in the order of their first bytes, a buffer overlaps an earlier one
-    // exactly when it begins before the furthest end seen so far
-    struct Span { uintptr_t begin, end; bool out; };
     std::vector<Span> spans;
     spans.reserve(2 * (size_t) n);
     const uintptr_t src_bytes = (uintptr_t) src_width * src_height * sizeof(uint32_t), dst_bytes = (uintptr_t) dst_width * dst_height * sizeof(uint32_t);
@@ -3495,13 +3682,7 @@ int resample_check(nq_handle* h, int n, const uint32_t* const* src, int src_widt
         spans.push_back({(uintptr_t) src[i], (uintptr_t) src[i] + src_bytes, false});
         spans.push_back({(uintptr_t) dst[i], (uintptr_t) dst[i] + dst_bytes, true});
     }
-    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.begin < b.begin; });
-    uintptr_t end_any = 0, end_out = 0;
-    for (const Span& sp : spans) {
-        if (sp.begin < (sp.out ? end_any : end_out)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source frame or another output");
-        end_any = std::max(end_any, sp.end);
-        if (sp.out) end_out = std::max(end_out, sp.end);
-    }
+    if (output_overlaps(spans)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source frame or another output");
     return NQ_OK;
 }
 
@@ -3515,9 +3696,8 @@ int resample_device(nq_handle* h, int n, const uint32_t* const* d_src, int src_w
         t[i] = const_cast<uint32_t*>(d_src[i]); t[n + (size_t) i] = d_dst[i];     // (the kernel reads the sources only)
         vec = vec && !((uintptr_t) d_src[i] & 15);
     }
-    NQ_HIP(h, h->resample_ptrs.reserve(t.size()));
-    // (the call returns with this upload only enqueued: safe for the reason given in hold_device)
-    NQ_HIP(h, hipMemcpyAsync(h->resample_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+    const int rc = upload_table(h->err, h->stream, t, h->resample_ptrs);
+    if (rc) return rc;
     launch_resample(reinterpret_cast<const unsigned* const*>(h->resample_ptrs.p), reinterpret_cast<unsigned* const*>(h->resample_ptrs.p + n), n,
                     src_width, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, (flags & NQ_RESAMPLE_LINEAR) != 0, vec, h->stream);
     NQ_HIP(h, launch_status());
@@ -3545,23 +3725,9 @@ int nq_resample_frames(nq_handle* h, int n, const uint32_t* const* src, int src_
     if (rc) return rc;
     rc = use_device(h);
     if (rc) return rc;
-    // frames and outputs lie a multiple of 4 elements apart in the staging buffers, so that every frame starts 16-byte aligned
-    const size_t spx = (size_t) src_width * src_height, spitch = (spx + 3) & ~(size_t) 3;
-    const size_t dpx = (size_t) dst_width * dst_height, dpitch = (dpx + 3) & ~(size_t) 3;
-    return host_form(h, [&]() -> int {
-        NQ_HIP(h, h->d_in.reserve(n * spitch));
-        NQ_HIP(h, h->d_out_argb.reserve(n * dpitch));
-        std::vector<const uint32_t*> d_src(n);
-        std::vector<uint32_t*> d_dst(n);
-        for (int i = 0; i < n; ++i) {
-            d_src[i] = h->d_in.p + i * spitch; d_dst[i] = h->d_out_argb.p + i * dpitch;
-            NQ_HIP(h, hipMemcpyAsync(h->d_in.p + i * spitch, src[i], spx * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        }
-        const int rc2 = resample_device(h, n, d_src.data(), src_width, crop_x, crop_y, crop_w, crop_h, d_dst.data(), dst_width, dst_height, flags);
-        if (rc2) return rc2;
-        for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dst[i], d_dst[i], dpx * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        NQ_HIP(h, hipStreamSynchronize(h->stream));
-        return NQ_OK;
+    return argb_host(h->err, h->stream, h->d_in, h->d_out_argb, n, src, (size_t) src_width * src_height, n, dst, (size_t) dst_width * dst_height,
+                     [&](const uint32_t* const* d_src, uint32_t* const* d_dst) {
+        return resample_device(h, n, d_src, src_width, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
     });
 }
 
@@ -3570,17 +3736,7 @@ int nq_resample_frames(nq_handle* h, int n, const uint32_t* const* src, int src_
 // ---- YUV input (nq_yuv.hip) ----
 namespace {
 
-// the n frames of a call: plane pointers (host arrays), one geometry and one flag word
-struct YuvFrames {
-    int n;
-    const uint8_t* const* y; const uint8_t* const* u; const uint8_t* const* v;
-    int width, height, y_stride, c_stride, c_step, yuv_flags;
-    // bytes from a plane's first sample to one past its last
-    uintptr_t y_span() const { return (uintptr_t) (height - 1) * (uintptr_t) y_stride + (uintptr_t) width; }
-    uintptr_t c_span() const {
-        return (uintptr_t) ((height + 1) / 2 - 1) * (uintptr_t) c_stride + (uintptr_t) ((width + 1) / 2 - 1) * (uintptr_t) c_step + 1;
-    }
-};
+using YuvFrames = PlaneFrames<uint8_t>;
 
 // floor(65536 e + 1/2) of the rationals of include/nquant_abi.h "YUV input", by flag word: {cy, crv, cgu, cgv, cbu, yo}
 const YuvCoef YUV_COEF[4] = {
@@ -3602,14 +3758,9 @@ int yuv_check(nq_handle* h, const YuvFrames& a, int crop_x, int crop_y, int crop
     if (a.c_step != 1 && a.c_step != 2) NQ_FAIL(h, NQ_ERR_INVALID, "c_step = %d: must be 1 or 2", a.c_step);
     if (a.c_stride < a.c_step * ((a.width + 1) / 2 - 1) + 1)
         NQ_FAIL(h, NQ_ERR_INVALID, "c_stride = %d: shorter than a chroma row of %d samples %d apart", a.c_stride, (a.width + 1) / 2, a.c_step);
-    if (a.yuv_flags & ~(NQ_YUV_BT709 | NQ_YUV_FULL_RANGE)) NQ_FAIL(h, NQ_ERR_INVALID, "yuv_flags = 0x%x: unknown bits", (unsigned) a.yuv_flags);
-    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > a.width - crop_w || crop_y > a.height - crop_h)
-        NQ_FAIL(h, NQ_ERR_INVALID, "crop %d x %d at (%d, %d): empty or outside the %d x %d frame", crop_w, crop_h, crop_x, crop_y, a.width,
-                a.height);
-    if (dst_width < 1 || dst_width > crop_w || dst_height < 1 || dst_height > crop_h)
-        NQ_FAIL(h, NQ_ERR_INVALID, "target %d x %d: sides must be 1 .. the crop's (%d x %d); this call only reduces", dst_width, dst_height,
-                crop_w, crop_h);
-    if (flags & ~NQ_RESAMPLE_LINEAR) NQ_FAIL(h, NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) flags);
+    if (a.flags & ~(NQ_YUV_BT709 | NQ_YUV_FULL_RANGE)) NQ_FAIL(h, NQ_ERR_INVALID, "yuv_flags = 0x%x: unknown bits", (unsigned) a.flags);
+    const int rc = reduce_check(h->err, a.width, a.height, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags);
+    if (rc) return rc;
     if ((long long) n * a.width * a.height > 2147483647ll)
         NQ_FAIL(h, NQ_ERR_INVALID, "%d frames of %d x %d: more than 2^31 - 1 pixels", n, a.width, a.height);
     if (!a.y || !a.u || !a.v || !dst) NQ_FAIL(h, NQ_ERR_INVALID, "an array of plane / output pointers is NULL");
@@ -3617,48 +3768,16 @@ int yuv_check(nq_handle* h, const YuvFrames& a, int crop_x, int crop_y, int crop
         if (!a.y[i] || !a.u[i] || !a.v[i]) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: a plane pointer is NULL", i);
         if (!dst[i] || ((uintptr_t) dst[i] & 3)) NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: output pointer NULL or not 4-byte aligned", i);
     }
-    // no output may overlap a plane's span or another output (resample_check's sweep, on byte spans): in the order of their first
-    // bytes, a buffer overlaps an earlier one exactly when it begins before the furthest end seen so far
-    struct Span { uintptr_t begin, end; bool out; };
-    std::vector<Span> spans;
-    spans.reserve(4 * (size_t) n);
-    const uintptr_t dst_bytes = (uintptr_t) dst_width * dst_height * sizeof(uint32_t);
-    for (int i = 0; i < n; ++i) {
-        spans.push_back({(uintptr_t) a.y[i], (uintptr_t) a.y[i] + a.y_span(), false});
-        spans.push_back({(uintptr_t) a.u[i], (uintptr_t) a.u[i] + a.c_span(), false});
-        spans.push_back({(uintptr_t) a.v[i], (uintptr_t) a.v[i] + a.c_span(), false});
-        spans.push_back({(uintptr_t) dst[i], (uintptr_t) dst[i] + dst_bytes, true});
-    }
-    std::sort(spans.begin(), spans.end(), [](const Span& p, const Span& q) { return p.begin < q.begin; });
-    uintptr_t end_any = 0, end_out = 0;
-    for (const Span& sp : spans) {
-        if (sp.begin < (sp.out ? end_any : end_out)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source plane or another output");
-        end_any = std::max(end_any, sp.end);
-        if (sp.out) end_out = std::max(end_out, sp.end);
-    }
+    std::vector<Span> spans = a.spans(dst, (uintptr_t) dst_width * dst_height * sizeof(uint32_t));
+    if (output_overlaps(spans)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source plane or another output");
     return NQ_OK;
 }
 
-// The kernels' path for DEVICE frames `a` and outputs d_dst, and the pointer table on its way to the device.  The wide paths need,
-// for EVERY frame: width, y and y_stride multiples of 4 (out16: and the output 16-byte aligned), and either c_step 2 with u and v
-// one byte apart in the same order, the lower one and c_stride multiples of 4 (interleaved: NV12, NV21), or c_step 1 with u, v and
-// c_stride even (planar: I420, YV12).  Everything else takes the byte path.  rows4 (the turning codes of nq_orient.hip): the wide paths
-// also need height a multiple of 4.
+// The kernels' path for DEVICE frames `a` and outputs d_dst -- plane_path over the whole call -- and the pointer table on its way to
+// the device.
 int yuv_table(nq_handle* h, const YuvFrames& a, uint32_t* const* d_dst, bool out16, int* path, bool* swap, bool rows4 = false) {
     const int n = a.n;
-    bool wide = a.width % 4 == 0 && a.y_stride % 4 == 0 && !(rows4 && a.height % 4);
-    bool inter = a.c_step == 2 && a.c_stride % 4 == 0, planar = a.c_step == 1 && a.c_stride % 2 == 0;
-    int order = 0;                                  // +1: u is the lower pointer of every frame so far, -1: v is
-    for (int i = 0; i < n; ++i) {
-        const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i];
-        wide = wide && !((uintptr_t) a.y[i] & 3) && !(out16 && ((uintptr_t) d_dst[i] & 15));
-        const int o = v == u + 1 ? 1 : u == v + 1 ? -1 : 0;
-        inter = inter && o != 0 && (order == 0 || order == o) && !(std::min(u, v) & 3);
-        if (o) order = o;
-        planar = planar && !((u | v) & 1);
-    }
-    *path = wide && inter ? YUV_WIDE_INTERLEAVED : wide && planar ? YUV_WIDE_PLANAR : YUV_BYTE;
-    *swap = order < 0;
+    *path = plane_path(a, d_dst, 0, n, out16, rows4, swap);
     std::vector<const void*>& t = h->h_yuv_ptrs;
     t.assign(4 * (size_t) n, nullptr);
     for (int i = 0; i < n; ++i) {
@@ -3667,10 +3786,7 @@ int yuv_table(nq_handle* h, const YuvFrames& a, uint32_t* const* d_dst, bool out
         t[2 * (size_t) n + i] = a.v[i];
         t[3 * (size_t) n + i] = d_dst[i];             // (the only pointers the kernels write through)
     }
-    NQ_HIP(h, h->yuv_ptrs.reserve(t.size()));
-    // (the call returns with this upload only enqueued: safe for the reason given in hold_device)
-    NQ_HIP(h, hipMemcpyAsync(h->yuv_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
-    return NQ_OK;
+    return upload_table(h->err, h->stream, t, h->yuv_ptrs);
 }
 
 // nq_frames_from_yuv_device after the checks: the pointer table goes up, one launch converts the sequence
@@ -3678,7 +3794,7 @@ int yuv_device(nq_handle* h, const YuvFrames& a, uint32_t* const* d_dst) {
     int path; bool swap;
     const int rc = yuv_table(h, a, d_dst, true, &path, &swap);
     if (rc) return rc;
-    launch_yuv_argb(h->yuv_ptrs.p, a.n, a.width, a.height, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.yuv_flags], h->stream);
+    launch_yuv_argb(h->yuv_ptrs.p, a.n, a.width, a.height, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.flags], h->stream);
     NQ_HIP(h, launch_status());
     return NQ_OK;
 }
@@ -3689,61 +3805,16 @@ int resample_yuv_device(nq_handle* h, const YuvFrames& a, int crop_x, int crop_y
     int path; bool swap;
     const int rc = yuv_table(h, a, d_dst, false, &path, &swap);
     if (rc) return rc;
-    launch_resample_yuv(h->yuv_ptrs.p, a.n, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.yuv_flags], crop_x, crop_y, crop_w,
+    launch_resample_yuv(h->yuv_ptrs.p, a.n, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.flags], crop_x, crop_y, crop_w,
                         crop_h, dst_width, dst_height, (flags & NQ_RESAMPLE_LINEAR) != 0, h->stream);
     NQ_HIP(h, launch_status());
     return NQ_OK;
 }
 
-// The host forms: per frame the luma span and the chroma spans go up into yuv_in -- ONE span where u's and v's overlap or touch (the
-// interleaved layouts, and planes that follow each other) -- each at a 16-byte boundary, which keeps what the wide paths need of a
-// layout that has it; the outputs (out_px words each) are staged in d_out_argb 16-byte aligned.  device(frames, outputs) runs the
-// device form on the staged copies.
+// The host forms: plane_host with the handle's buffers (the planes in yuv_in, the outputs of out_px words each in d_out_argb)
 template <typename Device>
 int yuv_host(nq_handle* h, const YuvFrames& a, uint32_t* const* dst, size_t out_px, Device device) {
-    const int n = a.n;
-    const size_t up16 = 15;
-    const uintptr_t yb = a.y_span(), cb = a.c_span();
-    struct Place { size_t y, lo, hi; bool joined; };          // offsets in yuv_in: luma, the lower chroma span, the other one
-    std::vector<Place> at(n);
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i], lo = std::min(u, v), hi = std::max(u, v);
-        at[i].y = total; total += (yb + up16) & ~up16;
-        at[i].joined = hi <= lo + cb;
-        at[i].lo = total;
-        if (at[i].joined) { at[i].hi = total + (hi - lo); total += (hi - lo + cb + up16) & ~up16; }
-        else { total += (cb + up16) & ~up16; at[i].hi = total; total += (cb + up16) & ~up16; }
-    }
-    const size_t dpitch = (out_px + 3) & ~(size_t) 3;
-    return host_form(h, [&]() -> int {
-        NQ_HIP(h, h->yuv_in.reserve(total));
-        NQ_HIP(h, h->d_out_argb.reserve(n * dpitch));
-        std::vector<const uint8_t*> dy(n), du(n), dv(n);
-        std::vector<uint32_t*> d_dst(n);
-        unsigned char* base = h->yuv_in.p;
-        for (int i = 0; i < n; ++i) {
-            const bool u_low = a.u[i] <= a.v[i];
-            const uint8_t* lo = u_low ? a.u[i] : a.v[i];
-            const uint8_t* hi = u_low ? a.v[i] : a.u[i];
-            dy[i] = base + at[i].y; d_dst[i] = h->d_out_argb.p + i * dpitch;
-            (u_low ? du : dv)[i] = base + at[i].lo; (u_low ? dv : du)[i] = base + at[i].hi;
-            NQ_HIP(h, hipMemcpyAsync(base + at[i].y, a.y[i], yb, hipMemcpyHostToDevice, h->stream));
-            if (at[i].joined) {
-                NQ_HIP(h, hipMemcpyAsync(base + at[i].lo, lo, (size_t) (hi - lo) + cb, hipMemcpyHostToDevice, h->stream));
-            } else {
-                NQ_HIP(h, hipMemcpyAsync(base + at[i].lo, lo, cb, hipMemcpyHostToDevice, h->stream));
-                NQ_HIP(h, hipMemcpyAsync(base + at[i].hi, hi, cb, hipMemcpyHostToDevice, h->stream));
-            }
-        }
-        YuvFrames d = a;
-        d.y = dy.data(); d.u = du.data(); d.v = dv.data();
-        const int rc = device(d, d_dst.data());
-        if (rc) return rc;
-        for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dst[i], d_dst[i], out_px * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        NQ_HIP(h, hipStreamSynchronize(h->stream));
-        return NQ_OK;
-    });
+    return plane_host(h->err, h->stream, h->yuv_in, h->d_out_argb, a, dst, out_px, device);
 }
 
 } // namespace
@@ -3840,9 +3911,8 @@ int orient_device(nq_handle* h, int n, const uint32_t* const* d_src, int width, 
         t[i] = const_cast<uint32_t*>(d_src[i]); t[n + (size_t) i] = d_dst[i];     // (the kernel reads the sources only)
         wide = wide && !(((uintptr_t) d_src[i] | (uintptr_t) d_dst[i]) & 15);
     }
-    NQ_HIP(h, h->orient_ptrs.reserve(t.size()));
-    // (the call returns with this upload only enqueued: safe for the reason given in hold_device)
-    NQ_HIP(h, hipMemcpyAsync(h->orient_ptrs.p, t.data(), t.size() * sizeof(void*), hipMemcpyHostToDevice, h->stream));
+    const int rc = upload_table(h->err, h->stream, t, h->orient_ptrs);
+    if (rc) return rc;
     launch_orient(reinterpret_cast<const unsigned* const*>(h->orient_ptrs.p), reinterpret_cast<unsigned* const*>(h->orient_ptrs.p + n), n, width,
                   height, orientation, wide, h->stream);
     NQ_HIP(h, launch_status());
@@ -3876,7 +3946,7 @@ int yuv_orient_device(nq_handle* h, const YuvFrames& a, int orientation, uint32_
     int path; bool swap;
     const int rc = yuv_table(h, a, d_dst, true, &path, &swap, orientation >= 5);
     if (rc) return rc;
-    launch_yuv_orient(h->yuv_ptrs.p, a.n, a.width, a.height, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.yuv_flags], orientation,
+    launch_yuv_orient(h->yuv_ptrs.p, a.n, a.width, a.height, a.y_stride, a.c_stride, a.c_step, path, swap, YUV_COEF[a.flags], orientation,
                       h->stream);
     NQ_HIP(h, launch_status());
     return NQ_OK;
@@ -3892,28 +3962,6 @@ int resample_yuv_oriented_device(nq_handle* h, const YuvFrames& a, int orientati
     rc = resample_yuv_device(h, a, crop_x, crop_y, crop_w, crop_h, d_tmp.data(), dst_width, dst_height, flags);
     if (rc) return rc;
     return orient_device(h, a.n, d_tmp.data(), dst_width, dst_height, orientation, d_dst);
-}
-
-// The host forms of the two ARGB calls: the frames go up into d_in, device(sources, outputs) runs on the staged copies (16-byte
-// aligned), the n outputs of out_px words come back from d_out_argb.
-template <typename Device>
-int orient_host(nq_handle* h, int n, const uint32_t* const* src, size_t src_px, uint32_t* const* dst, size_t out_px, Device device) {
-    const size_t spitch = (src_px + 3) & ~(size_t) 3, dpitch = (out_px + 3) & ~(size_t) 3;
-    return host_form(h, [&]() -> int {
-        NQ_HIP(h, h->d_in.reserve(n * spitch));
-        NQ_HIP(h, h->d_out_argb.reserve(n * dpitch));
-        std::vector<const uint32_t*> d_src(n);
-        std::vector<uint32_t*> d_dst(n);
-        for (int i = 0; i < n; ++i) {
-            d_src[i] = h->d_in.p + i * spitch; d_dst[i] = h->d_out_argb.p + i * dpitch;
-            NQ_HIP(h, hipMemcpyAsync(h->d_in.p + i * spitch, src[i], src_px * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        }
-        const int rc = device(d_src.data(), d_dst.data());
-        if (rc) return rc;
-        for (int i = 0; i < n; ++i) NQ_HIP(h, hipMemcpyAsync(dst[i], d_dst[i], out_px * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        NQ_HIP(h, hipStreamSynchronize(h->stream));
-        return NQ_OK;
-    });
 }
 
 // every argument of both forms of nq_orient_frames: resample_check's, with the whole frame as crop and target (a turned output
@@ -3951,7 +3999,7 @@ int nq_orient_frames(nq_handle* h, int n, const uint32_t* const* src, int src_wi
     rc = use_device(h);
     if (rc) return rc;
     const size_t px = (size_t) src_width * src_height;
-    return orient_host(h, n, src, px, dst, px, [&](const uint32_t* const* d_src, uint32_t* const* d_dst) {
+    return argb_host(h->err, h->stream, h->d_in, h->d_out_argb, n, src, px, n, dst, px, [&](const uint32_t* const* d_src, uint32_t* const* d_dst) {
         return orient_device(h, n, d_src, src_width, src_height, orientation, d_dst);
     });
 }
@@ -3977,8 +4025,8 @@ int nq_resample_frames_oriented(nq_handle* h, int n, const uint32_t* const* src,
     if (rc) return rc;
     rc = use_device(h);
     if (rc) return rc;
-    return orient_host(h, n, src, (size_t) src_width * src_height, dst, (size_t) dst_width * dst_height,
-                       [&](const uint32_t* const* d_src, uint32_t* const* d_dst) {
+    return argb_host(h->err, h->stream, h->d_in, h->d_out_argb, n, src, (size_t) src_width * src_height, n, dst, (size_t) dst_width * dst_height,
+                     [&](const uint32_t* const* d_src, uint32_t* const* d_dst) {
         return resample_oriented_device(h, n, d_src, src_width, orientation, crop_x, crop_y, crop_w, crop_h, d_dst, dst_width, dst_height, flags);
     });
 }
@@ -4064,9 +4112,6 @@ int ordered_check_frames(nq_handle* h, int n, const uint32_t* const* argb, const
         if (out_argb && (!out_argb[i] || ((uintptr_t) out_argb[i] & 3)))
             NQ_FAIL(h, NQ_ERR_INVALID, "frame %d: output pointer NULL or not 4-byte aligned", i);
     }
-    // no output may overlap a source frame or another output (the sources may overlap each other: they are only read); as in
-    // resample_check, a buffer overlaps an earlier one exactly when it begins before the furthest end seen so far
-    struct Span { uintptr_t begin, end; bool out; };
     std::vector<Span> spans;
     spans.reserve(3 * (size_t) n);
     for (int i = 0; i < n; ++i) {
@@ -4075,13 +4120,7 @@ int ordered_check_frames(nq_handle* h, int n, const uint32_t* const* argb, const
         spans.push_back({(uintptr_t) out_index[i], (uintptr_t) out_index[i] + px * sizeof(uint16_t), true});
         if (out_argb) spans.push_back({(uintptr_t) out_argb[i], (uintptr_t) out_argb[i] + px * sizeof(uint32_t), true});
     }
-    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.begin < b.begin; });
-    uintptr_t end_any = 0, end_out = 0;
-    for (const Span& sp : spans) {
-        if (sp.begin < (sp.out ? end_any : end_out)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source frame or another output");
-        end_any = std::max(end_any, sp.end);
-        if (sp.out) end_out = std::max(end_out, sp.end);
-    }
+    if (output_overlaps(spans)) NQ_FAIL(h, NQ_ERR_INVALID, "an output overlaps a source frame or another output");
     *out_total = total;
     return NQ_OK;
 }
@@ -4126,7 +4165,7 @@ int ordered_device(nq_handle* h, int n, const uint32_t* const* d_argb, const int
     NQ_HIP(h, h->d_ordered_frames.reserve(n));
     NQ_HIP(h, h->d_ordered_pal.reserve(256));
     if (out_stats) NQ_HIP(h, h->d_ordered_stats.reserve(2 * (size_t) n));
-    // (with out_stats == NULL the call returns with these uploads only enqueued: safe for the reason given in hold_device)
+    // (with out_stats == NULL the call returns with these uploads only enqueued: safe for the reason given at upload_table)
     NQ_HIP(h, hipMemcpyAsync(h->d_ordered_frames.p, t.data(), n * sizeof(nq::OrderedFrame), hipMemcpyHostToDevice, h->stream));
     NQ_HIP(h, hipMemcpyAsync(h->d_ordered_pal.p, pal.data(), 256 * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
     if (out_stats) NQ_HIP(h, hipMemsetAsync(h->d_ordered_stats.p, 0, 2 * (size_t) n * sizeof(unsigned long long), h->stream));
@@ -4250,10 +4289,6 @@ int nq_convert_frames_ordered(nq_handle* h, int n, const uint32_t* const* argb, 
 
 // ---- quality measurement (nq_compare.hip): stateless calls -- no handle, the error text goes to the thread's handle-free string ----
 namespace {
-
-#define NQ_CMP_FAIL(code, ...) do { char _b[512]; std::snprintf(_b, sizeof _b, __VA_ARGS__); g_create_error = _b; return (code); } while (0)
-#define NQ_CMP_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { \
-    NQ_CMP_FAIL(NQ_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); } } while (0)
 
 // one call: n pairs; out[i] is an ARGB frame or, with `indexed`, a uint16 index map into palette[0 .. K)
 struct CompareCall {
@@ -4888,18 +4923,7 @@ int nq_encode_webp(int device, int n, const uint16_t* const* index, int width, i
 // allocate nothing and wait for nothing ----
 namespace {
 
-// the n frames of a call: plane pointers (host arrays), one geometry (strides and step in samples) and one flag word
-struct Yuv16Frames {
-    int device, n;
-    const uint16_t* const* y; const uint16_t* const* u; const uint16_t* const* v;
-    int width, height, y_stride, c_stride, c_step, flags;
-    // bytes from a plane's first sample to one past its last
-    uintptr_t y_span() const { return ((uintptr_t) (height - 1) * (uintptr_t) y_stride + (uintptr_t) width) * sizeof(uint16_t); }
-    uintptr_t c_span() const {
-        return ((uintptr_t) ((height + 1) / 2 - 1) * (uintptr_t) c_stride + (uintptr_t) ((width + 1) / 2 - 1) * (uintptr_t) c_step + 1) *
-               sizeof(uint16_t);
-    }
-};
+using Yuv16Frames = PlaneFrames<uint16_t>;
 
 // floor(16384 e + 1/2) of the rationals of include/nquant_abi.h "10-bit YUV input", by matrix and range: {cy, crv, cgu, cgv, cbu, yo}
 const YuvCoef YUV16_COEF[3][2] = {
@@ -4912,8 +4936,8 @@ constexpr int kYuv16Flags = NQ_YUV_BT709 | NQ_YUV_FULL_RANGE | NQ_YUV16_BT2020 |
 
 // every argument of the four entry points, from the host arrays alone (no device work).  nq_frames_from_yuv16* pass the whole frame
 // as crop and target, and flags 0.
-int yuv16_check(const Yuv16Frames& a, int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* dst, int dst_width, int dst_height,
-                int flags) {
+int yuv16_check(int device, const Yuv16Frames& a, int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* dst, int dst_width,
+                int dst_height, int flags) {
     const int n = a.n;
     if (n < 1 || n > 65535) NQ_CMP_FAIL(NQ_ERR_INVALID, "n = %d: 1..65535 frames", n);
     if (a.width < 1 || a.width > 65535 || a.height < 1 || a.height > 65535)
@@ -4925,7 +4949,7 @@ int yuv16_check(const Yuv16Frames& a, int crop_x, int crop_y, int crop_w, int cr
     if (a.flags & ~kYuv16Flags) NQ_CMP_FAIL(NQ_ERR_INVALID, "yuv16_flags = 0x%x: unknown bits", (unsigned) a.flags);
     if ((a.flags & NQ_YUV_BT709) && (a.flags & NQ_YUV16_BT2020)) NQ_CMP_FAIL(NQ_ERR_INVALID, "yuv16_flags = 0x%x: two matrices", (unsigned) a.flags);
     if ((a.flags & NQ_YUV16_PQ) && (a.flags & NQ_YUV16_HLG)) NQ_CMP_FAIL(NQ_ERR_INVALID, "yuv16_flags = 0x%x: two transfers", (unsigned) a.flags);
-    if (a.device < 0) NQ_CMP_FAIL(NQ_ERR_INVALID, "device = %d: a device ordinal is not negative", a.device);
+    if (device < 0) NQ_CMP_FAIL(NQ_ERR_INVALID, "device = %d: a device ordinal is not negative", device);
     if (!a.y || !a.u || !a.v || !dst) NQ_CMP_FAIL(NQ_ERR_INVALID, "an array of plane / output pointers is NULL");
     for (int i = 0; i < n; ++i) {
         if (!a.y[i] || !a.u[i] || !a.v[i]) NQ_CMP_FAIL(NQ_ERR_INVALID, "frame %d: a plane pointer is NULL", i);
@@ -4935,66 +4959,32 @@ int yuv16_check(const Yuv16Frames& a, int crop_x, int crop_y, int crop_w, int cr
     }
     if ((long long) n * a.width * a.height > 2147483647ll)
         NQ_CMP_FAIL(NQ_ERR_INVALID, "%d frames of %d x %d: more than 2^31 - 1 pixels", n, a.width, a.height);
-    if (crop_w < 1 || crop_h < 1 || crop_x < 0 || crop_y < 0 || crop_x > a.width - crop_w || crop_y > a.height - crop_h)
-        NQ_CMP_FAIL(NQ_ERR_INVALID, "crop %d x %d at (%d, %d): empty or outside the %d x %d frame", crop_w, crop_h, crop_x, crop_y, a.width,
-                    a.height);
-    if (dst_width < 1 || dst_width > crop_w || dst_height < 1 || dst_height > crop_h)
-        NQ_CMP_FAIL(NQ_ERR_INVALID, "target %d x %d: sides must be 1 .. the crop's (%d x %d); this call only reduces", dst_width, dst_height,
-                    crop_w, crop_h);
-    if (flags & ~NQ_RESAMPLE_LINEAR) NQ_CMP_FAIL(NQ_ERR_INVALID, "flags = 0x%x: unknown bits", (unsigned) flags);
-    // no output may overlap a plane's span or another output (yuv_check's sweep)
-    struct Span { uintptr_t begin, end; bool out; };
-    std::vector<Span> spans;
-    spans.reserve(4 * (size_t) n);
-    const uintptr_t dst_bytes = (uintptr_t) dst_width * dst_height * sizeof(uint32_t);
-    for (int i = 0; i < n; ++i) {
-        spans.push_back({(uintptr_t) a.y[i], (uintptr_t) a.y[i] + a.y_span(), false});
-        spans.push_back({(uintptr_t) a.u[i], (uintptr_t) a.u[i] + a.c_span(), false});
-        spans.push_back({(uintptr_t) a.v[i], (uintptr_t) a.v[i] + a.c_span(), false});
-        spans.push_back({(uintptr_t) dst[i], (uintptr_t) dst[i] + dst_bytes, true});
-    }
-    std::sort(spans.begin(), spans.end(), [](const Span& p, const Span& q) { return p.begin < q.begin; });
-    uintptr_t end_any = 0, end_out = 0;
-    for (const Span& sp : spans) {
-        if (sp.begin < (sp.out ? end_any : end_out)) NQ_CMP_FAIL(NQ_ERR_INVALID, "an output overlaps a source plane or another output");
-        end_any = std::max(end_any, sp.end);
-        if (sp.out) end_out = std::max(end_out, sp.end);
-    }
+    const int rc = reduce_check(g_create_error, a.width, a.height, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags);
+    if (rc) return rc;
+    std::vector<Span> spans = a.spans(dst, (uintptr_t) dst_width * dst_height * sizeof(uint32_t));
+    if (output_overlaps(spans)) NQ_CMP_FAIL(NQ_ERR_INVALID, "an output overlaps a source plane or another output");
     return NQ_OK;
 }
 
 struct Yuv16Geometry { bool fused; int crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags; };
 
-// after the checks, for DEVICE frames `a` and outputs d_dst: one launch per YUV16_FRAMES_PER_LAUNCH frames, all on s.  The wide paths
-// need, for EVERY frame of a launch: width and y_stride multiples of 4, y 8-byte aligned (1:1: and the output 16-byte aligned), and
-// either c_step 2 with u and v one sample apart in the same order, the lower one 8-byte aligned and c_stride a multiple of 4
-// (interleaved: P010 and its chroma-swapped form), or c_step 1 with u and v 4-byte aligned and c_stride even (planar: I010, YV12 at ten
-// bits).  Everything else takes the one-pixel path.
+// after the checks, for DEVICE frames `a` and outputs d_dst: one launch per YUV16_FRAMES_PER_LAUNCH frames, each with the path of its
+// own frames (plane_path), all on s
 int yuv16_launches(const Yuv16Frames& a, uint32_t* const* d_dst, const Yuv16Geometry& g, hipStream_t s) {
     const int matrix = (a.flags & NQ_YUV16_BT2020) ? 2 : (a.flags & NQ_YUV_BT709) ? 1 : 0;
     for (int first = 0; first < a.n; first += YUV16_FRAMES_PER_LAUNCH) {
         const int count = std::min(a.n - first, (int) YUV16_FRAMES_PER_LAUNCH);
         Yuv16Launch l;
         std::memset(&l, 0, sizeof l);
-        bool wide = a.width % 4 == 0 && a.y_stride % 4 == 0;
-        bool inter = a.c_step == 2 && a.c_stride % 4 == 0, planar = a.c_step == 1 && a.c_stride % 2 == 0;
-        int order = 0;                              // +1: u is the lower pointer of every frame so far, -1: v is
-        for (int i = first; i < first + count; ++i) {
-            const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i];
-            wide = wide && !((uintptr_t) a.y[i] & 7) && !(!g.fused && ((uintptr_t) d_dst[i] & 15));
-            const int o = v == u + sizeof(uint16_t) ? 1 : u == v + sizeof(uint16_t) ? -1 : 0;
-            inter = inter && o != 0 && (order == 0 || order == o) && !(std::min(u, v) & 7);
-            if (o) order = o;
-            planar = planar && !((u | v) & 3);
-        }
-        l.path = wide && inter ? YUV_WIDE_INTERLEAVED : wide && planar ? YUV_WIDE_PLANAR : YUV_BYTE;
+        bool swap;
+        l.path = plane_path(a, d_dst, first, count, !g.fused, false, &swap);
         for (int i = 0; i < count; ++i) {
             const int j = first + i;
             l.frame[i] = {a.y[j], l.path == YUV_WIDE_INTERLEAVED ? std::min(a.u[j], a.v[j]) : a.u[j], a.v[j], d_dst[j]};
         }
         l.count = count;
         l.y_stride = a.y_stride; l.c_stride = a.c_stride; l.c_step = a.c_step;
-        l.swap = order < 0 ? 1 : 0;
+        l.swap = swap ? 1 : 0;
         l.shift = (a.flags & NQ_YUV16_MSB) ? 6 : 0;
         l.transfer = (a.flags & NQ_YUV16_PQ) ? YUV16_PQ : (a.flags & NQ_YUV16_HLG) ? YUV16_HLG : YUV16_SDR;
         l.k = YUV16_COEF[matrix][(a.flags & NQ_YUV_FULL_RANGE) ? 1 : 0];
@@ -5007,73 +4997,25 @@ int yuv16_launches(const Yuv16Frames& a, uint32_t* const* d_dst, const Yuv16Geom
     return NQ_OK;
 }
 
-int yuv16_device_form(const Yuv16Frames& a, uint32_t* const* d_dst, const Yuv16Geometry& g, void* hip_stream) {
-    int rc = yuv16_check(a, g.crop_x, g.crop_y, g.crop_w, g.crop_h, d_dst, g.dst_width, g.dst_height, g.flags);
+int yuv16_device_form(int device, const Yuv16Frames& a, uint32_t* const* d_dst, const Yuv16Geometry& g, void* hip_stream) {
+    int rc = yuv16_check(device, a, g.crop_x, g.crop_y, g.crop_w, g.crop_h, d_dst, g.dst_width, g.dst_height, g.flags);
     if (rc) return rc;
-    rc = compare_use_device(a.device);
+    rc = compare_use_device(device);
     if (rc) return rc;
     return yuv16_launches(a, d_dst, g, (hipStream_t) hip_stream);
 }
 
-// The host forms: per frame the luma span and the chroma spans go up into one temporary buffer -- ONE span where u's and v's overlap
-// or touch (the interleaved layouts, and planes that follow each other) -- each at a 16-byte boundary, which keeps what the wide paths
-// need of a layout that has it; the outputs are staged 16-byte aligned.  The device form runs on the staged copies, the outputs are
-// copied back, and everything is freed when the call returns.
-int yuv16_host_form(const Yuv16Frames& a, uint32_t* const* dst, const Yuv16Geometry& g) {
-    int rc = yuv16_check(a, g.crop_x, g.crop_y, g.crop_w, g.crop_h, dst, g.dst_width, g.dst_height, g.flags);
+// The host forms: plane_host with temporary buffers on the null stream; everything is freed when the call returns.
+int yuv16_host_form(int device, const Yuv16Frames& a, uint32_t* const* dst, const Yuv16Geometry& g) {
+    int rc = yuv16_check(device, a, g.crop_x, g.crop_y, g.crop_w, g.crop_h, dst, g.dst_width, g.dst_height, g.flags);
     if (rc) return rc;
-    rc = compare_use_device(a.device);
+    rc = compare_use_device(device);
     if (rc) return rc;
-    const int n = a.n;
-    const size_t up16 = 15, out_px = (size_t) g.dst_width * g.dst_height;
-    const uintptr_t yb = a.y_span(), cb = a.c_span();
-    struct Place { size_t y, lo, hi; bool joined; };          // offsets in the buffer: luma, the lower chroma span, the other one
-    std::vector<Place> at(n);
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        const uintptr_t u = (uintptr_t) a.u[i], v = (uintptr_t) a.v[i], lo = std::min(u, v), hi = std::max(u, v);
-        at[i].y = total; total += (yb + up16) & ~up16;
-        at[i].joined = hi <= lo + cb;
-        at[i].lo = total;
-        if (at[i].joined) { at[i].hi = total + (hi - lo); total += (hi - lo + cb + up16) & ~up16; }
-        else { total += (cb + up16) & ~up16; at[i].hi = total; total += (cb + up16) & ~up16; }
-    }
-    const size_t dpitch = (out_px + 3) & ~(size_t) 3;
     DevBuf<unsigned char> d_in;
     DevBuf<uint32_t> d_out;
     hipStream_t s = nullptr;
-    auto body = [&]() -> int {
-        NQ_CMP_HIP(d_in.reserve(total));
-        NQ_CMP_HIP(d_out.reserve(n * dpitch));
-        std::vector<const uint16_t*> dy(n), du(n), dv(n);
-        std::vector<uint32_t*> d_dst(n);
-        unsigned char* base = d_in.p;
-        for (int i = 0; i < n; ++i) {
-            const bool u_low = a.u[i] <= a.v[i];
-            const unsigned char* lo = reinterpret_cast<const unsigned char*>(u_low ? a.u[i] : a.v[i]);
-            const unsigned char* hi = reinterpret_cast<const unsigned char*>(u_low ? a.v[i] : a.u[i]);
-            dy[i] = reinterpret_cast<const uint16_t*>(base + at[i].y); d_dst[i] = d_out.p + i * dpitch;
-            (u_low ? du : dv)[i] = reinterpret_cast<const uint16_t*>(base + at[i].lo);
-            (u_low ? dv : du)[i] = reinterpret_cast<const uint16_t*>(base + at[i].hi);
-            NQ_CMP_HIP(hipMemcpyAsync(base + at[i].y, a.y[i], yb, hipMemcpyHostToDevice, s));
-            if (at[i].joined) {
-                NQ_CMP_HIP(hipMemcpyAsync(base + at[i].lo, lo, (size_t) (hi - lo) + cb, hipMemcpyHostToDevice, s));
-            } else {
-                NQ_CMP_HIP(hipMemcpyAsync(base + at[i].lo, lo, cb, hipMemcpyHostToDevice, s));
-                NQ_CMP_HIP(hipMemcpyAsync(base + at[i].hi, hi, cb, hipMemcpyHostToDevice, s));
-            }
-        }
-        Yuv16Frames d = a;
-        d.y = dy.data(); d.u = du.data(); d.v = dv.data();
-        const int rc2 = yuv16_launches(d, d_dst.data(), g, s);
-        if (rc2) return rc2;
-        for (int i = 0; i < n; ++i) NQ_CMP_HIP(hipMemcpyAsync(dst[i], d_dst[i], out_px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        NQ_CMP_HIP(hipStreamSynchronize(s));
-        return NQ_OK;
-    };
-    rc = body();
-    if (rc) (void) hipStreamSynchronize(s);
-    return rc;
+    return plane_host(g_create_error, s, d_in, d_out, a, dst, (size_t) g.dst_width * g.dst_height,
+                      [&](const Yuv16Frames& d, uint32_t* const* d_dst) { return yuv16_launches(d, d_dst, g, s); });
 }
 
 } // namespace
@@ -5083,13 +5025,13 @@ extern "C" {
 int nq_frames_from_yuv16_device(int device, void* hip_stream, int n, const uint16_t* const* d_y, const uint16_t* const* d_u,
                                 const uint16_t* const* d_v, int width, int height, int y_stride, int c_stride, int c_step, int yuv16_flags,
                                 uint32_t* const* d_dst) {
-    return yuv16_device_form({device, n, d_y, d_u, d_v, width, height, y_stride, c_stride, c_step, yuv16_flags}, d_dst,
+    return yuv16_device_form(device, {n, d_y, d_u, d_v, width, height, y_stride, c_stride, c_step, yuv16_flags}, d_dst,
                              {false, 0, 0, width, height, width, height, 0}, hip_stream);
 }
 
 int nq_frames_from_yuv16(int device, int n, const uint16_t* const* y, const uint16_t* const* u, const uint16_t* const* v, int width,
                          int height, int y_stride, int c_stride, int c_step, int yuv16_flags, uint32_t* const* dst) {
-    return yuv16_host_form({device, n, y, u, v, width, height, y_stride, c_stride, c_step, yuv16_flags}, dst,
+    return yuv16_host_form(device, {n, y, u, v, width, height, y_stride, c_stride, c_step, yuv16_flags}, dst,
                            {false, 0, 0, width, height, width, height, 0});
 }
 
@@ -5097,14 +5039,14 @@ int nq_resample_frames_yuv16_device(int device, void* hip_stream, int n, const u
                                     const uint16_t* const* d_v, int src_width, int src_height, int y_stride, int c_stride, int c_step,
                                     int yuv16_flags, int crop_x, int crop_y, int crop_w, int crop_h, uint32_t* const* d_dst, int dst_width,
                                     int dst_height, int flags) {
-    return yuv16_device_form({device, n, d_y, d_u, d_v, src_width, src_height, y_stride, c_stride, c_step, yuv16_flags}, d_dst,
+    return yuv16_device_form(device, {n, d_y, d_u, d_v, src_width, src_height, y_stride, c_stride, c_step, yuv16_flags}, d_dst,
                              {true, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags}, hip_stream);
 }
 
 int nq_resample_frames_yuv16(int device, int n, const uint16_t* const* y, const uint16_t* const* u, const uint16_t* const* v, int src_width,
                              int src_height, int y_stride, int c_stride, int c_step, int yuv16_flags, int crop_x, int crop_y, int crop_w,
                              int crop_h, uint32_t* const* dst, int dst_width, int dst_height, int flags) {
-    return yuv16_host_form({device, n, y, u, v, src_width, src_height, y_stride, c_stride, c_step, yuv16_flags}, dst,
+    return yuv16_host_form(device, {n, y, u, v, src_width, src_height, y_stride, c_stride, c_step, yuv16_flags}, dst,
                            {true, crop_x, crop_y, crop_w, crop_h, dst_width, dst_height, flags});
 }
 
@@ -5147,20 +5089,12 @@ int retime_check(int device, int n, const uint32_t* const* src, int width, int h
         }
         if (W < 1 || W > 2147483647ull) NQ_CMP_FAIL(NQ_ERR_INVALID, "output %d: its weights sum to %llu: 1 .. 2^31 - 1", j, (unsigned long long) W);
     }
-    // no output may overlap a source frame or another output (resample_check's sweep)
-    struct Span { uintptr_t begin, end; bool out; };
     std::vector<Span> spans;
     spans.reserve((size_t) n + m);
     const uintptr_t bytes = (uintptr_t) width * height * sizeof(uint32_t);
     for (int i = 0; i < n; ++i) spans.push_back({(uintptr_t) src[i], (uintptr_t) src[i] + bytes, false});
     for (int j = 0; j < m; ++j) spans.push_back({(uintptr_t) dst[j], (uintptr_t) dst[j] + bytes, true});
-    std::sort(spans.begin(), spans.end(), [](const Span& p, const Span& q) { return p.begin < q.begin; });
-    uintptr_t end_any = 0, end_out = 0;
-    for (const Span& sp : spans) {
-        if (sp.begin < (sp.out ? end_any : end_out)) NQ_CMP_FAIL(NQ_ERR_INVALID, "an output overlaps a source frame or another output");
-        end_any = std::max(end_any, sp.end);
-        if (sp.out) end_out = std::max(end_out, sp.end);
-    }
+    if (output_overlaps(spans)) NQ_CMP_FAIL(NQ_ERR_INVALID, "an output overlaps a source frame or another output");
     return NQ_OK;
 }
 
@@ -5259,36 +5193,19 @@ int nq_retime_frames_device(int device, void* hip_stream, int n, const uint32_t*
     return retime_launches(n, d_src, width, height, m, offset, source, weight, d_dst, flags, (hipStream_t) hip_stream);
 }
 
-// The host form: every source goes up on a 16-byte boundary of one temporary buffer, the outputs are staged likewise, the device form
-// runs on the copies, the m outputs are copied back, and everything is freed when the call returns.
+// The host form: argb_host with temporary buffers on the null stream; everything is freed when the call returns.
 int nq_retime_frames(int device, int n, const uint32_t* const* src, int width, int height, int m, const int32_t* offset,
                      const int32_t* source, const uint32_t* weight, uint32_t* const* dst, int flags) {
     int rc = retime_check(device, n, src, width, height, m, offset, source, weight, dst, flags);
     if (rc) return rc;
     rc = compare_use_device(device);
     if (rc) return rc;
-    const size_t px = (size_t) width * height, pitch = (px + 3) & ~(size_t) 3;
+    const size_t px = (size_t) width * height;
     DevBuf<uint32_t> d_in, d_out;
     hipStream_t s = nullptr;
-    auto body = [&]() -> int {
-        NQ_CMP_HIP(d_in.reserve(n * pitch));
-        NQ_CMP_HIP(d_out.reserve(m * pitch));
-        std::vector<const uint32_t*> d_src(n);
-        std::vector<uint32_t*> d_dst(m);
-        for (int i = 0; i < n; ++i) {
-            d_src[i] = d_in.p + i * pitch;
-            NQ_CMP_HIP(hipMemcpyAsync(d_in.p + i * pitch, src[i], px * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        }
-        for (int j = 0; j < m; ++j) d_dst[j] = d_out.p + j * pitch;
-        const int rc2 = retime_launches(n, d_src.data(), width, height, m, offset, source, weight, d_dst.data(), flags, s);
-        if (rc2) return rc2;
-        for (int j = 0; j < m; ++j) NQ_CMP_HIP(hipMemcpyAsync(dst[j], d_dst[j], px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        NQ_CMP_HIP(hipStreamSynchronize(s));
-        return NQ_OK;
-    };
-    rc = body();
-    if (rc) (void) hipStreamSynchronize(s);
-    return rc;
+    return argb_host(g_create_error, s, d_in, d_out, n, src, px, m, dst, px, [&](const uint32_t* const* d_src, uint32_t* const* d_dst) {
+        return retime_launches(n, d_src, width, height, m, offset, source, weight, d_dst, flags, s);
+    });
 }
 
 } // extern "C"

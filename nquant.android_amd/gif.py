@@ -16,8 +16,8 @@ import ctypes as C
 
 import numpy as np
 
-from .host import (MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frame_sizes, _frames_quantizer, _ordered_keyword, convert_frames,
-                   load_library)
+from ._frames_in import _opened, _pre_steps
+from .host import MODE_PARALLEL_TILED, NqError, _convert_frames_on, _frame_sizes, _ordered_keyword, convert_frames, load_library
 
 
 def _palette(palette):
@@ -307,24 +307,16 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
     (shot_starts=range(n): one palette per frame), then encode_gif_local_delta (delta=False: encode_gif_local) writes all frames, each
     with its shot's palette as its local colour table.  hold (delta=True only) runs per shot and never across a cut: a held index means
     nothing under another table.  seeds, tile, lossy as for convert_frames_to_gif; refine (0..64) runs that many k-means passes
-    (refine.py) on every shot's palette over that shot's frames.  size / crop / linear_resample and ordered as for
-    convert_frames_to_gif.
-    yuv (None: the frames are ARGB words): a dict with the keys bt709 / full_range says that `frames` are (y, u, v) tuples of 8-bit
-    YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
-    orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
-    converting kernel --; size and crop are then those of the oriented frames.
+    (refine.py) on every shot's palette over that shot's frames.  ordered as for convert_frames_to_gif.
+    size / crop / linear_resample, yuv, orient and yuv16 say what `frames` are and what is done to them first: _frames_in.py.
     Everything runs on one handle.  Cuts are the caller's to give here; convert_clip_to_gif finds them.
-    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
-    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
-    with orient: then turned -- before anything else runs.
     retime is refused here (ValueError): shot_starts name source frames, and retimed frames are other frames; convert_clip_to_gif
     takes it.
     Returns (file bytes, list of per-shot palettes)."""
     if retime is not None:
         raise ValueError("retime changes the frames that shot_starts name: retime first (retime.py), or let convert_clip_to_gif find the cuts")
-    if yuv16 is not None:
-        from .yuv16 import _converter_frames
-        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
+    frames, delays_cs, yuv, size, crop, orient = _pre_steps(frames, None, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient,
+                                                            device)
     lossy = _lossy_keyword(lossy)
     ordered = _ordered_keyword(ordered, seeds)
     from .orient import _code as _orient_code
@@ -341,20 +333,8 @@ def convert_shots_to_gif(kind, frames, shot_starts, nMaxColors, dither, delays_c
     if hold is not None:
         from .hold import _threshold
         hold = _threshold(hold)
-    if yuv is None:
-        frames, q = _frames_quantizer(kind, frames, device, mode, tile)
-    else:
-        from .yuv import _yuv_host, _yuv_quantizer
-        frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
-    try:
-        if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
-        elif size is not None or crop is not None or orient != 1:
-            from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
+    with _opened(kind, frames, yuv, size, crop, linear_resample, orient, device, mode, tile) as (q, frames):
         return _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine, ordered)
-    finally:
-        q.close()
 
 
 def _shots_to_gif_on(q, frames, shots, nMaxColors, dither, delays_cs, loop, segment_pixels, mode, seeds, hold, lossy, delta, refine=0,
@@ -393,21 +373,11 @@ def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, de
     """A list of frames in, an animation out: detect_shots (shots.py; cut in per mille, min_shot in frames) finds where the clip needs
     a new palette, then exactly convert_shots_to_gif with those starts -- both on one handle.  The frames must have one size (delta or
     not: a signature is compared between frames of one size).  With size or crop the frames are reduced first (resample.py) and the
-    shots are detected on the result.  Keywords otherwise as for convert_shots_to_gif (yuv: the frames are YUV 4:2:0 planes).
-    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
-    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
-    with orient: then turned -- before anything else runs.
-    retime (None: the frames are shown as they are): a dict with the keys timestamps_us / period_us or fps / shutter_us / linear
-    (retime.py) blends the frames to that rate -- after the YUV, orient and reduce steps, which then run before anything else -- and
-    supplies delays_cs, which may not be given as well; seeds (one per frame) may not be given either.
+    shots are detected on the result.  Keywords otherwise as for convert_shots_to_gif, and retime is taken.
+    size / crop / linear_resample, yuv, orient, yuv16 and retime say what `frames` are and what is done to them first: _frames_in.py.
     Returns (file bytes, list of per-shot palettes, shot_starts)."""
-    if retime is not None:
-        from .retime import _converter_frames as _retimed_frames
-        frames, delays_cs = _retimed_frames(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient, device)
-        yuv, yuv16, size, crop, orient = None, None, None, None, 1
-    if yuv16 is not None:
-        from .yuv16 import _converter_frames
-        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
+    frames, delays_cs, yuv, size, crop, orient = _pre_steps(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient,
+                                                            device)
     lossy = _lossy_keyword(lossy)
     ordered = _ordered_keyword(ordered, seeds)
     from .orient import _code as _orient_code
@@ -424,22 +394,10 @@ def convert_clip_to_gif(kind, frames, nMaxColors, dither, cut=60, min_shot=8, de
         from .hold import _threshold
         hold = _threshold(hold)
     from .shots import _detect_host
-    if yuv is None:
-        frames, q = _frames_quantizer(kind, frames, device, mode, tile)
-    else:
-        from .yuv import _yuv_host, _yuv_quantizer
-        frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
-    try:
-        if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
-        elif size is not None or crop is not None or orient != 1:
-            from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
+    with _opened(kind, frames, yuv, size, crop, linear_resample, orient, device, mode, tile) as (q, frames):
         starts, _ = _detect_host(q._L, q._h, q._check, frames, cut, min_shot)
         data, palettes = _shots_to_gif_on(q, frames, _shots(starts, len(frames)), nMaxColors, dither, delays_cs, loop, segment_pixels, mode,
                                           seeds, hold, lossy, delta, refine, ordered)
-    finally:
-        q.close()
     return data, palettes, starts
 
 
@@ -472,30 +430,13 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
     lossy: as for encode_gif, applied to whichever encoder runs (with hold: on that same handle).
     refine (0..64): that many k-means passes on the palette over the frames before the dither (refine.py, convert_frames_refined);
     0 is the call without it.
-    size / crop / linear_resample: with size=(width, height) or crop=(x, y, width, height) given, the frames (then all of one size)
-    are first cropped and area-averaged down to `size` (None: the crop's size) as resample_frames does it (resample.py; in linear
-    light unless linear_resample=False), and everything else runs on the result, all on one handle.
     ordered (None: the error-diffusion dither): an integer 0..255 dithers the frames with the ordered dither (ordered.py,
     convert_frames_ordered) with that limit instead: a pixel's index then depends on its colour, its position and the palette only, so
     unchanged pixels repeat without seeds.  dither, mode and tile then take no part, and seeds may not be given.
-    yuv (None: the frames are ARGB words): a dict with the keys bt709 / full_range says that `frames` are (y, u, v) tuples of 8-bit
-    YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
-    orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
-    converting kernel --; size and crop are then those of the oriented frames.
-    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
-    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
-    with orient: then turned -- before anything else runs.
-    retime (None: the frames are shown as they are): a dict with the keys timestamps_us / period_us or fps / shutter_us / linear
-    (retime.py) blends the frames to that rate -- after the YUV, orient and reduce steps, which then run before anything else -- and
-    supplies delays_cs, which may not be given as well; seeds (one per frame) may not be given either.
+    size / crop / linear_resample, yuv, orient, yuv16 and retime say what `frames` are and what is done to them first: _frames_in.py.
     Returns (file bytes, palette)."""
-    if retime is not None:
-        from .retime import _converter_frames as _retimed_frames
-        frames, delays_cs = _retimed_frames(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient, device)
-        yuv, yuv16, size, crop, orient = None, None, None, None, 1
-    if yuv16 is not None:
-        from .yuv16 import _converter_frames
-        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
+    frames, delays_cs, yuv, size, crop, orient = _pre_steps(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient,
+                                                            device)
     lossy = _lossy_keyword(lossy)
     ordered = _ordered_keyword(ordered, seeds)
     from .orient import _code as _orient_code
@@ -507,20 +448,10 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
     if yuv is None and delta and len({np.asarray(f).shape for f in frames}) > 1:
         raise ValueError("delta mode: all frames must have one size")
     if size is not None or crop is not None or yuv is not None or orient != 1:
-        from .resample import _resample_host
         if hold is not None:
             from .hold import _hold_host, _threshold
             hold = _threshold(hold)
-        if yuv is None:
-            frames, q = _frames_quantizer(kind, frames, device, mode, tile)
-        else:
-            from .yuv import _yuv_host, _yuv_quantizer
-            frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
-        try:
-            if yuv is None:
-                frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
-            else:
-                frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
+        with _opened(kind, frames, yuv, size, crop, linear_resample, orient, device, mode, tile) as (q, frames):
             palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
             maps = _index_maps([o.index for o in outs])
             height, width = _one_size(maps)
@@ -533,22 +464,17 @@ def convert_frames_to_gif(kind, frames, nMaxColors, dither, delays_cs=None, loop
             else:
                 data = _encode(q._L, q._h, "nq_encode_gif", ptrs, np.array([width] * len(maps), np.int32),
                                np.array([height] * len(maps), np.int32), palette, delays_cs, loop, segment_pixels, q._check, lossy)
-        finally:
-            q.close()
         return data, palette
     if hold is not None:
         from .hold import _hold_host, _threshold
         hold = _threshold(hold)
-        frames, q = _frames_quantizer(kind, frames, device, mode, tile)
-        try:
+        with _opened(kind, frames, None, None, None, linear_resample, 1, device, mode, tile) as (q, frames):
             palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
             maps = [o.index for o in outs]
             height, width = _one_size(maps)
             _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
             data, _ = _encode_delta(q._L, q._h, "nq_encode_gif_delta", [a.ctypes.data for a in maps], width, height, palette, delays_cs, loop,
                                     segment_pixels, q._check, lossy)
-        finally:
-            q.close()
         return data, palette
     if ordered is not None:
         from .ordered import convert_frames_ordered

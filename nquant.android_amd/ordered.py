@@ -9,8 +9,9 @@ import ctypes as C
 
 import numpy as np
 
+from ._frames_in import _opened, _pre_steps
 from .gif import _Handle
-from .host import MODE_PARALLEL_TILED, QuantizedImage, _convert_frames_on, _frame_sizes, _frames_quantizer
+from .host import MODE_PARALLEL_TILED, QuantizedImage, _convert_frames_on, _frame_sizes
 from .refine import _host_frames, _palette_io
 
 
@@ -66,28 +67,12 @@ def dither_ordered_device(q, d_pixels, widths, heights, palette, limit, d_out_in
 def convert_frames_ordered(kind, frames, nMaxColors, limit, refine=0, device=0, size=None, crop=None, linear_resample=True, yuv=None, orient=1, yuv16=None):
     """nq_convert_frames_ordered on host arrays: one shared palette for the frames (convert_frames' palette), `refine` (0..64) k-means
     passes on it over the same frames (refine.py), then the ordered dither with `limit` (0..255).  nMaxColors <= 256.
-    size / crop / linear_resample / yuv / orient as for convert_frames_refined.  Returns what convert_frames returns: (palette, [QuantizedImage per frame]).
-    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
-    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
-    with orient: then turned -- before anything else runs."""
-    if yuv16 is not None:
-        from .yuv16 import _converter_frames
-        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
+    size / crop / linear_resample, yuv, orient and yuv16 say what `frames` are and what is done to them first: _frames_in.py.
+    Returns what convert_frames returns: (palette, [QuantizedImage per frame])."""
+    frames, _, yuv, size, crop, orient = _pre_steps(frames, None, None, None, yuv, yuv16, size, crop, linear_resample, orient, device)
     if not 0 <= int(refine) <= 64:
         raise ValueError("refine must be 0..64, got %r" % (refine,))
     from .orient import _code as _orient_code
     orient = _orient_code(orient)
-    if yuv is None:
-        frames, q = _frames_quantizer(kind, frames, device, MODE_PARALLEL_TILED, None)
-    else:
-        from .yuv import _yuv_host, _yuv_quantizer
-        frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, MODE_PARALLEL_TILED, None)
-    try:
-        if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
-        elif size is not None or crop is not None or orient != 1:
-            from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
+    with _opened(kind, frames, yuv, size, crop, linear_resample, orient, device, MODE_PARALLEL_TILED, None) as (q, frames):
         return _convert_frames_on(q, frames, nMaxColors, False, MODE_PARALLEL_TILED, None, int(refine), _limit(limit))
-    finally:
-        q.close()

@@ -6,10 +6,9 @@ frame converters that take size= / crop= / yuv= take orient= and then produce th
 (as displayed) coordinates.  Words are moved, never changed: tests/orient_ref.py restates the codes.  orientation, oriented_size and
 source_rect are host arithmetic and need no device; the rest has no CPU fallback: without a HIP device every call raises NqError with
 status -5 (NQ_ERR_NO_DEVICE)."""
-import ctypes as C
-
 import numpy as np
 
+from ._frames_in import _arr
 from .gif import _Handle
 from .host import _as_i32
 
@@ -48,10 +47,6 @@ def source_rect(width, height, code, rect):
     # along the source's columns lies the oriented y axis when the code turns, else the x axis
     a, al, b, bl = (y, h, x, w) if turn else (x, w, y, h)
     return (width - a - al if fx else a), (height - b - bl if fy else b), al, bl
-
-
-def _arr(ptrs):
-    return (C.c_void_p * max(len(ptrs), 1))(*[int(p) for p in ptrs])
 
 
 def _orient(L, handle, check, entry, src_ptrs, width, height, dst_ptrs, code):

@@ -8,8 +8,9 @@ import ctypes as C
 
 import numpy as np
 
+from ._frames_in import _opened, _pre_steps
 from .gif import _Handle
-from .host import MODE_PARALLEL_TILED, _as_i32, _convert_frames_on, _frame_sizes, _frames_quantizer
+from .host import MODE_PARALLEL_TILED, _as_i32, _convert_frames_on, _frame_sizes
 
 
 def _palette_io(palette):
@@ -73,34 +74,12 @@ def convert_frames_refined(kind, frames, nMaxColors, dither, refine, device=0, m
                            crop=None, linear_resample=True, yuv=None, orient=1, yuv16=None):
     """nq_convert_frames_refined on host arrays: convert_frames with `refine` (0..64) k-means passes on the shared palette, over the
     same frames, between the palette and the dither.  nMaxColors <= 256 unless refine is 0, which gives convert_frames' results.
-    size / crop / linear_resample: with size=(width, height) or crop=(x, y, width, height) given, the frames (then all of one size) are
-    first cropped and area-averaged down to `size` (None: the crop's size) as resample_frames does it (resample.py), on the same handle.
-    yuv (None: the frames are ARGB words): a dict with the keys bt709 / full_range says that `frames` are (y, u, v) tuples of 8-bit
-    YUV 4:2:0 planes (yuv.py); they are converted -- with size or crop: converted and reduced in one kernel -- on the same handle.
-    orient (1: as they are): an orientation 1..8 (orient.py) turns / mirrors the frames first, on the same handle -- YUV frames in the
-    converting kernel --; size and crop are then those of the oriented frames.
-    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
-    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
-    with orient: then turned -- before anything else runs.
+    size / crop / linear_resample, yuv, orient and yuv16 say what `frames` are and what is done to them first: _frames_in.py.
     Returns (palette, [QuantizedImage per frame])."""
-    if yuv16 is not None:
-        from .yuv16 import _converter_frames
-        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
+    frames, _, yuv, size, crop, orient = _pre_steps(frames, None, None, None, yuv, yuv16, size, crop, linear_resample, orient, device)
     if not 0 <= int(refine) <= 64:
         raise ValueError("refine must be 0..64, got %r" % (refine,))
     from .orient import _code as _orient_code
     orient = _orient_code(orient)
-    if yuv is None:
-        frames, q = _frames_quantizer(kind, frames, device, mode, tile)
-    else:
-        from .yuv import _yuv_host, _yuv_quantizer
-        frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
-    try:
-        if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
-        elif size is not None or crop is not None or orient != 1:
-            from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
+    with _opened(kind, frames, yuv, size, crop, linear_resample, orient, device, mode, tile) as (q, frames):
         return _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, refine)
-    finally:
-        q.close()

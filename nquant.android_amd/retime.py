@@ -14,6 +14,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._frames_in import _arr, _reduced_on
 from .host import NqError, _as_i32, load_library
 
 RETIME_LINEAR = 1
@@ -90,10 +91,6 @@ def _plan_arrays(plan):
     return m, offset, source, weight
 
 
-def _arr(ptrs):
-    return (C.c_void_p * max(len(ptrs), 1))(*[int(p) for p in ptrs])
-
-
 def _retime_host(frames, plan, linear, device):
     """nq_retime_frames of host frames with a plan.  Returns the m frames as a list of int32 arrays."""
     frames = [np.ascontiguousarray(_as_i32(f)) for f in frames]
@@ -167,12 +164,9 @@ def _converter_frames(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, 
         from .gif import _Handle
         hd = _Handle(device)
         try:
-            if yuv is not None:
-                from .yuv import _yuv_host, _yuv_keyword
-                frames = _yuv_host(hd._L, hd._h, hd._check, frames, size, crop, linear_resample, _yuv_keyword(yuv), _code(orient))
-            else:
-                from .resample import _resample_host
-                frames = _resample_host(hd._L, hd._h, hd._check, frames, size, crop, linear_resample, _code(orient))
+            from .yuv import _yuv_keyword
+            frames = _reduced_on(hd._L, hd._h, hd._check, frames, None if yuv is None else _yuv_keyword(yuv), size, crop, linear_resample,
+                                 _code(orient))
         finally:
             hd.close()
     return _retime_host(frames, plan, retime.get("linear", True), device), plan.delays_cs

@@ -10,10 +10,11 @@ import ctypes as C
 
 import numpy as np
 
+from ._frames_in import _opened, _pre_steps
 from .gif import _delays, _index_maps, _palette
 from .hold import _hold_host, _threshold
-from .host import (MODE_PARALLEL_TILED, NQ_KIND_LAB, NqError, PnnLABQuantizer, PnnQuantizer, _convert_frames_on, _frames_quantizer,
-                   _ordered_keyword, load_library)
+from .host import (MODE_PARALLEL_TILED, NQ_KIND_LAB, NqError, PnnLABQuantizer, PnnQuantizer, _convert_frames_on, _ordered_keyword,
+                   load_library)
 
 
 def _one_size(maps):
@@ -105,22 +106,11 @@ def convert_frames_to_webp(kind, frames, nMaxColors, dither, delays_cs=None, loo
     """convert_frames (one shared palette for the ARGB frames, which must have one size) followed by encode_webp of the index maps on
     the same device.  nMaxColors <= 256.  The keywords are convert_frames_to_apng's (apng.py), with band_bits in place of
     segment_bytes and delta (True: every later frame stores its changed rectangle only) in addition: seeds, tile and mode go to the
-    dither; hold runs the temporal hold between the two steps; refine the k-means passes on the palette; size / crop /
-    linear_resample the reducer; ordered the ordered dither; yuv takes (y, u, v) planes; orient turns / mirrors the frames first.
-    yuv16 (None; exclusive with yuv): a dict with the keys matrix / full_range / transfer / msb says that `frames` are (y, u, v) tuples
-    of 10-bit YUV 4:2:0 planes in 16-bit words (yuv16.py); they are converted -- with size or crop: converted and reduced in one kernel,
-    with orient: then turned -- before anything else runs.
-    retime (None: the frames are shown as they are): a dict with the keys timestamps_us / period_us or fps / shutter_us / linear
-    (retime.py) blends the frames to that rate -- after the YUV, orient and reduce steps, which then run before anything else -- and
-    supplies delays_cs, which may not be given as well; seeds (one per frame) may not be given either.
+    dither; hold runs the temporal hold between the two steps; refine the k-means passes on the palette; ordered the ordered dither.
+    size / crop / linear_resample, yuv, orient, yuv16 and retime say what `frames` are and what is done to them first: _frames_in.py.
     Returns (file bytes, palette); with return_rects=True (file bytes, palette, rectangles)."""
-    if retime is not None:
-        from .retime import _converter_frames as _retimed_frames
-        frames, delays_cs = _retimed_frames(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient, device)
-        yuv, yuv16, size, crop, orient = None, None, None, None, 1
-    if yuv16 is not None:
-        from .yuv16 import _converter_frames
-        frames, size, crop, orient = _converter_frames(frames, yuv, yuv16, size, crop, linear_resample, orient, device), None, None, 1
+    frames, delays_cs, yuv, size, crop, orient = _pre_steps(frames, retime, delays_cs, seeds, yuv, yuv16, size, crop, linear_resample, orient,
+                                                            device)
     if not 1 <= int(nMaxColors) <= 256:
         raise ValueError("the colour table of a lossless WebP holds at most 256 entries")
     if yuv is None and len({np.asarray(f).shape for f in frames}) > 1:
@@ -130,17 +120,7 @@ def convert_frames_to_webp(kind, frames, nMaxColors, dither, delays_cs=None, loo
         hold = _threshold(hold)
     from .orient import _code as _orient_code
     orient = _orient_code(orient)
-    if yuv is None:
-        frames, q = _frames_quantizer(kind, frames, device, mode, tile)
-    else:
-        from .yuv import _yuv_host, _yuv_quantizer
-        frames, q, yuv = _yuv_quantizer(kind, frames, yuv, device, mode, tile)
-    try:
-        if yuv is not None:
-            frames = _yuv_host(q._L, q._h, q._check, frames, size, crop, linear_resample, yuv, orient)
-        elif size is not None or crop is not None or orient != 1:
-            from .resample import _resample_host
-            frames = _resample_host(q._L, q._h, q._check, frames, size, crop, linear_resample, orient)
+    with _opened(kind, frames, yuv, size, crop, linear_resample, orient, device, mode, tile) as (q, frames):
         palette, outs = _convert_frames_on(q, frames, nMaxColors, dither, mode, seeds, int(refine) or None, ordered)
         maps = _index_maps([o.index for o in outs])
         height, width = _one_size(maps)
@@ -148,6 +128,4 @@ def convert_frames_to_webp(kind, frames, nMaxColors, dither, delays_cs=None, loo
             _hold_host(q._L, q._h, q._check, frames, maps, None, hold)
         data, rects = _encode(q._L, "nq_encode_webp", device, 0, [a.ctypes.data for a in maps], width, height, palette, delays_cs, loop,
                               band_bits, delta)
-    finally:
-        q.close()
     return (data, palette, rects) if return_rects else (data, palette)

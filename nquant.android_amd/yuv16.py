@@ -11,10 +11,9 @@ needs no device; the rest has no CPU fallback: without a HIP device every call r
 A host frame is a tuple (y, u, v) of 2-D uint16 arrays: y is (height, width), u and v are ((height + 1) // 2, (width + 1) // 2).  They
 may be strided views (yuv16_planes gives those of one buffer): where the views of every frame share the row strides and the chroma
 element stride (1 or 2 samples), pointers and strides are passed as they are; otherwise the planes are copied tight first."""
-import ctypes as C
-
 import numpy as np
 
+from ._frames_in import _arr, _host_frames as _shared_host_frames
 from .host import NqError, load_library
 from .orient import _code, oriented_size, source_rect
 from .resample import RESAMPLE_LINEAR, _geometry
@@ -89,59 +88,9 @@ def _yuv16_keyword(yuv16):
     return _flags(**yuv16)
 
 
-def _strides(plane):
-    """(row stride, element stride) of a 2-D view in bytes; a side of one sample leaves its stride open (None)."""
-    return (plane.strides[0] if plane.shape[0] > 1 else None, plane.strides[1] if plane.shape[1] > 1 else None)
-
-
 def _host_frames(frames):
-    """(planes, width, height, y_stride, c_stride, c_step), strides and step in samples: `planes` a list of (y, u, v) uint16 arrays that
-    stay alive for the call.  The views are passed as they are when one (y_stride, c_stride, c_step) describes all of them; otherwise
-    they are copied tight."""
-    frames = list(frames)
-    if len(frames) == 0:
-        raise ValueError("no frames")
-    planes = []
-    for f in frames:
-        if not isinstance(f, (tuple, list)) or len(f) != 3:
-            raise TypeError("a 10-bit YUV frame is a tuple (y, u, v) of 2-D uint16 arrays")
-        y, u, v = (np.asarray(p) for p in f)
-        if any(p.dtype != np.uint16 or p.ndim != 2 for p in (y, u, v)):
-            raise TypeError("a 10-bit YUV frame is a tuple (y, u, v) of 2-D uint16 arrays")
-        planes.append((y, u, v))
-    height, width = planes[0][0].shape
-    if height < 1 or width < 1:
-        raise ValueError("yuv16: empty frame")
-    cshape = ((height + 1) // 2, (width + 1) // 2)
-    for y, u, v in planes:
-        if y.shape != (height, width) or u.shape != cshape or v.shape != cshape:
-            raise ValueError("yuv16: every frame needs y of shape %s and u, v of shape %s, got %s, %s, %s" % (
-                (height, width), cshape, y.shape, u.shape, v.shape))
-
-    def common(values, default, ok):
-        """The one value every plane of `values` that fixes it agrees on (default: none fixes it), or None."""
-        fixed = {v for v in values if v is not None}
-        if len(fixed) > 1:
-            return None
-        value = fixed.pop() if fixed else default
-        return value if ok(value) else None
-
-    ys = [_strides(y) for y, _, _ in planes]
-    cs = [_strides(p) for _, u, v in planes for p in (u, v)]
-    y_step = common([s[1] for s in ys], 2, lambda v: v == 2)
-    y_stride = common([s[0] for s in ys], 2 * width, lambda v: v % 2 == 0 and width <= v // 2 < 2**31)
-    c_step = common([s[1] for s in cs], 2, lambda v: v in (2, 4))
-    c_stride = None if c_step is None else common([s[0] for s in cs], c_step * (cshape[1] - 1) + 2,
-                                                  lambda v: v % 2 == 0 and c_step * (cshape[1] - 1) + 2 <= v < 2**32)
-    aligned = all(p.ctypes.data % 2 == 0 for f in planes for p in f)
-    if None in (y_step, y_stride, c_step, c_stride) or not aligned:
-        planes = [tuple(np.ascontiguousarray(p) for p in f) for f in planes]
-        y_stride, c_stride, c_step = 2 * width, 2 * cshape[1], 2
-    return planes, width, height, int(y_stride) // 2, int(c_stride) // 2, int(c_step) // 2
-
-
-def _arr(ptrs):
-    return (C.c_void_p * max(len(ptrs), 1))(*[int(p) for p in ptrs])
+    """_frames_in._host_frames for 10-bit planes in 16-bit words."""
+    return _shared_host_frames(frames, np.uint16, "yuv16")
 
 
 def _check(L, rc, what):

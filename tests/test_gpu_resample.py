@@ -228,6 +228,34 @@ def test_host_form_equals_the_device_form(nq, shape):
     assert all((g == r).all() for g, r in zip(nq.resample_frames(frames, None, crop=(299, 199, 1, 1), linear=False), want))
 
 
+def test_four_host_forms_on_one_handle_leave_nothing_to_each_other(nq):
+    """nq_resample_frames_oriented (code 6), nq_frames_from_yuv_oriented (code 5), nq_resample_frames and nq_orient_frames share the
+    handle's staging buffers and each keeps a pointer table of its own: run one after the other on one handle, 3 frames of 8 x 4
+    each (reduced to 4 x 2 where the call reduces), every one gives what it gives on a fresh handle."""
+    from nquant.android_amd import orient, resample, yuv
+    rng = np.random.default_rng(23)
+    frames = [rng.integers(-2**31, 2**31, (4, 8)).astype(np.int32) for _ in range(3)]
+    planes = [(rng.integers(0, 256, (4, 8), dtype=np.uint8), rng.integers(0, 256, (2, 4), dtype=np.uint8),
+               rng.integers(0, 256, (2, 4), dtype=np.uint8)) for _ in range(3)]
+    calls = [lambda h: resample._resample_host(h._L, h._h, h._check, frames, (2, 4), None, True, 6),       # (oriented: 4 x 8 -> 2 x 4)
+             lambda h: yuv._yuv_host(h._L, h._h, h._check, planes, None, None, True, yuv.YUV_BT709, 5),
+             lambda h: resample._resample_host(h._L, h._h, h._check, frames, (4, 2), None, True),
+             lambda h: orient._orient_host(h._L, h._h, h._check, frames, 7)]
+    shapes = [(4, 2), (8, 4), (2, 4), (8, 4)]
+    shared = G._Handle()
+    try:
+        for k, (call, shape) in enumerate(zip(calls, shapes)):
+            got = call(shared)
+            fresh = G._Handle()
+            try:
+                want = call(fresh)
+            finally:
+                fresh.close()
+            assert len(got) == len(want) == 3 and all(g.shape == shape and (g == w).all() for g, w in zip(got, want)), k
+    finally:
+        shared.close()
+
+
 def test_invalid_arguments_then_a_valid_call(nq, hd):
     import torch
     L = hd._L

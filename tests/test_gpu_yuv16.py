@@ -413,6 +413,41 @@ def test_host_forms_equal_the_device_forms(nq, layout):
     assert all((a == b).all() for a, b in zip(nq.resample_frames_yuv16(views, None, **_kw(SDR709)), Y.convert(tight, SDR709)))
 
 
+def _arranged(frames, arrangement):
+    """The tight frames with their chroma planes as one of the four arrangements the host forms' staging tells apart."""
+    out = []
+    for y, u, v in frames:
+        if arrangement in ("interleaved-uv", "interleaved-vu"):        # one span: the second plane begins one sample into the first
+            c = np.stack((u, v) if arrangement == "interleaved-uv" else (v, u), axis=2)
+            u, v = (c[:, :, 0], c[:, :, 1]) if arrangement == "interleaved-uv" else (c[:, :, 1], c[:, :, 0])
+        elif arrangement == "planar-touching":                        # one span: v begins where u's span ends
+            c = np.concatenate([u.ravel(), v.ravel()])
+            u, v = c[:u.size].reshape(u.shape), c[u.size:].reshape(v.shape)
+        else:                                                          # three allocations: two chroma spans
+            u, v = u.copy(), v.copy()
+        out.append((y.copy(), u, v))
+    return out
+
+
+@pytest.mark.parametrize("shape", [((8, 4), (4, 2)), ((5, 3), (2, 1))], ids=lambda s: "%dx%d-%dx%d" % (s[0] + s[1]))
+@pytest.mark.parametrize("arrangement", ["interleaved-uv", "interleaved-vu", "planar-touching", "separate"])
+def test_host_forms_in_every_arrangement_of_the_planes(nq, arrangement, shape):
+    """The staging of the host forms keeps what the kernels' paths need of each arrangement: 8 x 4 is eligible for the wide paths
+    (interleaved with either plane first, planar), 5 x 3 takes the one-pixel path.  1:1 and reducing, against the restatement."""
+    (w, h), size = shape
+    flags = PQ2020
+    frames, want = _converted(w, h, 3, flags)
+    planes = _arranged(frames, arrangement)
+    keep = [tuple(p.copy() for p in f) for f in planes]
+    got = nq.frames_from_yuv16(planes, **_kw(flags))
+    assert len(got) == 3 and all((g == r).all() for g, r in zip(got, want)), (arrangement, shape)
+    for linear in (True, False):
+        small = _reduced(w, h, 3, flags, size, None, linear)[1]
+        got = nq.resample_frames_yuv16(planes, size, linear=linear, **_kw(flags))
+        assert len(got) == 3 and all(g.shape == (size[1], size[0]) and (g == r).all() for g, r in zip(got, small)), (arrangement, shape, linear)
+    assert all((a == b).all() for f, k in zip(planes, keep) for a, b in zip(f, k))
+
+
 def test_invalid_arguments_then_a_valid_call(nq):
     import torch
     L = nq.load_library()

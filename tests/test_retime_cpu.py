@@ -122,6 +122,42 @@ def test_mix_refusals_come_before_any_device_is_touched(nq):
         assert (buf == -9).all()
 
 
+def test_the_overlap_sweep_from_both_sides(nq):
+    """The host-side sweep of nq_retime_frames at its edges, on 4 x 2 frames (32 bytes) in one arena: what it allows passes every
+    check (0 with a GPU, -5 without: the checks come before any device is touched) and what it refuses is -1 with the sweep's own
+    text.  Every pointer is 4-byte aligned, so the narrowest overlap is one word; sources and outputs have one size, so a buffer
+    that lies wholly inside another one coincides with it."""
+    L = nq.load_library()
+    arena = np.zeros(256, np.int32)
+    base = (arena.ctypes.data + 15) & ~15
+    S0, S1, D0, D1 = base + 256, base + 320, base + 512, base + 576
+    arr = lambda ptrs: (C.c_void_p * len(ptrs))(*ptrs)
+    offset, source, weight = np.array([0, 1, 2], np.int32), np.array([0, 1], np.int32), np.array([1, 1], np.uint32)
+
+    def call(src=(S0, S1), dst=(D0, D1), form="host"):
+        tail = (2, arr(src), 4, 2, 2, offset.ctypes.data, source.ctypes.data, weight.ctypes.data, arr(dst), 1)
+        return L.nq_retime_frames(0, *tail) if form == "host" else L.nq_retime_frames_device(0, None, *tail)
+
+    allowed = [dict(dst=(S1 + 32, D1)),                      # begins at the last byte + 1 of a source
+               dict(dst=(S0 - 32, D1)),                      # ends where a source begins
+               dict(dst=(S0 - 32, S0 + 32), src=(S0, S0 + 64)),   # ... and both, with an output between two sources
+               dict(src=(S0, S0 + 4)),                       # sources that overlap each other
+               dict(src=(S0, S0)),                           # two sources that are one buffer
+               dict(dst=(D0, D0 + 32))]                      # an output that begins where the other ends
+    refused = [dict(dst=(S1 + 28, D1)),                      # one word into the end of a source
+               dict(dst=(S0 - 28, D1)),                      # ... into its beginning
+               dict(dst=(S0, D1)),                           # an output wholly inside a source, a source wholly inside an output
+               dict(dst=(D0, S1)),
+               dict(dst=(D0, D0)),                           # two identical outputs
+               dict(dst=(D0, D0 + 28))]                      # two outputs that share one word
+    for kw in refused:
+        for form in ("host", "device"):
+            assert call(form=form, **kw) == -1 and b"an output overlaps a source frame or another output" in L.nq_last_error(None), (form, kw)
+    assert not arena.any()
+    for kw in allowed:
+        assert call(**kw) == (0 if HAS_GPU else -5), (kw, L.nq_last_error(None))
+
+
 def test_python_argument_errors_need_no_device(nq):
     t = nq.timestamps_from_pts([0, 33333, 66667])
     assert t.dtype == np.int64 and list(t) == [0, 33333, 66667, 100001]

@@ -326,3 +326,40 @@ def test_without_a_device_every_call_raises_no_device(nq):
         with pytest.raises(nq.NqError) as e:
             call()
         assert e.value.status == -5
+
+
+def test_the_overlap_sweep_from_both_sides(nq):
+    """The host-side sweep of nq_frames_from_yuv16 at its edges, on 8 x 4 P010 planes in one arena: what it allows passes every check
+    (0 with a GPU, -5 without: the checks come before any device is touched) and what it refuses is -1 with the sweep's own text.
+    Plane pointers are 2-byte and outputs 4-byte aligned, so the narrowest overlap an output can have with a plane is one sample."""
+    import ctypes as C
+    L = nq.load_library()
+    arena = np.zeros(2048, np.uint8)
+    base = (arena.ctypes.data + 15) & ~15
+    Y0, U0, OUT = base + 512, base + 768, 8 * 4 * 4    # y spans 64 bytes (stride 8); u, v = u + 2 span 30 bytes each: chroma ends at U0 + 32
+    arr = lambda ptrs: (C.c_void_p * len(ptrs))(*ptrs)
+
+    def call(dst, y=(Y0,), u=(U0,), ys=8, form="host"):
+        n = len(dst)
+        y, u = y * n if len(y) == 1 else y, u * n if len(u) == 1 else u
+        tail = (n, arr(y), arr(u), arr([p + 2 for p in u]), 8, 4, ys, 8, 2, Y.MSB, arr(dst))
+        return L.nq_frames_from_yuv16(0, *tail) if form == "host" else L.nq_frames_from_yuv16_device(0, None, *tail)
+
+    allowed = [dict(dst=(U0 + 32,)),                         # begins at the last byte + 1 of the chroma span
+               dict(dst=(Y0 + 64,)),                         # ... of the luma plane
+               dict(dst=(Y0 - OUT,)),                        # ends where the luma plane begins
+               dict(dst=(base,), u=(Y0 + 8,)),               # sources that overlap each other: the chroma inside the luma plane
+               dict(dst=(base, base + OUT))]                 # two outputs, the second where the first ends (and one set of planes twice)
+    refused = [dict(dst=(Y0 + 64,), y=(Y0 + 2,)),            # one sample into the end of the luma plane
+               dict(dst=(U0 + 28,)),                         # one sample into the end of u's span, two into v's
+               dict(dst=(Y0 + 64,), ys=40),                  # wholly inside a source: luma rows 40 samples apart span 256 bytes
+               dict(dst=(U0 - 16,)),                         # a source wholly inside an output: the chroma span
+               dict(dst=(base, base)),                       # two identical outputs
+               dict(dst=(base, base + OUT - 4))]             # two outputs that share one word
+    for kw in refused:
+        for form in ("host", "device"):
+            assert call(form=form, **kw) == -1 and b"an output overlaps a source plane or another output" in L.nq_last_error(None), (form, kw)
+    assert not arena.any()
+    for kw in allowed:
+        assert call(**kw) == (0 if HAS_GPU else -5), (kw, L.nq_last_error(None))
+
