@@ -190,10 +190,51 @@ def _dist_symbol(d):
             return c, d - DIST_CODES[c][0], DIST_CODES[c][1]
 
 
-@functools.lru_cache(maxsize=1 << 16)
-def block_of(seg, final):
-    """(value, bit count) of the one dynamic-Huffman block of a segment; bit i of the value is the i-th bit of the block."""
-    toks = tokens_of(seg)
+def unlimited_depth(freq):
+    """The largest depth of Huffman's tree over the used symbols when no limit cuts it (code_lengths with a limit no tree reaches)."""
+    return max(code_lengths(freq, max(len(freq), 2)))
+
+
+def step_groups(seg):
+    """What the parse's 64-position steps see of the hash, one entry per step that holds a position with three bytes:
+    (valid positions, groups of two or more positions that share a hash, size of the largest group, neighbours in a group -- a
+    position and the one it takes as its candidate -- whose three bytes differ: a collision of the 13-bit hash inside the step)."""
+    L = len(seg)
+    a = np.frombuffer(seg, np.uint8)
+    out = []
+    if L < MIN_MATCH:
+        return out
+    key = a[:-2].astype(np.uint64) | a[1:-1].astype(np.uint64) << np.uint64(8) | a[2:].astype(np.uint64) << np.uint64(16)
+    hsh = ((key * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)) >> np.uint64(32 - HASH_BITS)
+    for base in range(0, L - 2, 64):
+        h, k = hsh[base:base + 64], key[base:base + 64]
+        order = np.argsort(h, kind="stable")
+        same = h[order[1:]] == h[order[:-1]]
+        _, counts = np.unique(h, return_counts=True)
+        out.append((len(h), int((counts >= 2).sum()), int(counts.max()), int((same & (k[order[1:]] != k[order[:-1]])).sum())))
+    return out
+
+
+class Block:
+    """One segment's dynamic-Huffman block and how it came about (the `stats` of deflate() and encode()):
+    value, bits     the block: bit i of value is its i-th bit
+    tokens          the greedy parse: literals (int) and matches ((length, distance))
+    lit_hist, dist_hist, cl_hist      the three symbol histograms (286, 30 and 19 counts)
+    lit_lens, dist_lens, cl_lens      the code lengths with the limits 15, 15 and 7
+    lit_depth, dist_depth, cl_depth   the largest depth of each tree without a limit
+    hlit, hdist, hclen                the header's three counts
+    runs            the code-length sequence: [(code-length-code symbol, extra value, extra bits)]
+    items           per token (bit position in the block, bit count, value): what the bit writer takes as one item
+    steps           step_groups() of the segment"""
+    __slots__ = ("value", "bits", "tokens", "lit_hist", "dist_hist", "cl_hist", "lit_lens", "dist_lens", "cl_lens", "lit_depth", "dist_depth",
+                 "cl_depth", "hlit", "hdist", "hclen", "runs", "items", "steps", "length")
+
+
+def _block(seg, final, full):
+    """The Block of a segment; `full`: with the fields that only the statistics need (the depths, items and steps)."""
+    B = Block()
+    B.length = len(seg)
+    toks = B.tokens = tokens_of(seg)
     lf, df = [0] * 286, [0] * 30
     lf[256] = 1
     for t in toks:
@@ -213,6 +254,11 @@ def block_of(seg, final):
     cl = code_lengths(cf, 7)
     cc = canonical_codes(cl)
     hclen = max(4, max(i for i in range(19) if cl[CL_ORDER[i]]) + 1)
+    B.lit_hist, B.dist_hist, B.cl_hist = lf, df, cf
+    B.lit_lens, B.dist_lens, B.cl_lens = ll, dl, cl
+    if full:
+        B.lit_depth, B.dist_depth, B.cl_depth = unlimited_depth(lf), unlimited_depth(df), unlimited_depth(cf)
+    B.hlit, B.hdist, B.hclen, B.runs = hlit, hdist, hclen, rl
     val, nb = 0, 0
 
     def put(v, b):
@@ -230,7 +276,9 @@ def block_of(seg, final):
     for s, e, eb in rl:
         put(cc[s], cl[s])
         put(e, eb)
+    items = B.items = []
     for t in toks:
+        at = nb
         if isinstance(t, tuple):
             s, e, eb = _length_symbol(t[0])
             put(lc[s], ll[s])
@@ -240,21 +288,43 @@ def block_of(seg, final):
             put(e, eb)
         else:
             put(lc[t], ll[t])
+        if full:
+            items.append((at, nb - at, val >> at))
     put(lc[256], ll[256])
-    return val, nb
+    B.value, B.bits = val, nb
+    if full:
+        B.steps = step_groups(seg)
+    return B
+
+
+@functools.lru_cache(maxsize=1 << 16)
+def block_of(seg, final):
+    """(value, bit count) of the one dynamic-Huffman block of a segment; bit i of the value is the i-th bit of the block."""
+    B = _block(seg, final, False)
+    return B.value, B.bits
+
+
+@functools.lru_cache(maxsize=64)
+def block_stats(seg, final):
+    """The Block of a segment with every field."""
+    return _block(seg, final, True)
 
 
 def segment_length(raw_len, segment_bytes):
     return min(segment_bytes if segment_bytes else DEFAULT_SEGMENT, raw_len)
 
 
-def deflate(raw, segment_bytes=0):
-    """The segments' blocks one after another, the last byte zero-padded."""
+def deflate(raw, segment_bytes=0, stats=None):
+    """The segments' blocks one after another, the last byte zero-padded.  `stats`: a list that receives every segment's Block."""
     S = segment_length(len(raw), segment_bytes)
     val, nb = 0, 0
     parts = []
     for o in range(0, len(raw), S):
-        v, b = block_of(raw[o:o + S], o + S >= len(raw))
+        if stats is None:
+            v, b = block_of(raw[o:o + S], o + S >= len(raw))
+        else:
+            stats.append(block_stats(raw[o:o + S], o + S >= len(raw)))
+            v, b = stats[-1].value, stats[-1].bits
         val |= v << nb
         nb += b
         if nb >= 1 << 16:                            # keep the big integer short
@@ -270,7 +340,8 @@ def chunk(kind, data):
     return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data))
 
 
-def encode(index, palette, segment_bytes=0):
+def encode(index, palette, segment_bytes=0, stats=None):
+    """The file.  `stats`: a list that receives the Block of every segment, in order."""
     index = np.asarray(index)
     h, w = index.shape
     pal = [int(c) & 0xFFFFFFFF for c in np.asarray(palette).reshape(-1)]
@@ -281,7 +352,7 @@ def encode(index, palette, segment_bytes=0):
     nt = max((i + 1 for i, c in enumerate(pal) if (c >> 24) != 255), default=0)
     if nt:
         out += chunk(b"tRNS", bytes(c >> 24 for c in pal[:nt]))
-    out += chunk(b"IDAT", b"\x78\x01" + deflate(raw, segment_bytes) + struct.pack(">I", zlib.adler32(raw)))
+    out += chunk(b"IDAT", b"\x78\x01" + deflate(raw, segment_bytes, stats) + struct.pack(">I", zlib.adler32(raw)))
     return out + chunk(b"IEND", b"")
 
 

@@ -3,7 +3,8 @@ for every K, segment length, shape, palette kind and kind of change tried; every
 apng_ref.compose and through Pillow; a sprite over a transparent region un-paints its old place (crop mode); rectangles that start in
 mid-word of the source at depths 1, 2 and 4; frames larger than one grid stride of the difference pass; frames at odd 2-byte offsets in device memory, never written; convert_frames_to_apng on
 a sprite animation, also over a transparent background (which delta GIF refuses); every invalid input, each followed by a valid call
-on the same handle."""
+on the same handle.  The limit cases of png_cases.py as frame 1 of a two-frame file, whole (crop mode) and with unchanged pixels packed
+as u (mark mode): png_deflate_kernel<true> at its limiters, its bit writer's third word and its window's edges."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,7 @@ import pytest
 
 import apng_ref
 import gif_delta_ref
+import png_cases
 import png_ref
 from nquant.android_amd import apng as A
 from nquant.android_amd import gif as G
@@ -174,6 +176,60 @@ def test_device_form_at_odd_offsets_leaves_the_frames_alone(nq, hd):
         assert nq.encode_apng(frames, pal, delays) == apng_ref.encode(frames, pal, delays_cs=delays)     # host and device forms agree
         assert (buf.cpu().numpy().view(np.uint16) == host).all()
     q.close()
+
+
+def _other_corners(frame, K):
+    """The frame with other indices in its four corners: the changed rectangle of (this, frame) is the whole frame."""
+    f = np.array(frame, np.int64)
+    for y in (0, -1):
+        for x in (0, -1):
+            f[y, x] = (frame[y, x] + 1) % K
+    return f
+
+
+@pytest.mark.parametrize("name", [n for n in png_cases.names() if n != "pooled"])
+def test_limit_cases_as_the_second_frame(nq, hd, name):
+    """Crop mode (K = 256), frame 0 differs from frame 1 in the four corners: frame 1's chains encode the limit case's whole map, read
+    as a rectangle by png_deflate_kernel<true>.  Host form, and device form at odd 2-byte offsets with the frames left unchanged."""
+    _, idx, pal, S = png_cases.case(name)
+    assert len(pal) == 256 and apng_ref.unchanged_index(pal) is None
+    h, w = idx.shape
+    frames = [_other_corners(idx, 256), idx]
+    assert _rects(frames) == [[0, 0, w, h]] * 2
+    want = apng_ref.encode(frames, pal, delays_cs=[3, 4], loop=1, segment_bytes=S)
+    assert apng_ref.zlib_stream(idx, 256, S) in want                         # frame 1's stream is the still image's
+    got, rects = _enc(hd, frames, pal, [3, 4], 1, S)
+    assert rects.tolist() == [[0, 0, w, h]] * 2
+    assert got == want, (name, len(got), len(want))
+    buf, host, ptrs = png_cases.device_maps(frames)
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        got = nq.encode_apng_device(q, ptrs, w, h, pal, [3, 4], 1, S)
+    finally:
+        q.close()
+    assert got == want, (name, "device form")
+    assert (buf.cpu().numpy().view(np.uint16) == host).all()
+
+
+def test_dist_limit_in_mark_mode_with_unchanged_pixels(hd):
+    """Mark mode (K = 255, every alpha 255; u = 255): frame 0 differs from the dist_limit map in pixel 0 and in every pixel from 1000
+    on, so pixels 1 .. 999 of frame 1's body are u.  What is left of the map still takes the distance code past 15."""
+    _, idx, _, S = png_cases.case("dist_limit")
+    K = 255
+    assert idx.max() < K
+    pal = palette_of(K, np.random.default_rng(18))
+    prev = (idx + 1) % K
+    prev[0, 1:1000] = idx[0, 1:1000]
+    frames = [prev, idx]
+    assert apng_ref.unchanged_index(pal) == K and _rects(frames) == [[0, 0, idx.shape[1], 1]] * 2
+    body = apng_ref.bodies(frames, pal)[1]
+    assert (body[0, 1:1000] == K).all() and (body[0, 1000:] == idx[0, 1000:]).all() and body[0, 0] == idx[0, 0]
+    stats = []
+    png_ref.deflate(png_ref.raw_stream(body, K + 1), S, stats)
+    assert stats[0].dist_depth == 16 and max(stats[0].dist_lens) == 15
+    got, rects = _enc(hd, frames, pal, S=S)
+    assert got == apng_ref.encode(frames, pal, segment_bytes=S)
+    composes_back(got, frames, pal, "dist_limit in mark mode")
 
 
 def test_one_frame_and_two_frames(nq, hd):

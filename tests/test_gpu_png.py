@@ -1,6 +1,9 @@
 """PNG encoding on the GPU (nq_encode_png / nq_encode_png_device): the bytes equal the restatement in png_ref.py for every K, segment
 length, shape and content tried; a batch of mixed sizes, K and palettes at odd 2-byte offsets; alpha in tRNS; convert_to_png results
-read back; the 4096^2 bench image against zlib; every invalid input, each followed by a valid call on the same handle."""
+read back; the 4096^2 bench image against zlib; every invalid input, each followed by a valid call on the same handle.  The limit
+cases of png_cases.py (the three length limiters, items that reach the third word of the emit window, the edges of the distance window,
+of the match lengths and of the run-length coder, the header's extremes, more chains than the grid holds) go through the host form, the
+device form and one batched call."""
 import ctypes as C
 import io
 import zlib
@@ -8,6 +11,7 @@ import zlib
 import numpy as np
 import pytest
 
+import png_cases
 import png_ref
 from nquant.android_amd import gif as G
 from nquant.android_amd import png as P
@@ -46,10 +50,72 @@ def test_bytes_equal_the_restatement(hd, K):
 
 
 def test_length_limited_codes(hd):
+    """skewed_map() at three segment lengths.  Its name is older than what is known about it: no tree of these blocks is deeper than
+    its limit (13, 9 and 6 at the most; test_png_cpu.py::test_skewed_map_reaches_no_limit), so the limiter does not run here.  The cases
+    that carry the limiters are len_limit, dist_limit, clc_limit and header_max of test_limit_cases_equal_the_restatement."""
     idx = skewed_map()
     pal = 0xFF000000 | np.arange(256)
     for S in (65535, 0, 5000):
         assert _enc(hd, [idx], [pal], S)[0] == png_ref.encode(idx, pal, S), S
+
+
+@pytest.mark.parametrize("name", png_cases.names())
+def test_limit_cases_equal_the_restatement(nq, name):
+    """Byte for byte, through nq_encode_png and through nq_encode_png_device with the map at an odd 2-byte offset and left unchanged;
+    the library holds the same device memory before and after."""
+    import torch
+    _, idx, pal, S = png_cases.case(name)
+    want, _ = png_cases.restated(name)
+    before = nq.device_bytes()
+    got = nq.encode_png(idx, pal, S)
+    assert nq.device_bytes() == before
+    assert got == want, (name, "nq_encode_png", len(got), len(want))
+    buf, host, ptrs = png_cases.device_maps([idx])
+    torch.cuda.synchronize()
+    before = nq.device_bytes()
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        got, = nq.encode_png_device(q, ptrs, [idx.shape[1]], [idx.shape[0]], [pal], S)
+    finally:
+        q.close()
+    assert nq.device_bytes() == before
+    assert got == want, (name, "nq_encode_png_device", len(got), len(want))
+    assert (buf.cpu().numpy().view(np.uint16) == host).all()                 # the map is never written
+
+
+def test_limit_cases_in_one_batched_call(nq, hd):
+    """A call has one segment length, so the cases of each segment length (65535: eleven of them) go through one call, a tiny image in
+    front of every limit case: a chain with full tables follows one that left them nearly empty.  Host form and device form."""
+    rng = np.random.default_rng(3)
+    tiny = [rng.integers(0, 2, (1, 3)), np.zeros((1, 1), np.int64), rng.integers(0, 256, (2, 5))]
+    by_S = {}
+    for name, idx, pal, S in png_cases.limit_cases():
+        by_S.setdefault(S, []).append((idx, pal))
+    q = nq.PnnQuantizer(np.zeros((2, 2), np.int32))
+    try:
+        for S, group in by_S.items():
+            maps, pals = [], []
+            for i, (idx, pal) in enumerate(group):
+                maps += [tiny[i % 3], idx]
+                pals += [pal[:2] if i % 3 == 0 else pal, pal]
+            want = [png_ref.encode(m, p, S) for m, p in zip(maps, pals)]
+            assert _enc(hd, maps, pals, S) == want, S
+            buf, host, ptrs = png_cases.device_maps(maps)
+            got = nq.encode_png_device(q, ptrs, [m.shape[1] for m in maps], [m.shape[0] for m in maps], pals, S)
+            assert got == want, S
+            assert (buf.cpu().numpy().view(np.uint16) == host).all()
+    finally:
+        q.close()
+
+
+def test_more_chains_than_the_grid_holds(nq):
+    """The pooled case is there for a workgroup's later chains: it must hold more segments than the grid of 4 workgroups per compute
+    unit of this device, whatever its size."""
+    import torch
+    grid = 4 * torch.cuda.get_device_properties(0).multi_processor_count
+    chains = len(png_cases.restated("pooled")[1])
+    print("pooled:", chains, "chains, grid", grid)
+    assert chains > grid, (chains, grid)
 
 
 def test_long_matches_and_far_distances(hd):
