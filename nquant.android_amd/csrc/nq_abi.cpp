@@ -159,6 +159,7 @@ struct Scratch {
     DevBuf<unsigned long long> dheads;         // {colour, first index} pairs (uint2)
     DevBuf<float> cell_box;           // Lab bounding box of every 5-6-5 cell (palette independent, built once)
     bool cell_box_ready = false;
+    bool lab_table = false;           // the palette's Lab stands behind the packed records of cell_lists (written with the lists now in it)
 };
 
 inline size_t path_bytes(int w, int hgt) { const size_t n = (size_t) w * hgt; return (n ? n : 1) * sizeof(uint32_t); }
@@ -419,6 +420,8 @@ static std::atomic<long long> g_split_passes{0}, g_split_side{0}, g_split_listed
 int* failed_list(nq_handle* h) { return h->d_failed.p + 1; }
 size_t failed_words(const nq::TileGeom& T) { return 2 * ((size_t) T.tiles_x * T.tiles_y + 1); }
 void* packed_lists(nq_handle* h) { return h->sc->cell_lists.p + 2 * (size_t) 65536 * 32 + 2 * 65536; }
+// the Lab table of the palette whose lists the scratch set holds (nq_kernels.h launch_build_lists), or null where none was written
+const void* lab_table(nq_handle* h) { return h->sc->lab_table ? (const unsigned char*) packed_lists(h) + nq::NQ_PACKED_BYTES : nullptr; }
 
 // candidate lists per colour cell for this palette (nq_lists.inc); empty view = full scans
 // sal_pixels != null: the saliency map of these n pixels is wanted in h->sc->saliency as well; *sal_done says whether it was built here
@@ -432,7 +435,9 @@ int prepare_lists(nq_handle* h, const DevParams& P, nq::ListsView* out, const in
     out->closest = out->closestCount = out->nearest = out->nearestCount = nullptr;
     if (!h->use_lists || P.K > 256 || P.K < 8) return NQ_OK;
     const size_t LB = (size_t) 65536 * 32;
-    NQ_HIP(h, h->sc->cell_lists.reserve(2 * LB + 2 * 65536 + 2 * LB));     // + the packed records of the specialised dither kernel
+    // + the packed records of the specialised dither kernel (2 * LB = NQ_PACKED_BYTES) + the palette's Lab behind them
+    NQ_HIP(h, h->sc->cell_lists.reserve(2 * LB + 2 * 65536 + nq::NQ_PACKED_BYTES + nq::NQ_LAB_TABLE_BYTES));
+    h->sc->lab_table = false;
     unsigned char* base = h->sc->cell_lists.p;
     double wA, wR, wG, wB;
     if (h->kind == NQ_KIND_LAB) {
@@ -469,6 +474,7 @@ int prepare_lists(nq_handle* h, const DevParams& P, nq::ListsView* out, const in
                                               pack && pack_in_builders ? packed_lists(h) : nullptr, d_failed, &folded);
     if (sal_done) *sal_done = sal_built;
     if (failed_cleared) *failed_cleared = folded && d_failed;
+    h->sc->lab_table = pack && pack_in_builders && folded;
     if (pack && !(folded && pack_in_builders)) launch_pack_lists(*out, packed_lists(h), h->stream);
     return NQ_OK;
 }
@@ -1156,7 +1162,7 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
         h->split_uncounted = split;
         NQ_HIP(h, launch_gilbert_fast(P, G, T, lv, (const int*) d_argb, d_sal, h->d_palette.p, (long long) seed, d_out_index,
                                       post ? nullptr : (int*) d_out_argb, failed_list(h), packed_lists(h), h->stream, failed_cleared,
-                                      chain_mode, side ? h->chain_stream : nullptr, side ? h->chain_gate : nullptr));
+                                      chain_mode, side ? h->chain_stream : nullptr, side ? h->chain_gate : nullptr, lab_table(h)));
         if (side) tail_stream = h->chain_stream;
         d_tile_list = failed_list(h);
         h->last_dither_fast = 1;

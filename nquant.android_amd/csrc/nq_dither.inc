@@ -186,12 +186,19 @@ __global__ void __launch_bounds__(256) build_lab_lists_kernel(DevParams P, const
                                                               double wB, int kstart, const float* __restrict__ box,
                                                               unsigned char* __restrict__ closest, unsigned char* __restrict__ closestCount,
                                                               unsigned char* __restrict__ nearest, unsigned char* __restrict__ nearestCount, SalJob sal,
-                                                              void* packed, int* failed) {
+                                                              void* packed, int* failed, float4* lab_table) {
     extern __shared__ __align__(16) unsigned char smem[];
     // packed (nullable): each builder also writes its half of the specialised kernels' records; failed (nullable): the hand-back count of
     // the dither kernel that follows on the stream starts at zero (one fill per image less), and the need count of its split form, the
     // word in front of it (launch_gilbert_fast, nq_kernels.h)
     if (failed && blockIdx.x == 0 && threadIdx.x == 0) { failed[-1] = 0; failed[0] = 0; }
+    // lab_table (nullable): the palette's Lab as the dither kernels stage it -- getLab(palette[i]) (NQ/PnnLABQuantizer.java:352), zero from
+    // entry K on -- once per image; the pixel-form light pass loads it instead of converting the palette in every workgroup (one closest-list
+    // workgroup takes it: 256 threads, one entry each)
+    if (lab_table && blockIdx.x == 255) {
+        const Lab l2 = RGB2LAB((int) threadIdx.x < P.K ? g_palette[threadIdx.x] : 0);
+        lab_table[threadIdx.x] = make_float4(l2.L, l2.A, l2.B, 0.f);
+    }
     if (blockIdx.x < 256) closest_lists_body(P, g_palette, wA, wR, wG, wB, closest, closestCount, (int) blockIdx.x, packed);
     else if (blockIdx.x < 512) nearest_lists_body(P, g_palette, kstart, box, nearest, nearestCount, (int) blockIdx.x - 256, smem, packed);
     else saliency_body(P, sal.salSubst, sal.pixels, sal.N, sal.out, sal.vec4, (int) blockIdx.x - 512, sal.blocks, reinterpret_cast<double*>(smem));

@@ -58,6 +58,9 @@ struct FastArgs {
     // iteration: 64 >> tileShift tiles) per workgroup, and the test switch NQ_LIGHT_REJECT (a draw whose bits under the mask are all zero counts as rejected; 0 = off)
     int tileShift, pixelRun;
     unsigned rejectMask;
+    // ... and the palette's Lab as build_lab_lists_kernel left it behind the packed records (256 x {L, A, B, 0}, zero from entry K on), or
+    // nullptr: the kernel converts the palette itself
+    const float4* labTable;
 };
 // instruction budget by block (tools/fast_budget.py compiles this file with -DNQ_FAST_MARKS and counts between the markers)
 #ifdef NQ_FAST_MARKS
@@ -79,7 +82,9 @@ struct FastArgs {
 enum { FC_NEAREST = 0, FC_NEAREST_EXACT, FC_NEAREST_EXACT_LANES, FC_NEAREST_EXACT_N2_SUM, FC_NEAREST_EXACT_N2_MAX, FC_NEAREST_TAIL, FC_CLOSEST,
        FC_CLOSEST_TAIL, FC_CLOSEST_EXACT, FC_YDIFF, FC_YDIFF_F64, FC_TANH, FC_TANH_LIBRARY, FC_CHAIN_LIGHT, FC_CHAIN_REWALK,
        FC_PIXEL_NODRAW,       // gilbert_pixel_kernel: looked-up steps whose pick does not draw (closest[2] == 0)
-       FC_SLOTS = 16 };
+       FC_PIXEL_STEPS,        // ... its wavefront-steps with a looked-up lane, those of them with a lane in fast_nearest, and the lanes in it
+       FC_PIXEL_NEAREST, FC_PIXEL_NEAREST_LANES,
+       FC_SLOTS = 24 };
 __device__ unsigned long long g_fast_count[FC_SLOTS];
 __device__ __forceinline__ void fast_count_add(int slot, bool cond, unsigned long long v, bool use_max) {
     const unsigned long long active = __ballot(1), m = __ballot(cond);
@@ -1043,6 +1048,13 @@ __global__ void __launch_bounds__(256, 4) gilbert_light_kernel(DevParams P, Gilb
 // wavefronts of a workgroup take neighbouring tile groups, so tile rows of one image row leave the CU together.  Pixel and saliency of the
 // wavefront's next group are requested before the current group's scans.  Not persistent: a workgroup walks F.pixelRun groups and retires,
 // so the chain pass and the hand-back pass of the previous image keep getting onto the chip.
+//
+// WAVE_TILE (tileShift == 6, the 8x8 tiles of the headline): a wavefront iteration is exactly one tile, so the tile number, its row and column
+// (a division by tiles_x), its shape, its origin and the whole 64-bit seed (mix64, jr_seed) are the same in all 64 lanes.  The wave index goes
+// through readfirstlane, which is what lets the compiler see that: all of it lands on the scalar unit, and a lane keeps its path entry, its
+// pixel address, the popcount of the draws below it and the jump product.  Tiles of 16 and 32 pixels run the per-lane form.
+// The palette's Lab comes from F.labTable where the list builders left one (once per image instead of once per workgroup).
+template <bool WAVE_TILE>
 __global__ void __launch_bounds__(256, 5) gilbert_pixel_kernel(DevParams P, GilbertConsts G, TileGeom T, FastArgs F,
                                                                const int* __restrict__ pixels, const float* __restrict__ saliency,
                                                                const int* __restrict__ g_palette, long long seed,
@@ -1055,12 +1067,15 @@ __global__ void __launch_bounds__(256, 5) gilbert_pixel_kernel(DevParams P, Gilb
     __shared__ __align__(16) ulonglong2 s_jump[NQ_JUMP_MAX + 1];
     const int K = P.K;
     const int tid = threadIdx.x;
-    const int sh = F.tileShift, tilepx = 1 << sh;
+    const int sh = WAVE_TILE ? 6 : F.tileShift, tilepx = 1 << sh;
     {
         const int c2 = tid < K ? g_palette[tid] : 0;
         s_argb[tid] = c2;
-        const Lab l2 = RGB2LAB(c2);                    // getLab(palette[i]) (NQ/PnnLABQuantizer.java:352)
-        s_lab[tid] = make_float4(l2.L, l2.A, l2.B, 0.f);
+        if (F.labTable) s_lab[tid] = F.labTable[tid];
+        else {
+            const Lab l2 = RGB2LAB(c2);                // getLab(palette[i]) (NQ/PnnLABQuantizer.java:352)
+            s_lab[tid] = make_float4(l2.L, l2.A, l2.B, 0.f);
+        }
         s_gamma32[tid] = (float) g_tab.gamma[tid];
         for (int i = tid; i < 1024; i += 256) ((int*) s_blue)[i] = ((const int*) g_tab.blue)[i];
         const int s = tid >> 6, i = tid & 63;
@@ -1077,8 +1092,8 @@ __global__ void __launch_bounds__(256, 5) gilbert_pixel_kernel(DevParams P, Gilb
 
     const int ntiles = T.tiles_x * T.tiles_y;
     const int width = T.width;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int step = lane & (tilepx - 1), sub = lane >> sh;       // this lane: path step `step` of tile `sub` of the group
+    const int lane = tid & 63, wave = WAVE_TILE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
+    const int step = lane & (tilepx - 1), sub = WAVE_TILE ? 0 : lane >> sh;       // this lane: path step `step` of tile `sub` of the group
     const int tpw = 64 >> sh;                                     // tiles per group
     const int ngroups = (ntiles + tpw - 1) / tpw;
     const int g_end = min((int) blockIdx.x * F.pixelRun + F.pixelRun, ngroups);
@@ -1097,9 +1112,10 @@ __global__ void __launch_bounds__(256, 5) gilbert_pixel_kernel(DevParams P, Gilb
             const int shape = (tx == T.tiles_x - 1 ? 1 : 0) | (ty == T.tiles_y - 1 ? 2 : 0);
             if (step < T.path_len[shape]) {
                 const unsigned d = s_path[shape * tilepx + step];
-                const int x = tx * T.tile_w + (int) (d & 0xFFFFu), y = ty * T.tile_h + (int) (d >> 16);
-                tile_n = tile; xx_n = x; yy_n = y + T.y_origin;
-                bidx_n = x + y * width;
+                const int dx = (int) (d & 0xFFFFu), dy = (int) (d >> 16);
+                const int x0 = tx * T.tile_w, y0 = ty * T.tile_h;               // (WAVE_TILE: scalar, like everything above the path entry)
+                tile_n = tile; xx_n = x0 + dx; yy_n = (y0 + T.y_origin) + dy;
+                bidx_n = (x0 + y0 * width) + (dx + dy * width);
                 pixel_n = pixels[bidx_n];
                 sal_n = saliency[bidx_n];
             }
@@ -1129,11 +1145,13 @@ __global__ void __launch_bounds__(256, 5) gilbert_pixel_kernel(DevParams P, Gilb
         NQ_COUNT_SUM(FC_PIXEL_NODRAW, look && !draws, 1);
         const unsigned long long dmask = __ballot(draws);
         bool reject = false;
+        int idx = 0;
         if (look) {
-            int idx = 0;
             if (draws) {
                 // random.nextInt(32767) % (closest[3] + closest[2]) <= closest[3] (fast_closest_pick), the draw by jump-ahead
-                const long long s0 = jr_seed((long long) mix64((unsigned long long) seed + (unsigned long long) (T.tile_base + tile)));
+                // (WAVE_TILE: the wavefront's tile is g itself, a scalar -- `tile` is the same number behind a per-lane select)
+                const int seed_tile = WAVE_TILE ? g : tile;
+                const long long s0 = jr_seed((long long) mix64((unsigned long long) seed + (unsigned long long) (T.tile_base + seed_tile)));
                 const int uu = fast_jump_draw(s_jump, s0, __popcll(dmask & below));
                 bool accept;
                 const int r = fast_nextint_fold(uu, accept);
@@ -1143,6 +1161,15 @@ __global__ void __launch_bounds__(256, 5) gilbert_pixel_kernel(DevParams P, Gilb
             }
             qidx = fast_lab_tail<true>(S, X, F, K, c, H, idx);
         }
+#ifdef NQ_FAST_COUNT
+        {   // fast_lab_tail's own condition for the nearest fallback
+            const int ci = idx ? H.t.c1 : H.t.c0, ei = idx ? H.t.e1 : H.t.e0;
+            const bool nearest = look && (ei >= K || ci == 0 || c_alpha(s_argb[ci]) < c_alpha(c));
+            NQ_COUNT(FC_PIXEL_STEPS, look);
+            NQ_COUNT(FC_PIXEL_NEAREST, nearest);
+            NQ_COUNT_SUM(FC_PIXEL_NEAREST_LANES, nearest, 1);
+        }
+#endif
         const bool tile_listed = (__ballot(need || reject) & tile_lanes) != 0ULL;
         const bool tile_failed = (__ballot(failed) & tile_lanes) != 0ULL;
         NQ_COUNT_SUM(FC_CHAIN_LIGHT, active && step == 0 && !tile_listed, 1);
@@ -1559,7 +1586,7 @@ static FastArgs fast_args(const DevParams& P, const ListsView& lv, void* d_packe
 hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv, const int* d_pixels,
                                const float* d_saliency, const int* d_palette, long long seed, unsigned short* d_index, int* d_argb,
                                int* d_failed, void* d_packed, hipStream_t s, bool failed_cleared, int chain_mode, hipStream_t chain_stream,
-                               hipEvent_t chain_gate) {
+                               hipEvent_t chain_gate, const void* d_lab) {
     const int ntiles = T.tiles_x * T.tiles_y;
     const int tilepx = T.tile_w * T.tile_h;
     FastArgs F = fast_args(P, lv, d_packed, s);
@@ -1596,7 +1623,16 @@ hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const
             F.pixelRun = std::max(1, std::min(run_tiles / tpw, ngroups));
             F.rejectMask = reject_bits ? (1u << reject_bits) - 1u : 0u;
             const int pgrid = (ngroups + F.pixelRun - 1) / F.pixelRun;
-            hipLaunchKernelGGL(gilbert_pixel_kernel, dim3(pgrid), dim3(256), 0, s, P, G, T, F, d_pixels, d_saliency, d_palette, seed, d_index, d_argb);
+            // NQ_PIXEL_SCALAR=0: 64-pixel tiles through the per-lane form as well; NQ_LAB_TABLE=0: every workgroup converts the palette
+            // itself (both for A/B timing, DESIGN.md section 6 r23, and read at every launch)
+            bool wave_tile = F.tileShift == 6;
+            if (const char* r = std::getenv("NQ_PIXEL_SCALAR")) { if (std::atoi(r) == 0) wave_tile = false; }
+            F.labTable = (const float4*) d_lab;
+            if (const char* r = std::getenv("NQ_LAB_TABLE")) { if (std::atoi(r) == 0) F.labTable = nullptr; }
+            if (wave_tile)
+                hipLaunchKernelGGL(gilbert_pixel_kernel<true>, dim3(pgrid), dim3(256), 0, s, P, G, T, F, d_pixels, d_saliency, d_palette, seed, d_index, d_argb);
+            else
+                hipLaunchKernelGGL(gilbert_pixel_kernel<false>, dim3(pgrid), dim3(256), 0, s, P, G, T, F, d_pixels, d_saliency, d_palette, seed, d_index, d_argb);
         } else {
             if (llds > 64 * 1024) {
                 e = hipFuncSetAttribute((const void*) gilbert_light_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
@@ -1690,8 +1726,8 @@ void launch_fast_selftest(const DevParams& P, const int* d_palette, int which, c
 
 #ifdef NQ_FAST_COUNT
 // counting build only: the counters since the last reset (FC_* order), read after the caller has waited for its kernels
-extern "C" int nq_fast_counts(unsigned long long* out16, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(nq::g_fast_count), sizeof nq::g_fast_count);
+extern "C" int nq_fast_counts(unsigned long long* out24, int reset) {
+    hipError_t e = hipMemcpyFromSymbol(out24, HIP_SYMBOL(nq::g_fast_count), sizeof nq::g_fast_count);
     if (e == hipSuccess && reset) {
         const unsigned long long z[nq::FC_SLOTS] = {0};
         e = hipMemcpyToSymbol(HIP_SYMBOL(nq::g_fast_count), z, sizeof z);

@@ -62,7 +62,10 @@ struct SalJob { const int* pixels; long long N; float* out; long long vec4; int 
 // nearest lists), false when the caller has to launch_saliency itself.
 // d_packed / d_failed (nullable): the LAB launch also writes the packed records of launch_pack_lists (both lists must be in use) and
 // zeroes d_failed[0], the hand-back count of launch_gilbert_fast; *folded says whether it did -- false: the caller launches
-// launch_pack_lists itself and launch_gilbert_fast clears the count
+// launch_pack_lists itself and launch_gilbert_fast clears the count.  With d_packed the LAB launch also leaves the palette's Lab behind the
+// packed records (NQ_LAB_TABLE_BYTES at d_packed + NQ_PACKED_BYTES: 256 x {L, A, B, 0} of RGB2LAB, zero from entry K on) for
+// launch_gilbert_fast's d_lab, so the table lives and travels with the records of its palette
+constexpr size_t NQ_PACKED_BYTES = (size_t) 65536 * 64, NQ_LAB_TABLE_BYTES = 256 * 16;
 bool launch_build_lists(const DevParams& P, const int* d_palette, double wA, double wR, double wG, double wB, bool nearest,
                         const float* d_box, unsigned char* d_closest, unsigned char* d_closestCount, unsigned char* d_nearest,
                         unsigned char* d_nearestCount, hipStream_t s, const int* d_sal_pixels = nullptr, int64_t N = 0, float* d_sal_out = nullptr,
@@ -97,12 +100,14 @@ bool gilbert_pixel_eligible(const TileGeom& T);       // power-of-two tiles of 1
 // d_failed points at word 1 of an int[2 + 2 * tiles] block: d_failed[-1] = the need count of the split form, d_failed[0] = the hand-back
 // count, d_failed[1 .. tiles] the tiles handed back, d_failed[1 + tiles ..] the need list.  chain_stream (split form only, nullable): the chain
 // pass goes onto that stream behind chain_gate, recorded on s after the light kernel; the caller orders what follows (the generic kernel over
-// the hand-back list must run behind the chain pass)
+// the hand-back list must run behind the chain pass).  d_lab (nullable): the Lab table a folded launch_build_lists wrote for this palette;
+// without it the pixel-form light pass converts the palette in every workgroup
 hipError_t launch_gilbert_fast(const DevParams& P, const GilbertConsts& G, const TileGeom& T, const ListsView& lv, const int* d_pixels,
                                const float* d_saliency, const int* d_palette, long long seed, unsigned short* d_index, int* d_argb,
                                int* d_failed, void* d_packed /* 65536 x 64 bytes */, hipStream_t s,
                                bool failed_cleared = false /* d_failed[-1..0] were zeroed by the launch_build_lists in front of this call */,
-                               int chain_mode = FAST_CHAIN_FUSED, hipStream_t chain_stream = nullptr, hipEvent_t chain_gate = nullptr);
+                               int chain_mode = FAST_CHAIN_FUSED, hipStream_t chain_stream = nullptr, hipEvent_t chain_gate = nullptr,
+                               const void* d_lab = nullptr);
 bool fast_lookup_eligible(const DevParams& P, const ListsView& lv);
 bool fast_pack_wanted(const DevParams& P, const ListsView& lv);     // the packed records are needed (LAB lookups, or the RGB dither kernel)
 // packs the two lists of every colour cell into the 32-byte records (+ continuations) the specialised kernels read; must follow

@@ -69,7 +69,8 @@ bool launch_build_lists(const DevParams& P, const int* d_palette, double wA, dou
         const size_t smem = std::max(palette_smem_bytes(P.kind, P.K), (size_t) 256 * sizeof(double));
         allow_big_lds(build_lab_lists_kernel, smem);
         hipLaunchKernelGGL(build_lab_lists_kernel, dim3(2 * 65536 / 256 + sal.blocks), dim3(256), smem, s, P, d_palette,
-                           wA, wR, wG, wB, P.hasAlpha ? 1 : 0, d_box, d_closest, d_closestCount, d_nearest, d_nearestCount, sal, d_packed, d_failed);
+                           wA, wR, wG, wB, P.hasAlpha ? 1 : 0, d_box, d_closest, d_closestCount, d_nearest, d_nearestCount, sal, d_packed, d_failed,
+                           d_packed ? reinterpret_cast<float4*>(static_cast<unsigned char*>(d_packed) + NQ_PACKED_BYTES) : nullptr);
         if (folded) *folded = true;
         return sal.blocks > 0;
     }

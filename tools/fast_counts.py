@@ -33,7 +33,7 @@ def main():
     q.width, q.height = W, H
     d_out = torch.empty(W * H, dtype=torch.int32, device="cuda")
     d_idx = torch.empty(W * H, dtype=torch.int16, device="cuda")
-    buf = (C.c_ulonglong * 16)()
+    buf = (C.c_ulonglong * 24)()
     q.convert_device(d_in.data_ptr(), 256, True, d_out.data_ptr(), d_idx.data_ptr())       # (first call: tables, scratch)
     torch.cuda.synchronize()
     assert lib.nq_fast_counts(buf, 1) == 0
@@ -55,6 +55,17 @@ def main():
     # phase of a batch -- the same two slots count TILES: finished by gilbert_light_kernel / listed for the chain pass)
     lines += ["", "light walk (NQ_OPT_DITHER_CHAIN = 0): %d wavefronts finished without the error chain, %d walked again with it (of %d)"
               % (v[13], v[14], W * H // 4096)]
+    # the pixel-form light pass (NQ_OPT_DITHER_CHAIN = 4): how many lanes of a wavefront-step enter fast_nearest
+    q.set_option(4, 4)
+    assert lib.nq_fast_counts(buf, 1) == 0
+    q.convert_device(d_in.data_ptr(), 256, True, d_out.data_ptr(), d_idx.data_ptr())
+    torch.cuda.synchronize()
+    assert lib.nq_fast_counts(buf, 0) == 0
+    p = list(buf)
+    lines += ["", "pixel-form light pass (NQ_OPT_DITHER_CHAIN = 4), gilbert_pixel_kernel:",
+              "wavefront-steps with a looked-up lane %d, of those with >= 1 lane in fast_nearest %d (%.4f)" % (p[16], p[17], p[17] / max(p[16], 1)),
+              "lanes in fast_nearest %d: %.2f of 64 per wavefront-step, %.2f per step that enters it" % (p[18], p[18] / max(p[16], 1), p[18] / max(p[17], 1)),
+              "steps without a draw (lanes) %d" % p[15]]
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if len(sys.argv) > 1:

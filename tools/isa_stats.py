@@ -1,6 +1,6 @@
 """Compile one unit of csrc/ with --save-temps into build/isa and print the register / scratch / occupancy summary and the
 instruction mix of the kernels whose mangled name contains the given substring (default: gilbert_fast).  The unit follows the
-substring: "fast" -> nq_dither_fast.hip, "png" -> nq_png.hip, "gif" -> nq_gif.hip, "hold" -> nq_hold.hip, "signature" -> nq_shots.hip, "refine" -> nq_refine.hip, "orient" -> nq_orient.hip, "retime" -> nq_retime.hip, "yuv16" -> nq_yuv16.hip, "yuv" (without "orient") -> nq_yuv.hip, "resample" (without "yuv") -> nq_resample.hip, anything else -> nq_kernels.hip.
+substring: "fast" or "gilbert_pixel" -> nq_dither_fast.hip, "png" -> nq_png.hip, "gif" -> nq_gif.hip, "hold" -> nq_hold.hip, "signature" -> nq_shots.hip, "refine" -> nq_refine.hip, "orient" -> nq_orient.hip, "retime" -> nq_retime.hip, "yuv16" -> nq_yuv16.hip, "yuv" (without "orient") -> nq_yuv.hip, "resample" (without "yuv") -> nq_resample.hip, anything else -> nq_kernels.hip.
 Usage: python tools/isa_stats.py [substring] [--nobuild]"""
 import collections
 import os
@@ -16,7 +16,7 @@ CSRC = os.path.join(ROOT, "nquant.android_amd", "csrc")
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     pat = args[0] if args else "gilbert_fast"
-    unit = "nq_retime" if "retime" in pat else "nq_orient" if "orient" in pat else "nq_yuv16" if "yuv16" in pat else "nq_yuv" if "yuv" in pat else "nq_resample" if "resample" in pat else "nq_dither_fast" if "fast" in pat else "nq_png" if "png" in pat else "nq_gif" if "gif" in pat else "nq_hold" if "hold" in pat else "nq_shots" if "signature" in pat else "nq_refine" if "refine" in pat else "nq_kernels"
+    unit = "nq_retime" if "retime" in pat else "nq_orient" if "orient" in pat else "nq_yuv16" if "yuv16" in pat else "nq_yuv" if "yuv" in pat else "nq_resample" if "resample" in pat else "nq_dither_fast" if "fast" in pat or "gilbert_pixel" in pat else "nq_png" if "png" in pat else "nq_gif" if "gif" in pat else "nq_hold" if "hold" in pat else "nq_shots" if "signature" in pat else "nq_refine" if "refine" in pat else "nq_kernels"
     SRC = os.path.join(CSRC, unit + ".hip")
     ASM = os.path.join(OUT, unit + "-hip-amdgcn-amd-amdhsa-gfx950.s")
     if "--nobuild" not in sys.argv:
