@@ -1244,7 +1244,11 @@ int nq_band_color_presence_device(nq_handle* h, const uint32_t* d_argb, int64_t 
  * DITHER PASS -- it leaves out the BlueNoise post-pass of convert(n, false).  nq_get_batch_phase_ms gives the amortised phases.
  * `dither` in a batch call whose dither passes take the split form (NQ_OPT_DITHER_CHAIN): the span ends behind the LIGHT kernel on the
  * launch stream; the image's chain pass and hand-back pass run on a side stream beside the next image and are not inside it (their
- * time shows in the finish phase of nq_get_batch_phase_ms, which waits for them).  Everywhere else it is the whole per-pixel pass. */
+ * time shows in the finish phase of nq_get_batch_phase_ms, which waits for them).  Everywhere else it is the whole per-pixel pass.
+ * `palette_fill` in nq_convert_batch_device with the finish phase's prep stream (NQ_FINISH_PREP): the image's candidate lists, Lab table
+ * and saliency map are built on that stream beside the light kernels of the images in front of it, and the boundary between
+ * `palette_fill` and `dither` is recorded on the launch stream behind its wait for them -- `palette_fill` then holds only what the launch
+ * stream still waited of the list build, and `dither` stays the light kernel alone (slower there than by itself: it shares the GPU). */
 #define NQ_N_STAGES 8
 int nq_get_stage_ms(const nq_handle* h, float* out8);
 /* Counters of the last merge loop (diagnostics), 16 values: {find_nn calls, merges, 100 MHz ticks inside find_nn, ticks in

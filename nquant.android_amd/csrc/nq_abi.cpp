@@ -198,6 +198,11 @@ struct nq_handle {
     hipStream_t chain_stream = nullptr;
     hipEvent_t chain_gate = nullptr, chain_done = nullptr;
     bool chain_on_side = false;       // the last dither pass ended on chain_stream (chain_done was recorded there)
+    // nq_convert_batch_device, finish phase with a prep stream: the image's lists, Lab table, saliency map and counter clear go onto
+    // prep_stream (behind set_free, the end of the dither work of the image that had the scratch set before; null: the set is free);
+    // prep_done: behind them on prep_stream, the handle's stream waits for it in front of the light pass
+    hipStream_t prep_stream = nullptr;
+    hipEvent_t prep_done = nullptr, set_free = nullptr;
     bool dither_events_fresh = false; // the last call on the handle was a stand-alone dither (events 5..7 are newer than stage_ms)
     int last_dither_fast = 0;         // diagnostics: 1 if the last dither pass ran gilbert_fast_kernel
     bool split_uncounted = false;     // ... it took the split form and its need count is not yet in nq_get_dither_split_stats
@@ -329,6 +334,7 @@ struct nq_handle {
         if (lane_gate) (void) hipEventDestroy(lane_gate);
         if (chain_gate) (void) hipEventDestroy(chain_gate);
         if (chain_done) (void) hipEventDestroy(chain_done);
+        if (prep_done) (void) hipEventDestroy(prep_done);
         if (copy_stream) (void) hipStreamDestroy(copy_stream);
         if (lane_stream) (void) hipStreamDestroy(lane_stream);
         for (auto& ls : more_lanes) if (ls) (void) hipStreamDestroy(ls);
@@ -1020,6 +1026,19 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
     // stage events 5..7 belong to THIS call only once it has recorded all of them (set at the successful exits below); until then
     // nq_get_stage_ms reports what the last finished convert left
     h->dither_events_fresh = false;
+    // Finish phase of a batch with a prep stream: what builds the scratch set's content for this image -- lists, Lab table, saliency map,
+    // the hand-back counts' clear -- runs there, behind the set's previous user (set_free) and, where the palette was uploaded just now,
+    // behind that copy (prep_done serves as the marker on the handle's stream first).  PrepScope puts the handle's stream back.
+    struct PrepScope {
+        nq_handle* h; hipStream_t main;
+        ~PrepScope() { h->stream = main; }
+    } prep_scope{h, h->stream};
+    const bool prep = h->prep_stream && h->prep_stream != h->stream && mode != NQ_MODE_LOOKUP_ONLY;
+    if (h->set_free) NQ_HIP(h, hipStreamWaitEvent(prep ? h->prep_stream : h->stream, h->set_free, 0));
+    if (prep && !h->palette_synced) {
+        NQ_HIP(h, hipEventRecord(h->prep_done, h->stream));
+        NQ_HIP(h, hipStreamWaitEvent(h->prep_stream, h->prep_done, 0));
+    }
 
     if (mode == NQ_MODE_LOOKUP_ONLY) {
         DevParams P = dev_params(h, K);
@@ -1119,16 +1138,34 @@ int dither_device(nq_handle* h, const uint32_t* d_argb, int width, int height, c
     const bool maybe_fast = !ov.blue_only && !sequential && h->use_fast_dither && K > 32 && K <= 256;
     bool failed_cleared = false;
     if (maybe_fast) NQ_HIP(h, h->d_failed.reserve(failed_words(T)));
-    { int rcl = lists_for_call(h, P, &lv, want_sal ? (const int*) d_argb : nullptr, n, salSubst ? 1 : 0, &sal_done, maybe_fast ? failed_list(h) : nullptr,
-                               &failed_cleared); if (rcl) return rcl; }
+    // (A/B timing, prep stream only: NQ_FINISH_SAL = 1 / 2: the saliency map as a launch of its own in front of / behind the list
+    // builders on the prep stream, 3: on the handle's stream in front of the light pass)
+    int sal_own = 0;
+    if (prep && want_sal) if (const char* e = std::getenv("NQ_FINISH_SAL")) { const int v = std::atoi(e); if (v >= 1 && v <= 3) sal_own = v; }
+    if (prep) h->stream = h->prep_stream;
+    if (sal_own) NQ_HIP(h, h->sc->saliency.reserve((size_t) n));
+    if (sal_own == 1) { launch_saliency(P, salSubst ? 1 : 0, (const int*) d_argb, n, h->sc->saliency.p, h->stream); sal_done = true; }
+    { bool folded_sal = false;
+      int rcl = lists_for_call(h, P, &lv, want_sal && !sal_own ? (const int*) d_argb : nullptr, n, salSubst ? 1 : 0, &folded_sal,
+                               maybe_fast ? failed_list(h) : nullptr, &failed_cleared);
+      if (rcl) return rcl;
+      sal_done = sal_done || folded_sal; }
     const float* d_sal = nullptr;
     if (staged) d_sal = hasSal ? ov.d_sal : nullptr;
     else if (hasSal) {
         NQ_HIP(h, h->sc->saliency.reserve((size_t) n));
-        if (!sal_done) launch_saliency(P, salSubst ? 1 : 0, (const int*) d_argb, n, h->sc->saliency.p, h->stream);
+        if (!sal_done && sal_own != 3) launch_saliency(P, salSubst ? 1 : 0, (const int*) d_argb, n, h->sc->saliency.p, h->stream);
         d_sal = h->sc->saliency.p;
     }
-    rec(h, 5);       // stage "palette_fill" ends here: it includes the candidate-list build and the saliency map
+    if (prep) {
+        NQ_HIP(h, hipEventRecord(h->prep_done, h->prep_stream));
+        h->stream = prep_scope.main;
+        NQ_HIP(h, hipStreamWaitEvent(h->stream, h->prep_done, 0));
+        if (sal_own == 3) launch_saliency(P, salSubst ? 1 : 0, (const int*) d_argb, n, h->sc->saliency.p, h->stream);
+    }
+    // stage "palette_fill" ends here: it includes the candidate-list build and the saliency map -- except behind a prep stream, where it
+    // is what the launch stream still waits of them
+    rec(h, 5);
     int log_cap = 0;
     if (seq_lab_post) {
         // every colour handed to nearestColorIndex on a cache miss (<= 3 lookups per pixel) + a flag per palette entry
@@ -1408,11 +1445,15 @@ struct BatchGuard {
     nq_handle* const* hs; int n;
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> events;
-    hipStream_t side[3] = {nullptr, nullptr, nullptr};    // the finish phase's side streams, once work may be on them
+    hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};    // the finish phase's side streams (chain streams, prep stream), once work may be on them
     BatchGuard(nq_handle* const* hh, int nn) : hs(hh), n(nn) { for (int i = 0; i < n; ++i) streams.push_back(hs[i]->stream); }
     ~BatchGuard() {
-        for (hipStream_t s : side) if (s) (void) hipStreamSynchronize(s);        // (a chain pass of a call that failed half-way may still run there)
-        for (int i = 0; i < n; ++i) { hs[i]->stream = streams[i]; hs[i]->sc = &hs[i]->own; hs[i]->light_events = false; hs[i]->chain_stream = nullptr; }
+        // (a chain pass or a list build of a call that failed half-way may still run there, writing a scratch set or a handle's d_failed)
+        for (hipStream_t s : side) if (s) (void) hipStreamSynchronize(s);
+        for (int i = 0; i < n; ++i) {
+            hs[i]->stream = streams[i]; hs[i]->sc = &hs[i]->own; hs[i]->light_events = false;
+            hs[i]->chain_stream = nullptr; hs[i]->prep_stream = nullptr; hs[i]->set_free = nullptr;
+        }
         for (hipEvent_t e : events) (void) hipEventDestroy(e);
     }
 };
@@ -1857,32 +1898,48 @@ int nq_convert_frames(nq_handle* h, int n, const uint32_t* const* argb, const in
 }
 
 // Finish phase of the batch entry points: every handle's chain_stream for the dither passes that follow.  With S scratch sets (the per-pixel
-// scratch of the first S handles) image i takes set i % S and side stream i % (S - 1); the caller orders the main stream behind chain_done of
-// image i - S before image i reuses its set, and joins the last S images at the end of the phase.  S = 2, the default, is one side stream
-// and two sets by image parity; NQ_FINISH_SETS = 2..4 overrides, bounded by the number of handles (a single image has one set).  *sets = S and side[0 .. S - 2] = the side streams, or *sets = 0 with NQ_DITHER_SIDE_STREAM=0 (A/B
-// timing): the split form in plain serial order on the main stream.  The BatchGuard of the call takes chain_stream back.
-int finish_side_streams(nq_handle* h0, nq_handle* const* hs, int n, int* sets, hipStream_t side[3]) {
+// scratch of the first S handles) image i takes set i % S; a set goes prep(i) -> light(i) -> chain and hand-back(i), and its next user
+// starts behind chain_done of image i - S.  The caller joins the last S images at the end of the phase.  Two forms:
+//  - with a prep stream (*prep set; nq_convert_batch_device with n >= 2): lists, Lab table, saliency map and counter clear of image i go
+//    onto *prep (dither_device, prep_stream), beside the light pass of the images in front of it; S = min(4, n) sets, the chain passes
+//    alternate over two side streams (NQ_FINISH_CHAIN_STREAMS=1: one).  With four sets the prep stream runs up to two images ahead and
+//    nothing else throttles it.  Launch, prep and two chain streams: four streams, the lanes of the prepare phase again.
+//  - without (prep == null, a single image, or NQ_FINISH_PREP=0): the lists stay on the launch stream; S = 2, one side stream, sets by
+//    image parity, and image i on side stream i % (S - 1).
+// NQ_FINISH_SETS = 2..4 overrides S in both, bounded by the number of handles.  *sets = S, side[0..2] = the chain streams and side[3] = the
+// prep stream, or *sets = 0 with NQ_DITHER_SIDE_STREAM=0 (A/B timing): the split form in plain serial order on the main stream, no
+// prep stream.  The BatchGuard of the call takes chain_stream, prep_stream and set_free back.
+int finish_side_streams(nq_handle* h0, nq_handle* const* hs, int n, int* sets, hipStream_t side[4], hipStream_t* prep = nullptr) {
     *sets = 0;
-    side[0] = side[1] = side[2] = nullptr;
+    side[0] = side[1] = side[2] = side[3] = nullptr;
+    if (prep) *prep = nullptr;
     bool use_side = true;
     if (const char* e = std::getenv("NQ_DITHER_SIDE_STREAM")) use_side = std::atoi(e) != 0;
     if (!use_side) {
         for (int i = 0; i < n; ++i) hs[i]->chain_stream = hs[i]->stream;
         return NQ_OK;
     }
-    int S = 2;
+    bool use_prep = prep && n > 1;
+    if (const char* e = std::getenv("NQ_FINISH_PREP")) use_prep = use_prep && std::atoi(e) != 0;
+    int S = use_prep ? 4 : 2;
     if (const char* e = std::getenv("NQ_FINISH_SETS")) { const int v = std::atoi(e); if (v >= 2 && v <= 4) S = v; }
     S = std::max(2, std::min(S, n));
-    if (!h0->lane_stream) NQ_HIP(h0, hipStreamCreateWithFlags(&h0->lane_stream, hipStreamNonBlocking));
-    side[0] = h0->lane_stream;
-    for (int k = 1; k < S - 1; ++k) {
-        if (!h0->more_lanes[k - 1]) NQ_HIP(h0, hipStreamCreateWithFlags(&h0->more_lanes[k - 1], hipStreamNonBlocking));
-        side[k] = h0->more_lanes[k - 1];
+    int C = S - 1;                    // chain streams
+    if (use_prep) {
+        C = 2;
+        if (const char* e = std::getenv("NQ_FINISH_CHAIN_STREAMS")) { const int v = std::atoi(e); if (v == 1 || v == 2) C = v; }
     }
+    auto lane = [&](int k) -> hipStream_t* { return k == 0 ? &h0->lane_stream : &h0->more_lanes[k - 1]; };
+    for (int k = 0; k < C + (use_prep ? 1 : 0); ++k)
+        if (!*lane(k)) NQ_HIP(h0, hipStreamCreateWithFlags(lane(k), hipStreamNonBlocking));
+    for (int k = 0; k < C; ++k) side[k] = *lane(k);
+    if (use_prep) side[3] = *prep = *lane(C);
     for (int i = 0; i < n; ++i) {
         if (!hs[i]->chain_gate) NQ_HIP(h0, hipEventCreateWithFlags(&hs[i]->chain_gate, hipEventDisableTiming));
         if (!hs[i]->chain_done) NQ_HIP(h0, hipEventCreateWithFlags(&hs[i]->chain_done, hipEventDisableTiming));
-        hs[i]->chain_stream = side[i % (S - 1)];
+        if (use_prep && !hs[i]->prep_done) NQ_HIP(h0, hipEventCreateWithFlags(&hs[i]->prep_done, hipEventDisableTiming));
+        hs[i]->chain_stream = side[i % C];
+        hs[i]->prep_stream = side[3];
     }
     *sets = S;
     return NQ_OK;
@@ -2013,21 +2070,28 @@ int nq_convert_batch_device(nq_handle* const* hs, int n, const uint32_t* const* 
         }
     // The chain pass and the hand-back pass of image i (a few wavefronts, one chain's latency) run on a side stream beside the lists,
     // saliency map and light kernel of image i + 1 (dither_device, chain_stream).  What they read of the per-image scratch -- saliency plane,
-    // list records -- rotates through S sets (finish_side_streams; two by default: image parity); the main stream waits for image i's side
-    // work before image i + S reuses its set, and at the end of the phase.
+    // list records -- rotates through S sets (finish_side_streams); image i's side work ends before image i + S reuses its set, and the main
+    // stream waits for it at the end of the phase.  With a prep stream the lists and the saliency map of image i + 1 run there, beside the
+    // light kernel of image i, and the main stream keeps the light kernels alone.
     int S = 0;
-    rc = finish_side_streams(h0, hs, n, &S, guard.side);
+    hipStream_t prep = nullptr;
+    rc = finish_side_streams(h0, hs, n, &S, guard.side, &prep);
     if (rc) return batch_fail(h0, h0, rc);
     for (int i = 0; i < n; ++i) {
         uint32_t* pal = out_palettes + (size_t) i * palette_stride;
         if (S) {
             hs[i]->sc = &hs[n > 1 ? i % S : 0]->own;
-            if (i >= S && hs[i - S]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(lane_s[0], hs[i - S]->chain_done, 0));
+            // the set's first writer waits for the dither work of image i - S: the prep stream (dither_device, set_free), else this stream
+            if (prep) hs[i]->set_free = i >= S ? hs[i - S]->chain_done : nullptr;
+            else if (i >= S && hs[i - S]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(lane_s[0], hs[i - S]->chain_done, 0));
         }
         rc = dither_device(hs[i], d_argb[i], widths[i], heights[i], pal, out_K[i], dither, rng_seeds[i], mode, d_out_argb[i],
                            d_out_index ? d_out_index[i] : nullptr);
         if (rc) return batch_fail(h0, hs[i], rc);
+        // (a pass that ended on this stream: chain_done marks its end here, for the prep stream of image i + S)
+        if (prep && !hs[i]->chain_on_side && i + S < n) NQ_HIP(h0, hipEventRecord(hs[i]->chain_done, lane_s[0]));
     }
+    // (the prep stream needs no join of its own: this stream has waited for prep_done of the last image, and the stream runs in order)
     for (int i = std::max(0, n - std::max(S, 2)); i < n; ++i)
         if (hs[i]->chain_on_side) NQ_HIP(h0, hipStreamWaitEvent(lane_s[0], hs[i]->chain_done, 0));
     (void) hipEventRecord(h0->bev[3], lane_s[0]);
